@@ -475,8 +475,13 @@ def main():
                     help="tiled = engine-native tiled SoA (hydro_step_wrench_tiled); soa = plain field pointers; "
                          "aos = the simulator's (N,3)/(N,4)/(N,6) tensors (hydro_step_wrench_aos, 168 B per body-step)")
     ap.add_argument("--explain", action="store_true", help="print what the fields of the line and of the side file mean, and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the wrench of the last timed step (rank 0) as DIR/force.npy, DIR/torque.npy "
+                         "(e.g. DIR = bench_outputs, which git ignores)")
     args = ap.parse_args()
 
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
     if args.explain:
         from scripts.bench_extras import FIELD_NOTES
         print(FIELD_NOTES)
@@ -539,6 +544,8 @@ def main():
 
     spin_up(replicas, stream, args.spinup_seconds)
     wall, ev_ms = timed_steps(replicas, args.steps, args.warmup, stream, multi)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(_last_stepped(replicas, args.steps), args.dump_outputs)
     n_all = torch.tensor([float(sc.n)], dtype=torch.float64, device=hd.collective_device(dev) if multi else "cpu")
     hd.all_reduce_sum_(n_all)
     value = float(n_all.item()) * args.steps / wall
@@ -684,6 +691,29 @@ def _cpu_leg(sc, replicas, args):
         return cpu_baseline_leg(sc, _last_stepped(replicas, args.steps), args.cpu_seconds)
     except Exception as e:                                  # noqa: BLE001 - report, never lose the line
         return {"value": None, "unit": "body-steps/s", "cores": 1, "kind": "port", "sample": "failed", "error": repr(e)[:200]}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20260
+
+
+def dump_outputs(replica, out_dir: str, limit: int = DUMP_LIMIT_BYTES) -> list[str]:
+    """What a caller of the timed path receives from its last step: the (n,3) force and torque of `replica`, float32, rows in
+    the order the replica's bodies were handed to the engine.  Above `limit` bytes a fixed sample of rows (seeded, sorted)
+    is written instead, with its row numbers as body_index.npy (float64, exact).  The inputs are seeded, so two runs with
+    the same arguments compute on the same bodies."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.asarray(replica.wrench_rows(replica.n), dtype=np.float32)
+    arrays = {"force": rows[:, 0:3], "torque": rows[:, 3:6]}
+    if rows.nbytes > limit:
+        m = limit // (rows.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(replica.n, m, replace=False))
+        arrays = {"force": rows[idx, 0:3], "torque": rows[idx, 3:6], "body_index": idx.astype(np.float64)}
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, f"{name}.npy"))
+        np.save(paths[-1], np.ascontiguousarray(a))
+    return paths
 
 
 def _last_stepped(replicas, steps):

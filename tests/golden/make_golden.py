@@ -360,11 +360,32 @@ def save_edge_cases():
     print(f"edge_cases: {len(ec.NAMES)} cases, rest-completed {int(rest.sum())}, dry {int((ratio == 0).sum())} -> {os.path.getsize(path)} B")
 
 
+FUZZ_SEEDS = (20251, 20252)        # tests/test_reference_fuzz.py
+FUZZ_BODIES = 3000                 # the fewest that still hold every count the test asserts (> 1000 thin plates, > 500 dry / full)
+
+
+def save_fuzz(seed, n=FUZZ_BODIES):
+    """The reference's outputs on tests/tools/reference_fuzz.py's special-value population(n, seed)."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "tools"))
+    import reference_fuzz as rf
+    pop = rf.population(n, seed)
+    ref = rf.reference_outputs(pop, sys.modules[__name__])
+    path = rf.fixture_path(seed)
+    np.savez_compressed(path, n=np.int64(n), seed=np.int64(seed), population_sha256=np.array(rf.population_digest(*pop[:3])),
+                        **ref)
+    print(f"fuzz_{seed}: {n} bodies, rest-completed {int(ref['rest_completed'].sum())}, "
+          f"tiny {len(ref['tiny_index'])} -> {os.path.getsize(path)} B")
+
+
 def main():
     from silver2_isaacsim_amd import scenes
     if "--only-ties" in sys.argv:
         save_ties()
         return save_edge_cases()
+    if "--only-fuzz" in sys.argv:
+        for seed in FUZZ_SEEDS:
+            save_fuzz(seed)
+        return
     save_known_answers()
     save_ties()
     save_edge_cases()
@@ -380,6 +401,8 @@ def main():
     sc.name = "C4-adversarial"
     save_scene_fixture("c4_adversarial", sc, np.arange(sc.n))
     save_c1_trajectory()
+    for seed in FUZZ_SEEDS:
+        save_fuzz(seed)
 
 
 if __name__ == "__main__":

@@ -332,3 +332,30 @@ def test_bench_strong_scaling_flag_two_ranks(native_built):
     assert d["scaling"] == "strong" and d["config"]["bodies_per_gpu"] == 32768 and "strong scaling: 65536 bodies over 2 GPUs" in d["config"]["workload"]
     assert d["value"] == pytest.approx(65536 / (d["ms_per_step"] * 1e-3), rel=1e-6) and "c4_strong" not in d
     assert d["collective"]["ke_rel_err"] <= 1e-12
+
+
+def test_dump_outputs_are_the_last_timed_step_and_repeat(native_built, tmp_path):
+    """`--dump-outputs DIR`: the wrench of the last timed step - replica (K - 1) mod `--scenes` - the same in two runs with the
+    same arguments, and inside the gate of the fp64 oracle on that replica's bodies."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    from oracle import hydro_oracle as ho
+    steps, n_scenes = 7, 4
+    got = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--workload", "c2",
+               "--scenes", str(n_scenes), "--cpu-seconds", "0", "--no-extras", "--no-configs", "--spinup-seconds", "0",
+               "--dump-outputs", str(tmp_path / run)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        assert json.loads([l for l in res.stdout.splitlines() if l.strip()][0])["steps"] == steps
+        assert sorted(os.listdir(tmp_path / run)) == ["force.npy", "torque.npy"]
+        got.append((np.load(tmp_path / run / "force.npy"), np.load(tmp_path / run / "torque.npy")))
+    (f, t), (f2, t2) = got
+    assert f.shape == t.shape == (4096, 3) and f.dtype == t.dtype == np.float32
+    assert np.array_equal(f, f2) and np.array_equal(t, t2)
+    sc = bench.build_scene("c2", 4096, seed=5)
+    idx = np.roll(np.arange(sc.n), ((steps - 1) % n_scenes) * 131071)        # bench.Replica's body order
+    rf, rt, _ = ho.step_wrench(sc.state[idx], sc.prev[idx], sc.params[idx], sc.rho, sc.g, sc.dt)
+    assert ho.wrench_error(f, t, rf, rt, sc.params[idx], sc.rho, sc.g).max() <= 1e-5

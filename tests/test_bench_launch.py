@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 from conftest import REPO
 
 
@@ -145,3 +147,40 @@ def test_box_summary_from_canned_probes():
     only_probes = be.box_summary({"bound_probes_1m": probes, "clocks_1m": {"skipped": "extras time budget"}})
     assert "clock_held_ghz" not in only_probes and only_probes["kernel_us"] == 21.4
     assert be.THROTTLE_RATIO == 1.15 and "kernel_over_memory_only >= 1.15" in be.FIELD_NOTES
+
+
+class _FakeReplica:
+    def __init__(self, n):
+        self.n = n
+        self.rows = np.arange(n * 6, dtype=np.float32).reshape(n, 6)
+
+    def wrench_rows(self, m):
+        return self.rows[:m]
+
+
+def test_dump_outputs_writes_the_wrench_whole_or_as_a_fixed_sample(tmp_path):
+    """--dump-outputs: force / torque of the last timed step as float32 .npy, under the byte limit; a larger output is a
+    seeded sample of rows (the same rows every run) with their row numbers."""
+    sys.path.insert(0, REPO)
+    import bench
+    rep = _FakeReplica(1000)
+    paths = bench.dump_outputs(rep, str(tmp_path / "full"))
+    assert sorted(os.path.basename(p) for p in paths) == ["force.npy", "torque.npy"]
+    f, t = np.load(tmp_path / "full" / "force.npy"), np.load(tmp_path / "full" / "torque.npy")
+    assert f.dtype == t.dtype == np.float32 and np.array_equal(f, rep.rows[:, :3]) and np.array_equal(t, rep.rows[:, 3:])
+    limit = 10000
+    for run in ("a", "b"):
+        bench.dump_outputs(rep, str(tmp_path / run), limit=limit)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("force", "torque", "body_index")}
+    assert sum(a.nbytes for a in got.values()) <= limit and got["body_index"].dtype == np.float64
+    idx = got["body_index"].astype(np.int64)
+    assert len(idx) > 0 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["force"], rep.rows[idx, :3]) and np.array_equal(got["torque"], rep.rows[idx, 3:])
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy")), k
+
+
+def test_dump_outputs_needs_a_timed_step():
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "0", "--dump-outputs", "x"],
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode != 0 and "--dump-outputs needs --steps >= 1" in res.stderr and res.stdout.strip() == ""

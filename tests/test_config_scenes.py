@@ -1,5 +1,6 @@
 """Host logic: parameter schema + JSON override rule (hydrodynamics_behavior.py:28-46,72-112),
 synthetic scene laws and the block partition (8e)."""
+import hashlib
 import json
 
 import numpy as np
@@ -8,6 +9,9 @@ import pytest
 from silver2_isaacsim_amd import config as cfg
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.distributed import shard_range
+
+# sha256 of json.dumps(json.load(f), sort_keys=True) for the reference's hydrodynamics_config.json
+REFERENCE_CONFIG_SHA256 = "14bbce0cb50d7658741d33048fcab471654fd0daeeeb99a6984774b8e74f1681"
 
 
 def test_schema_names_order_and_defaults():
@@ -146,8 +150,6 @@ def test_default_kit_host_applies_the_shipped_table_like_the_reference(tmp_path)
     A default drop-in - KitHost() with no config_dir - must run with the same parameters out of the box: it resolves to
     the table the package carries as constants (config.default_config() = hydrodynamics_config.json:2-54).  A host that
     names a directory keeps the literal rule for a missing file (warning, USD values stay)."""
-    import json
-    import os
     from silver2_isaacsim_amd import config as cfg
     from silver2_isaacsim_amd.behavior import KitHost
     data = cfg.load_config(KitHost().config_path())
@@ -160,6 +162,5 @@ def test_default_kit_host_applies_the_shipped_table_like_the_reference(tmp_path)
     assert KitHost(config_dir=str(tmp_path)).config_path() == str(tmp_path / cfg.CONFIG_FILE_NAME)
     assert KitHost(use_builtin_table=False).config_path().endswith(cfg.CONFIG_FILE_NAME)
     # a JSON dropped beside the package wins over the constants (a user's file always does)
-    ref = "/root/reference/src/scripts/physics/hydrodynamics_config.json"
-    if os.path.exists(ref):                                                   # (the build container only: the reference never travels)
-        assert json.load(open(ref)) == data
+    # the constants are the reference's hydrodynamics_config.json: sha256 of that file's parsed content, keys sorted
+    assert hashlib.sha256(json.dumps(data, sort_keys=True).encode()).hexdigest() == REFERENCE_CONFIG_SHA256

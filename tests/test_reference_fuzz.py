@@ -1,8 +1,10 @@
-"""The reference AS EXECUTED against the oracle and the kernel arithmetic, with the suite: 2 x 20 000
+"""The reference AS EXECUTED against the oracle and the kernel arithmetic, with the suite: 2 x 3 000
 bodies in which every field is, with some probability, a special value - exact zeros, the model's thresholds (speeds of 1e-6
 and 0.2), quantised and axis-aligned vectors, cube rotations, non-unit and zero quaternions, dimensions of 0 / 1e-7 / 3e-7 m,
-p_z on exact ties (tests/tools/reference_fuzz.py).  CPU only, and only where /root/reference exists: the reference never
-travels to the GPU box (there the frozen fixtures of tests/golden/ stand for it).
+p_z on exact ties (tests/tools/reference_fuzz.py).  CPU only.  The reference's outputs on the two populations are the
+committed fixtures tests/golden/fuzz_<seed>.npz, which tests/golden/make_golden.py writes by executing the reference; each
+carries a digest of the population it was made from.  3 000 bodies per seed keeps them small and still holds every count
+asserted below (round 4 ran 2 x 20 000 against the reference directly: tests/tools/reference_fuzz.py still does, for any size).
 
 What is asserted is the classification the tool used to print:
   * oracle == reference: the nine outputs and the ratio to 1e-9 of the body's scale on every body, the behaviour-level net
@@ -22,9 +24,6 @@ import pytest
 
 from conftest import REPO
 
-REFERENCE = "/root/reference/src/scripts/physics/numba_hydrodynamics.py"
-pytestmark = pytest.mark.skipif(not os.path.exists(REFERENCE), reason="the reference is not on this box (it never travels): fixtures stand for it")
-
 
 @pytest.fixture(scope="module")
 def fuzz(native_built):
@@ -35,7 +34,8 @@ def fuzz(native_built):
 
 @pytest.mark.parametrize("seed", [20251, 20252])
 def test_reference_as_executed_on_special_value_populations(fuzz, seed):
-    r = fuzz.run(20000, seed)
+    r = fuzz.run(3000, seed)
+    assert r["reference_source"] == "fixture", r                      # the committed outputs of the reference, never a re-run
     assert r["reference_finite"] > 0.8 * r["n"] and r["rest_completed"] > 0 and r["dry"] > 500 and r["full"] > 500, r
     assert r["tiny_bodies"] > 1000                                    # the thin plates are in the population
     # oracle == reference

@@ -1,20 +1,31 @@
 """USD-crate parameter reader.
 
-The decoders are tested on hand-made data; the full reader is run on the reference's scene files
-when they are present (build container) and must reproduce the table committed in
-tests/golden/usd_hydrodynamics_tables.json and the values listed in SURVEY.md's appendix."""
+The decoders are tested on hand-made data.  tests/golden/usd_hydrodynamics_tables.json holds what the reader recovered
+from the reference's three scene files; tests/crate_writer.py writes each table back into a crate file, and the full
+reader run on that file must reproduce the table and the values listed in SURVEY.md's appendix."""
 import json
 import os
+import random
 import struct
 
 import numpy as np
 import pytest
 
+import crate_writer
 from conftest import GOLDEN
 from silver2_isaacsim_amd import usd_crate as uc
 
-SCENES = "/root/reference/src/scenes"
-needs_reference = pytest.mark.skipif(not os.path.isdir(SCENES), reason="reference scenes not available on this box")
+
+def golden_tables():
+    with open(os.path.join(GOLDEN, "usd_hydrodynamics_tables.json")) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def scene_file(tmp_path_factory):
+    """scene name -> a crate file written from its committed table."""
+    d = tmp_path_factory.mktemp("scenes")
+    return {scene: crate_writer.write_crate(str(d / scene), table) for scene, table in golden_tables().items()}
 
 
 def test_lz4_block_decoder():
@@ -40,22 +51,27 @@ def test_integer_decoder():
     buf = struct.pack("<i", 1) + bytes(packed) + struct.pack("<b", 10) + struct.pack("<b", 100) + struct.pack("<b", -100) + struct.pack("<i", 70000)
     assert uc.decode_ints(buf, 6) == [10, 11, 12, 112, 12, 70012]
     assert uc.decode_ints(b"", 0) == []
+    # the test writer's encoder is its inverse, 32-bit wrap-around included (0xFFFFFFFF ends every fieldset)
+    rng = random.Random(7)
+    vals = [rng.randrange(1 << 32) for _ in range(300)] + [0xFFFFFFFF, 0, 3, 3, 3, 200, 70000]
+    assert uc.decode_ints(crate_writer.encode_ints(vals), len(vals)) == vals
+    assert uc.fast_decompress(crate_writer.lz4_literals(b"y" * 600), 600) == b"y" * 600
 
 
-@needs_reference
 @pytest.mark.parametrize("scene,n_prims,rate", [("silver2_isaac_sim.usd", 20, 60), ("silver2_isaac_sim_locomotion.usd", 19, 120),
                                                ("silver2_isaac_sim_terrestrial_environment.usd", 0, 120)])
-def test_scene_tables(scene, n_prims, rate):
-    tab = uc.hydrodynamics_table(os.path.join(SCENES, scene))
+def test_scene_tables(scene_file, scene, n_prims, rate):
+    tab = uc.hydrodynamics_table(scene_file[scene])
     assert tab["__scene__"]["timeStepsPerSecond"] == rate
     assert len(tab) - 1 == n_prims
-    golden = json.load(open(os.path.join(GOLDEN, "usd_hydrodynamics_tables.json")))[scene]
+    golden = golden_tables()[scene]
     assert json.loads(json.dumps(tab)) == golden
+    attrs = uc.CrateFile(scene_file[scene]).attributes()      # what the table leaves out is in the file, and passed over
+    assert "/World/GroundPlane.physics:mass" in attrs and not any(p.endswith(".points") for p in attrs)
 
 
-@needs_reference
-def test_main_scene_values_match_the_survey_appendix():
-    tab = uc.hydrodynamics_table(os.path.join(SCENES, "silver2_isaac_sim.usd"))
+def test_main_scene_values_match_the_survey_appendix(scene_file):
+    tab = uc.hydrodynamics_table(scene_file["silver2_isaac_sim.usd"])
     buoy = tab["/World/Environment/Obsea_Buoy"]
     f32 = lambda x: float(np.float32(x))                                    # noqa: E731
     assert (buoy["xDimension"], buoy["yDimension"], buoy["zDimension"]) == (1.0, 1.0, 3.0)
@@ -75,8 +91,8 @@ def test_main_scene_values_match_the_survey_appendix():
 
 
 def test_table_from_the_committed_fixture_feeds_the_engine_rows():
-    """Without the scene files: the committed table still turns into engine parameter rows."""
-    golden = json.load(open(os.path.join(GOLDEN, "usd_hydrodynamics_tables.json")))["silver2_isaac_sim_locomotion.usd"]
+    """The committed table turns straight into engine parameter rows."""
+    golden = golden_tables()["silver2_isaac_sim_locomotion.usd"]
     prims, rows, rho, g = uc.params_rows(golden)
     assert len(prims) == 19 and rows.dtype == np.float32 and rows[prims.index("/World/SILVER2/Body"), 10] == 18.0
 

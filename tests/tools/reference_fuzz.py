@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""BUILD CONTAINER ONLY (needs /root/reference): fuzz the oracle AND the kernel arithmetic (host instantiation of
-csrc/hydro_body.h) against the REFERENCE ITSELF on populations in which special values are injected field by field - exact
-zeros, thresholds of the model (speeds of 1e-6 and 0.2, angular likewise), axis-aligned and quantised vectors, cube
-rotations, non-unit quaternions, tiny and zero dimensions, p_z on exact ties - on top of continuous random bodies.
+"""Fuzz the oracle AND the kernel arithmetic (host instantiation of csrc/hydro_body.h) against the REFERENCE'S OWN OUTPUTS
+on populations in which special values are injected field by field - exact zeros, thresholds of the model (speeds of 1e-6
+and 0.2, angular likewise), axis-aligned and quantised vectors, cube rotations, non-unit quaternions, tiny and zero
+dimensions, p_z on exact ties - on top of continuous random bodies.
     python3 -B tests/tools/reference_fuzz.py [bodies] [seed]
 Prints how many bodies disagree (oracle vs reference at 1e-9 of the body's scale; kernel arithmetic vs reference at the
 1e-5 gate, centres at half an fp32 ulp + 1e-6) and the worst cases.  `run(n, seed)` returns the same as a dict:
-tests/test_reference_fuzz.py asserts it with the CPU suite (skipped where /root/reference is absent)."""
+tests/test_reference_fuzz.py asserts it with the CPU suite.
+
+Where the reference's outputs come from: for the committed seeds, tests/golden/fuzz_<seed>.npz (written by
+tests/golden/make_golden.py, which executes the reference; the fixture carries a digest of the population it was made
+from, so a population that drifts fails loudly instead of comparing against someone else's numbers).  Any other
+(bodies, seed) executes the reference through make_golden.py, which needs a checkout of the reference."""
 import ctypes
+import hashlib
 import os
 import sys
 
@@ -80,20 +86,69 @@ def _wrench_error(ho, f, t, ref_f, ref_t, params, rho, g):
     return np.where(vol0, alt, err)
 
 
-def run(n: int = 20000, seed: int = 1, verbose: bool = False) -> dict:
-    """Execute the reference, the oracle and the host instantiation of the kernel arithmetic on population(n, seed)."""
-    import make_golden as mg                      # (imports the reference through the identity-njit stub)
-    from oracle import hydro_oracle as ho
-    say = print if verbose else (lambda *a, **k: None)
-    state, prev, params, rho, g, dt, accel = population(n, seed)
+def population_digest(state, prev, params) -> str:
+    """sha256 of the fp32 inputs: ties a fixture to the population it was made from."""
+    h = hashlib.sha256()
+    for a in (state, prev, params):
+        h.update(np.ascontiguousarray(a, dtype=np.float32).tobytes())
+    return h.hexdigest()
+
+
+def fixture_path(seed: int) -> str:
+    return os.path.join(REPO, "tests", "golden", f"fuzz_{seed}.npz")
+
+
+def reference_outputs(pop, mg=None) -> dict:
+    """Execute the reference on `pop` (= population(n, seed)): its nine outputs, the net wrench of its `_apply_behavior`,
+    and that net wrench again at p_x = p_y = 0 for the tiny bodies (see run()).  `mg` is tests/golden/make_golden.py,
+    which imports the reference through the identity-njit stub."""
+    if mg is None:
+        import make_golden as mg
+    state, prev, params, rho, g, dt, accel = pop
     with np.errstate(all="ignore"):
         comps, ratio, rest = mg.reference_batch(state, accel, params, rho, g)
         net_f, net_t = mg.reference_behavior_batch(state, prev, params, rho, g, dt)
+        finite = np.isfinite(comps).all(axis=(1, 2)) & np.isfinite(net_f).all(axis=1) & np.isfinite(net_t).all(axis=1)
+        idx = np.where(finite & (params[:, :3].min(axis=1) < TINY_DIMENSION))[0]
+        st0 = state[idx].copy(); st0[:, 0:2] = 0.0
+        nf0, nt0 = mg.reference_behavior_batch(st0, prev[idx], params[idx], rho, g, dt)
+    return {"components": comps, "ratio": ratio, "rest_completed": rest, "net_force": net_f, "net_torque": net_t,
+            "tiny_index": idx.astype(np.int64), "tiny_net_force_pxy0": nf0, "tiny_net_torque_pxy0": nt0}
+
+
+def stored_reference_outputs(n: int, seed: int, pop):
+    """The reference's outputs on population(n, seed) from its committed fixture, or None if there is none for (n, seed)."""
+    path = fixture_path(seed)
+    if not os.path.exists(path):
+        return None
+    z = np.load(path)
+    if int(z["n"]) != n:
+        return None
+    state, prev, params = pop[:3]
+    got = population_digest(state, prev, params)
+    assert str(z["population_sha256"]) == got, f"{path} was made from another population than population({n}, {seed})"
+    return {k: z[k] for k in z.files if k not in ("n", "seed", "population_sha256")}
+
+
+def run(n: int = 20000, seed: int = 1, verbose: bool = False) -> dict:
+    """Compare the oracle and the host instantiation of the kernel arithmetic with the reference on population(n, seed):
+    the reference's outputs come from the committed fixture where there is one for (n, seed), else it is executed."""
+    from oracle import hydro_oracle as ho
+    say = print if verbose else (lambda *a, **k: None)
+    pop = population(n, seed)
+    state, prev, params, rho, g, dt, accel = pop
+    ref = stored_reference_outputs(n, seed, pop)
+    res = {"reference_source": "fixture" if ref is not None else "executed"}
+    if ref is None:
+        ref = reference_outputs(pop)
+    comps, ratio, rest = ref["components"], ref["ratio"], ref["rest_completed"]
+    net_f, net_t = ref["net_force"], ref["net_torque"]
+    with np.errstate(all="ignore"):
         o = ho.solve_components(state, accel, params.astype(np.float64), rho, g)
         rf, rt, aux = ho.step_wrench(state, prev, params, rho, g, dt)
     finite = np.isfinite(comps).all(axis=(1, 2)) & np.isfinite(net_f).all(axis=1) & np.isfinite(net_t).all(axis=1)
-    res = {"n": n, "seed": seed, "reference_finite": int(finite.sum()), "rest_completed": int(rest.sum()),
-           "dry": int((ratio == 0).sum()), "full": int((ratio == 1).sum())}
+    res.update({"n": n, "seed": seed, "reference_finite": int(finite.sum()), "rest_completed": int(rest.sum()),
+                "dry": int((ratio == 0).sum()), "full": int((ratio == 1).sum())})
     say(f"{n} bodies (seed {seed}): reference finite on {finite.sum()}, rest-completed {rest.sum()}, dry {(ratio == 0).sum()}, full {(ratio == 1).sum()}")
     # ---- oracle vs reference: the nine outputs, then the behaviour-level net wrench ----
     scale = np.maximum(1.0, np.abs(comps[:, :6]).max(axis=(1, 2)))
@@ -132,11 +187,10 @@ def run(n: int = 20000, seed: int = 1, verbose: bool = False) -> dict:
     # 1e-7 m thin and its torque a 300-fold cancellation.  Re-run the reference with p_x = p_y = 0 (the wrench does not
     # depend on them) on EVERY tiny body: those must agree with the kernels inside the gate.
     idx = np.where(finite & tiny)[0]
+    assert np.array_equal(idx, ref["tiny_index"])
     res["tiny_over_gate_at_pxy0"], res["tiny_max_at_pxy0"] = 0, 0.0
     if len(idx):
-        st0 = state[idx].copy(); st0[:, 0:2] = 0.0
-        with np.errstate(all="ignore"):
-            nf0, nt0 = mg.reference_behavior_batch(st0, prev[idx], params[idx], rho, g, dt)
+        nf0, nt0 = ref["tiny_net_force_pxy0"], ref["tiny_net_torque_pxy0"]
         e0 = _wrench_error(ho, f[idx], t[idx], nf0, nt0, params[idx], rho, g)
         ok0 = np.isfinite(nf0).all(axis=1) & np.isfinite(nt0).all(axis=1)
         res["tiny_over_gate_at_pxy0"] = int((ok0 & ~(e0 <= GATE)).sum())
