@@ -163,6 +163,48 @@ def surface_ties(n=4096, seed=21):
     return state, prev, params, kind
 
 
+def integrator_population(n=20000, seed=31, margin=1e-4):
+    """Designed bodies for the integrator tests (tests/test_integrator_*.py): every orientation (5 % of the quaternions
+    scaled by 1 +- 1e-3, used as given), boxes and slabs up to 1:10 so that the inertia is anisotropic, |w| up to ~10 rad/s
+    where the gyroscopic term dominates, dry / partial / submerged, light bodies on which the 500 m/s^2 clamp acts
+    (scale < 1), |k| dt / m from 0 to ~50 for the implicit form, w = 0 and v = 0 exactly, coordinates out to 1e4 m.
+    Gated on branch margins >= `margin` like the config scenes: drag_jacobian uses oracle quantities that have branches.
+    Returns (state, prev, params) as fp32; dt is DT."""
+    def draw(rng, k, idx=None):
+        size = np.exp(rng.uniform(np.log(0.1), np.log(2.0), k))
+        dims = size[:, None] * np.exp(rng.uniform(np.log(0.1), 0.0, (k, 3)))              # aspect up to 1:10
+        q = scenes.random_unit_quats(rng, k)
+        q *= np.where(rng.uniform(0, 1, k) < 0.05, 1.0 + rng.choice([-1e-3, 1e-3], k), 1.0)[:, None]
+        dims32, q32 = _f32(dims), _f32(q)
+        ext = scenes.vertical_extent(q32, dims32)
+        kind = rng.uniform(0, 1, k)
+        pz = np.where(kind < 0.2, ext * rng.uniform(1.05, 4.0, k),                         # dry
+             np.where(kind < 0.6, ext * rng.uniform(-0.95, 0.95, k),                       # partial
+                      -ext * rng.uniform(1.05, 30.0, k)))                                  # submerged
+        far = rng.uniform(0, 1, k) < 0.05
+        pxy = np.where(far[:, None], rng.uniform(-1e4, 1e4, (k, 2)), rng.uniform(-20.0, 20.0, (k, 2)))
+        pz = np.where(far & (kind >= 0.6), pz - rng.uniform(0.0, 1e4, k), pz)              # deep ones down to -1e4 m
+
+        def direction():
+            x = rng.normal(size=(k, 3))
+            return x / np.linalg.norm(x, axis=1, keepdims=True)
+        v = direction() * np.exp(rng.uniform(np.log(1e-3), np.log(5.0), k))[:, None]
+        w = direction() * np.exp(rng.uniform(np.log(1e-3), np.log(10.0), k))[:, None]
+        v[rng.uniform(0, 1, k) < 0.05] = 0.0
+        w[rng.uniform(0, 1, k) < 0.05] = 0.0
+        coeffs = np.array([1.2, 0.8, 300.0, 150.0, 1.0, 0.05, 0.02]) * np.exp(rng.uniform(np.log(0.1), np.log(10.0), (k, 7)))
+        coeffs[rng.uniform(0, 1, k) < 0.05, 2:4] = 0.0                                     # no damping: k from the quadratic part only
+        # density from 1e-3 to 3 times that of water: |k| dt / m spans 0 .. ~50, the light ones are clamped
+        mass = RHO * dims.prod(axis=1) * np.exp(rng.uniform(np.log(1e-3), np.log(3.0), k))
+        state = np.concatenate([pxy, pz[:, None], q32, v, w], axis=1)
+        prev = np.concatenate([v - rng.normal(0, 2.0, (k, 3)) * DT, w - rng.normal(0, 2.0, (k, 3)) * DT], axis=1)
+        params = np.concatenate([dims32, coeffs, mass[:, None]], axis=1)
+        return _f32(state), _f32(prev), _f32(params)
+
+    state, prev, params, _ = scenes._gated(np.random.default_rng(seed), n, draw, margin)
+    return state, prev, params
+
+
 def tie_census(state, params):
     """How many bodies have which exact tie (evaluated in fp64 as the oracle does: R @ k + p)."""
     q = state[:, 3:7].astype(np.float64)

@@ -12,6 +12,7 @@ import torch
 
 from conftest import SCENE_FIXTURES, accel_of, load_golden
 from oracle import hydro_oracle as ho
+from oracle import integrator_oracle as io
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd._native import HydroError
 from silver2_isaacsim_amd.engine import HydroEngine
@@ -494,24 +495,6 @@ def test_plain_soa_step_is_capturable_after_reserve_soa(order, native_built):
     eng.close()
 
 
-def _integrate_ref(state, wrench, params, g, dt):
-    s = state.astype(np.float64); w6 = wrench.astype(np.float64); p = params.astype(np.float64)
-    m = p[:, 10]; d = p[:, :3]
-    v = s[:, 7:10] + dt * (w6[:, :3] / m[:, None] + np.array([0, 0, -g]))
-    pos = s[:, :3] + dt * v
-    R = ho._rot_batch(s[:, 3:7])
-    I = (m / 12.0)[:, None] * np.stack([d[:, 1] ** 2 + d[:, 2] ** 2, d[:, 0] ** 2 + d[:, 2] ** 2, d[:, 0] ** 2 + d[:, 1] ** 2], 1)
-    wb = np.einsum("nba,nb->na", R, s[:, 10:13]); tb = np.einsum("nba,nb->na", R, w6[:, 3:])
-    nb = wb + dt * (tb - np.cross(wb, I * wb)) / I
-    w = np.einsum("nab,nb->na", R, nb)
-    q = s[:, 3:7]
-    qv, qw = q[:, :3], q[:, 3]
-    dq = np.concatenate([w * qw[:, None] + np.cross(w, qv), -(w * qv).sum(1, keepdims=True)], 1)
-    qn = q + 0.5 * dt * dq
-    qn /= np.linalg.norm(qn, axis=1, keepdims=True)
-    return np.concatenate([pos, qn, v, w], axis=1)
-
-
 def test_integrator_and_closed_loop(native_built):
     # buoys (C2): the explicit toy integrator is only stable while damping * dt / mass < 2, which
     # the 0.45 kg SILVER2 links at 120 Hz violate (the reference leaves integration to PhysX)
@@ -522,9 +505,13 @@ def test_integrator_and_closed_loop(native_built):
     W = eng.step_wrench(S, sc.dt, prev=soa(sc.prev))
     S2 = eng.integrate(S, W, sc.dt)
     torch.cuda.synchronize()
-    ref = _integrate_ref(sc.state, W.cpu().numpy().T, sc.params, sc.g, sc.dt)
+    w6 = W.cpu().numpy().T
+    ref = io.integrate(sc.state, w6, sc.params, sc.g, sc.dt)
     got = S2.cpu().numpy().T
     assert np.abs(got - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
+    # ... and per body and field group (tests/test_integrator_gpu.py has every entry)
+    err = io.integrator_error_ulps(got, ref, sc.state, w6, sc.params, sc.g, sc.dt)
+    assert io.max_error_ulps(err) <= io.STEP_ULP_BOUND, {g: float(e.max()) for g, e in err.items()}
     assert np.abs(np.linalg.norm(got[:, 3:7], axis=1) - 1).max() < 1e-6
     # closed loop, ping-pong state buffers: previous velocity = the other buffer's velocity rows
     A, B = S.clone(), torch.empty_like(S)
