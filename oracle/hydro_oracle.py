@@ -61,6 +61,14 @@ AXIS_EPS = 1e-6               # :210
 MAX_ACCEL = 500.0             # hydrodynamics_behavior.py:221
 CLAMP_EPS = 1e-6              # hydrodynamics_behavior.py:224
 
+# bits of aux['branches']: every decision of the model (solve_components, step_wrench), so that two evaluations can be
+# compared decision by decision: 27 wet keypoints (lattice order), moving, spinning, the six faces' `take` (+X -X +Y
+# -Y +Z -Z), has_area, lift_ok, wet (ratio > 1e-9), partially submerged, clamp active (scale < 1)
+BRANCH_NAMES = (tuple(f"wet_keypoint_{k}" for k in range(27)) + ("moving", "spinning")
+                + tuple(f"take_{f}" for f in ("+x", "-x", "+y", "-y", "+z", "-z"))
+                + ("has_area", "lift_ok", "live", "partial", "clamp"))
+BRANCH_CLAMP = BRANCH_NAMES.index("clamp")
+
 
 # --------------------------------------------------------------------------
 # geometry (numba_hydrodynamics_wrapper.py:55-112)
@@ -117,14 +125,19 @@ def rotation_from_quat_xyzw(q):
                      [xz - wy, yz + wx, 1.0 - (xx + yy)]], dtype=np.float64)
 
 
-def submersion_and_cob(world_pts, position):
+def submersion_and_cob(world_pts, position, semantics="numba"):
     """Submersion ratio from the z-extent, CoB = mean of points with z<0
-    (numba_hydrodynamics.py:54-105)."""
+    (numba_hydrodynamics.py:54-105).  semantics="warp": no early return for a body that is fully in by bounds - its
+    CoB is the mean of whatever points are wet (warp_hydrodynamics.py:58-61), which differs from the position only when
+    the top keypoint is exactly on the surface (z = 0 is not wet)."""
     z = world_pts[:, 2]
     z_lo, z_hi = float(z.min()), float(z.max())
     if z_lo >= 0.0:
         return 0.0, position.copy()
     if z_hi <= 0.0:
+        wet = z < 0.0
+        if semantics == "warp" and 0 < int(wet.sum()) < len(z):     # all 27 wet: the mean IS the position
+            return 1.0, world_pts[wet].sum(axis=0) / int(wet.sum())
         return 1.0, position.copy()
     height = z_hi - z_lo
     if height < HEIGHT_EPS:
@@ -219,7 +232,7 @@ def solve_components_one(p, q, v, w, a, alpha, params, rho, g, semantics="numba"
 
     rot = rotation_from_quat_xyzw(q)
     world = lattice_keypoints(dims) @ rot.T + p
-    ratio, cob = submersion_and_cob(world, p)
+    ratio, cob = submersion_and_cob(world, p, semantics)
     if ratio <= DRY_EPS:
         z3 = np.zeros(3)
         if semantics == "warp":                # warp_hydrodynamics.py:58-61,283-290: outputs initialised, cop = cob
@@ -261,7 +274,7 @@ def _rot_batch(q):
     xx, xy, xz = x * x2, x * y2, x * z2
     yy, yz, zz = y * y2, y * z2, z * z2
     wx, wy, wz = w * x2, w * y2, w * z2
-    r = np.empty((q.shape[0], 3, 3))
+    r = np.empty((q.shape[0], 3, 3), dtype=np.result_type(q.dtype, np.float64))
     r[:, 0, 0] = 1.0 - (yy + zz); r[:, 0, 1] = xy - wz;         r[:, 0, 2] = xz + wy
     r[:, 1, 0] = xy + wz;         r[:, 1, 1] = 1.0 - (xx + zz); r[:, 1, 2] = yz - wx
     r[:, 2, 0] = xz - wy;         r[:, 2, 1] = yz + wx;         r[:, 2, 2] = 1.0 - (xx + yy)
@@ -272,16 +285,32 @@ _LATTICE_IJK = np.array([(i, j, k) for k in (1, 0, -1) for j in (1, 0, -1) for i
                         dtype=np.float64)  # (27,3)
 
 
-def solve_components(state, accel, params, rho, g, semantics="numba"):
+def _f32(x):
+    """x rounded to fp32 and back to the type it had (the mutants of `solve_components`)."""
+    return np.asarray(x).astype(np.float32).astype(np.asarray(x).dtype)
+
+
+# Deliberate fp32 steps for tests/test_wrench_metric.py, which shows that `wrench_error_ulps` catches them; every
+# other caller leaves `mutate` empty.
+MUTATIONS = ("rotation_f32", "heights_f32", "inv_speed_seed")
+
+
+def solve_components(state, accel, params, rho, g, semantics="numba", dtype=np.float64, mutate=()):
     """Vectorised A1-A11 (semantics as in `solve_components_one`).
 
-    state  (N,13) float64, accel (N,6) [a | alpha], params (N,11).
+    state  (N,13), accel (N,6) [a | alpha], params (N,11), evaluated in `dtype`: float64 (default), or np.longdouble
+    for the high-precision reference of `wrench_error_ulps` (the same operations, x87 80-bit where numpy has it).
     Returns dict with the eight (N,3) COMPONENT_FIELDS plus 'ratio' (N,) and
-    diagnostic 'area' (N,), 'rest' (N,) bool = N1 completion fired.
+    diagnostic 'area' (N,), 'rest' (N,) bool = N1 completion fired, 'branches' (N,) int64 = BRANCH_BITS of the
+    decisions taken (see `branch_flips`).
+    `mutate` (names from MUTATIONS): the rotation matrix rounded to fp32, the keypoint heights rounded to fp32, or
+    1/|v| taken from the fp32 reciprocal of the fp32 speed (a hardware seed without its Newton step).
     """
-    state = np.asarray(state, dtype=np.float64)
-    accel = np.asarray(accel, dtype=np.float64)
-    params = np.asarray(params, dtype=np.float64)
+    if not set(mutate) <= set(MUTATIONS):
+        raise ValueError(f"unknown mutation in {mutate}")
+    state = np.asarray(state, dtype=dtype)
+    accel = np.asarray(accel, dtype=dtype)
+    params = np.asarray(params, dtype=dtype)
     n = state.shape[0]
     p, q, v, w = state[:, 0:3], state[:, 3:7], state[:, 7:10], state[:, 10:13]
     a, alpha = accel[:, 0:3], accel[:, 3:6]
@@ -290,10 +319,14 @@ def solve_components(state, accel, params, rho, g, semantics="numba"):
     half = 0.5 * dims
     volume = dims[:, 0] * dims[:, 1] * dims[:, 2]
     rot = _rot_batch(q)
+    if "rotation_f32" in mutate:
+        rot = _f32(rot)
 
     # A2/A3: world keypoints, extent ratio, CoB
     local = _LATTICE_IJK[None, :, :] * half[:, None, :]              # (N,27,3)
     world = np.einsum("nab,nkb->nka", rot, local) + p[:, None, :]     # (N,27,3)
+    if "heights_f32" in mutate:
+        world[:, :, 2] = _f32(world[:, :, 2])
     z = world[:, :, 2]
     z_lo, z_hi = z.min(axis=1), z.max(axis=1)
     height = z_hi - z_lo
@@ -305,22 +338,30 @@ def solve_components(state, accel, params, rho, g, semantics="numba"):
     n_wet = wet.sum(axis=1)
     partial = (z_lo < 0.0) & (z_hi > 0.0) & (n_wet > 0)
     mean_wet = (world * wet[:, :, None]).sum(axis=1) / np.maximum(n_wet, 1)[:, None]
-    cob = np.where(partial[:, None], mean_wet, p)
+    # Warp twin: the mean of the wet points whenever there are any (warp_hydrodynamics.py:58-61), also for a body whose
+    # top keypoint is exactly on the surface; with all 27 wet the mean is the position itself
+    use_mean = (partial | ((n_wet > 0) & (n_wet < 27))) if semantics == "warp" else partial
+    cob = np.where(use_mean[:, None], mean_wet, p)
 
     live = ratio > DRY_EPS
 
     # A5
-    buoy = np.zeros((n, 3))
+    buoy = np.zeros((n, 3), dtype=dtype)
     buoy[:, 2] = rho * (ratio * volume) * g
 
     # A6
     speed = np.linalg.norm(v, axis=1)
     moving = speed > SPEED_EPS
-    vel_dir = np.where(moving[:, None], v / np.where(moving, speed, 1.0)[:, None], 0.0)
+    if "inv_speed_seed" in mutate:
+        inv = _f32(1.0 / _f32(np.where(moving, speed, 1.0)))
+        vel_dir = np.where(moving[:, None], v * inv[:, None], 0.0)
+    else:
+        vel_dir = np.where(moving[:, None], v / np.where(moving, speed, 1.0)[:, None], 0.0)
 
     # A7 (N1 completion when not moving)
-    area = np.zeros(n)
-    weighted = np.zeros((n, 3))
+    area = np.zeros(n, dtype=dtype)
+    weighted = np.zeros((n, 3), dtype=dtype)
+    takes = []
     face_area = np.stack([dims[:, 1] * dims[:, 2], dims[:, 0] * dims[:, 2], dims[:, 0] * dims[:, 1]], axis=1)
     for axis in range(3):
         for sign in (1.0, -1.0):
@@ -328,6 +369,7 @@ def solve_components(state, accel, params, rho, g, semantics="numba"):
             c_w = sign * half[:, axis, None] * rot[:, :, axis] + p
             alignment = -np.einsum("na,na->n", n_w, vel_dir)
             take = moving & (alignment > 0.0) & (c_w[:, 2] < 0.0)
+            takes.append(take)
             a_f = np.where(take, alignment * face_area[:, axis], 0.0)
             area += a_f
             weighted += c_w * a_f[:, None]
@@ -381,19 +423,21 @@ def solve_components(state, accel, params, rho, g, semantics="numba"):
     out["ratio"] = np.where(live, ratio, 0.0)
     out["area"] = np.where(live, area, 0.0)
     out["rest"] = live & ~moving
+    flags = [wet[:, k] for k in range(27)] + [moving, spinning] + takes + [has_area, lift_ok, live, partial]
+    out["branches"] = sum(f.astype(np.int64) << b for b, f in enumerate(flags))
     return out
 
 
-def finite_difference_accel(state, prev, dt):
+def finite_difference_accel(state, prev, dt, dtype=np.float64):
     """A13: a = (v - v_last)/dt, alpha likewise (hydrodynamics_behavior.py:196-202)."""
-    state = np.asarray(state, dtype=np.float64)
-    prev = np.asarray(prev, dtype=np.float64)
+    state = np.asarray(state, dtype=dtype)
+    prev = np.asarray(prev, dtype=dtype)
     return (state[:, 7:13] - prev) / float(dt)
 
 
-def behavior_epilogue(position, comps, mass):
+def behavior_epilogue(position, comps, mass, dtype=np.float64):
     """Vectorised A14-A15 (hydrodynamics_behavior.py:212-226)."""
-    p = np.asarray(position, dtype=np.float64)
+    p = np.asarray(position, dtype=dtype)
     arm_b = comps["center_of_buoyancy"] - p
     arm_p = comps["center_of_pressure"] - p
     net_f = (comps["buoyancy_force"] + comps["drag_force"] + comps["lift_force"]
@@ -402,20 +446,25 @@ def behavior_epilogue(position, comps, mass):
              + np.cross(arm_p, comps["lift_force"]) + comps["drag_torque"]
              + comps["added_mass_torque"])
     f_mag = np.linalg.norm(net_f, axis=1)
-    scale = np.minimum(1.0, np.asarray(mass, dtype=np.float64) * MAX_ACCEL / (f_mag + CLAMP_EPS))
+    scale = np.minimum(1.0, np.asarray(mass, dtype=dtype) * MAX_ACCEL / (f_mag + CLAMP_EPS))
     return net_f * scale[:, None], net_t * scale[:, None], scale
 
 
-def step_wrench(state, prev, params, rho, g, dt, semantics="numba"):
-    """The fused entry point the HIP path implements: A13 + A1-A11 + A14 + A15.
+def step_wrench(state, prev, params, rho, g, dt, semantics="numba", dtype=np.float64):
+    """The fused entry point the HIP path implements: A13 + A1-A11 + A14 + A15, evaluated in `dtype`
+    (see solve_components).
 
-    Returns (net_force (N,3), net_torque (N,3), aux dict)."""
-    state = np.asarray(state, dtype=np.float64)
-    params = np.asarray(params, dtype=np.float64)
-    accel = finite_difference_accel(state, prev, dt)
-    comps = solve_components(state, accel, params, rho, g, semantics)
-    net_f, net_t, scale = behavior_epilogue(state[:, 0:3], comps, params[:, 10])
+    Returns (net_force (N,3), net_torque (N,3), aux dict); aux['branches'] also has BRANCH_CLAMP set where the clamp
+    acts (scale < 1)."""
+    state = np.asarray(state, dtype=dtype)
+    params = np.asarray(params, dtype=dtype)
+    accel = finite_difference_accel(state, prev, dt, dtype)
+    comps = solve_components(state, accel, params, rho, g, semantics, dtype)
+    net_f, net_t, scale = behavior_epilogue(state[:, 0:3], comps, params[:, 10], dtype)
     comps["scale"] = scale
+    net = comps["buoyancy_force"] + comps["drag_force"] + comps["lift_force"] + comps["added_mass_force"]
+    comps["clamp_factor"] = params[:, 10] * MAX_ACCEL / (np.linalg.norm(net, axis=1) + CLAMP_EPS)    # before min(1, .)
+    comps["branches"] = comps["branches"] | ((scale < 1.0).astype(np.int64) << BRANCH_CLAMP)
     return net_f, net_t, comps
 
 
@@ -448,3 +497,84 @@ def wrench_error(net_f, net_t, ref_f, ref_t, params, rho, g):
     e_f = np.linalg.norm(np.asarray(net_f, np.float64) - ref_f, axis=1) / np.maximum(np.linalg.norm(ref_f, axis=1), floor_f)
     e_t = np.linalg.norm(np.asarray(net_t, np.float64) - ref_t, axis=1) / np.maximum(np.linalg.norm(ref_t, axis=1), floor_t)
     return np.maximum(e_f, e_t)
+
+
+# --------------------------------------------------------------------------
+# per-component metric against a high-precision reference (tests/test_wrench_metric.py, tests/test_wrench_ulps_gpu.py)
+# --------------------------------------------------------------------------
+ULP = 2.0 ** -24              # unit roundoff of fp32: a correctly rounded y is within ULP * |y|
+FLT_MIN = float(np.finfo(np.float32).tiny)
+NORM_WEIGHT = 2.0 ** -20
+# Non-clamped bodies: the kernels round each fp64 (1e-14-accurate) sum to fp32 ONCE, |y32 - y| <= ULP |y| <= ULP s_i.
+# The norm part of s_i costs at most 2^-9 of a unit: the bound is 1 + 2^-8 by correct rounding, not a tuned number.
+WRENCH_ULP_BOUND = 1.0 + 2.0 ** -8
+# Clamp-active bodies: hydro_body.h assemble_wrench forms the clamp factor c = m 500 / (|F| + 1e-6) in fp32 and returns
+# fl(c~ * fl(y)).  Relative errors, first order (1 ulp of an fp32 result <= 2^-23 of it = 2 ULP):
+#   |F|^2 rounded to fp32                         ULP -> ULP/2 after the square root
+#   v_sqrt_f32 (1 ulp)                            2 ULP        |F|~ : 2.5 ULP
+#   + 1e-6f: the constant's own rounding (ULP, relative to its share of the sum) and the fp32 add (ULP)
+#                                                  max(2.5, 1) + 1 = 3.5 ULP for the denominator
+#   m * 500 in fp32                               ULP
+#   v_rcp_f32 (1 ulp)                             2 ULP
+#   the product                                   ULP          c~ : 3.5 + 1 + 2 + 1 = 7.5 ULP
+#   fp32 rounding of y, then the product c~ * y   ULP + ULP
+# -> |y_dev - c y| <= 9.5 ULP c |y| <= 9.5 ULP s_i (s_i carries the factor c), plus second-order terms (~1e-13) and the
+# fp64 noise that 2^-8 covers.  fminf(1, .) is 1-Lipschitz, so a factor just above 1 on one side and just below on the
+# other stays inside the same bound.  The host instantiation (libm's correctly rounded sqrt and division: ULP each)
+# obeys 7.5 + 2^-8 by the same count.  Measured maxima over clamp-active bodies: host 4.07 (tests/test_wrench_metric.py),
+# MI355X 4.44 (tests/test_wrench_ulps_gpu.py, every wrench entry); non-clamped: host 0.9972, MI355X 0.9972.
+CLAMP_ULP_BOUND = 9.5 + 2.0 ** -8
+
+
+def _abs_cross(a, f):
+    """Component-wise |a x f| bound: (|a_y f_z| + |a_z f_y|, ...)."""
+    a, f = np.abs(a), np.abs(f)
+    return np.stack([a[:, 1] * f[:, 2] + a[:, 2] * f[:, 1], a[:, 2] * f[:, 0] + a[:, 0] * f[:, 2],
+                     a[:, 0] * f[:, 1] + a[:, 1] * f[:, 0]], axis=1)
+
+
+def wrench_scales(position, comps):
+    """(s_force, s_torque), each (N,3): per component the sum of the magnitudes of the terms that form it, plus
+    NORM_WEIGHT times the sum of the terms' norms, times the clamp scale.  Force terms: buoyancy, drag, lift, added
+    mass.  Torque terms: the three lever-arm torques (as |a| x |F| component-wise, norm |a| |F|), drag torque, added-mass
+    torque.  The norm part absorbs the ~1e-16 |F| residue of the rotation in components that are zero by symmetry."""
+    p = np.asarray(position, dtype=comps["buoyancy_force"].dtype)
+    nrm = lambda x: np.linalg.norm(x, axis=1)
+    f_terms = [comps[k] for k in ("buoyancy_force", "drag_force", "lift_force", "added_mass_force")]
+    s_f = sum(np.abs(x) for x in f_terms) + (NORM_WEIGHT * sum(nrm(x) for x in f_terms))[:, None]
+    arms = [(comps["center_of_buoyancy"] - p, comps["buoyancy_force"]), (comps["center_of_pressure"] - p, comps["drag_force"]),
+            (comps["center_of_pressure"] - p, comps["lift_force"])]
+    s_t = (sum(_abs_cross(a, f) for a, f in arms) + np.abs(comps["drag_torque"]) + np.abs(comps["added_mass_torque"])
+           + (NORM_WEIGHT * (sum(nrm(a) * nrm(f) for a, f in arms) + nrm(comps["drag_torque"])
+                             + nrm(comps["added_mass_torque"])))[:, None])
+    scale = comps["scale"][:, None]
+    return s_f * scale, s_t * scale
+
+
+def _component_ulps(got, ref, s):
+    got = np.asarray(got, dtype=ref.dtype)
+    d = np.abs(got - ref)
+    # The device may flush fp32 denormals: a reference component below FLT_MIN is held to an absolute FLT_MIN.
+    d = np.where(np.abs(ref) < FLT_MIN, np.maximum(d - FLT_MIN, 0.0), d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.where(d == 0, 0.0, d / (ULP * s))              # s = 0 (no term at all): only an exact 0 passes
+    return np.nan_to_num(e.astype(np.float64), nan=np.inf, posinf=np.inf).max(axis=1)
+
+
+def wrench_error_ulps(got_f, got_t, ref, position):
+    """Per-body worst force component and worst torque component of a device wrench, in units of ULP * s_i
+    (wrench_scales).  `ref` = (net_force, net_torque, aux) from `step_wrench(..., dtype=np.longdouble)`, `position` the
+    (N,3) positions it was evaluated at.  Returns {'force': (N,), 'torque': (N,), 'clamped': (N,) bool}.
+    Bounds: WRENCH_ULP_BOUND where the clamp does not act, CLAMP_ULP_BOUND where it does.  'clamped' is scale < 1, and
+    also a factor below 1 + 2^-20: the kernels' fp32 factor (7.5 ULP, see CLAMP_ULP_BOUND) can fall below 1 there."""
+    ref_f, ref_t, comps = ref
+    s_f, s_t = wrench_scales(position, comps)
+    return {"force": _component_ulps(got_f, ref_f, s_f), "torque": _component_ulps(got_t, ref_t, s_t),
+            "clamped": np.asarray(comps["clamp_factor"] < 1.0 + 2.0 ** -20)}
+
+
+def branch_flips(aux_a, aux_b):
+    """Bodies on which two evaluations (fp64 and longdouble) took a different decision (BRANCH_NAMES), and the names of
+    the decisions that differ, as {body index: [names]}."""
+    diff = np.asarray(aux_a["branches"]) ^ np.asarray(aux_b["branches"])
+    return {int(i): [nm for b, nm in enumerate(BRANCH_NAMES) if (int(diff[i]) >> b) & 1] for i in np.nonzero(diff)[0]}

@@ -58,6 +58,38 @@ def test_oracle_warp_dry_body_centres():
     assert np.array_equal(wp[6], p) and np.array_equal(wp[7], p)
 
 
+def test_oracle_warp_cob_when_the_top_keypoint_is_on_the_surface():
+    """No keypoint above the surface, the top nine exactly on it (z = 0 is not wet): Numba returns cob = position
+    ("fully in by bounds", numba_hydrodynamics.py:87-88); the Warp twin has no such return and averages the 18 wet
+    points (warp_hydrodynamics.py:58-61): cob_z = p_z - 0.25 for a unit cube.  Scalar and vectorised oracle alike."""
+    params = np.array([1.0, 1.0, 1.0, 1.2, 0.8, 300.0, 150.0, 1.0, 0.05, 0.02, 500.0])
+    p = np.array([2.0, -1.0, -0.5])
+    args = (p, np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(3), params, 1025.0, 9.81)
+    nb = ho.solve_components_one(*args)
+    wp = ho.solve_components_one(*args, semantics="warp")
+    assert nb[8] == wp[8] == 1.0
+    assert np.array_equal(nb[6], p) and np.array_equal(wp[6], [2.0, -1.0, -0.75])
+    st = np.concatenate([p, args[1], np.zeros(6)])[None, :]
+    for sem, cob in (("numba", p), ("warp", [2.0, -1.0, -0.75])):
+        c = ho.solve_components(st, np.zeros((1, 6)), params[None, :], 1025.0, 9.81, semantics=sem)
+        assert np.array_equal(c["center_of_buoyancy"][0], cob) and np.array_equal(c["center_of_pressure"][0], cob)
+    # fully submerged with all 27 points wet: the mean IS the position, in both
+    deep = ho.solve_components(st - np.eye(13)[2], np.zeros((1, 6)), params[None, :], 1025.0, 9.81, semantics="warp")
+    assert np.array_equal(deep["center_of_buoyancy"][0], p - [0.0, 0.0, 1.0])
+
+
+@pytest.mark.parametrize("name", ["ties"])
+def test_host_arithmetic_warp_mode_on_exact_ties(name, emul):
+    """The host instantiation and the Warp oracle agree on the quantised bodies, whose top keypoints sit exactly on the
+    surface.  Before the oracle's Warp CoB followed warp_hydrodynamics.py:58-61 there, their torques differed by up to
+    ~100 % (the CoB lever arm); tests/test_wrench_metric.py found it."""
+    fx = load_golden(name)
+    rho, g, dt = float(fx["rho"]), float(fx["g"]), float(fx["dt"])
+    f, t = emul(fx["state"], fx["prev"], fx["params"], rho, g, dt, warp=True)
+    rf, rt, _ = ho.step_wrench(fx["state"], fx["prev"], fx["params"], rho, g, dt, semantics="warp")
+    assert ho.wrench_error(f, t, rf, rt, fx["params"], rho, g).max() <= GATE
+
+
 def test_oracle_warp_scalar_equals_vectorised():
     fx = load_golden("c4")
     st, pr = fx["state"].astype(np.float64), fx["params"].astype(np.float64)
