@@ -8,18 +8,22 @@
 One "step" = one launch of `hydro_step_wrench_tiled` over every body of one scene replica on this rank's GPU:
 finite-difference acceleration + nine-component model + lever arms + sum + clamp.  Inputs are resident
 in HBM before the timed region.  Bodies shard embarrassingly: every rank owns its own replica(s) (weak scaling), no
-data-path collective; the one RCCL call is the global kinetic-energy all-reduce after the timed loop.
+data-path collective; with --full, the global kinetic-energy all-reduce after the timed loop is the one RCCL call of the data.
 
 Workload (default `c5` = BASELINE.json configs[4]): 1 048 576 synthetic bodies per GPU, fp32 state, 7 coefficients
 stored fp16, fp64 arithmetic rounded to fp32 once, 130 algorithmic bytes per body-step; `--scenes` (default 4)
 replicas are stepped round-robin so that the bytes between two uses of a line exceed the 256 MiB Infinity Cache.
 
-Prints ONE JSON line on rank 0, at most LINE_LIMIT (8 192) bytes: the contract fields, `roofline`, `cpu_baseline`,
-`roofline_4m`, `configs` (C2 / C3 / C4-shard / C4, eager and graph), `box` (which bound binds on this box, clock held)
-and, for N > 1, `per_rank` and `c4_strong` (BASELINE configs[3] as stated, kinetic energy sampled inside the region).
-Everything else (scripts/bench_extras.py) goes to the side file `--extras-out` (default bench_extras.json beside this
-file) and to stderr.  `python bench.py --explain` says what every field means; no prose travels on the line.
-Exit code: 0; 3 when the N > 1 leg raised or hung (the line, with "ok": false, is out before the exit).
+Prints ONE JSON line on rank 0, at most LINE_LIMIT (8 192) bytes.  A plain run does what the headline needs and no more:
+it sets up, spins up, warms up, times the K steps, writes --dump-outputs and prints the contract fields, `config`,
+`roofline` (of the timed steps) and, for N > 1, `per_rank`; `cpu_baseline` is null.  `--full` adds every other
+measurement and check: `cpu_baseline` (the CPU port, also the checker of the GPU result), the live `roofline.traffic`, the
+median of 5, `roofline_4m`, `configs` (C2 / C3 / C4-shard / C4, eager and graph), `box` (which bound binds on this box,
+clock held), the kinetic energy checked against a float64 host sum and, for N > 1, `c4_strong` (BASELINE configs[3] as
+stated, kinetic energy sampled inside the region).  Everything else of a --full run (scripts/bench_extras.py) goes to the
+side file `--extras-out` (default bench_extras.json beside this file) and to stderr.  `python bench.py --explain` says
+what every field means; no prose travels on the line.
+Exit code: 0; 3 when the N > 1 leg of a --full run raised or hung (the line, with "ok": false, is out before the exit).
 """
 from __future__ import annotations
 
@@ -457,16 +461,19 @@ def main():
     ap.add_argument("--workload", default="c5", choices=sorted(WORKLOADS))
     ap.add_argument("--bodies", type=int, default=0, help="bodies per GPU (default: the workload's)")
     ap.add_argument("--scenes", type=int, default=4, help="scene replicas stepped round-robin per GPU")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip scripts/bench_extras.py (side file) and the `box` block")
-    ap.add_argument("--extras-out", default=os.path.join(REPO, "bench_extras.json"), help="side file: the full-precision line + the secondary measurements")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (C2 / C3 / C4, eager and graph)")
-    ap.add_argument("--no-roofline-4m", action="store_true", help="skip the 4 194 304-body second roofline object (N=1 default run)")
-    ap.add_argument("--no-strong-leg", action="store_true", help="N>1: skip the configs[3] strong-scaling leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (CPU baseline, other sizes and configs, live traffic, "
+                         "median of 5, kinetic-energy check, the N>1 configs[3] leg, side file); the options marked --full narrow it")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip scripts/bench_extras.py (side file) and the `box` block")
+    ap.add_argument("--extras-out", default=os.path.join(REPO, "bench_extras.json"), help="--full: side file: the full-precision line + the secondary measurements")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the `configs` block (C2 / C3 / C4, eager and graph)")
+    ap.add_argument("--no-roofline-4m", action="store_true", help="--full: skip the 4 194 304-body second roofline object (N=1 default workload)")
+    ap.add_argument("--no-strong-leg", action="store_true", help="--full, N>1: skip the configs[3] strong-scaling leg")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic with rocprofv3 child runs (N=1 default workload); use profiles/traffic.json")
+                    help="--full: do not measure roofline.traffic with rocprofv3 child runs (N=1 default workload); use profiles/traffic.json")
     ap.add_argument("--extras-budget-seconds", type=float, default=200.0,
-                    help="secondary measurements are skipped once this much time has gone into them")
+                    help="--full: secondary measurements are skipped once this much time has gone into them")
     ap.add_argument("--bodies-per-lane", type=int, default=0)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every GPU gets the workload's bodies (default); strong: the workload's bodies are block-partitioned over the GPUs")
@@ -482,6 +489,9 @@ def main():
 
     if args.dump_outputs and args.steps < 1:
         ap.error("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
+    if not args.full:             # a plain run is the headline alone: every leg after the timed steps is off
+        args.cpu_seconds = 0.0
+        args.no_extras = args.no_configs = args.no_roofline_4m = args.no_strong_leg = args.no_live_traffic = True
     if args.explain:
         from scripts.bench_extras import FIELD_NOTES
         print(FIELD_NOTES)
@@ -557,19 +567,23 @@ def main():
     # ONE clock for `value` and `roofline.frac`: algorithmic bytes per launch / (timed interval / K)
     achieved = sc.n * bpb / (step_us * 1e-6) / 1e9
 
-    # the one collective of the path: global kinetic energy (every rank reduces its shard on device) ...
-    with torch.cuda.stream(stream):
-        ke = replicas[0].kinetic_energy()
-    stream.synchronize()
-    ke = ke.to(hd.collective_device(dev))
-    t0 = time.perf_counter()
-    hd.global_kinetic_energy(ke)
-    torch.cuda.synchronize(dev)
-    ke_us = (time.perf_counter() - t0) * 1e6
-    # ... checked against float64 host sums gathered exactly (nothing of the reference value went through the all-reduce)
-    host_ke = hd.gather_rows(scenes.kinetic_energy_fp64(sc.state, sc.params, rotational=True), dev)
-    host_ke = [math.fsum(host_ke[:, k].tolist()) for k in range(2)]
-    ke_rel_err = max(abs(float(ke[k]) - host_ke[k]) / host_ke[k] for k in range(2))
+    ke_check = {}
+    if args.full:
+        # the one collective of the path: global kinetic energy (every rank reduces its shard on device) ...
+        with torch.cuda.stream(stream):
+            ke = replicas[0].kinetic_energy()
+        stream.synchronize()
+        ke = ke.to(hd.collective_device(dev))
+        t0 = time.perf_counter()
+        hd.global_kinetic_energy(ke)
+        torch.cuda.synchronize(dev)
+        ke_us = (time.perf_counter() - t0) * 1e6
+        # ... checked against float64 host sums gathered exactly (nothing of the reference value went through the all-reduce)
+        host_ke = hd.gather_rows(scenes.kinetic_energy_fp64(sc.state, sc.params, rotational=True), dev)
+        host_ke = [math.fsum(host_ke[:, k].tolist()) for k in range(2)]
+        ke_rel_err = max(abs(float(ke[k]) - host_ke[k]) / host_ke[k] for k in range(2))
+        ke_check = {"global_ke_J": [float(x) for x in ke.cpu().tolist()], "host_fp64_ke_J": host_ke,
+                    "ke_rel_err": ke_rel_err, "ke_allreduce_us": ke_us}
 
     out, traffic = None, None
     if rank == 0:
@@ -599,9 +613,7 @@ def main():
                          **residency(sc.n, coeff, args.scenes)},
             "max_rel_err": None,
             "collective": {"backend": (f"{'nccl (RCCL)' if on_gpu else 'gloo'}" if multi else "none"), "ranks": live_ranks,
-                           "rccl_ranks": live_ranks if multi and on_gpu else 0, "barrier": hd.barrier_kind(),
-                           "global_ke_J": [float(x) for x in ke.cpu().tolist()], "host_fp64_ke_J": host_ke,
-                           "ke_rel_err": ke_rel_err, "ke_allreduce_us": ke_us},
+                           "rccl_ranks": live_ranks if multi and on_gpu else 0, "barrier": hd.barrier_kind(), **ke_check},
         }
         if per_rank is not None:
             out["per_rank"] = {"step_us": [float(x) for x in per_rank[:, 0]], "kernel_us": [float(x) for x in per_rank[:, 1]]}

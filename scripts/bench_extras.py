@@ -5,7 +5,7 @@ bench.py prints ONE compact JSON line (<= 8 192 bytes: the driver must be able t
 line as `extras` - bound probes, clocks, two streams, several scenes per launch, the array-of-structs entry, the plugin
 surface, the closed loop with its VALU-issue rooflines - is measured here and written to a side file
 (`bench.py --extras-out PATH`, default bench_extras.json beside bench.py, echoed to stderr).  `run()` is called by
-bench.py on rank 0 of an N = 1 run under --extras-budget-seconds; every leg is also callable by itself
+bench.py on rank 0 of an N = 1 --full run under --extras-budget-seconds; every leg is also callable by itself
 (tests/test_bench_gpu.py, scripts/run_aux.py).  What the fields mean: FIELD_NOTES below (`python bench.py --explain`)
 and DESIGN.md section 6 - no explanatory text travels in the JSON.
 """
@@ -28,6 +28,10 @@ THROTTLE_RATIO = 1.15
 FIELD_NOTES = """\
 bench.py - what the fields of the JSON line and of the side file mean
 =====================================================================
+a plain run             without --full: the contract fields, config, roofline (of the timed steps; traffic from
+                        profiles/traffic.json), collective (no kinetic energy) and, N > 1, per_rank; cpu_baseline and
+                        max_rel_err are null.  frac_median_of_5, live traffic, roofline_4m, the CPU leg, configs, box, the
+                        kinetic-energy check, c4_strong and the side file come from --full runs.
 value, ms_per_step      whole-job body-steps/s and the wall interval per step: wall time between the barrier + synchronize
                         pairs around EXACTLY --steps launches, max over ranks.  Inputs resident in HBM before the region.
 roofline.frac           algorithmic bytes per launch (130 B x bodies, fp16 coefficients; 144 with fp32) / ms_per_step / 8 TB/s.

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -12,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_contract(native_built):
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
            "--bodies", "65536", "--cpu-seconds", "1", "--no-extras"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -58,12 +59,12 @@ def _leaves(x):
         yield x
 
 
-def test_default_run_writes_the_side_file_and_a_short_line(native_built, tmp_path):
-    """The driver's own command shape (`--gpus 1 --steps 20 --warmup 5`, nothing else), with the secondary measurements on a
+def test_full_run_writes_the_side_file_and_a_short_line(native_built, tmp_path):
+    """The driver's --full command shape (`--gpus 1 --steps 20 --warmup 5 --full`), with the secondary measurements on a
     short budget: ONE line of at most 8 192 bytes on stdout carrying `roofline`, `cpu_baseline`, `roofline_4m`, `configs` and
     `box`; the extras in the side file and on stderr, not on the line."""
     side = tmp_path / "extras.json"
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "2",
            "--extras-out", str(side), "--extras-budget-seconds", "25", "--no-live-traffic"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -79,6 +80,34 @@ def test_default_run_writes_the_side_file_and_a_short_line(native_built, tmp_pat
     payload = json.loads(side.read_text())
     assert payload["line"]["value"] == d["value"] and "bound_probes_1m" in payload["extras"] and "clocks_1m" in payload["extras"]
     assert "bench.py: side file (extras):" in res.stderr
+
+
+def test_plain_run_is_the_headline_alone(native_built):
+    """The driver's plain command (`--gpus 1 --steps 20 --warmup 5`, nothing else): set-up, spin-up, warm-up, the timed steps
+    and ONE line with the contract fields and `roofline` of those steps - no CPU leg, no other size or configuration, no
+    kinetic-energy check, no side file.  From process start to exit it spends at most 30 s outside its steps."""
+    t0 = time.monotonic()
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                         capture_output=True, text=True, timeout=600)
+    took = time.monotonic() - t0
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and len(lines[0].encode()) <= 8192
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["metric"] == "body-steps/sec" and d["unit"] == "body-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["ok"] is True
+    assert d["config"]["baseline_config"] == "configs[4]" and d["config"]["bodies_per_gpu"] == 1048576
+    assert d["value"] == pytest.approx(1048576 / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    r = d["roofline"]
+    assert r["resident"] == "hbm" and 0.3 < r["frac"] <= 1.0 and r["kernel_us"] <= r["step_us"] * 1.0001
+    assert r["traffic_measured"] == "committed" and "kernel_us_median_of_5" not in r
+    assert d["cpu_baseline"] is None and d["max_rel_err"] is None and "ke_rel_err" not in d["collective"]
+    assert not {"roofline_4m", "configs", "box", "extras_file", "c4_strong", "dropped_for_size"} & set(d)
+    assert "bench.py: side file (extras):" not in res.stderr
+    assert took - (20 + 5) * d["ms_per_step"] * 1e-3 <= 30.0, took
 
 
 def _two_rank_run(steps, warmup, extra=()):
@@ -98,13 +127,13 @@ def _two_rank_run(steps, warmup, extra=()):
 
 
 def test_bench_two_ranks_share_the_gpu(native_built):
-    """The driver's N>1 launch (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N --steps 20 --warmup 5`)
-    rehearsed with two ranks on this box's one GPU (gloo for the collectives, HYDRO_BENCH_SHARE_GPU=1): one JSON line from
+    """The driver's N>1 --full launch (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N --steps 20 --warmup 5
+    --full`) rehearsed with two ranks on this box's one GPU (gloo for the collectives, HYDRO_BENCH_SHARE_GPU=1): one JSON line from
     rank 0, whole-job aggregate over both ranks, no CPU leg - and the run PROVES SURVEY.md 8e by itself: the kinetic energy
     is sampled at least twice inside the 20 timed steps through the asynchronous monitor, the global value equals a
     float64 host sum over all bodies to 1e-12, every shard's wrench has the bits of the unsharded scene, and the number of
     ranks is the one the live group's all-reduce counted."""
-    d = _two_rank_run(20, 5)
+    d = _two_rank_run(20, 5, extra=("--full",))
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["cpu_baseline"] is None and d["steps"] == 20 and d["warmup"] == 5
     assert d["config"]["bodies_per_gpu"] == 65536 and "x2" in d["config"]["sharding"]
     assert d["value"] == pytest.approx(2 * 65536 * 20 / (d["ms_per_step"] * 1e-3 * 20), rel=1e-6)
@@ -134,9 +163,19 @@ def test_bench_two_ranks_share_the_gpu(native_built):
     assert ke["host_fp64_J"][0] == pytest.approx(lin, rel=1e-11) and ke["global_J"][0] == pytest.approx(lin, rel=1e-11)      # (12 digits on the line)
 
 
+def test_plain_two_rank_run_is_the_headline_alone(native_built):
+    """The plain N>1 command, rehearsed with two ranks sharing the GPU over gloo: the whole-job headline and `per_rank` of the
+    timed steps; no configs[3] leg, no CPU leg, no kinetic-energy check."""
+    d = _two_rank_run(20, 5)
+    assert d["n_gpus"] == 2 and d["ok"] is True and d["collective"]["ranks"] == 2 and "x2" in d["config"]["sharding"]
+    assert d["value"] == pytest.approx(2 * 65536 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    assert len(d["per_rank"]["step_us"]) == 2 and max(d["per_rank"]["step_us"]) <= d["ms_per_step"] * 1e3 * 1.0001
+    assert "c4_strong" not in d and d["cpu_baseline"] is None and "ke_rel_err" not in d["collective"]
+
+
 def test_bench_two_ranks_long_region_keeps_the_256_step_cadence(native_built):
     """600 timed steps: one sample per 256 steps (two in the region), 64-step graph replays, same self-checks."""
-    cs = _two_rank_run(600, 8)["c4_strong"]
+    cs = _two_rank_run(600, 8, extra=("--full",))["c4_strong"]
     ke = cs["ke"]
     assert ke["every_steps"] == 256 and ke["samples"] == 2 and ke["last_step"] == 512 and cs["graph_steps"] == 64
     assert ke["rel_err"] <= 1e-12 and cs["shards_bit_identical"] is True
@@ -149,7 +188,7 @@ def test_bench_gpus_2_launches_its_own_ranks(native_built):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HYDRO_BENCH_SHARE_GPU="1", HYDRO_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "8", "--bodies", "65536",
-           "--spinup-seconds", "0.2"]
+           "--spinup-seconds", "0.2", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -216,7 +255,7 @@ def test_bench_four_ranks_share_the_gpu(native_built):
     env = dict(os.environ, HYDRO_BENCH_SHARE_GPU="1", HYDRO_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "4", "--steps", "20", "--warmup", "5",
-           "--bodies", "32768", "--spinup-seconds", "0.1"]
+           "--bodies", "32768", "--spinup-seconds", "0.1", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.strip()][0])
@@ -234,7 +273,8 @@ def _faulty_run(fault, via_torchrun=True, strong_timeout="8", teardown_timeout="
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HYDRO_BENCH_SHARE_GPU="1", HYDRO_DIST_BACKEND="gloo", HYDRO_BENCH_STRONG_FAULT=fault, HYDRO_BENCH_STRONG_TIMEOUT=strong_timeout,
                HYDRO_BENCH_TEARDOWN_TIMEOUT=teardown_timeout)
-    tail = [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--bodies", "65536", "--spinup-seconds", "0.1"]
+    tail = [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--bodies", "65536", "--spinup-seconds", "0.1",
+            "--full"]
     if via_torchrun:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port)] + tail
@@ -298,7 +338,7 @@ def test_bench_through_the_array_of_structs_entry(native_built):
     """`--layout aos` (what scripts/profile_aos.sh profiles): the simulator-facing entry as the bench workload - 168 algorithmic bytes
     per body-step, all of them real traffic, eight or more rotating sets so that no rows stay in the Infinity Cache."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--layout", "aos", "--workload", "c5-f32",
-           "--bodies", "65536", "--cpu-seconds", "1", "--no-extras", "--no-configs"]
+           "--bodies", "65536", "--full", "--cpu-seconds", "1", "--no-extras", "--no-configs"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.strip()][0])
@@ -316,7 +356,7 @@ def test_bench_through_the_array_of_structs_entry(native_built):
 ])
 def test_bench_other_workloads_and_layouts(native_built, flags, entry, n):
     """Every workload / layout the bench offers still produces a checked line (the CPU leg is the checker: gate 1e-5)."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0.5",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0.5",
            "--no-extras", "--no-configs", "--spinup-seconds", "0.1"] + flags
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -328,7 +368,7 @@ def test_bench_other_workloads_and_layouts(native_built, flags, entry, n):
 
 def test_bench_strong_scaling_flag_two_ranks(native_built):
     """`--scaling strong`: the workload's bodies block-partitioned over the ranks (two, sharing the GPU over gloo)."""
-    d = _two_rank_run(20, 5, extra=("--scaling", "strong", "--no-strong-leg"))
+    d = _two_rank_run(20, 5, extra=("--full", "--scaling", "strong", "--no-strong-leg"))
     assert d["scaling"] == "strong" and d["config"]["bodies_per_gpu"] == 32768 and "strong scaling: 65536 bodies over 2 GPUs" in d["config"]["workload"]
     assert d["value"] == pytest.approx(65536 / (d["ms_per_step"] * 1e-3), rel=1e-6) and "c4_strong" not in d
     assert d["collective"]["ke_rel_err"] <= 1e-12

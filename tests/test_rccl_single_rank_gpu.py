@@ -67,7 +67,7 @@ def _bench_over_rccl(steps, warmup):
     env = dict(os.environ, HYDRO_DIST_ALWAYS="1", HYDRO_BENCH_FORCE_GROUP="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--bodies", "65536",
-           "--spinup-seconds", "0.1", "--cpu-seconds", "0", "--no-extras"]
+           "--spinup-seconds", "0.1", "--full", "--cpu-seconds", "0", "--no-extras"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     return json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
