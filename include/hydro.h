@@ -47,7 +47,9 @@ extern "C" {
  *        finish leaves NaNs, never a stale pair; hydro_step_wrench validates before it allocates
  * 0.7.1: hydro_debug_ke_fault is refused unless HYDRO_ENABLE_TEST_HOOKS=1 at load time; the class finishers of the
  *        kinetic-energy reduction poison the partials they consumed; re-arming happens after the cross-stream wait and
- *        never inside a stream capture */
+ *        never inside a stream capture
+ *        added to 0.7.1 (no existing entry changed): hydro_set_watch, hydro_watch_count, hydro_step_fused_tiled_multi_rec - a
+ *        trajectory recorder inside the multi-step kernel (watched bodies' states, every `every`-th step, to a device log) */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -64,6 +66,7 @@ extern "C" {
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
+#define HYDRO_WATCH_MAX  65536   /* bodies in one watch list (hydro_set_watch) */
 
 typedef struct hydro_engine hydro_t;
 
@@ -326,7 +329,8 @@ int hydro_step_fused_tiled_ke(hydro_t *h, int64_t n, const float *state, int64_t
  * the state after the last step and `prev_out` (6 fields, tiled) the velocity of the step before it, i.e. what the next
  * call needs as `prev`.  Same arithmetic in the same order, hence the same bits, as `steps` calls of
  * hydro_step_fused_tiled - with (120 + 76) / steps bytes of traffic per body-step instead of 172 and one launch
- * instead of `steps` (intermediate states never exist in memory: sample, log or couple at multiples of `steps`).
+ * instead of `steps` (intermediate states never exist in memory: sample, log or couple at multiples of `steps` - or
+ * record the bodies you want to see from inside the launch, hydro_step_fused_tiled_multi_rec below).
  * Aliasing: `state_out` may alias the buffer `prev` points into, `prev_out` may alias `state` + 7 * 64 (the velocity
  * fields of the state being read) - with both, the two-buffer ping-pong of the single-step entry carries over unchanged;
  * `state_out` must not alias `state`.  ke_out_dev != NULL: also sample the kinetic energy of the final state (two doubles
@@ -337,6 +341,45 @@ int hydro_step_fused_tiled_multi(hydro_t *h, int64_t n, const float *state, int6
                                  float *state_out, int64_t out_tile_stride,
                                  float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
                                  int rotational, double *ke_out_dev, void *stream);
+
+/* Trajectory recorder: the states BETWEEN the first and the last step of a multi-step launch exist in registers only, so
+ * a short list of WATCHED bodies is written to a device log from inside the kernel, every `every`-th step - the device-side
+ * counterpart of the reference's one validation artefact, the per-frame pose / velocity rows of log_velocity.py:29-57.
+ *
+ * hydro_set_watch: `bodies_host` (HOST memory) holds `count` strictly ascending body indices in [0, capacity),
+ * 1 <= count <= HYDRO_WATCH_MAX; body bodies_host[j] records into COLUMN j of the log.  Builds the engine's watch tables
+ * (12 B per tile of the capacity, allocated by the first call, freed by hydro_destroy) on the engine's private stream and
+ * waits for them, like hydro_set_params_*: the caller orders it after recording launches of this engine still in flight on
+ * other streams.  count == 0 or bodies_host == NULL clears the list.  HYDRO_E_ARG for a count above the maximum, an index
+ * out of range, an unsorted list or a duplicate - the previous list stays in force.  hydro_watch_count: bodies on the
+ * list, 0 without one.
+ *
+ * hydro_step_fused_tiled_multi_rec: hydro_step_fused_tiled_multi - same arguments, same aliasing rules, the same state,
+ * prev_out and kinetic-energy bits - that also records.  With k = 1 .. steps the steps of this launch, a sample is taken
+ * AFTER step k when k >= phase and (k - phase) % every == 0, into row row0 + (k - phase) / every:
+ *     log[(row * fields + f) * log_stride + j]      j = column of the watched body, log_stride >= hydro_watch_count
+ * i.e. a (rows_capacity, fields, log_stride) float array in device memory.  fields = 13: f is the field of `state` after
+ * that step; fields = 19: followed by the six fields of the `wrench` that produced it (the wrench of the state BEFORE the
+ * step).  Rows are bit for bit what hydro_step_fused_tiled leaves in memory at that step.  The caller derives phase
+ * (1 .. every) and row0 from its own step count, so launches need not be multiples of `every`; phase > steps is legal and
+ * records nothing.  *rows_written_host (may be NULL) receives the number of rows this launch writes.  Elements of the log
+ * that belong to no (row, field, column) written are not touched.
+ * Cost: two scalar loads per wavefront and launch, one scalar compare per step; 13 or 19 dword stores per watched body and
+ * sample.  Bodies that are not watched move no extra byte.
+ * HYDRO_E_STATE without a watch list.  HYDRO_E_ARG for every < 1 (or > 2^30), phase outside 1 .. every, fields other than
+ * 13 / 19, log_stride < the watch count, a watched body >= n, a row at or beyond rows_capacity (< 2^31), besides what
+ * hydro_step_fused_tiled_multi refuses - all before anything is launched or written.  Asynchronous, no allocation, no
+ * synchronisation, safe to capture (a captured launch replays with the row0 it was captured with).
+ * New functionality: the reference logs through one host round trip per row. */
+int     hydro_set_watch(hydro_t *h, int64_t count, const int64_t *bodies_host);
+int64_t hydro_watch_count(const hydro_t *h);
+int hydro_step_fused_tiled_multi_rec(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -40,6 +40,10 @@ KERNELS = {
         ("step_fused_multi_tiled_kernelILb0ELb0ELb0ELb0ELb0E", True),
     "resident closed loop, one step, implicit drag (step_fused_multi_tiled_kernel<f32, temporal, implicit, no KE, Numba>)":
         ("step_fused_multi_tiled_kernelILb0ELb0ELb1ELb0ELb0E", True),
+    # the same loop with the trajectory recorder in it (hydro_step_fused_tiled_multi_rec): what a step costs with a recorder
+    # attached - the scalar compare every wave pays, and the sampling block only a wave with a watched body enters
+    "resident closed loop with recorder, one step (step_fused_multi_rec_tiled_kernel<f32 parameters, temporal, explicit, no KE, Numba>)":
+        ("step_fused_multi_rec_tiled_kernelILb0ELb0ELb0ELb0ELb0E", True),
     "headline wrench (wrench_tiled_kernel<256, fp16 coefficients, caller's previous velocity, streaming, no KE, Numba>)":
         ("wrench_tiled_kernelILi256ELb1ELb0ELb1ELb0ELb0E", False),
 }

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhydro.so")
 STATE_FIELDS, PREV_FIELDS, PARAM_FIELDS, WRENCH_FIELDS, COMP_FIELDS = 13, 6, 11, 6, 24
 TILE = 64
 BATCH_MAX = 32
+WATCH_MAX = 65536
 
 
 class Scene(ctypes.Structure):
@@ -62,6 +63,11 @@ SIGNATURES = {
                                           c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "hydro_step_fused_tiled_multi": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
                                              c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "hydro_set_watch": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "hydro_watch_count": (c_int64, [c_void_p]),
+    "hydro_step_fused_tiled_multi_rec": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64), c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -32,6 +32,7 @@
 
 #include "../../include/hydro.h"
 #include "hydro_body.h"
+#include "hydro_watch.h"
 
 // The tiled wrench kernel is built for AT MOST 4 waves per SIMD.  After the instruction diet of round 3 two of its
 // instantiations need only 95 VGPRs and would run 5 waves per SIMD; interleaved A/B on three boxes:
@@ -1138,6 +1139,22 @@ __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k
     if constexpr (KE) ke_block_reduce(ke_lin, ke_rot, ke_partials, ke_stride, ke_out);
 }
 
+// One closed-loop step of a body held in registers - the loop body of the two multi-step kernels below: the wrench of
+// (s, pv), the integrator, then pv <- the velocity just used and s <- the new state.  f6 is the wrench that produced the new s.
+template <bool IMPLICIT, bool WARP>
+__device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], const float (&d)[3], const float (&c)[7], float mass,
+                                                        double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS])
+{
+    const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
+    f6[0] = w.fx; f6[1] = w.fy; f6[2] = w.fz; f6[3] = w.tx; f6[4] = w.ty; f6[5] = w.tz;
+    float o[HYDRO_STATE_FIELDS];
+    integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
+#pragma unroll
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = s[7 + f];
+#pragma unroll
+    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = o[f];
+}
+
 // --------------------------------------------------------------------------
 // `steps` closed-loop steps in ONE pass: no term of the model couples two bodies, so a lane can carry its body through any
 // number of steps in registers - state, previous velocity and the 11 parameters are read once, the state after the last
@@ -1167,14 +1184,76 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
         load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
-            const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
-            const float f6[HYDRO_WRENCH_FIELDS] = {w.fx, w.fy, w.fz, w.tx, w.ty, w.tz};
-            float o[HYDRO_STATE_FIELDS];
-            integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
+            float f6[HYDRO_WRENCH_FIELDS];
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6);
+        }
+        if constexpr (KE)
+            hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
+                                  ke_rotational != 0, ke_lin, ke_rot);
+        float* pvo = k_pvo + (size_t)tile * pvo_stride;
 #pragma unroll
-            for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = s[7 + f];
+        for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg<NT>(at<float>(pvo, lane4, f * 256u), pv[f]);
+        float* so = k_so + (size_t)tile * so_stride;
 #pragma unroll
-            for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = o[f];
+        for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) stg<NT>(at<float>(so, lane4, f * 256u), s[f]);
+    }
+    if constexpr (KE) ke_block_reduce(ke_lin, ke_rot, ke_partials, ke_stride, ke_out);
+}
+
+// --------------------------------------------------------------------------
+// The same kernel with a TRAJECTORY RECORDER in its loop (hydro_step_fused_tiled_multi_rec): the states between the first
+// and the last step of a launch exist in registers only, so the bodies on the engine's watch list are written to a device
+// log from inside the loop.  Everything the recorder decides on is wave-uniform:
+//   w_mask / w_first : the watch tables of hydro_set_watch (hydro_watch.h), one entry per tile = per wavefront: which lanes
+//                      are watched and the log column of the first of them; two scalar loads per wave and LAUNCH.  A
+//                      watched lane's column is w_first[tile] + popcount(w_mask[tile] & lanes below it) - v_mbcnt
+//   cadence          : a sample is due after local step k (1-based) when k >= phase and (k - phase) % every == 0, at row
+//                      row0 + (k - phase) / every; kept as a running pair (next due step, its row), so the loop pays one
+//                      scalar compare per step and no division.  A wave that watches nobody has no due step at all
+//   log              : log[(row * fields + f) * log_stride + column], fields = 13 (state) or 19 (+ the wrench that produced
+//                      it; a run-time flag: the instantiations are those of the plain kernel).  Ordinary vector stores, from
+//                      the watched lanes only; the host has checked that every row of the launch exists
+// The recorder reads registers and nothing it computes feeds back: state, prev_out and kinetic-energy bits are those of
+// step_fused_multi_tiled_kernel.  Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
+// --------------------------------------------------------------------------
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
+    const bool live = tile * 64u + lane < n;
+    if constexpr (!KE) {
+        if (!live) return;
+    }
+    double ke_lin = 0.0, ke_rot = 0.0;
+    if (!KE || live) {
+        float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
+        load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
+        const uint64_t m = w_mask[tile];
+        const bool watched = ((m >> lane) & 1u) != 0;       // (the host has checked that every watched body is < n: a live lane)
+        const uint32_t column = w_first[tile] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        uint32_t due = m ? phase : 0u, row = row0;           // due == 0: never (the step counter below starts at 1)
+#pragma unroll 1
+        for (uint32_t k = 0; k < steps; ++k) {
+            float f6[HYDRO_WRENCH_FIELDS];
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6);
+            if (k + 1u == due) {
+                if (watched) {
+                    float* p = log + (size_t)row * fields * log_stride + column;
+#pragma unroll
+                    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) p[(size_t)f * log_stride] = s[f];
+                    if (fields > (uint32_t)HYDRO_STATE_FIELDS) {
+#pragma unroll
+                        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) p[(size_t)(HYDRO_STATE_FIELDS + f) * log_stride] = f6[f];
+                    }
+                }
+                due += every;
+                row += 1u;
+            }
         }
         if constexpr (KE)
             hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
@@ -1221,6 +1300,12 @@ struct hydro_engine {
     bool ke_launched = false;
     hipStream_t ke_last_stream = nullptr;
     hipEvent_t ke_event = nullptr;
+    // The trajectory recorder's watch list (hydro_set_watch): per tile of the capacity, the mask of watched lanes and the
+    // log column of the first of them (hydro_watch.h); allocated by the first hydro_set_watch, kept until hydro_destroy.
+    uint64_t* watch_mask = nullptr;  // [tiles of capacity]
+    uint32_t* watch_first = nullptr; // [tiles of capacity]
+    int64_t watch_count = 0;         // 0: no watch list
+    int64_t watch_last = -1;         // the largest watched body (a recording launch needs it below its n)
     hipStream_t stream = nullptr;
     int vec = 0;                   // bodies per lane, 0 = default (1)
     int block = 0;                 // threads per block, 0 = by size
@@ -1670,6 +1755,8 @@ int hydro_destroy(hydro_t* h)
     if (h->prev_tiled) (void)hipFree(h->prev_tiled);
     if (h->ke_partials) (void)hipFree(h->ke_partials);
     if (h->ke_event) (void)hipEventDestroy(h->ke_event);
+    if (h->watch_mask) (void)hipFree(h->watch_mask);
+    if (h->watch_first) (void)hipFree(h->watch_first);
     delete h;
     return HYDRO_OK;
 }
@@ -2054,11 +2141,21 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
                                  wrench, wrench_tile_stride, implicit_drag, rotational ? 1 : 0, ke_out_dev, stream);
 }
 
-int hydro_step_fused_tiled_multi(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
-                                 const float* prev, int64_t prev_tile_stride, double dt, int steps,
-                                 float* state_out, int64_t out_tile_stride,
-                                 float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
-                                 int rotational, double* ke_out_dev, void* stream)
+}  // extern "C"
+
+namespace {
+
+// hydro_step_fused_tiled_multi and its recording twin: one validation, one variant selection.  rec == nullptr launches
+// step_fused_multi_tiled_kernel, else step_fused_multi_rec_tiled_kernel with the recorder's arguments appended.
+struct RecArgs {
+    const uint64_t* mask; const uint32_t* first;     // the engine's watch tables
+    float* log; uint32_t stride, fields, every, phase, row0;
+};
+int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                float* state_out, int64_t out_tile_stride,
+                                float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                int rotational, double* ke_out_dev, const RecArgs* rec, int64_t* rows_written_host, int64_t rows, void* stream)
 {
     int rc = check_common(h, n);
     if (rc) return rc;
@@ -2069,8 +2166,10 @@ int hydro_step_fused_tiled_multi(hydro_t* h, int64_t n, const float* state, int6
     if ((rc = check_tiled(h, n, state_out, out_tile_stride, HYDRO_STATE_FIELDS, "null state_out"))) return rc;
     if ((rc = check_tiled(h, n, prev_out, prev_out_tile_stride, HYDRO_PREV_FIELDS, "null prev_out (pass state + 7*64 to keep the two-buffer ping-pong)"))) return rc;
     if (state_out == state) return fail(h, HYDRO_E_ARG, "state_out must not alias state (it may alias the previous-state buffer)");
+    if (rec && h->watch_last >= n) return fail(h, HYDRO_E_ARG, "a watched body is >= n");
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (rows_written_host) *rows_written_host = n == 0 ? 0 : rows;
     if (n == 0) return ke_out_dev ? ke_of_nothing(h, ke_out_dev, s) : HYDRO_OK;
     const double inv_dt = 1.0 / dt;
     const float dtf = (float)dt;
@@ -2080,8 +2179,10 @@ int hydro_step_fused_tiled_multi(hydro_t* h, int64_t n, const float* state, int6
     if (ke_out_dev && (rc = ke_prepare(h, s))) return rc;
 #define HYDRO_MULTI_ARGS state, prev, h->params_tiled, state_out, prev_out, (uint32_t)state_tile_stride, (uint32_t)prev_tile_stride, (uint32_t)out_tile_stride, \
         (uint32_t)prev_out_tile_stride, (uint32_t)n, (uint32_t)steps, dtf, h->rho, h->g, inv_dt, h->ke_partials, h->ke_stride, ke_rot, ke_out_dev
-#define HYDRO_MULTI_W(HALF, NT, KE, WARP) do { if (implicit_drag) hipLaunchKernelGGL((step_fused_multi_tiled_kernel<HALF, NT, true, KE, WARP>), grid, blk, 0, s, HYDRO_MULTI_ARGS); \
-                                               else hipLaunchKernelGGL((step_fused_multi_tiled_kernel<HALF, NT, false, KE, WARP>), grid, blk, 0, s, HYDRO_MULTI_ARGS); } while (0)
+#define HYDRO_MULTI_REC_ARGS HYDRO_MULTI_ARGS, rec->mask, rec->first, rec->log, rec->stride, rec->fields, rec->every, rec->phase, rec->row0
+#define HYDRO_MULTI_R(HALF, NT, IMPL, KE, WARP) do { if (rec) hipLaunchKernelGGL((step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>), grid, blk, 0, s, HYDRO_MULTI_REC_ARGS); \
+                                                     else hipLaunchKernelGGL((step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>), grid, blk, 0, s, HYDRO_MULTI_ARGS); } while (0)
+#define HYDRO_MULTI_W(HALF, NT, KE, WARP) do { if (implicit_drag) HYDRO_MULTI_R(HALF, NT, true, KE, WARP); else HYDRO_MULTI_R(HALF, NT, false, KE, WARP); } while (0)
 #define HYDRO_MULTI_I(HALF, NT, KE) do { if (h->semantics) HYDRO_MULTI_W(HALF, NT, KE, true); else HYDRO_MULTI_W(HALF, NT, KE, false); } while (0)
 #define HYDRO_MULTI(HALF, NT) do { if (ke_out_dev) HYDRO_MULTI_I(HALF, NT, true); else HYDRO_MULTI_I(HALF, NT, false); } while (0)
     if (h->half_coeffs) { if (nt) HYDRO_MULTI(true, true); else HYDRO_MULTI(true, false); }
@@ -2089,9 +2190,92 @@ int hydro_step_fused_tiled_multi(hydro_t* h, int64_t n, const float* state, int6
 #undef HYDRO_MULTI
 #undef HYDRO_MULTI_I
 #undef HYDRO_MULTI_W
+#undef HYDRO_MULTI_R
+#undef HYDRO_MULTI_REC_ARGS
 #undef HYDRO_MULTI_ARGS
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hydro_step_fused_tiled_multi(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                 const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                 float* state_out, int64_t out_tile_stride,
+                                 float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                 int rotational, double* ke_out_dev, void* stream)
+{
+    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
+                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, nullptr, nullptr, 0, stream);
+}
+
+int hydro_set_watch(hydro_t* h, int64_t count, const int64_t* bodies_host)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (count == 0 || !bodies_host) {
+        if (count > 0) return fail(h, HYDRO_E_ARG, "null watch list with count > 0");
+        if (count < 0) return fail(h, HYDRO_E_ARG, "watch list: count < 0");
+        h->watch_count = 0;
+        h->watch_last = -1;
+        return HYDRO_OK;
+    }
+    switch (hydro::watch_check(count, bodies_host, h->capacity)) {
+        case 0: break;
+        case 1: return fail(h, HYDRO_E_ARG, "watch list: count out of range (0 .. HYDRO_WATCH_MAX)");
+        case 2: return fail(h, HYDRO_E_ARG, "watch list: body index out of range (0 <= body < capacity)");
+        default: return fail(h, HYDRO_E_ARG, "watch list: indices must be strictly ascending (sorted, no duplicates)");
+    }
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    const size_t tiles = (size_t)((h->capacity + HYDRO_TILE - 1) / HYDRO_TILE);
+    if (!h->watch_mask && hipMalloc(&h->watch_mask, tiles * sizeof(uint64_t)) != hipSuccess) { h->watch_mask = nullptr; return fail(h, HYDRO_E_ALLOC, "watch tables: allocation failed"); }
+    if (!h->watch_first && hipMalloc(&h->watch_first, tiles * sizeof(uint32_t)) != hipSuccess) { h->watch_first = nullptr; return fail(h, HYDRO_E_ALLOC, "watch tables: allocation failed"); }
+    uint64_t* mask = static_cast<uint64_t*>(malloc(tiles * sizeof(uint64_t)));
+    uint32_t* first = static_cast<uint32_t*>(malloc(tiles * sizeof(uint32_t)));
+    if (!mask || !first) { free(mask); free(first); return fail(h, HYDRO_E_ALLOC, "watch tables: host allocation failed"); }
+    hydro::watch_tables(count, bodies_host, (int64_t)tiles, mask, first);
+    // from here on the device tables are being rewritten: a failure leaves NO list, never half of one
+    h->watch_count = 0;
+    h->watch_last = -1;
+    hipError_t e = hipMemcpyAsync(h->watch_mask, mask, tiles * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->watch_first, first, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    free(mask);
+    free(first);
+    if (e != hipSuccess) return fail(h, HYDRO_E_LAUNCH, "watch tables: copy to the device", e);
+    h->watch_count = count;
+    h->watch_last = bodies_host[count - 1];
+    return HYDRO_OK;
+}
+
+int64_t hydro_watch_count(const hydro_t* h) { return h ? h->watch_count : 0; }
+
+int hydro_step_fused_tiled_multi_rec(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (h->watch_count == 0) return fail(h, HYDRO_E_STATE, "no watch list (call hydro_set_watch first)");
+    if (!log || !aligned_to(log, 4)) return fail(h, HYDRO_E_ARG, "null or misaligned log");
+    if (fields != HYDRO_STATE_FIELDS && fields != HYDRO_STATE_FIELDS + HYDRO_WRENCH_FIELDS) return fail(h, HYDRO_E_ARG, "fields must be 13 (state) or 19 (state + wrench)");
+    if (every < 1 || every > (1 << 30)) return fail(h, HYDRO_E_ARG, "every must be in 1 .. 2^30");
+    if (phase < 1 || phase > every) return fail(h, HYDRO_E_ARG, "phase must be in 1 .. every");
+    if (log_stride < h->watch_count || log_stride >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "log_stride must be >= the watch count (and < 2^31)");
+    if (row0 < 0 || rows_capacity < 0 || rows_capacity >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "row0 / rows_capacity out of range (0 .. 2^31)");
+    if (steps < 1 || steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
+    // the rows this launch writes: row0 .. row0 + rows - 1, all of them below rows_capacity before anything is launched
+    const int64_t rows = phase > steps ? 0 : (int64_t)(steps - phase) / every + 1;
+    if (rows > 0 && row0 + rows > rows_capacity) return fail(h, HYDRO_E_ARG, "the launch would write past rows_capacity");
+    RecArgs rec;
+    rec.mask = h->watch_mask; rec.first = h->watch_first; rec.log = log; rec.stride = (uint32_t)log_stride; rec.fields = (uint32_t)fields;
+    rec.every = (uint32_t)every; rec.phase = (uint32_t)phase; rec.row0 = (uint32_t)row0;
+    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
+                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, &rec, rows_written_host, rows, stream);
 }
 
 int hydro_pack_state_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,

@@ -373,6 +373,49 @@ class HydroEngine:
             ke_out.data_ptr() if ke_out is not None else None, self._stream(stream)))
         return state_out
 
+    def set_watch(self, bodies) -> int:
+        """The trajectory recorder's watch list (hydro_set_watch): strictly ascending body indices below the capacity, at most
+        `_native.WATCH_MAX` of them; body bodies[j] records into column j of the log.  None or an empty list clears it.
+        Synchronous.  Returns the number of watched bodies."""
+        if bodies is None or len(bodies) == 0:
+            self._check(self._lib.hydro_set_watch(self._h, 0, None))
+            return 0
+        arr = (ctypes.c_int64 * len(bodies))(*[int(b) for b in bodies])
+        self._check(self._lib.hydro_set_watch(self._h, len(bodies), arr))
+        return int(self._lib.hydro_watch_count(self._h))
+
+    @property
+    def watch_count(self) -> int:
+        return int(self._lib.hydro_watch_count(self._h))
+
+    def step_fused_tiled_multi_rec(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
+                                   log: torch.Tensor, every: int, phase: int, row0: int,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi that also records the watched bodies (set_watch) from inside the kernel: after local step
+        k = phase, phase + every, ... of this launch, into rows row0, row0 + 1, ... of `log`, a contiguous float32 device
+        tensor (rows, 13 | 19, columns >= watch count) - 19 fields: the state, then the wrench that produced it.  State,
+        previous-velocity and kinetic-energy bits are those of step_fused_tiled_multi.  Returns the number of rows written."""
+        self._check_tiled(state, nat.STATE_FIELDS, n)
+        self._check_tiled(prev_state, nat.STATE_FIELDS, n)
+        if state_out is None:
+            state_out = prev_state
+        self._check_tiled(state_out, nat.STATE_FIELDS, n)
+        if ke_out is not None:
+            self._check_ke_out(ke_out)
+        if (log.dim() != 3 or log.dtype != torch.float32 or not log.is_contiguous() or log.device != self.device
+                or log.shape[1] not in (nat.STATE_FIELDS, nat.STATE_FIELDS + nat.WRENCH_FIELDS)):
+            raise ValueError("log must be a contiguous float32 (rows, 13 | 19, columns) tensor on the engine's device")
+        written = ctypes.c_int64(0)
+        st, vel = nat.STATE_FIELDS * nat.TILE, 7 * nat.TILE * 4
+        self._check(self._lib.hydro_step_fused_tiled_multi_rec(
+            self._h, n, state.data_ptr(), st, prev_state.data_ptr() + vel, st, float(dt), int(steps),
+            state_out.data_ptr(), st, state.data_ptr() + vel, st, int(bool(implicit_drag)), int(bool(rotational)),
+            ke_out.data_ptr() if ke_out is not None else None,
+            log.data_ptr(), log.shape[2], log.shape[0], log.shape[1], int(every), int(phase), int(row0),
+            ctypes.byref(written), self._stream(stream)))
+        return written.value
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

@@ -249,6 +249,91 @@ class KineticEnergyMonitor:
         return self.samples[-1] if self.samples else None
 
 
+def recorder_cadence(steps_done: int, every: int, steps: int) -> tuple:
+    """Where the samples of a launch fall.  A recorder samples after every physics step whose NUMBER (1-based, counted from
+    the start of the run) is a multiple of `every`; sample number r (0-based) is the state after step (r + 1) * every.  For a
+    launch that takes the run from `steps_done` to `steps_done + steps`:  (phase, row, rows) -
+    phase: the local step (1 .. every) after which its first sample is due; row: the number of that sample; rows: how many
+    samples it takes (0 if phase > steps).  These are the `phase` / `row0` arguments of hydro_step_fused_tiled_multi_rec, so
+    the length of a launch and `every` need not know of each other."""
+    if every < 1 or steps < 0 or steps_done < 0:
+        raise ValueError("every >= 1, steps >= 0, steps_done >= 0")
+    phase = every - steps_done % every
+    rows = 0 if phase > steps else (steps - phase) // every + 1
+    return phase, steps_done // every, rows
+
+
+class TrajectoryRecorder:
+    """Device log of a few watched bodies, written from INSIDE the stepping kernels every `every`-th physics step
+    (hydro_step_fused_tiled_multi_rec) - the resident loop's counterpart of the reference's per-frame `velocity_log.csv`
+    (log_velocity.py), without ending a launch and without a host round trip per row.  Made and attached by
+    `ClosedLoopSim.record`.  Row r holds the state after the r-th sampled step (`steps()[r]`), bit for bit what single-step
+    stepping leaves in memory there; with `wrench=True` also the wrench that produced that state.
+
+    `bodies` may come in any order (no duplicates); `states()` / `wrenches()` present them in that order.  `log` is the raw
+    device tensor (rows, 13 | 19, len(bodies)) - columns in ASCENDING body order, the library's - for consumers that stay on
+    the device.  The log is not a ring: a run that would pass `rows` raises before it launches anything; `rewind()` starts
+    over at row 0.  Under a process group a recorder is local to its rank's shard (`bodies` index the shard); no collective
+    is involved."""
+
+    def __init__(self, bodies, every: int = 1, rows: int = 4096, wrench: bool = False, device="cpu", steps_done: int = 0, sim=None):
+        self.bodies = tuple(int(b) for b in bodies)
+        if not self.bodies or len(set(self.bodies)) != len(self.bodies) or min(self.bodies) < 0:
+            raise ValueError("bodies: a non-empty list of distinct body indices")
+        if every < 1 or rows < 1:
+            raise ValueError("every >= 1 and rows >= 1")
+        order = sorted(range(len(self.bodies)), key=self.bodies.__getitem__)
+        self.sorted_bodies = [self.bodies[i] for i in order]       # what the library is given: column j = sorted_bodies[j]
+        self._column = np.empty(len(order), dtype=np.int64)        # column of the caller's i-th body
+        self._column[order] = np.arange(len(order))
+        self.every, self.rows, self.wrench = int(every), int(rows), bool(wrench)
+        self.fields = 19 if wrench else 13
+        self.log = torch.full((self.rows, self.fields, len(self.bodies)), float("nan"), dtype=torch.float32, device=device)
+        self.rows_written = 0
+        self._row_base = steps_done // self.every                  # samples of the run that were due before this recorder existed
+        self._sim = sim
+
+    def launch(self, steps_done: int, steps: int) -> tuple:
+        """(phase, row0, rows) of a launch of `steps` steps starting at `steps_done`, row0 counted in this log.
+        ValueError if the launch would write past the last row."""
+        phase, row, rows = recorder_cadence(steps_done, self.every, steps)
+        row0 = row - self._row_base
+        if rows and row0 + rows > self.rows:
+            raise ValueError(f"trajectory recorder: steps {steps_done + 1} .. {steps_done + steps} need rows up to {row0 + rows} "
+                             f"and the log has {self.rows} (record(rows=...) or rewind())")
+        return phase, row0, rows
+
+    def rewind(self, steps_done: int | None = None) -> None:
+        """Forget the rows written: the next sample goes to row 0.  (`steps_done`: the run's step count, taken from the
+        sim the recorder is attached to when omitted.)"""
+        if steps_done is None:
+            steps_done = self._sim.steps_done if self._sim is not None else 0
+        self.rows_written = 0
+        self._row_base = steps_done // self.every
+
+    def _synchronize(self) -> None:
+        if self._sim is not None:
+            self._sim.synchronize()
+
+    def steps(self) -> np.ndarray:
+        """Step numbers of the rows written so far: consecutive multiples of `every`."""
+        return (self._row_base + 1 + np.arange(self.rows_written, dtype=np.int64)) * self.every
+
+    def states(self) -> np.ndarray:
+        """(rows written, len(bodies), 13) host copy, bodies in the caller's order; waits for the step stream first."""
+        self._synchronize()
+        a = self.log[:self.rows_written, :13].cpu().numpy()
+        return np.ascontiguousarray(a.transpose(0, 2, 1)[:, self._column])
+
+    def wrenches(self) -> np.ndarray:
+        """(rows written, len(bodies), 6): the wrench of the step that produced each recorded state (wrench=True only)."""
+        if not self.wrench:
+            raise ValueError("this recorder was made without wrench=True")
+        self._synchronize()
+        a = self.log[:self.rows_written, 13:19].cpu().numpy()
+        return np.ascontiguousarray(a.transpose(0, 2, 1)[:, self._column])
+
+
 class ClosedLoopSim:
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
@@ -295,6 +380,41 @@ class ClosedLoopSim:
         self._graph_sampling_ok = want and self.monitor is not None and self.monitor.graph_capturable
         self.ke_dev = torch.zeros(2, dtype=torch.float64, device=dev) if ke_every else None
         self._monitor_warm = self.monitor is None
+        self.recorder: TrajectoryRecorder | None = None         # record()
+
+    def record(self, bodies, every: int = 1, rows: int = 4096, wrench: bool = False) -> TrajectoryRecorder:
+        """Watch `bodies` (any order, distinct, < n): from now on run_resident and run_eager write their state - with
+        `wrench=True` also the wrench that produced it - into the returned recorder's device log after every physics step
+        whose number is a multiple of `every`, from inside the stepping kernel.  `every` and run_resident's `chunk` are
+        independent.  `rows`: capacity of the log; a run that would pass it raises ValueError before launching anything.
+        One recorder per sim (a second call replaces the first); `stop_recording()` detaches it.  Graph replays (`run`
+        with graph_steps) cannot record - the row a captured launch writes to is frozen at capture - and raise ValueError.
+        Under a process group the recorder is local to this rank's shard; no collective is involved."""
+        if not self.fused:
+            raise ValueError("the recorder lives in the fused step kernels (fused=True)")
+        rec = TrajectoryRecorder(bodies, every, rows, wrench, device=self.engine.device, steps_done=self.steps_done, sim=self)
+        if rec.sorted_bodies[-1] >= self.n:
+            raise ValueError(f"bodies must be < n ({self.n})")
+        self.synchronize()                                      # launches in flight read the watch tables this rewrites
+        self.engine.set_watch(rec.sorted_bodies)
+        self.recorder = rec
+        return rec
+
+    def stop_recording(self) -> None:
+        if self.recorder is not None:
+            self.synchronize()
+            self.engine.set_watch(None)
+            self.recorder._sim = None
+            self.recorder = None
+
+    # `k` steps in one recording launch (k = 1 from run_eager: the bits of the single-step entry, include/hydro.h)
+    def _step_recorded(self, k: int, sample: bool) -> None:
+        rec = self.recorder
+        phase, row0, _ = rec.launch(self.steps_done, k)
+        rec.rows_written += self.engine.step_fused_tiled_multi_rec(
+            self.cur, self.old, self.n, self.dt, k, rec.log, rec.every, phase, row0, implicit_drag=self.implicit_drag,
+            ke_out=self.ke_dev if sample else None)
+        self.cur, self.old = self.old, self.cur
 
     def _warm_monitor(self) -> None:
         """First run*() with a monitor: one discarded pass of the sampling pipeline per slot (side-stream queue, pinned
@@ -320,13 +440,18 @@ class ClosedLoopSim:
         self.cur, self.old = self.old, self.cur
 
     def run_eager(self, steps: int) -> None:
+        if self.recorder is not None:
+            self.recorder.launch(self.steps_done, steps)        # room for the whole run, before anything is launched
         self._warm_monitor()
         with torch.cuda.stream(self.stream):
             for _ in range(steps):
                 sample = self.monitor is not None and (self.steps_done + 1) % self.monitor.every == 0
                 if sample:
                     self.monitor.wait_before_overwrite(self.stream)
-                self._step_once(sample)
+                if self.recorder is not None:
+                    self._step_recorded(1, sample)
+                else:
+                    self._step_once(sample)
                 self.steps_done += 1
                 if sample:
                     self.monitor.observe(self.steps_done, stream=self.stream, sampled=self.ke_dev)
@@ -368,6 +493,9 @@ class ClosedLoopSim:
     def run(self, steps: int, graph_steps: int = 64) -> None:
         """Advance `steps` physics steps; full groups of `graph_steps` are graph replays.  With a monitor under a process
         group this is COLLECTIVE (every rank runs the same number of steps with the same cadence)."""
+        if self.recorder is not None and graph_steps and steps >= graph_steps:
+            raise ValueError("a trajectory recorder cannot ride in graph replays: the log row a captured launch writes to is "
+                             "frozen at capture - use run_resident (or run_eager), or stop_recording() first")
         self._warm_monitor()
         if graph_steps and steps >= graph_steps:
             if self.steps_done % graph_steps and self.monitor is not None:
@@ -404,7 +532,9 @@ class ClosedLoopSim:
         per `chunk` steps (and one for the remainder).  The bodies are independent, so a launch reads every body once,
         carries it through `chunk` steps and writes it once - no HBM traffic and no launch between the steps, same bits
         as run_eager.  States between the ends of chunks never exist in memory: a kinetic-energy monitor samples at the
-        end of a chunk, so `ke_every` must be a multiple of `chunk` (and the run must start on such a boundary)."""
+        end of a chunk, so `ke_every` must be a multiple of `chunk` (and the run must start on such a boundary).
+        With a recorder attached (`record`) the watched bodies' states ARE written, from inside the launch, every
+        `recorder.every` steps - whatever `chunk` is."""
         if not self.fused:
             raise ValueError("the resident loop is the fused step")
         if chunk < 1:
@@ -412,6 +542,8 @@ class ClosedLoopSim:
         if self.monitor is not None and (self.monitor.every % chunk or self.steps_done % chunk):
             raise ValueError(f"ke_every ({self.monitor.every}) must be a multiple of chunk ({chunk}) and the run must start "
                              f"at one: the kinetic energy is sampled by the last step of a launch")
+        if self.recorder is not None:
+            self.recorder.launch(self.steps_done, steps)        # room for the whole run, before anything is launched
         self._warm_monitor()
         with torch.cuda.stream(self.stream):
             while steps > 0:
@@ -419,9 +551,12 @@ class ClosedLoopSim:
                 sample = self.monitor is not None and k == chunk and (self.steps_done + k) % self.monitor.every == 0
                 if sample:
                     self.monitor.wait_before_overwrite(self.stream)
-                self.engine.step_fused_tiled_multi(self.cur, self.old, self.n, self.dt, k, implicit_drag=self.implicit_drag,
-                                                   ke_out=self.ke_dev if sample else None)
-                self.cur, self.old = self.old, self.cur
+                if self.recorder is not None:
+                    self._step_recorded(k, sample)
+                else:
+                    self.engine.step_fused_tiled_multi(self.cur, self.old, self.n, self.dt, k, implicit_drag=self.implicit_drag,
+                                                       ke_out=self.ke_dev if sample else None)
+                    self.cur, self.old = self.old, self.cur
                 self.steps_done += k
                 steps -= k
                 if sample:

@@ -5,6 +5,8 @@
   600 steps and a final block with wall time, sim time, steps, `RTF = sim / wall`, `FPS = steps / wall`.
 * `LogVelocity`   - per-frame CSV logger, counterpart of `log_velocity.py:9-63`: same file name,
   same ten columns in the same (z, x, y) order.
+* `write_velocity_log` - the same file from a trajectory recorded ON THE DEVICE by the resident closed loop
+  (`simulate.TrajectoryRecorder`): one row per recorded step, no host round trip per row.
 
 Both talk to the simulator through the `SimHost` / `BodyView` protocols of `behavior.py`, so they run
 under Kit and under `silver2_isaacsim_amd.testing.FakeHost` alike.
@@ -113,6 +115,35 @@ class BenchmarkRtf:
         return None if self.run is None else self.run.summary(self._clock())
 
 
+def velocity_row(when: datetime.datetime, position, velocity) -> list:
+    """One row of velocity_log.csv (log_velocity.py:44-52): ISO timestamp, then position / linear / angular velocity of the
+    z, x and y axes in that order, as Python floats.  `position`: (x, y, z); `velocity`: (vx, vy, vz, wx, wy, wz)."""
+    p, v = position, velocity
+    f = lambda x: float(x)                               # noqa: E731
+    return [when.isoformat(),
+            f(p[2]), f(v[2]), f(v[5]),
+            f(p[0]), f(v[0]), f(v[3]),
+            f(p[1]), f(v[1]), f(v[4])]
+
+
+def write_velocity_log(path: str, recorder, body: int, start: datetime.datetime | None = None, dt: float = 1.0 / 60.0) -> str:
+    """The reference's velocity_log.csv from a trajectory recorded on the device (`ClosedLoopSim.record`): header and row
+    format of `LogVelocity`, one row per recorded step of `body` (one of the recorder's bodies), timestamp = `start`
+    (default: now) + step number x `dt` seconds.  `path`: the file, or a directory to put CSV_FILE_NAME into.
+    Returns the file's path."""
+    if os.path.isdir(path):
+        path = os.path.join(path, CSV_FILE_NAME)
+    start = start if start is not None else datetime.datetime.now()
+    column = list(recorder.bodies).index(int(body))
+    steps, states = recorder.steps(), recorder.states()[:, column]
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(CSV_HEADER)
+        for k, st in zip(steps, states):
+            w.writerow(velocity_row(start + datetime.timedelta(seconds=float(k) * dt), st[0:3], st[7:13]))
+    return path
+
+
 class LogVelocity:
     """CSV logger of one prim's pose / velocity, one row per render frame (`on_update`)."""
 
@@ -144,12 +175,7 @@ class LogVelocity:
             return
         positions, _ = self._rigid_prim.get_world_poses()
         vel = self._rigid_prim.get_velocities()
-        p, v = positions[0], vel[0]
-        f = lambda x: float(x)                           # noqa: E731
-        row = [self._now().isoformat(),
-               f(p[2]), f(v[2]), f(v[5]),
-               f(p[0]), f(v[0]), f(v[3]),
-               f(p[1]), f(v[1]), f(v[4])]
+        row = velocity_row(self._now(), positions[0], vel[0])
         try:
             with open(self._log_file_path, "a", newline="") as fh:
                 csv.writer(fh).writerow(row)
