@@ -29,6 +29,7 @@
 #include <string.h>
 #include <mutex>
 #include <new>
+#include <type_traits>
 
 #include "../../include/hydro.h"
 #include "hydro_body.h"
@@ -364,6 +365,10 @@ __device__ __forceinline__ hydro::Wrench body_wrench(const float (&s)[HYDRO_STAT
 {
     return hydro::solve_wrench(make_body(s, d, c), pv, mass, rho, g, inv_dt, warp);
 }
+__device__ __forceinline__ void wrench_fields(const hydro::Wrench& w, float (&f6)[HYDRO_WRENCH_FIELDS])
+{
+    f6[0] = w.fx; f6[1] = w.fy; f6[2] = w.fz; f6[3] = w.tx; f6[4] = w.ty; f6[5] = w.tz;
+}
 
 // --------------------------------------------------------------------------
 // fused wrench, struct-of-arrays.  Each lane owns VEC consecutive bodies.
@@ -406,9 +411,10 @@ __global__ void __launch_bounds__(BLOCK) wrench_soa_kernel(const SoaArgs a)
         for (int f = 0; f < 3; ++f) d[f] = dm[f][j];
 #pragma unroll
         for (int f = 0; f < 7; ++f) c[f] = cf[f][j];
-        const hydro::Wrench w = body_wrench(s, p, d, c, ms[j], a.rho, a.g, a.inv_dt, WARP);
-        out[0][j] = w.fx; out[1][j] = w.fy; out[2][j] = w.fz;
-        out[3][j] = w.tx; out[4][j] = w.ty; out[5][j] = w.tz;
+        float f6[HYDRO_WRENCH_FIELDS];
+        wrench_fields(body_wrench(s, p, d, c, ms[j], a.rho, a.g, a.inv_dt, WARP), f6);
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) out[f][j] = f6[f];
     }
 
 #pragma unroll
@@ -432,38 +438,16 @@ __global__ void __launch_bounds__(BLOCK) wrench_soa_kernel(const SoaArgs a)
 // 6.1 TB/s against 5.4 TB/s for plain SoA, i.e. the float4-copy ceiling of the box.  All field offsets f*256 B fit the 12-bit
 // immediate of global_load, so a wave needs ONE 32-bit offset register per record.
 // --------------------------------------------------------------------------
-struct TiledArgs {
-    const float* st;  uint32_t st_stride;      // 13 fields
-    const float* pv;  uint32_t pv_stride;      // 6 fields (may alias a previous state buffer + 7*64)
-    float* pv_out;    uint32_t pvo_stride;     // WRITE_PREV only
-    const float* prm;                          // engine-owned: [tiles][11][64] f32, or f16 record (below)
-    float* out;       uint32_t out_stride;     // 6 fields
-    double rho, g;                           // scene scalars stay fp64 up to the kernel (hydro_body.h)
-    double inv_dt;                           // 1 / dt in fp64 (dt is a double through the C ABI)
-    int warp;                                // HYDRO_SEM_WARP (uniform)
-    uint32_t n;
-};
-// fp16-coefficient parameter record per tile: [dimx dimy dimz mass][64] f32 (1024 B) then
-// [cd_lin cd_ang damp_lin damp_ang lift am_lin am_ang][64] f16 (896 B) = 1920 B = 480 floats.
+// The engine's parameter record per tile is [dimx dimy dimz cd_lin cd_ang damp_lin damp_ang lift am_lin am_ang mass][64] f32, or
+// with fp16 coefficients [dimx dimy dimz mass][64] f32 (1024 B) then the seven coefficients [64] f16 (896 B) = 1920 B = 480 floats.
 constexpr uint32_t kPrmTileF32 = 11 * 64;
 constexpr uint32_t kPrmTileF16 = 480;
 
-// state, previous velocity and parameter records of body (tile, lane): the ~28 loads of a wave are three
-// contiguous records, every field offset in the load instruction's immediate.
-// One wavefront = one tile, so the tile index is WAVE-UNIFORM: the callers hand it over as a scalar (wave_tile below) and
-// the three record bases are scalar 64-bit adds; what is left per lane is ONE offset register for every 4-byte field of
-// every record (lane * 4) and one for the fp16 coefficients (lane * 2) - 5 vector instructions of addressing per body where
-// per-lane tile arithmetic (24-bit multiplies, add-shifts) took 15.  `st`, `pv` are the tile's records, not the buffers.
+// Dimensions, coefficients and mass of body (tile, lane) from the engine's parameter records (see load_tile_records).
 template <bool HALF, bool NT>
-__device__ __forceinline__ void load_tile_records(const float* __restrict__ st, const float* __restrict__ pvr, const float* __restrict__ prm_all,
-                                                  uint32_t tile, uint32_t lane4,
-                                                  float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS],
+__device__ __forceinline__ void load_param_record(const float* __restrict__ prm_all, uint32_t tile, uint32_t lane4,
                                                   float (&d)[3], float (&c)[7], float& mass)
 {
-#pragma unroll
-    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = ldg<NT>(at<float>(st, lane4, f * 256u));
-#pragma unroll
-    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = ldg<NT>(at<float>(pvr, lane4, f * 256u));
     if constexpr (HALF) {
         const float* prm = prm_all + (size_t)tile * kPrmTileF16;
 #pragma unroll
@@ -481,6 +465,31 @@ __device__ __forceinline__ void load_tile_records(const float* __restrict__ st, 
         mass = ldg<NT>(at<float>(prm, lane4, 10 * 256u));
     }
 }
+// state, previous velocity and parameter records of body (tile, lane): the ~28 loads of a wave are three
+// contiguous records, every field offset in the load instruction's immediate.
+// One wavefront = one tile, so the tile index is WAVE-UNIFORM: the callers hand it over as a scalar (wave_tile below) and
+// the three record bases are scalar 64-bit adds; what is left per lane is ONE offset register for every 4-byte field of
+// every record (lane * 4) and one for the fp16 coefficients (lane * 2) - 5 vector instructions of addressing per body where
+// per-lane tile arithmetic (24-bit multiplies, add-shifts) took 15.  `st`, `pv` are the tile's records, not the buffers.
+template <bool HALF, bool NT>
+__device__ __forceinline__ void load_tile_records(const float* __restrict__ st, const float* __restrict__ pvr, const float* __restrict__ prm_all,
+                                                  uint32_t tile, uint32_t lane4,
+                                                  float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS],
+                                                  float (&d)[3], float (&c)[7], float& mass)
+{
+#pragma unroll
+    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = ldg<NT>(at<float>(st, lane4, f * 256u));
+#pragma unroll
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = ldg<NT>(at<float>(pvr, lane4, f * 256u));
+    load_param_record<HALF, NT>(prm_all, tile, lane4, d, c, mass);
+}
+// One field group of body (tile, lane) into its tiled record: v[0 .. F-1] to F consecutive 256-B runs.
+template <int F, bool NT>
+__device__ __forceinline__ void store_record(float* rec, uint32_t lane4, const float* v)
+{
+#pragma unroll
+    for (int f = 0; f < F; ++f) stg<NT>(at<float>(rec, lane4, f * 256u), v[f]);
+}
 // The tile a wavefront works on, as a scalar: body i = block * BLOCK + thread with BLOCK a multiple of 64, so i >> 6 is
 // the same in all 64 lanes - told to the compiler with v_readfirstlane on the wave-in-block index.
 template <int BLOCK>
@@ -490,6 +499,27 @@ __device__ __forceinline__ uint32_t wave_tile(uint32_t block)
     return block * (BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 }
 
+// The wrench step of body (tile, lane), shared with the batch kernel, in two halves: records in, wrench computed; then the wrench
+// and (WRITE_PREV) this step's velocity out.  Two, because the energy sample of a KE instantiation sits BETWEEN them in
+// program order (behind the stores it costs the sampling kernels registers).
+template <bool HALF, bool NT, bool WARP>
+__device__ __forceinline__ void tile_wrench(const float* st, const float* pv_in, const float* prm, uint32_t st_stride, uint32_t pv_stride,
+                                            uint32_t tile, uint32_t lane4, double rho, double g, double inv_dt,
+                                            float (&s)[HYDRO_STATE_FIELDS], float (&d)[3], float& mass, float (&f6)[HYDRO_WRENCH_FIELDS])
+{
+    // tile < 2^24 and strides < 2^24, byte offsets < 2^32 (checked on the host)
+    float pv[HYDRO_PREV_FIELDS], c[7];
+    load_tile_records<HALF, NT>(st + (size_t)tile * st_stride, pv_in + (size_t)tile * pv_stride, prm, tile, lane4, s, pv, d, c, mass);
+    wrench_fields(body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP), f6);
+}
+template <bool WRITE_PREV, bool NT>
+__device__ __forceinline__ void store_tile_wrench(float* out, float* pv_out, uint32_t out_stride, uint32_t pvo_stride, uint32_t tile, uint32_t lane4,
+                                                  const float (&f6)[HYDRO_WRENCH_FIELDS], const float (&s)[HYDRO_STATE_FIELDS])
+{
+    store_record<HYDRO_WRENCH_FIELDS, NT>(out + (size_t)tile * out_stride, lane4, f6);
+    if constexpr (WRITE_PREV) store_record<HYDRO_PREV_FIELDS, NT>(pv_out + (size_t)tile * pvo_stride, lane4, s + 7);
+}
+
 // The arguments are passed as individual scalars, the ones every wave needs before it can issue its first load in
 // the first 16 dwords: with -mllvm -amdgpu-kernarg-preload-count=16 (build.py) those arrive in SGPRs with the wave
 // (gfx950 kernarg preload) instead of behind three dependent scalar-memory round trips (~0.3 us per wave start,
@@ -497,40 +527,30 @@ __device__ __forceinline__ uint32_t wave_tile(uint32_t block)
 // KE = true (BLOCK 256 only): the kernel also samples the kinetic energy of the bodies it holds - the state it READS,
 // i.e. the state after the previous step - and leaves one fp64 pair per block in `ke_partials` ([2][ke_stride]) for
 // the fixed-order second stage: no second pass over the state ("reduced in-kernel").
+// (The `int warp` argument of this and the other preloaded kernels is not read - WARP is the template argument - and stays:
+// the argument lists are the kernarg-preload contract and part of the kernels' mangled names.)
 template <int BLOCK, bool HALF, bool WRITE_PREV, bool NT, bool KE, bool WARP>
 __global__ void __launch_bounds__(BLOCK) HYDRO_TILED_OCC_ATTR wrench_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_out, float* k_pv_out,
                                                              uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
                                                              uint32_t n, int warp, double rho, double g, double inv_dt,
                                                              double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
-    TiledArgs a;
-    a.st = k_st; a.st_stride = st_stride; a.pv = k_pv; a.pv_stride = pv_stride; a.pv_out = k_pv_out; a.pvo_stride = pvo_stride;
-    a.prm = k_prm; a.out = k_out; a.out_stride = out_stride; a.rho = rho; a.g = g; a.inv_dt = inv_dt; a.warp = warp; a.n = n;
     const uint32_t tile = wave_tile<BLOCK>(blockIdx.x), lane = threadIdx.x & 63u;
     const uint32_t first = tile * 64u;                              // (scalar) bodies of this tile that exist: all 64 but in the last one
     // (scalar; written as n - min(n, first) through readfirstlane: as a saturating subtract the compiler moves it to the vector unit)
-    const uint32_t left = a.n - __builtin_amdgcn_readfirstlane(a.n < first ? a.n : first);
+    const uint32_t left = n - __builtin_amdgcn_readfirstlane(n < first ? n : first);
     if constexpr (!KE) {
         if (lane >= left) return;
     }
     double ke_lin = 0.0, ke_rot = 0.0;
     if (!KE || lane < left) {                   // (KE: no early return - every thread reaches the block reduction)
-        // tile < 2^24 and strides < 2^24, byte offsets < 2^32 (checked on the host)
         const uint32_t lane4 = lane * 4u;
-        float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
-        load_tile_records<HALF, NT>(a.st + (size_t)tile * a.st_stride, a.pv + (size_t)tile * a.pv_stride, a.prm, tile, lane4, s, pv, d, c, mass);
-        const hydro::Wrench w = body_wrench(s, pv, d, c, mass, a.rho, a.g, a.inv_dt, WARP);
+        float s[HYDRO_STATE_FIELDS], d[3], mass, f6[HYDRO_WRENCH_FIELDS];
+        tile_wrench<HALF, NT, WARP>(k_st, k_pv, k_prm, st_stride, pv_stride, tile, lane4, rho, g, inv_dt, s, d, mass, f6);
         if constexpr (KE)
             hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
                                   ke_rotational != 0, ke_lin, ke_rot);
-        float* out = a.out + (size_t)tile * a.out_stride;
-        stg<NT>(at<float>(out, lane4, 0u), w.fx); stg<NT>(at<float>(out, lane4, 256u), w.fy); stg<NT>(at<float>(out, lane4, 512u), w.fz);
-        stg<NT>(at<float>(out, lane4, 768u), w.tx); stg<NT>(at<float>(out, lane4, 1024u), w.ty); stg<NT>(at<float>(out, lane4, 1280u), w.tz);
-        if constexpr (WRITE_PREV) {
-            float* pvo = a.pv_out + (size_t)tile * a.pvo_stride;
-#pragma unroll
-            for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg<NT>(at<float>(pvo, lane4, f * 256u), s[7 + f]);
-        }
+        store_tile_wrench<WRITE_PREV, NT>(k_out, k_pv_out, out_stride, pvo_stride, tile, lane4, f6, s);
     }
     if constexpr (KE) {
         static_assert(BLOCK == kBlock, "the kinetic-energy partials are one per 256 bodies");
@@ -597,22 +617,12 @@ __global__ void __launch_bounds__(kBlock) HYDRO_TILED_OCC_ATTR wrench_tiled_batc
     } else {
         b = args.sc[scene];
     }
-    TiledArgs a;
-    a.st = b.st; a.st_stride = b.st_stride; a.pv = b.pv; a.pv_stride = b.pv_stride; a.pv_out = b.pv_out; a.pvo_stride = b.pvo_stride;
-    a.prm = b.prm; a.out = b.out; a.out_stride = b.out_stride; a.rho = b.rho; a.g = b.g; a.inv_dt = args.inv_dt; a.warp = WARP; a.n = b.n;
+    const double inv_dt = args.inv_dt;          // (asked for here, ahead of the early exit, with the scene's scalars)
     const uint32_t tile = wave_tile<kBlock>(bid - first), lane = threadIdx.x & 63u, lane4 = lane * 4u;     // (wave-uniform, see load_tile_records)
-    if (tile * 64u + lane >= a.n) return;
-    float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
-    load_tile_records<HALF, NT>(a.st + (size_t)tile * a.st_stride, a.pv + (size_t)tile * a.pv_stride, a.prm, tile, lane4, s, pv, d, c, mass);
-    const hydro::Wrench w = body_wrench(s, pv, d, c, mass, a.rho, a.g, a.inv_dt, WARP);
-    float* out = a.out + (size_t)tile * a.out_stride;
-    stg<NT>(at<float>(out, lane4, 0u), w.fx); stg<NT>(at<float>(out, lane4, 256u), w.fy); stg<NT>(at<float>(out, lane4, 512u), w.fz);
-    stg<NT>(at<float>(out, lane4, 768u), w.tx); stg<NT>(at<float>(out, lane4, 1024u), w.ty); stg<NT>(at<float>(out, lane4, 1280u), w.tz);
-    if constexpr (WRITE_PREV) {
-        float* pvo = a.pv_out + (size_t)tile * a.pvo_stride;
-#pragma unroll
-        for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg<NT>(at<float>(pvo, lane4, f * 256u), s[7 + f]);
-    }
+    if (tile * 64u + lane >= b.n) return;
+    float s[HYDRO_STATE_FIELDS], d[3], mass, f6[HYDRO_WRENCH_FIELDS];
+    tile_wrench<HALF, NT, WARP>(b.st, b.pv, b.prm, b.st_stride, b.pv_stride, tile, lane4, b.rho, b.g, inv_dt, s, d, mass, f6);
+    store_tile_wrench<WRITE_PREV, NT>(b.out, b.pv_out, b.out_stride, b.pvo_stride, tile, lane4, f6, s);
 }
 
 // Parameters: the caller's 11 field arrays -> the engine's tiled records (once per hydro_set_params_*), and back into
@@ -736,21 +746,6 @@ __global__ void __launch_bounds__(kBlock) unpack_wrench_aos_kernel(const UnpackA
     }
 }
 
-struct AosArgs {
-    const float* pos;       // (n,3)
-    const float* quat;      // (n,4)
-    int quat_xyzw;          // 0: simulator order w,x,y,z   1: kernel order x,y,z,w
-    const float* vel;       // (n,6)
-    float* force;           // (n,3)
-    float* torque;          // (n,3)
-    float* pv;              // engine-owned previous velocity, tiled [tiles][6][64] (read, then updated)
-    const float* prm;       // engine-owned parameters, tiled record (f32 or fp16-coefficient form)
-    double rho, g;                           // scene scalars stay fp64 up to the kernel (hydro_body.h)
-    double inv_dt;                           // 1 / dt in fp64 (dt is a double through the C ABI)
-    int warp;                                // HYDRO_SEM_WARP (uniform)
-    int64_t n;
-};
-
 // --------------------------------------------------------------------------
 // fused wrench on the simulator's array-of-structs tensors (hydro_step_wrench_aos): positions (n,3), orientations
 // (n,4) wxyz or xyzw, velocities (n,6) in; forces (n,3), torques (n,3) out; previous velocity and parameters are the
@@ -788,6 +783,8 @@ __global__ void __launch_bounds__(kBlock) wrench_aos_direct_kernel(const float* 
                                                                   float* k_pv, const float* k_prm, int quat_xyzw, uint32_t n,      // 16 dwords: preloaded
                                                                   int warp, double rho, double g, double inv_dt)
 {
+    // quat_xyzw: 0 = the simulator's order w,x,y,z, 1 = the kernels' x,y,z,w.  k_pv, k_prm: the engine's tiled previous velocity
+    // (read, then updated) and parameter records.
     // (wave-uniform tile: the bases of the tile's rows and records are scalar adds, see load_tile_records)
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
     if (tile * 64u + lane >= n) return;
@@ -811,22 +808,7 @@ __global__ void __launch_bounds__(kBlock) wrench_aos_direct_kernel(const float* 
     float* t_pv = k_pv + (size_t)tile * (HYDRO_PREV_FIELDS * HYDRO_TILE);
 #pragma unroll
     for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = ldg<NT>(at<float>(t_pv, lane4, f * 256u));
-    if constexpr (HALF) {
-        const float* prm = k_prm + (size_t)tile * kPrmTileF16;
-#pragma unroll
-        for (int f = 0; f < 3; ++f) d[f] = ldg<NT>(at<float>(prm, lane4, f * 256u));
-        mass = ldg<NT>(at<float>(prm, lane4, 3 * 256u));
-        const uint32_t lane2 = lane4 >> 1;
-#pragma unroll
-        for (int f = 0; f < 7; ++f) c[f] = half_bits_to_float(ldg<NT>(at<unsigned short>(prm, lane2, 1024u + f * 128u)));
-    } else {
-        const float* prm = k_prm + (size_t)tile * kPrmTileF32;
-#pragma unroll
-        for (int f = 0; f < 3; ++f) d[f] = ldg<NT>(at<float>(prm, lane4, f * 256u));
-#pragma unroll
-        for (int f = 0; f < 7; ++f) c[f] = ldg<NT>(at<float>(prm, lane4, (3 + f) * 256u));
-        mass = ldg<NT>(at<float>(prm, lane4, 10 * 256u));
-    }
+    load_param_record<HALF, NT>(k_prm, tile, lane4, d, c, mass);
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
 #pragma unroll
     for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg_aos<NT>(at<float>(t_pv, lane4, f * 256u), s[7 + f]);
@@ -1092,49 +1074,31 @@ __global__ void __launch_bounds__(kBlock) integrate_kernel(const IntArgs a)
 // body-step instead of 280 B for the two separate kernels.  state_out may alias the buffer the
 // previous velocity is read from (ping-pong): each lane reads its own fields before writing them.
 // --------------------------------------------------------------------------
-struct FusedArgs {
-    TiledArgs t;            // t.out == nullptr: wrench not stored
-    float* so; uint32_t so_stride;
-    float dt;
-};
-
 // KE = true: also samples the kinetic energy of the state it WRITES (the state after this step), see wrench_tiled_kernel.
+// k_out == nullptr: the wrench is not stored.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
 __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_out,
                                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t out_stride,
                                                                  uint32_t n, int warp, float dt, double rho, double g, double inv_dt,
                                                                  double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
-    FusedArgs fa;                               // (scalar arguments: see wrench_tiled_kernel)
-    fa.t.st = k_st; fa.t.st_stride = st_stride; fa.t.pv = k_pv; fa.t.pv_stride = pv_stride; fa.t.pv_out = nullptr; fa.t.pvo_stride = 0;
-    fa.t.prm = k_prm; fa.t.out = k_out; fa.t.out_stride = out_stride; fa.t.rho = rho; fa.t.g = g; fa.t.inv_dt = inv_dt; fa.t.warp = warp; fa.t.n = n;
-    fa.so = k_so; fa.so_stride = so_stride; fa.dt = dt;
-    const TiledArgs& a = fa.t;
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
-    const bool live = tile * 64u + lane < a.n;
+    const bool live = tile * 64u + lane < n;
     if constexpr (!KE) {
         if (!live) return;
     }
     double ke_lin = 0.0, ke_rot = 0.0;
     if (!KE || live) {
-        float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
-        load_tile_records<HALF, NT>(a.st + (size_t)tile * a.st_stride, a.pv + (size_t)tile * a.pv_stride, a.prm, tile, lane4, s, pv, d, c, mass);
-        const hydro::Wrench w = body_wrench(s, pv, d, c, mass, a.rho, a.g, a.inv_dt, WARP);
-        const float k_lin = w.k_lin, k_ang = w.k_ang;     // used by the implicit form only
-        const float f6[HYDRO_WRENCH_FIELDS] = {w.fx, w.fy, w.fz, w.tx, w.ty, w.tz};
-        float o[HYDRO_STATE_FIELDS];
-        integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], a.g, fa.dt, k_lin, k_ang, o);
+        float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass, f6[HYDRO_WRENCH_FIELDS], o[HYDRO_STATE_FIELDS];
+        load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
+        const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
+        wrench_fields(w, f6);
+        integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);     // (k_lin, k_ang: the implicit form only)
         if constexpr (KE)
             hydro::kinetic_energy(o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12], d[0], d[1], d[2], mass,
                                   ke_rotational != 0, ke_lin, ke_rot);
-        float* so = fa.so + (size_t)tile * fa.so_stride;
-#pragma unroll
-        for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) stg<NT>(at<float>(so, lane4, f * 256u), o[f]);
-        if (a.out) {
-            float* wout = a.out + (size_t)tile * a.out_stride;
-#pragma unroll
-            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) stg<NT>(at<float>(wout, lane4, f * 256u), f6[f]);
-        }
+        store_record<HYDRO_STATE_FIELDS, NT>(k_so + (size_t)tile * so_stride, lane4, o);
+        if (k_out) store_record<HYDRO_WRENCH_FIELDS, NT>(k_out + (size_t)tile * out_stride, lane4, f6);
     }
     if constexpr (KE) ke_block_reduce(ke_lin, ke_rot, ke_partials, ke_stride, ke_out);
 }
@@ -1146,7 +1110,7 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
                                                         double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS])
 {
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
-    f6[0] = w.fx; f6[1] = w.fy; f6[2] = w.fz; f6[3] = w.tx; f6[4] = w.ty; f6[5] = w.tz;
+    wrench_fields(w, f6);
     float o[HYDRO_STATE_FIELDS];
     integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
 #pragma unroll
@@ -1164,15 +1128,14 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // k_pvo may alias the velocity fields of the state this kernel READS (each lane reads its own fields first): the
 // two-buffer ping-pong of the single-step entry then carries over unchanged.
 // --------------------------------------------------------------------------
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                       uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                       uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                       double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
+// The body of the two kernels below.  `rec` is the recorder policy: begin(tile, lane) once the records are loaded, then
+// after_step(k, s, f6) behind every step with the state it produced and the wrench that produced it.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder>
+__device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                 uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                 uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec)
 {
-    TiledArgs a;
-    a.st = k_st; a.st_stride = st_stride; a.pv = k_pv; a.pv_stride = pv_stride; a.pv_out = k_pvo; a.pvo_stride = pvo_stride;
-    a.prm = k_prm; a.out = nullptr; a.out_stride = 0; a.rho = rho; a.g = g; a.inv_dt = inv_dt; a.warp = WARP; a.n = n;
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
     if constexpr (!KE) {
@@ -1182,28 +1145,31 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
     if (!KE || live) {
         float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
         load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
+        rec.begin(tile, lane);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
             fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6);
+            rec.after_step(k, s, f6);
         }
         if constexpr (KE)
             hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
                                   ke_rotational != 0, ke_lin, ke_rot);
-        float* pvo = k_pvo + (size_t)tile * pvo_stride;
-#pragma unroll
-        for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg<NT>(at<float>(pvo, lane4, f * 256u), pv[f]);
-        float* so = k_so + (size_t)tile * so_stride;
-#pragma unroll
-        for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) stg<NT>(at<float>(so, lane4, f * 256u), s[f]);
+        store_record<HYDRO_PREV_FIELDS, NT>(k_pvo + (size_t)tile * pvo_stride, lane4, pv);
+        store_record<HYDRO_STATE_FIELDS, NT>(k_so + (size_t)tile * so_stride, lane4, s);
     }
     if constexpr (KE) ke_block_reduce(ke_lin, ke_rot, ke_partials, ke_stride, ke_out);
 }
 
+struct NoRecorder {
+    __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void after_step(uint32_t, const float (&)[HYDRO_STATE_FIELDS], const float (&)[HYDRO_WRENCH_FIELDS]) {}
+};
+
 // --------------------------------------------------------------------------
-// The same kernel with a TRAJECTORY RECORDER in its loop (hydro_step_fused_tiled_multi_rec): the states between the first
-// and the last step of a launch exist in registers only, so the bodies on the engine's watch list are written to a device
-// log from inside the loop.  Everything the recorder decides on is wave-uniform:
+// The TRAJECTORY RECORDER in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_rec): the states between the
+// first and the last step of a launch exist in registers only, so the bodies on the engine's watch list are written to a
+// device log from inside the loop.  Everything the recorder decides on is wave-uniform:
 //   w_mask / w_first : the watch tables of hydro_set_watch (hydro_watch.h), one entry per tile = per wavefront: which lanes
 //                      are watched and the log column of the first of them; two scalar loads per wave and LAUNCH.  A
 //                      watched lane's column is w_first[tile] + popcount(w_mask[tile] & lanes below it) - v_mbcnt
@@ -1214,8 +1180,46 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
 //                      it; a run-time flag: the instantiations are those of the plain kernel).  Ordinary vector stores, from
 //                      the watched lanes only; the host has checked that every row of the launch exists
 // The recorder reads registers and nothing it computes feeds back: state, prev_out and kinetic-energy bits are those of
-// step_fused_multi_tiled_kernel.  Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
+// step_fused_multi_tiled_kernel.
 // --------------------------------------------------------------------------
+struct LogRecorder {
+    const uint64_t* w_mask; const uint32_t* w_first; float* log; uint32_t log_stride, fields, every, phase, row0;
+    bool watched; uint32_t column, due, row;
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane)
+    {
+        const uint64_t m = w_mask[tile];
+        watched = ((m >> lane) & 1u) != 0;                  // (the host has checked that every watched body is < n: a live lane)
+        column = w_first[tile] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        due = m ? phase : 0u; row = row0;                   // due == 0: never (a step's 1-based number is compared with it)
+    }
+    __device__ __forceinline__ void after_step(uint32_t k, const float (&s)[HYDRO_STATE_FIELDS], const float (&f6)[HYDRO_WRENCH_FIELDS])
+    {
+        if (k + 1u != due) return;
+        if (watched) {
+            float* p = log + (size_t)row * fields * log_stride + column;
+#pragma unroll
+            for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) p[(size_t)f * log_stride] = s[f];
+            if (fields > (uint32_t)HYDRO_STATE_FIELDS) {
+#pragma unroll
+                for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) p[(size_t)(HYDRO_STATE_FIELDS + f) * log_stride] = f6[f];
+            }
+        }
+        due += every;
+        row += 1u;
+    }
+};
+
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                       uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                       uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                       double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{});
+}
+
+// Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
 __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                                            uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
@@ -1224,48 +1228,9 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
                                                                            const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
                                                                            uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0)
 {
-    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
-    const bool live = tile * 64u + lane < n;
-    if constexpr (!KE) {
-        if (!live) return;
-    }
-    double ke_lin = 0.0, ke_rot = 0.0;
-    if (!KE || live) {
-        float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
-        load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
-        const uint64_t m = w_mask[tile];
-        const bool watched = ((m >> lane) & 1u) != 0;       // (the host has checked that every watched body is < n: a live lane)
-        const uint32_t column = w_first[tile] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t due = m ? phase : 0u, row = row0;           // due == 0: never (the step counter below starts at 1)
-#pragma unroll 1
-        for (uint32_t k = 0; k < steps; ++k) {
-            float f6[HYDRO_WRENCH_FIELDS];
-            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6);
-            if (k + 1u == due) {
-                if (watched) {
-                    float* p = log + (size_t)row * fields * log_stride + column;
-#pragma unroll
-                    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) p[(size_t)f * log_stride] = s[f];
-                    if (fields > (uint32_t)HYDRO_STATE_FIELDS) {
-#pragma unroll
-                        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) p[(size_t)(HYDRO_STATE_FIELDS + f) * log_stride] = f6[f];
-                    }
-                }
-                due += every;
-                row += 1u;
-            }
-        }
-        if constexpr (KE)
-            hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
-                                  ke_rotational != 0, ke_lin, ke_rot);
-        float* pvo = k_pvo + (size_t)tile * pvo_stride;
-#pragma unroll
-        for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg<NT>(at<float>(pvo, lane4, f * 256u), pv[f]);
-        float* so = k_so + (size_t)tile * so_stride;
-#pragma unroll
-        for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) stg<NT>(at<float>(so, lane4, f * 256u), s[f]);
-    }
-    if constexpr (KE) ke_block_reduce(ke_lin, ke_rot, ke_partials, ke_stride, ke_out);
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u});
 }
 
 }  // namespace
@@ -1402,6 +1367,15 @@ int ensure_soa_params(hydro_engine* h)
     return h->soa_params_valid ? HYDRO_OK : refresh_soa_params(h);
 }
 
+// the six fields of the engine's plain-SoA previous velocity
+struct PrevRows { float* f[HYDRO_PREV_FIELDS]; };
+inline PrevRows prev_rows(const hydro_engine* h)
+{
+    PrevRows r;
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) r.f[f] = h->prev + f * h->stride;
+    return r;
+}
+
 int ensure_soa_prev(hydro_engine* h)
 {
     if (h->prev) return HYDRO_OK;
@@ -1429,33 +1403,31 @@ constexpr int64_t kNtMinBodies = 131072;
 constexpr int64_t kFusedTemporalMin = 458752, kFusedTemporalMax = 2621440;
 constexpr int64_t kBigBlockMinBodies = 2097152;
 
-template <int BLOCK, int VEC, bool WRITE_PREV, bool WARP>
-void launch_soa_w(hydro_engine* h, const SoaArgs& a, hipStream_t s, bool nt)
+// streaming (non-temporal) accesses: by the size of the launch unless hydro_set_tuning says otherwise
+inline bool streaming(const hydro_engine* h, int64_t n) { return h->nt < 0 ? n >= kNtMinBodies : h->nt != 0; }
+inline bool streaming_fused(const hydro_engine* h, int64_t n)
 {
-    const dim3 grid(grid_for(a.n, BLOCK * VEC)), block(BLOCK);
-    if (h->half_coeffs) {
-        if (nt) hipLaunchKernelGGL((wrench_soa_kernel<BLOCK, VEC, true, WRITE_PREV, true, WARP>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wrench_soa_kernel<BLOCK, VEC, true, WRITE_PREV, false, WARP>), grid, block, 0, s, a);
-    } else {
-        if (nt) hipLaunchKernelGGL((wrench_soa_kernel<BLOCK, VEC, false, WRITE_PREV, true, WARP>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wrench_soa_kernel<BLOCK, VEC, false, WRITE_PREV, false, WARP>), grid, block, 0, s, a);
-    }
+    return h->nt < 0 ? n >= kNtMinBodies && !(n >= kFusedTemporalMin && n <= kFusedTemporalMax) : h->nt != 0;
 }
+inline bool is_warp(const hydro_engine* h) { return h->semantics == HYDRO_SEM_WARP; }
 
-template <int BLOCK, int VEC, bool WRITE_PREV>
-void launch_soa_b(hydro_engine* h, const SoaArgs& a, hipStream_t s, bool nt)
+// Which instantiation of a kernel a launch takes: N run-time flags become N compile-time ones.  f is called once, with a
+// std::true_type or std::false_type per flag in the order of the flags; a generic lambda uses them as template arguments.
+template <typename F> void dispatch_flags(F&& f) { f(); }
+template <typename F, typename... Rest> void dispatch_flags(F&& f, bool b, Rest... rest)
 {
-    if (h->semantics == HYDRO_SEM_WARP) launch_soa_w<BLOCK, VEC, WRITE_PREV, true>(h, a, s, nt);
-    else launch_soa_w<BLOCK, VEC, WRITE_PREV, false>(h, a, s, nt);
+    if (b) dispatch_flags([&](auto... done) { f(std::true_type{}, done...); }, rest...);
+    else dispatch_flags([&](auto... done) { f(std::false_type{}, done...); }, rest...);
 }
 
 template <int VEC, bool WRITE_PREV>
 void launch_soa_n(hydro_engine* h, const SoaArgs& a, hipStream_t s, int64_t n_total)
 {
-    const bool nt = h->nt < 0 ? (n_total >= kNtMinBodies) : (h->nt != 0);
     const int block = h->block ? h->block : (n_total >= kBigBlockMinBodies ? 256 : 128);
-    if (block == 256) launch_soa_b<256, VEC, WRITE_PREV>(h, a, s, nt);
-    else launch_soa_b<128, VEC, WRITE_PREV>(h, a, s, nt);
+    dispatch_flags([&](auto BIG, auto HALF, auto NT, auto WARP) {
+        constexpr int BLOCK = BIG ? 256 : 128;
+        hipLaunchKernelGGL((wrench_soa_kernel<BLOCK, VEC, HALF, WRITE_PREV, NT, WARP>), dim3(grid_for(a.n, BLOCK * VEC)), dim3(BLOCK), 0, s, a);
+    }, block == 256, h->half_coeffs, streaming(h, n_total), is_warp(h));
 }
 
 // args shifted by `off` bodies (for the ragged remainder of a vector launch)
@@ -1488,16 +1460,18 @@ void launch_soa(hydro_engine* h, const SoaArgs& a, hipStream_t s)
     }
 }
 
-// the argument checks of a plain-SoA step that do not involve the previous velocity (shared by hydro_step_wrench, which must
-// pass them before it touches its own copy of it)
-int check_soa_step(hydro_engine* h, int64_t n, const float* const state[], double dt, float* const wrench[])
+// The argument checks of a plain-SoA step, in the order the errors are reported.  with_prev = false leaves the previous
+// velocity out: hydro_step_wrench must pass the others before it touches (allocates, repacks) its own copy of it.
+int check_soa_step(hydro_engine* h, int64_t n, const float* const state[], const float* const prev[], bool with_prev,
+                   double dt, float* const wrench[])
 {
     int rc = check_common(h, n);
     if (rc) return rc;
-    if (!state || !wrench) return fail(h, HYDRO_E_ARG, "null pointer table");
+    if (!state || !wrench || (with_prev && !prev)) return fail(h, HYDRO_E_ARG, "null pointer table");
     if (!(dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
     if (n == 0) return HYDRO_OK;
     for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) if (!state[f]) return fail(h, HYDRO_E_ARG, "null state field");
+    for (int f = 0; with_prev && f < HYDRO_PREV_FIELDS; ++f) if (!prev[f]) return fail(h, HYDRO_E_ARG, "null previous-velocity field");
     for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) if (!wrench[f]) return fail(h, HYDRO_E_ARG, "null wrench field");
     return HYDRO_OK;
 }
@@ -1506,29 +1480,14 @@ template <bool WRITE_PREV>
 int step_soa(hydro_engine* h, int64_t n, const float* const state[], const float* const prev[], float* const prev_out[],
              double dt, float* const wrench[], void* stream)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if (!state || !wrench || !prev) return fail(h, HYDRO_E_ARG, "null pointer table");
-    if (!(dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
-    if (n == 0) return HYDRO_OK;
+    int rc = check_soa_step(h, n, state, prev, true, dt, wrench);
+    if (rc || n == 0) return rc;
     SoaArgs a;
-    int vec = h->vec ? h->vec : 1;
-    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) {
-        if (!state[f]) return fail(h, HYDRO_E_ARG, "null state field");
-        a.st[f] = state[f];
-        while (vec > 1 && !aligned_to(state[f], sizeof(float) * vec)) vec >>= 1;
-    }
-    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) {
-        if (!prev[f]) return fail(h, HYDRO_E_ARG, "null previous-velocity field");
-        a.pv[f] = prev[f];
-        a.pv_out[f] = prev_out ? prev_out[f] : nullptr;
-        while (vec > 1 && !aligned_to(prev[f], sizeof(float) * vec)) vec >>= 1;
-    }
-    for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) {
-        if (!wrench[f]) return fail(h, HYDRO_E_ARG, "null wrench field");
-        a.out[f] = wrench[f];
-        while (vec > 1 && !aligned_to(wrench[f], sizeof(float) * vec)) vec >>= 1;
-    }
+    int vec = h->vec ? h->vec : 1;          // bodies per lane: what every field pointer's alignment allows
+    const auto fit = [&vec](const void* p) { while (vec > 1 && !aligned_to(p, sizeof(float) * vec)) vec >>= 1; };
+    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) { a.st[f] = state[f]; fit(state[f]); }
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) { a.pv[f] = prev[f]; a.pv_out[f] = prev_out ? prev_out[f] : nullptr; fit(prev[f]); }
+    for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) { a.out[f] = wrench[f]; fit(wrench[f]); }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if ((rc = ensure_soa_params(h))) return rc;                    // plain-SoA parameter copies: made on first use
@@ -1674,10 +1633,8 @@ int prev_acquire(hydro_engine* h, hydro_engine::PrevCopy want, int64_t n, hipStr
         if (rc) return rc;
     }
     if (h->prev_current != hydro_engine::kPrevBoth && h->prev_current != want && n > 0) {
-        float* rows[HYDRO_PREV_FIELDS];
-        for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) rows[f] = h->prev + f * h->stride;
         const int64_t m = h->n_params;            // every body that may have been stepped
-        int rc = repack(h, rows, HYDRO_PREV_FIELDS, h->prev_tiled, HYDRO_PREV_FIELDS * HYDRO_TILE, m > n ? m : n,
+        int rc = repack(h, prev_rows(h).f, HYDRO_PREV_FIELDS, h->prev_tiled, HYDRO_PREV_FIELDS * HYDRO_TILE, m > n ? m : n,
                         want == hydro_engine::kPrevTiled, s);
         if (rc) return rc;
     }
@@ -1733,7 +1690,7 @@ int hydro_create(int device, int64_t capacity, hydro_t** out)
     ok = ok && hipMalloc(&h->params_tiled, fbytes * HYDRO_PARAM_FIELDS) == hipSuccess;
     ok = ok && hipMalloc(&h->prev_tiled, fbytes * HYDRO_PREV_FIELDS) == hipSuccess;
     ok = ok && hipMemsetAsync(h->prev_tiled, 0, fbytes * HYDRO_PREV_FIELDS, h->stream) == hipSuccess;
-    // [2][ke_stride] partials + class sums and ticket counters of the reduction (zero between launches, see ke_finish_block)
+    // [2][ke_stride] partials + class sums and ticket counters of the reduction (zero between launches, see ke_block_reduce)
     const size_t ke_bytes = sizeof(double) * 2 * (size_t)h->ke_stride + kKeScratchTailBytes;
     ok = ok && hipMalloc(&h->ke_partials, ke_bytes) == hipSuccess;
     ok = ok && hipMemsetAsync(h->ke_partials, 0, ke_bytes, h->stream) == hipSuccess;
@@ -1769,9 +1726,7 @@ int hydro_reserve_soa(hydro_t* h)
     if (rc) return rc;
     if ((rc = ensure_soa_prev(h))) return rc;
     if (h->prev_current == hydro_engine::kPrevTiled && h->n_params > 0) {      // bring the plain copy up to date
-        float* rows[HYDRO_PREV_FIELDS];
-        for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) rows[f] = h->prev + f * h->stride;
-        if ((rc = repack(h, rows, HYDRO_PREV_FIELDS, h->prev_tiled, HYDRO_PREV_FIELDS * HYDRO_TILE, h->n_params, false, h->stream))) return rc;
+        if ((rc = repack(h, prev_rows(h).f, HYDRO_PREV_FIELDS, h->prev_tiled, HYDRO_PREV_FIELDS * HYDRO_TILE, h->n_params, false, h->stream))) return rc;
         HYDRO_HIP(h, hipStreamSynchronize(h->stream), HYDRO_E_LAUNCH);
         h->prev_current = hydro_engine::kPrevBoth;
     }
@@ -1879,13 +1834,12 @@ int hydro_step_wrench(hydro_t* h, int64_t n, const float* const state[HYDRO_STAT
                       float* const wrench[HYDRO_WRENCH_FIELDS], void* stream)
 {
     // everything that can be refused is refused BEFORE the engine's plain-SoA previous velocity is allocated and repacked
-    int rc = check_soa_step(h, n, state, dt, wrench);
+    int rc = check_soa_step(h, n, state, nullptr, false, dt, wrench);
     if (rc || n == 0) return rc;
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     if ((rc = prev_acquire(h, hydro_engine::kPrevSoa, n, static_cast<hipStream_t>(stream)))) return rc;   // (allocates the plain copy on first use)
-    float* pv[HYDRO_PREV_FIELDS];
-    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = h->prev + f * h->stride;
-    return step_soa<true>(h, n, state, pv, pv, dt, wrench, stream);
+    const PrevRows pv = prev_rows(h);
+    return step_soa<true>(h, n, state, pv.f, pv.f, dt, wrench, stream);
 }
 
 int hydro_step_wrench_ext(hydro_t* h, int64_t n, const float* const state[HYDRO_STATE_FIELDS],
@@ -1913,17 +1867,13 @@ int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t st
     if (!own_prev && (rc = check_tiled(h, n, prev, prev_tile_stride, HYDRO_PREV_FIELDS, "null prev"))) return rc;
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     if (n == 0) return ke_out ? ke_of_nothing(h, ke_out, static_cast<hipStream_t>(stream)) : HYDRO_OK;
-    TiledArgs a;
-    a.st = state; a.st_stride = (uint32_t)state_tile_stride;
-    if (own_prev) { a.pv = h->prev_tiled; a.pv_stride = HYDRO_PREV_FIELDS * HYDRO_TILE; a.pv_out = h->prev_tiled; a.pvo_stride = a.pv_stride; }
-    else { a.pv = prev; a.pv_stride = (uint32_t)prev_tile_stride; a.pv_out = nullptr; a.pvo_stride = 0; }
-    a.prm = h->params_tiled;
-    a.out = wrench; a.out_stride = (uint32_t)wrench_tile_stride;
-    a.rho = h->rho; a.g = h->g; a.warp = h->semantics; a.inv_dt = 1.0 / dt; a.n = (uint32_t)n;
+    // the engine's own previous velocity is read, then overwritten with this step's; the caller's is only read
+    const float* pv = own_prev ? h->prev_tiled : prev;
+    float* pv_out = own_prev ? h->prev_tiled : nullptr;
+    const uint32_t pv_stride = own_prev ? HYDRO_PREV_FIELDS * HYDRO_TILE : (uint32_t)prev_tile_stride, pvo_stride = own_prev ? pv_stride : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (own_prev && (rc = prev_acquire(h, hydro_engine::kPrevTiled, n, s))) return rc;
     if (ke_out && (rc = ke_prepare(h, s))) return rc;
-    const bool nt = h->nt < 0 ? (n >= kNtMinBodies) : (h->nt != 0);
     const int block = (h->block && !ke_out) ? h->block : 256;               // (the energy partials are one per 256 bodies)
     const dim3 grid(grid_for(n, block)), blk(block);
     // Occupancy shaping: the kernel uses no LDS, so a dynamic-LDS request is a pure residency cap
@@ -1935,31 +1885,25 @@ int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t st
         lds = blocks_per_cu > 0 ? ((size_t)160 * 1024 / (size_t)blocks_per_cu) & ~(size_t)255 : 0;
         if (lds > 64 * 1024) lds = 64 * 1024;                               // per-block LDS limit
     }
-#define HYDRO_TILED_ARGS a.st, a.pv, a.prm, a.out, a.pv_out, a.st_stride, a.pv_stride, a.out_stride, a.pvo_stride, a.n, a.warp, a.rho, a.g, a.inv_dt, \
-        h->ke_partials, h->ke_stride, ke_rotational, ke_out
-#define HYDRO_TILED_LAUNCH(BLOCK, HALF, WP, NT) do { if (a.warp) hipLaunchKernelGGL((wrench_tiled_kernel<BLOCK, HALF, WP, NT, false, true>), grid, blk, lds, s, HYDRO_TILED_ARGS); \
-        else hipLaunchKernelGGL((wrench_tiled_kernel<BLOCK, HALF, WP, NT, false, false>), grid, blk, lds, s, HYDRO_TILED_ARGS); } while (0)
-#define HYDRO_TILED_NT(BLOCK, HALF, WP) do { if (nt) HYDRO_TILED_LAUNCH(BLOCK, HALF, WP, true); else HYDRO_TILED_LAUNCH(BLOCK, HALF, WP, false); } while (0)
-#define HYDRO_TILED_WP(BLOCK, HALF) do { if (own_prev) HYDRO_TILED_NT(BLOCK, HALF, true); else HYDRO_TILED_NT(BLOCK, HALF, false); } while (0)
-#define HYDRO_TILED_HALF(BLOCK) do { if (h->half_coeffs) HYDRO_TILED_WP(BLOCK, true); else HYDRO_TILED_WP(BLOCK, false); } while (0)
-    if (ke_out) {
-        // the sampling variant: same body, same bits, plus one fp64 pair per block and the fixed-order final sum (same launch)
-#define HYDRO_TILED_KE_W(HALF, WP, WARP) do { if (nt) hipLaunchKernelGGL((wrench_tiled_kernel<256, HALF, WP, true, true, WARP>), grid, blk, lds, s, HYDRO_TILED_ARGS); \
-                                              else hipLaunchKernelGGL((wrench_tiled_kernel<256, HALF, WP, false, true, WARP>), grid, blk, lds, s, HYDRO_TILED_ARGS); } while (0)
-#define HYDRO_TILED_KE(HALF, WP) do { if (a.warp) HYDRO_TILED_KE_W(HALF, WP, true); else HYDRO_TILED_KE_W(HALF, WP, false); } while (0)
-        if (h->half_coeffs) { if (own_prev) HYDRO_TILED_KE(true, true); else HYDRO_TILED_KE(true, false); }
-        else { if (own_prev) HYDRO_TILED_KE(false, true); else HYDRO_TILED_KE(false, false); }
-#undef HYDRO_TILED_KE
-#undef HYDRO_TILED_KE_W
-    }
-    else if (block == 128) HYDRO_TILED_HALF(128); else HYDRO_TILED_HALF(256);
-#undef HYDRO_TILED_HALF
-#undef HYDRO_TILED_WP
-#undef HYDRO_TILED_NT
-#undef HYDRO_TILED_LAUNCH
-#undef HYDRO_TILED_ARGS
+    // ke_out: the sampling variant - same body, same bits, plus one fp64 pair per block and the fixed-order final sum (same
+    // launch).  It exists for 256-thread blocks only, which is what `block` is whenever it is asked for.
+    dispatch_flags([&](auto BIG, auto HALF, auto WP, auto NT, auto KE, auto WARP) {
+        if constexpr (BIG || !KE)
+            hipLaunchKernelGGL((wrench_tiled_kernel<BIG ? 256 : 128, HALF, WP, NT, KE, WARP>), grid, blk, lds, s,
+                               state, pv, h->params_tiled, wrench, pv_out, (uint32_t)state_tile_stride, pv_stride, (uint32_t)wrench_tile_stride, pvo_stride,
+                               (uint32_t)n, h->semantics, h->rho, h->g, 1.0 / dt, h->ke_partials, h->ke_stride, ke_rotational, ke_out);
+    }, block == 256, h->half_coeffs, own_prev, streaming(h, n), ke_out != nullptr, is_warp(h));
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
+}
+
+// hydro_step_wrench_tiled_batch with a kernarg table of K scenes
+template <int K>
+void launch_batch(const BatchArgs<K>& table, const hydro_engine* h0, bool own_prev, bool nt, uint32_t blocks, hipStream_t s)
+{
+    dispatch_flags([&](auto HALF, auto WP, auto NT, auto WARP) {
+        hipLaunchKernelGGL((wrench_tiled_batch_kernel<K, HALF, WP, NT, WARP>), dim3(blocks), dim3(kBlock), 0, s, table);
+    }, h0->half_coeffs, own_prev, nt, is_warp(h0));
 }
 }  // namespace
 
@@ -2028,22 +1972,14 @@ int hydro_step_wrench_tiled_batch(int count, const hydro_scene_t* scenes, double
             int rc = prev_acquire(scenes[k].engine, hydro_engine::kPrevTiled, scenes[k].n, s);
             if (rc) return rc;
         }
-    const bool nt = h0->nt < 0 ? (bodies >= kNtMinBodies) : (h0->nt != 0);       // streaming accesses by the size of the LAUNCH
-    const dim3 grid((uint32_t)blocks), blk(kBlock);
-    BatchArgs<4> small{};                                        // up to four scenes: the short table (see the kernel)
-    if (count <= 4) {
+    const bool nt = streaming(h0, bodies);                      // streaming accesses by the size of the LAUNCH
+    if (count <= 4) {                                            // up to four scenes: the short table (see the kernel)
+        BatchArgs<4> small{};
         for (int k = 0; k < 4; ++k) { small.first_block[k] = args.first_block[k]; small.sc[k] = args.sc[k < count ? k : 0]; }
         small.inv_dt = args.inv_dt;
+        launch_batch(small, h0, own_prev, nt, (uint32_t)blocks, s);
     }
-#define HYDRO_BATCH_K(HALF, WP, NT, W) do { if (count <= 4) hipLaunchKernelGGL((wrench_tiled_batch_kernel<4, HALF, WP, NT, W>), grid, blk, 0, s, small); \
-                                            else hipLaunchKernelGGL((wrench_tiled_batch_kernel<HYDRO_BATCH_MAX, HALF, WP, NT, W>), grid, blk, 0, s, args); } while (0)
-#define HYDRO_BATCH_W(HALF, WP, NT) do { if (h0->semantics) HYDRO_BATCH_K(HALF, WP, NT, true); else HYDRO_BATCH_K(HALF, WP, NT, false); } while (0)
-#define HYDRO_BATCH_NT(HALF, WP) do { if (nt) HYDRO_BATCH_W(HALF, WP, true); else HYDRO_BATCH_W(HALF, WP, false); } while (0)
-    if (h0->half_coeffs) { if (own_prev) HYDRO_BATCH_NT(true, true); else HYDRO_BATCH_NT(true, false); }
-    else { if (own_prev) HYDRO_BATCH_NT(false, true); else HYDRO_BATCH_NT(false, false); }
-#undef HYDRO_BATCH_NT
-#undef HYDRO_BATCH_W
-#undef HYDRO_BATCH_K
+    else launch_batch(args, h0, own_prev, nt, (uint32_t)blocks, s);
     HYDRO_HIP(h0, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }
@@ -2091,29 +2027,14 @@ int step_fused_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t sta
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n == 0) return ke_out ? ke_of_nothing(h, ke_out, s) : HYDRO_OK;
-    FusedArgs fa;
-    TiledArgs& a = fa.t;
-    a.st = state; a.st_stride = (uint32_t)state_tile_stride;
-    a.pv = prev; a.pv_stride = (uint32_t)prev_tile_stride; a.pv_out = nullptr; a.pvo_stride = 0;
-    a.prm = h->params_tiled;
-    a.out = wrench; a.out_stride = wrench ? (uint32_t)wrench_tile_stride : 0;
-    a.rho = h->rho; a.g = h->g; a.warp = h->semantics; a.inv_dt = 1.0 / dt; a.n = (uint32_t)n;
-    fa.so = state_out; fa.so_stride = (uint32_t)out_tile_stride; fa.dt = (float)dt;
     if (ke_out && (rc = ke_prepare(h, s))) return rc;
-    const bool nt = h->nt < 0 ? (n >= kNtMinBodies && !(n >= kFusedTemporalMin && n <= kFusedTemporalMax)) : (h->nt != 0);
     const dim3 grid(grid_for(n, kBlock)), blk(kBlock);
-#define HYDRO_FUSED_ARGS a.st, a.pv, a.prm, fa.so, a.out, a.st_stride, a.pv_stride, fa.so_stride, a.out_stride, a.n, a.warp, fa.dt, a.rho, a.g, a.inv_dt, \
-        h->ke_partials, h->ke_stride, ke_rotational, ke_out
-#define HYDRO_FUSED_W(HALF, NT, KE, WARP) do { if (implicit_drag) hipLaunchKernelGGL((step_fused_tiled_kernel<HALF, NT, true, KE, WARP>), grid, blk, 0, s, HYDRO_FUSED_ARGS); \
-                                               else hipLaunchKernelGGL((step_fused_tiled_kernel<HALF, NT, false, KE, WARP>), grid, blk, 0, s, HYDRO_FUSED_ARGS); } while (0)
-#define HYDRO_FUSED_I(HALF, NT, KE) do { if (a.warp) HYDRO_FUSED_W(HALF, NT, KE, true); else HYDRO_FUSED_W(HALF, NT, KE, false); } while (0)
-#define HYDRO_FUSED(HALF, NT) do { if (ke_out) HYDRO_FUSED_I(HALF, NT, true); else HYDRO_FUSED_I(HALF, NT, false); } while (0)
-    if (h->half_coeffs) { if (nt) HYDRO_FUSED(true, true); else HYDRO_FUSED(true, false); }
-    else { if (nt) HYDRO_FUSED(false, true); else HYDRO_FUSED(false, false); }
-#undef HYDRO_FUSED
-#undef HYDRO_FUSED_I
-#undef HYDRO_FUSED_W
-#undef HYDRO_FUSED_ARGS
+    dispatch_flags([&](auto HALF, auto NT, auto IMPL, auto KE, auto WARP) {
+        hipLaunchKernelGGL((step_fused_tiled_kernel<HALF, NT, IMPL, KE, WARP>), grid, blk, 0, s,
+                           state, prev, h->params_tiled, state_out, wrench, (uint32_t)state_tile_stride, (uint32_t)prev_tile_stride, (uint32_t)out_tile_stride,
+                           wrench ? (uint32_t)wrench_tile_stride : 0u, (uint32_t)n, h->semantics, (float)dt, h->rho, h->g, 1.0 / dt,
+                           h->ke_partials, h->ke_stride, ke_rotational, ke_out);
+    }, h->half_coeffs, streaming_fused(h, n), implicit_drag != 0, ke_out != nullptr, is_warp(h));
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }
@@ -2171,28 +2092,19 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (rows_written_host) *rows_written_host = n == 0 ? 0 : rows;
     if (n == 0) return ke_out_dev ? ke_of_nothing(h, ke_out_dev, s) : HYDRO_OK;
-    const double inv_dt = 1.0 / dt;
-    const float dtf = (float)dt;
-    const bool nt = h->nt < 0 ? (n >= kNtMinBodies && !(n >= kFusedTemporalMin && n <= kFusedTemporalMax)) : (h->nt != 0);
     const dim3 grid(grid_for(n, kBlock)), blk(kBlock);
-    const int ke_rot = rotational ? 1 : 0;
     if (ke_out_dev && (rc = ke_prepare(h, s))) return rc;
-#define HYDRO_MULTI_ARGS state, prev, h->params_tiled, state_out, prev_out, (uint32_t)state_tile_stride, (uint32_t)prev_tile_stride, (uint32_t)out_tile_stride, \
-        (uint32_t)prev_out_tile_stride, (uint32_t)n, (uint32_t)steps, dtf, h->rho, h->g, inv_dt, h->ke_partials, h->ke_stride, ke_rot, ke_out_dev
-#define HYDRO_MULTI_REC_ARGS HYDRO_MULTI_ARGS, rec->mask, rec->first, rec->log, rec->stride, rec->fields, rec->every, rec->phase, rec->row0
-#define HYDRO_MULTI_R(HALF, NT, IMPL, KE, WARP) do { if (rec) hipLaunchKernelGGL((step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>), grid, blk, 0, s, HYDRO_MULTI_REC_ARGS); \
-                                                     else hipLaunchKernelGGL((step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>), grid, blk, 0, s, HYDRO_MULTI_ARGS); } while (0)
-#define HYDRO_MULTI_W(HALF, NT, KE, WARP) do { if (implicit_drag) HYDRO_MULTI_R(HALF, NT, true, KE, WARP); else HYDRO_MULTI_R(HALF, NT, false, KE, WARP); } while (0)
-#define HYDRO_MULTI_I(HALF, NT, KE) do { if (h->semantics) HYDRO_MULTI_W(HALF, NT, KE, true); else HYDRO_MULTI_W(HALF, NT, KE, false); } while (0)
-#define HYDRO_MULTI(HALF, NT) do { if (ke_out_dev) HYDRO_MULTI_I(HALF, NT, true); else HYDRO_MULTI_I(HALF, NT, false); } while (0)
-    if (h->half_coeffs) { if (nt) HYDRO_MULTI(true, true); else HYDRO_MULTI(true, false); }
-    else { if (nt) HYDRO_MULTI(false, true); else HYDRO_MULTI(false, false); }
-#undef HYDRO_MULTI
-#undef HYDRO_MULTI_I
-#undef HYDRO_MULTI_W
-#undef HYDRO_MULTI_R
-#undef HYDRO_MULTI_REC_ARGS
-#undef HYDRO_MULTI_ARGS
+    dispatch_flags([&](auto HALF, auto NT, auto IMPL, auto KE, auto WARP) {
+        // the arguments both kernels take, then the launch of one of them
+        const auto launch = [&](auto kernel, auto... recorder) {
+            hipLaunchKernelGGL(kernel, grid, blk, 0, s, state, prev, h->params_tiled, state_out, prev_out,
+                               (uint32_t)state_tile_stride, (uint32_t)prev_tile_stride, (uint32_t)out_tile_stride, (uint32_t)prev_out_tile_stride,
+                               (uint32_t)n, (uint32_t)steps, (float)dt, h->rho, h->g, 1.0 / dt, h->ke_partials, h->ke_stride, rotational ? 1 : 0, ke_out_dev,
+                               recorder...);
+        };
+        if (rec) launch(step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>, rec->mask, rec->first, rec->log, rec->stride, rec->fields, rec->every, rec->phase, rec->row0);
+        else launch(step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+    }, h->half_coeffs, streaming_fused(h, n), implicit_drag != 0, ke_out_dev != nullptr, is_warp(h));
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }
@@ -2342,22 +2254,14 @@ int hydro_step_wrench_aos(hydro_t* h, int64_t n, const float* positions, const f
         !aligned_to(forces, 16) || !aligned_to(torques, 16))
         return fail(h, HYDRO_E_ARG, "array-of-structs tensors must be 16-byte aligned");
     if (n == 0) return HYDRO_OK;
-    AosArgs a;
-    a.pos = positions; a.quat = orientations; a.quat_xyzw = quat_xyzw ? 1 : 0; a.vel = velocities; a.force = forces; a.torque = torques;
-    a.pv = h->prev_tiled; a.prm = h->params_tiled;
-    a.rho = h->rho; a.g = h->g; a.warp = h->semantics; a.inv_dt = 1.0 / dt; a.n = n;
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if ((rc = prev_acquire(h, hydro_engine::kPrevTiled, n, s))) return rc;
-    const int grid = grid_for(n, kBlock);
-    const bool nt = h->nt < 0 ? (n >= kNtMinBodies) : (h->nt != 0);
-#define HYDRO_AOS_ARGS a.pos, a.quat, a.vel, a.force, a.torque, a.pv, a.prm, a.quat_xyzw, (uint32_t)a.n, a.warp, a.rho, a.g, a.inv_dt
-#define HYDRO_AOS_W(HALF, NT) do { if (a.warp) hipLaunchKernelGGL((wrench_aos_direct_kernel<HALF, NT, true>), dim3(grid), dim3(kBlock), 0, s, HYDRO_AOS_ARGS); \
-                                   else hipLaunchKernelGGL((wrench_aos_direct_kernel<HALF, NT, false>), dim3(grid), dim3(kBlock), 0, s, HYDRO_AOS_ARGS); } while (0)
-    if (h->half_coeffs) { if (nt) HYDRO_AOS_W(true, true); else HYDRO_AOS_W(true, false); }
-    else { if (nt) HYDRO_AOS_W(false, true); else HYDRO_AOS_W(false, false); }
-#undef HYDRO_AOS_W
-#undef HYDRO_AOS_ARGS
+    dispatch_flags([&](auto HALF, auto NT, auto WARP) {
+        hipLaunchKernelGGL((wrench_aos_direct_kernel<HALF, NT, WARP>), dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
+                           positions, orientations, velocities, forces, torques, h->prev_tiled, h->params_tiled, quat_xyzw ? 1 : 0, (uint32_t)n,
+                           h->semantics, h->rho, h->g, 1.0 / dt);
+    }, h->half_coeffs, streaming(h, n), is_warp(h));
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }

@@ -657,7 +657,7 @@ def test_batched_scenes_in_one_launch_give_the_bits_of_single_launches(coeff, ow
     previous velocity: every scene's wrench (and, engine-owned, its stored previous velocity) has the bits of its own
     hydro_step_wrench_tiled call."""
     sizes = [4096, 1, 257, 100003, 63, 1000]
-    engines, states, prevs, refs, host_prev = [], [], [], [], []
+    engines, states, prevs, refs, host_prev, first_prev = [], [], [], [], [], []
     for k, n in enumerate(sizes):
         sc = scenes.scene_c4(n=n, seed=100 + k)
         eng = HydroEngine(n, DEV, 1000.0 + 5.0 * k, 9.81 - 0.01 * k)               # scene scalars differ
@@ -669,12 +669,23 @@ def test_batched_scenes_in_one_launch_give_the_bits_of_single_launches(coeff, ow
             eng.set_prev_velocity(sc.prev)
         else:
             refs.append(eng.step_wrench_tiled(st, n, sc.dt, prev=pv).clone())
-        engines.append(eng); states.append(st); prevs.append(pv); host_prev.append(sc.state[:, 7:13])
+        engines.append(eng); states.append(st); prevs.append(pv); host_prev.append(sc.state[:, 7:13]); first_prev.append(sc.prev)
     dt = scenes.scene_c4(n=1).dt
     outs = HydroEngine.step_wrench_tiled_batch(engines, states, dt, prevs=None if own_prev else prevs)
     torch.cuda.synchronize()
     for k, (o, r) in enumerate(zip(outs, refs)):
         assert torch.equal(o, r), f"scene {k} ({sizes[k]} bodies)"
+        if own_prev:
+            assert np.array_equal(engines[k].get_prev_velocity().cpu().numpy().T, host_prev[k])
+    # a launch of at most four scenes takes the short kernarg table, a kernel instantiation of its own: same bits
+    few = 3
+    if own_prev:
+        for k in range(few):
+            engines[k].set_prev_velocity(first_prev[k])
+    outs_few = HydroEngine.step_wrench_tiled_batch(engines[:few], states[:few], dt, prevs=None if own_prev else prevs[:few])
+    torch.cuda.synchronize()
+    for k in range(few):
+        assert torch.equal(outs_few[k], refs[k]), f"short table, scene {k} ({sizes[k]} bodies)"
         if own_prev:
             assert np.array_equal(engines[k].get_prev_velocity().cpu().numpy().T, host_prev[k])
     # prepared form: re-issued, follows the buffers' contents; the previous STATE buffer's velocity fields serve as prev
