@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """DEV-ONLY: host cost of one step call (4 096 bodies) - engine method vs the raw ctypes call with prebuilt
-arguments vs HIP-graph replay.   python scripts/diag_launch_overhead.py"""
+arguments vs the prepared call, then the calls the closed loop (fused steps) and the plugin (prepared
+array-of-structs step, 20 bodies) issue.   python scripts/diag_launch_overhead.py"""
 import ctypes, os, sys, time
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -40,3 +41,17 @@ with torch.cuda.stream(stream):
         step = eng.prepare_step_wrench_tiled(S, sc.n, sc.dt, out=O, prev=P, stream=stream)
         c = bench(step)
         print(f"prepared step                 host issue {c[0]:6.2f} us/call   wall {c[1]:6.2f} us/step")
+    # the closed loop's unprepared calls: two state buffers in ping-pong (the result is not looked at)
+    S2 = S.clone()
+    d = bench(lambda: eng.step_fused_tiled(S, S2, sc.n, sc.dt))
+    print(f"engine.step_fused_tiled       host issue {d[0]:6.2f} us/call   wall {d[1]:6.2f} us/step")
+    e = bench(lambda: eng.step_fused_tiled_multi(S, S2, sc.n, sc.dt, 1))
+    print(f"engine.step_fused_tiled_multi host issue {e[0]:6.2f} us/call   wall {e[1]:6.2f} us/step")
+    # the plugin's call: 20 bodies on the simulator's tensors, prepared once, stream = the current one at each call
+    m = 20
+    eng20 = HydroEngine(m, dev, sc.rho, sc.g); eng20.set_params(sc.params[:m])
+    st = torch.from_numpy(sc.state[:m]).to(dev)
+    pos, ori, vel = st[:, 0:3].contiguous(), st[:, 3:7].contiguous(), st[:, 7:13].contiguous()
+    aos = eng20.prepare_step_wrench_aos(pos, ori, vel)
+    f = bench(lambda: aos(sc.dt))
+    print(f"prepared step_wrench_aos (20) host issue {f[0]:6.2f} us/call   wall {f[1]:6.2f} us/step")

@@ -28,10 +28,9 @@ class Scene(ctypes.Structure):
                 ("wrench", c_void_p), ("wrench_tile_stride", c_int64)]
 
 
-HYDRO_OK = 0
+HYDRO_OK, HYDRO_E_ARG, HYDRO_E_ALLOC, HYDRO_E_LAUNCH, HYDRO_E_DEVICE, HYDRO_E_STATE = 0, -1, -2, -3, -4, -5
 HYDRO_SEM_NUMBA, HYDRO_SEM_WARP = 0, 1
-STATUS_NAMES = {0: "HYDRO_OK", -1: "HYDRO_E_ARG", -2: "HYDRO_E_ALLOC", -3: "HYDRO_E_LAUNCH",
-                -4: "HYDRO_E_DEVICE", -5: "HYDRO_E_STATE"}
+STATUS_NAMES = {v: k for k, v in list(globals().items()) if k == "HYDRO_OK" or k.startswith("HYDRO_E_")}
 
 # every symbol include/hydro.h declares: (restype, argtypes)
 _FP = POINTER(c_void_p)      # table of field pointers (const float *const [N])

@@ -7,6 +7,12 @@ there is no CPU or eager-PyTorch fallback.
 
 Layouts: "SoA" tensors are contiguous `(F, N)` float32 device tensors - row f is
 field f (orders in include/hydro.h).
+
+Each rule for turning a Python argument into C arguments is written once: `_tiled` (a tiled buffer ->
+pointer, tile stride), `_prev_velocity` (None / state buffer / 6-field buffer), `_wrench_tiled_call` and
+`_wrench_aos_call` (the direct and the prepared form of a step share one argument list), `_fused_head`
+(the three fused steps) and `_rows` / `_force_torque` (simulator tensors).  tests/test_engine_calls.py
+pins the resulting calls without a GPU.
 """
 from __future__ import annotations
 
@@ -21,6 +27,13 @@ from ._native import HydroError
 
 log = logging.getLogger("silver2_isaacsim_amd")
 _warp_mode_announced = False
+_VEL_BYTES = 7 * nat.TILE * 4          # where the six velocity fields start inside a state tile
+
+
+def _prebuilt(name: str, args, first: int = 0) -> tuple:
+    """`args` (arguments `first`, `first` + 1, ... of C function `name`) as the ctypes values its prototype would
+    convert them to on every call: a prepared launch builds them once."""
+    return tuple(a if isinstance(a, ctypes.c_void_p) else t(a) for t, a in zip(nat.SIGNATURES[name][1][first:], args))
 
 
 def _as_soa_tensor(x, fields: int, device: torch.device) -> torch.Tensor:
@@ -171,31 +184,58 @@ class HydroEngine:
         """Zeroed (tiles, fields, 64) float32 buffer: body i, field f at [i // 64, f, i % 64]."""
         return torch.zeros((self.tiles(n), fields, nat.TILE), dtype=torch.float32, device=self.device)
 
-    def _check_tiled(self, t: torch.Tensor, fields: int, n: int) -> None:
+    def _tiled(self, t: torch.Tensor, fields: int, n: int):
+        """Validate a (>= tiles(n), fields, 64) buffer - the last test reads "fewer than tiles(n) tiles" - and return its
+        (address, tile stride in floats)."""
         if (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.ndim != 3
-                or t.shape[1] != fields or t.shape[2] != nat.TILE or t.shape[0] < self.tiles(n)):
+                or t.shape[1] != fields or t.shape[2] != nat.TILE or t.shape[0] * nat.TILE < n):
             raise ValueError(f"expected contiguous float32 (>= {self.tiles(n)}, {fields}, {nat.TILE}) tensor on {self.device}")
+        return t.data_ptr(), fields * nat.TILE
+
+    def _prev_velocity(self, prev: torch.Tensor | None, n: int):
+        """(address, tile stride) of a step's previous velocity: None = engine-owned; a 13-field STATE buffer = its six
+        velocity fields, in place; anything else is held to be a 6-field buffer."""
+        if prev is None:
+            return None, 0
+        if prev.shape[1] == nat.STATE_FIELDS:
+            ptr, stride = self._tiled(prev, nat.STATE_FIELDS, n)
+            return ptr + _VEL_BYTES, stride
+        return self._tiled(prev, nat.PREV_FIELDS, n)
 
     def to_tiled(self, soa: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         """(F,N) plain SoA -> (tiles,F,64) tiled, on device (hydro_repack)."""
         f, n = soa.shape
         if out is None:
             out = self.alloc_tiled(f, n)
-        self._check_tiled(out, f, n)
-        self._check(self._lib.hydro_repack(self._h, n, f, self._table(soa, f), out.data_ptr(), f * nat.TILE, 1, self._stream(stream)))
+        ptr, stride = self._tiled(out, f, n)
+        self._check(self._lib.hydro_repack(self._h, n, f, self._table(soa, f), ptr, stride, 1, self._stream(stream)))
         return out
 
     def from_tiled(self, tiled: torch.Tensor, n: int, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         f = tiled.shape[1]
-        self._check_tiled(tiled, f, n)
+        ptr, stride = self._tiled(tiled, f, n)
         if out is None:
             out = torch.empty((f, n), dtype=torch.float32, device=self.device)
-        self._check(self._lib.hydro_repack(self._h, n, f, self._table(out, f), tiled.data_ptr(), f * nat.TILE, 0, self._stream(stream)))
+        self._check(self._lib.hydro_repack(self._h, n, f, self._table(out, f), ptr, stride, 0, self._stream(stream)))
         return out
 
     def _check_ke_out(self, ke_out: torch.Tensor) -> None:
         if ke_out.dtype != torch.float64 or ke_out.device != self.device or ke_out.numel() < 2 or not ke_out.is_contiguous():
             raise ValueError(f"ke_out: expected a contiguous float64 tensor of 2 elements on {self.device}")
+
+    def _wrench_tiled_call(self, state, n, dt, out, prev, stream, ke_out, rotational):
+        """(name, args, out) of one `hydro_step_wrench_tiled[_ke]` launch: the buffers validated, `out` allocated when
+        None, the stream resolved now."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
+        p_ptr, p_stride = self._prev_velocity(prev, n)
+        args = (self._h, n, s_ptr, s_stride, p_ptr, p_stride, float(dt), o_ptr, o_stride)
+        if ke_out is None:
+            return "hydro_step_wrench_tiled", args + (self._stream(stream),), out
+        self._check_ke_out(ke_out)                      # the variant that samples the kinetic energy of `state` on the way
+        return "hydro_step_wrench_tiled_ke", args + (int(bool(rotational)), ke_out.data_ptr(), self._stream(stream)), out
 
     def step_wrench_tiled(self, state: torch.Tensor, n: int, dt: float, out: torch.Tensor | None = None,
                           prev: torch.Tensor | None = None, stream=None, ke_out: torch.Tensor | None = None,
@@ -206,65 +246,26 @@ class HydroEngine:
         pass the previous step's state buffer - nothing is copied).
         ke_out (float64, 2 elements, on the device): the kernel also samples the kinetic energy of `state` - the
         bodies it holds in registers anyway, no second pass - into ke_out[0:2] = [translational, rotational]."""
-        self._check_tiled(state, nat.STATE_FIELDS, n)
-        if out is None:
-            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
-        self._check_tiled(out, nat.WRENCH_FIELDS, n)
-        if prev is None:
-            p_ptr, p_stride = None, 0
-        elif prev.shape[1] == nat.STATE_FIELDS:
-            self._check_tiled(prev, nat.STATE_FIELDS, n)
-            p_ptr, p_stride = prev.data_ptr() + 7 * nat.TILE * 4, nat.STATE_FIELDS * nat.TILE
-        else:
-            self._check_tiled(prev, nat.PREV_FIELDS, n)
-            p_ptr, p_stride = prev.data_ptr(), nat.PREV_FIELDS * nat.TILE
-        if ke_out is None:
-            self._check(self._lib.hydro_step_wrench_tiled(
-                self._h, n, state.data_ptr(), nat.STATE_FIELDS * nat.TILE, p_ptr, p_stride, float(dt),
-                out.data_ptr(), nat.WRENCH_FIELDS * nat.TILE, self._stream(stream)))
-        else:
-            self._check_ke_out(ke_out)
-            self._check(self._lib.hydro_step_wrench_tiled_ke(
-                self._h, n, state.data_ptr(), nat.STATE_FIELDS * nat.TILE, p_ptr, p_stride, float(dt),
-                out.data_ptr(), nat.WRENCH_FIELDS * nat.TILE, int(bool(rotational)), ke_out.data_ptr(), self._stream(stream)))
+        name, args, out = self._wrench_tiled_call(state, n, dt, out, prev, stream, ke_out, rotational)
+        self._check(getattr(self._lib, name)(*args))
         return out
 
     def prepare_step_wrench_tiled(self, state: torch.Tensor, n: int, dt: float, out: torch.Tensor | None = None,
                                   prev: torch.Tensor | None = None, stream=None, ke_out: torch.Tensor | None = None,
                                   rotational: bool = True):
-        """Validate the arguments of `step_wrench_tiled` ONCE and return a zero-argument callable that issues
-        that launch again (same buffers, same stream - the one current now if `stream` is None).  For step
-        loops over small scenes, where the per-call Python work (shape checks, ctypes conversions: ~10 us)
-        exceeds the kernel (~3 us at 4 096 bodies): the prepared call costs ~4 us of host time.  The callable
-        returns `out`; errors raise HydroError as usual."""
-        self._check_tiled(state, nat.STATE_FIELDS, n)
-        if out is None:
-            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
-        self._check_tiled(out, nat.WRENCH_FIELDS, n)
-        if prev is None:
-            p_ptr, p_stride = None, 0
-        elif prev.shape[1] == nat.STATE_FIELDS:
-            self._check_tiled(prev, nat.STATE_FIELDS, n)
-            p_ptr, p_stride = prev.data_ptr() + 7 * nat.TILE * 4, nat.STATE_FIELDS * nat.TILE
-        else:
-            self._check_tiled(prev, nat.PREV_FIELDS, n)
-            p_ptr, p_stride = prev.data_ptr(), nat.PREV_FIELDS * nat.TILE
-        args = (self._h, ctypes.c_int64(n), ctypes.c_void_p(state.data_ptr()), ctypes.c_int64(nat.STATE_FIELDS * nat.TILE),
-                ctypes.c_void_p(p_ptr), ctypes.c_int64(p_stride), ctypes.c_double(float(dt)),
-                ctypes.c_void_p(out.data_ptr()), ctypes.c_int64(nat.WRENCH_FIELDS * nat.TILE))
-        if ke_out is None:
-            fn = self._lib.hydro_step_wrench_tiled
-            args = args + (self._stream(stream),)
-        else:                                           # the variant that samples the kinetic energy of `state` on the way
-            self._check_ke_out(ke_out)
-            fn = self._lib.hydro_step_wrench_tiled_ke
-            args = args + (ctypes.c_int(int(bool(rotational))), ctypes.c_void_p(ke_out.data_ptr()), self._stream(stream))
+        """Build the launch of `step_wrench_tiled` ONCE (same validation, same arguments: `_wrench_tiled_call`) and
+        return a zero-argument callable that issues it again (same buffers, same stream - the one current now if
+        `stream` is None).  For step loops over small scenes, where the per-call Python work (shape checks, ctypes
+        conversions: ~10 us) exceeds the kernel (~3 us at 4 096 bodies): the prepared call costs ~4 us of host time.
+        The callable returns `out`; errors raise HydroError as usual."""
+        name, args, out = self._wrench_tiled_call(state, n, dt, out, prev, stream, ke_out, rotational)
+        fn, args = getattr(self._lib, name), _prebuilt(name, args)
         keep = (state, prev, out, ke_out)               # the buffers must outlive the callable
         check = self._check
 
         def step():
             if self._h is None:                         # engine closed: the captured handle is gone
-                raise HydroError(-5, "engine is closed")
+                raise HydroError(nat.HYDRO_E_STATE, "engine is closed")
             rc = fn(*args)
             if rc:
                 check(rc)
@@ -286,23 +287,13 @@ class HydroEngine:
         arr = (nat.Scene * k)()
         keep = []
         for i, (e, st, n, out) in enumerate(zip(engines, states, ns, outs)):
-            e._check_tiled(st, nat.STATE_FIELDS, n)
-            e._check_tiled(out, nat.WRENCH_FIELDS, n)
             sc = arr[i]
             sc.engine, sc.n = e._h, n
-            sc.state, sc.state_tile_stride = st.data_ptr(), st.shape[1] * nat.TILE
-            sc.wrench, sc.wrench_tile_stride = out.data_ptr(), out.shape[1] * nat.TILE
-            if prevs is None:
-                sc.prev, sc.prev_tile_stride = None, 0
-            else:
-                pv = prevs[i]
-                if pv.shape[1] == nat.STATE_FIELDS:                 # a previous STATE buffer: its six velocity fields
-                    e._check_tiled(pv, nat.STATE_FIELDS, n)
-                    sc.prev, sc.prev_tile_stride = pv.data_ptr() + 7 * nat.TILE * 4, nat.STATE_FIELDS * nat.TILE
-                else:
-                    e._check_tiled(pv, nat.PREV_FIELDS, n)
-                    sc.prev, sc.prev_tile_stride = pv.data_ptr(), nat.PREV_FIELDS * nat.TILE
-                keep.append(pv)
+            sc.state, sc.state_tile_stride = e._tiled(st, nat.STATE_FIELDS, n)
+            sc.wrench, sc.wrench_tile_stride = e._tiled(out, nat.WRENCH_FIELDS, n)
+            if prevs is not None:                                   # else NULL, 0: every engine's own
+                sc.prev, sc.prev_tile_stride = e._prev_velocity(prevs[i], n)
+                keep.append(prevs[i])
             keep += [st, out]
         first = engines[0]
         fn, dtc = first._lib.hydro_step_wrench_tiled_batch, ctypes.c_double(dt)
@@ -322,6 +313,16 @@ class HydroEngine:
         step()
         return outs
 
+    def _fused_head(self, state, prev_state, n, dt, state_out):
+        """What the three fused steps share: the state buffers validated, `state_out` defaulted to `prev_state`.
+        Returns (state_out, the tile stride of a state buffer, the leading C arguments up to `dt`)."""
+        s_ptr, st = self._tiled(state, nat.STATE_FIELDS, n)
+        p_ptr, _ = self._tiled(prev_state, nat.STATE_FIELDS, n)
+        if state_out is None:
+            state_out = prev_state
+        self._tiled(state_out, nat.STATE_FIELDS, n)
+        return state_out, st, (self._h, n, s_ptr, st, p_ptr + _VEL_BYTES, st, float(dt))
+
     def step_fused_tiled(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float,
                          state_out: torch.Tensor | None = None, wrench: torch.Tensor | None = None,
                          implicit_drag: bool = False, stream=None, ke_out: torch.Tensor | None = None,
@@ -329,27 +330,26 @@ class HydroEngine:
         """Wrench + integrator in one kernel.  `prev_state` (tiles,13,64) supplies the previous velocity;
         `state_out` defaults to `prev_state` itself (ping-pong: the old buffer receives the new state).
         ke_out (float64, 2 elements, device): also sample the kinetic energy of the NEW state into it."""
-        self._check_tiled(state, nat.STATE_FIELDS, n)
-        self._check_tiled(prev_state, nat.STATE_FIELDS, n)
-        if state_out is None:
-            state_out = prev_state
-        self._check_tiled(state_out, nat.STATE_FIELDS, n)
-        w_ptr, w_stride = None, 0
-        if wrench is not None:
-            self._check_tiled(wrench, nat.WRENCH_FIELDS, n)
-            w_ptr, w_stride = wrench.data_ptr(), nat.WRENCH_FIELDS * nat.TILE
-        st = nat.STATE_FIELDS * nat.TILE
+        state_out, st, head = self._fused_head(state, prev_state, n, dt, state_out)
+        w_ptr, w_stride = self._tiled(wrench, nat.WRENCH_FIELDS, n) if wrench is not None else (None, 0)
+        tail = (state_out.data_ptr(), st, w_ptr, w_stride, int(bool(implicit_drag)))
         if ke_out is None:
-            self._check(self._lib.hydro_step_fused_tiled(
-                self._h, n, state.data_ptr(), st, prev_state.data_ptr() + 7 * nat.TILE * 4, st, float(dt),
-                state_out.data_ptr(), st, w_ptr, w_stride, int(bool(implicit_drag)), self._stream(stream)))
+            self._check(self._lib.hydro_step_fused_tiled(*head, *tail, self._stream(stream)))
         else:
             self._check_ke_out(ke_out)
-            self._check(self._lib.hydro_step_fused_tiled_ke(
-                self._h, n, state.data_ptr(), st, prev_state.data_ptr() + 7 * nat.TILE * 4, st, float(dt),
-                state_out.data_ptr(), st, w_ptr, w_stride, int(bool(implicit_drag)), int(bool(rotational)),
-                ke_out.data_ptr(), self._stream(stream)))
+            self._check(self._lib.hydro_step_fused_tiled_ke(*head, *tail, int(bool(rotational)), ke_out.data_ptr(),
+                                                            self._stream(stream)))
         return state_out
+
+    def _fused_multi_args(self, state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational):
+        """(state_out, the arguments `hydro_step_fused_tiled_multi[_rec]` share): the final state goes to `state_out`,
+        the velocity of the step before the last one into the velocity fields of `state`."""
+        state_out, st, head = self._fused_head(state, prev_state, n, dt, state_out)
+        if ke_out is not None:
+            self._check_ke_out(ke_out)
+        return state_out, head + (int(steps), state_out.data_ptr(), st, state.data_ptr() + _VEL_BYTES, st,
+                                  int(bool(implicit_drag)), int(bool(rotational)),
+                                  ke_out.data_ptr() if ke_out is not None else None)
 
     def step_fused_tiled_multi(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
                                state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
@@ -359,18 +359,8 @@ class HydroEngine:
         default, receives the final state; the velocity fields of `state` receive the velocity of the step before the
         last one, so that after the call (state_out, state) are the (current, previous) pair of the next call.
         ke_out: also sample the kinetic energy of the final state."""
-        self._check_tiled(state, nat.STATE_FIELDS, n)
-        self._check_tiled(prev_state, nat.STATE_FIELDS, n)
-        if state_out is None:
-            state_out = prev_state
-        self._check_tiled(state_out, nat.STATE_FIELDS, n)
-        if ke_out is not None:
-            self._check_ke_out(ke_out)
-        st, vel = nat.STATE_FIELDS * nat.TILE, 7 * nat.TILE * 4
-        self._check(self._lib.hydro_step_fused_tiled_multi(
-            self._h, n, state.data_ptr(), st, prev_state.data_ptr() + vel, st, float(dt), int(steps),
-            state_out.data_ptr(), st, state.data_ptr() + vel, st, int(bool(implicit_drag)), int(bool(rotational)),
-            ke_out.data_ptr() if ke_out is not None else None, self._stream(stream)))
+        state_out, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
+        self._check(self._lib.hydro_step_fused_tiled_multi(*args, self._stream(stream)))
         return state_out
 
     def set_watch(self, bodies) -> int:
@@ -396,23 +386,13 @@ class HydroEngine:
         k = phase, phase + every, ... of this launch, into rows row0, row0 + 1, ... of `log`, a contiguous float32 device
         tensor (rows, 13 | 19, columns >= watch count) - 19 fields: the state, then the wrench that produced it.  State,
         previous-velocity and kinetic-energy bits are those of step_fused_tiled_multi.  Returns the number of rows written."""
-        self._check_tiled(state, nat.STATE_FIELDS, n)
-        self._check_tiled(prev_state, nat.STATE_FIELDS, n)
-        if state_out is None:
-            state_out = prev_state
-        self._check_tiled(state_out, nat.STATE_FIELDS, n)
-        if ke_out is not None:
-            self._check_ke_out(ke_out)
+        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
         if (log.dim() != 3 or log.dtype != torch.float32 or not log.is_contiguous() or log.device != self.device
                 or log.shape[1] not in (nat.STATE_FIELDS, nat.STATE_FIELDS + nat.WRENCH_FIELDS)):
             raise ValueError("log must be a contiguous float32 (rows, 13 | 19, columns) tensor on the engine's device")
         written = ctypes.c_int64(0)
-        st, vel = nat.STATE_FIELDS * nat.TILE, 7 * nat.TILE * 4
         self._check(self._lib.hydro_step_fused_tiled_multi_rec(
-            self._h, n, state.data_ptr(), st, prev_state.data_ptr() + vel, st, float(dt), int(steps),
-            state_out.data_ptr(), st, state.data_ptr() + vel, st, int(bool(implicit_drag)), int(bool(rotational)),
-            ke_out.data_ptr() if ke_out is not None else None,
-            log.data_ptr(), log.shape[2], log.shape[0], log.shape[1], int(every), int(phase), int(row0),
+            *args, log.data_ptr(), log.shape[2], log.shape[0], log.shape[1], int(every), int(phase), int(row0),
             ctypes.byref(written), self._stream(stream)))
         return written.value
 
@@ -420,12 +400,25 @@ class HydroEngine:
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:
             state_out = torch.zeros_like(state_in)
-        for t, f in ((state_in, nat.STATE_FIELDS), (wrench, nat.WRENCH_FIELDS), (state_out, nat.STATE_FIELDS)):
-            self._check_tiled(t, f, n)
-        self._check(self._lib.hydro_integrate_tiled(
-            self._h, n, state_in.data_ptr(), nat.STATE_FIELDS * nat.TILE, wrench.data_ptr(), nat.WRENCH_FIELDS * nat.TILE,
-            float(dt), state_out.data_ptr(), nat.STATE_FIELDS * nat.TILE, self._stream(stream)))
+        ins = self._tiled(state_in, nat.STATE_FIELDS, n) + self._tiled(wrench, nat.WRENCH_FIELDS, n)
+        self._check(self._lib.hydro_integrate_tiled(self._h, n, *ins, float(dt), *self._tiled(state_out, nat.STATE_FIELDS, n),
+                                                    self._stream(stream)))
         return state_out
+
+    # ------------------------------------------- simulator tensors (array of structs)
+    def _rows(self, tensors, widths, n: int, what: str = "tensor") -> None:
+        """Each of `tensors` must be a contiguous float32 (n, width) tensor on the engine's device."""
+        for t, w in zip(tensors, widths):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, w) or t.device != self.device:
+                raise ValueError(f"expected contiguous float32 ({n},{w}) {what} on {self.device}")
+
+    def _force_torque(self, n: int, forces, torques):
+        """The (n,3) outputs of an array-of-structs entry, allocated where None (given ones are taken as they are)."""
+        if forces is None:
+            forces = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        if torques is None:
+            torques = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        return forces, torques
 
     def pack_state_aos(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
                        out: torch.Tensor | None = None, quat_xyzw: bool = False, stream=None) -> torch.Tensor:
@@ -433,22 +426,27 @@ class HydroEngine:
         n = positions.shape[0]
         if out is None:
             out = self.alloc_tiled(nat.STATE_FIELDS, n)
-        self._check_tiled(out, nat.STATE_FIELDS, n)
         self._check(self._lib.hydro_pack_state_aos(
             self._h, n, positions.data_ptr(), orientations.data_ptr(), int(bool(quat_xyzw)), velocities.data_ptr(),
-            out.data_ptr(), nat.STATE_FIELDS * nat.TILE, self._stream(stream)))
+            *self._tiled(out, nat.STATE_FIELDS, n), self._stream(stream)))
         return out
 
     def unpack_wrench_aos(self, wrench: torch.Tensor, n: int, forces: torch.Tensor | None = None,
                           torques: torch.Tensor | None = None, stream=None):
-        self._check_tiled(wrench, nat.WRENCH_FIELDS, n)
-        if forces is None:
-            forces = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        if torques is None:
-            torques = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        self._check(self._lib.hydro_unpack_wrench_aos(self._h, n, wrench.data_ptr(), nat.WRENCH_FIELDS * nat.TILE,
-                                                      forces.data_ptr(), torques.data_ptr(), self._stream(stream)))
+        w = self._tiled(wrench, nat.WRENCH_FIELDS, n)
+        forces, torques = self._force_torque(n, forces, torques)
+        self._check(self._lib.hydro_unpack_wrench_aos(self._h, n, *w, forces.data_ptr(), torques.data_ptr(),
+                                                      self._stream(stream)))
         return forces, torques
+
+    def _wrench_aos_call(self, positions, orientations, velocities, forces, torques, quat_xyzw):
+        """The arguments of `hydro_step_wrench_aos` before and after `dt` (the stream follows) and the outputs: the three
+        inputs validated, `forces` / `torques` allocated where None."""
+        n = positions.shape[0]
+        self._rows((positions, orientations, velocities), (3, 4, 6), n)
+        forces, torques = self._force_torque(n, forces, torques)
+        head = (self._h, n, positions.data_ptr(), orientations.data_ptr(), int(bool(quat_xyzw)), velocities.data_ptr())
+        return head, (forces.data_ptr(), torques.data_ptr()), forces, torques
 
     def step_wrench_aos(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
                         dt: float, forces: torch.Tensor | None = None, torques: torch.Tensor | None = None,
@@ -456,42 +454,22 @@ class HydroEngine:
         """Fused wrench on the simulator's tensors: positions (N,3), orientations (N,4) (WXYZ as the
         simulator gives them, or XYZW with quat_xyzw=True), velocities (N,6) -> forces (N,3),
         torques (N,3).  Uses and updates the engine's previous-velocity state."""
-        n = positions.shape[0]
-        for t, w in ((positions, 3), (orientations, 4), (velocities, 6)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, w) or t.device != self.device:
-                raise ValueError(f"expected contiguous float32 ({n},{w}) tensor on {self.device}")
-        if forces is None:
-            forces = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        if torques is None:
-            torques = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        self._check(self._lib.hydro_step_wrench_aos(
-            self._h, n, positions.data_ptr(), orientations.data_ptr(), int(bool(quat_xyzw)), velocities.data_ptr(), float(dt),
-            forces.data_ptr(), torques.data_ptr(), self._stream(stream)))
+        head, tail, forces, torques = self._wrench_aos_call(positions, orientations, velocities, forces, torques, quat_xyzw)
+        self._check(self._lib.hydro_step_wrench_aos(*head, float(dt), *tail, self._stream(stream)))
         return forces, torques
 
     def prepare_step_wrench_aos(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
                                 forces: torch.Tensor | None = None, torques: torch.Tensor | None = None,
                                 quat_xyzw: bool = False):
-        """Validate the arguments of `step_wrench_aos` ONCE and return `step(dt, stream=None) -> (forces, torques)`,
-        which re-issues that launch on the same buffers (a simulator's tensor API hands out views of the same
-        device buffers every physics step).  For the plugin path, where the per-call Python work of
-        `step_wrench_aos` (five tensor checks, pointer conversions) is several times the kernel at 20 bodies.
-        `stream`: a torch stream / raw handle; None = the stream current at the time of the call."""
-        n = positions.shape[0]
-        for t, w in ((positions, 3), (orientations, 4), (velocities, 6)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, w) or t.device != self.device:
-                raise ValueError(f"expected contiguous float32 ({n},{w}) tensor on {self.device}")
-        if forces is None:
-            forces = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        if torques is None:
-            torques = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        for t in (forces, torques):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, 3) or t.device != self.device:
-                raise ValueError(f"expected contiguous float32 ({n},3) output on {self.device}")
+        """Build the launch of `step_wrench_aos` ONCE (`_wrench_aos_call`; given outputs are validated here as well) and
+        return `step(dt, stream=None) -> (forces, torques)`, which re-issues that launch on the same buffers (a
+        simulator's tensor API hands out views of the same device buffers every physics step).  For the plugin path,
+        where the per-call Python work of `step_wrench_aos` (tensor checks, pointer conversions) is several times the
+        kernel at 20 bodies.  `stream`: a torch stream / raw handle; None = the stream current at the time of the call."""
+        head, tail, forces, torques = self._wrench_aos_call(positions, orientations, velocities, forces, torques, quat_xyzw)
+        self._rows((forces, torques), (3, 3), positions.shape[0], "output")
+        head, tail = _prebuilt("hydro_step_wrench_aos", head), _prebuilt("hydro_step_wrench_aos", tail, len(head) + 1)
         fn, check = self._lib.hydro_step_wrench_aos, self._check
-        head = (self._h, ctypes.c_int64(n), ctypes.c_void_p(positions.data_ptr()), ctypes.c_void_p(orientations.data_ptr()),
-                ctypes.c_int(int(bool(quat_xyzw))), ctypes.c_void_p(velocities.data_ptr()))
-        tail = (ctypes.c_void_p(forces.data_ptr()), ctypes.c_void_p(torques.data_ptr()))
         keep = (positions, orientations, velocities, forces, torques)          # the buffers must outlive the callable
         dev, cur = self.device, torch.cuda.current_stream
         # the current stream's raw handle without building a torch.cuda.Stream object (0.2 instead of 1 us per step)
@@ -500,7 +478,7 @@ class HydroEngine:
 
         def step(dt: float, stream=None):
             if self._h is None:
-                raise HydroError(-5, "engine is closed")
+                raise HydroError(nat.HYDRO_E_STATE, "engine is closed")
             if stream is None:
                 sp = raw_current(dev_index) if raw_current is not None else cur(dev).cuda_stream
             else:
@@ -531,9 +509,7 @@ class HydroEngine:
         """Component mode on the calculator's argument layout: (N,3)/(N,4) tensors in, out (8,N,3)."""
         n = position.shape[0]
         ins = (position, orientation_xyzw, linear_vel, angular_vel, linear_accel, angular_accel)
-        for t, w in zip(ins, (3, 4, 3, 3, 3, 3)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (n, w) or t.device != self.device:
-                raise ValueError(f"expected contiguous float32 ({n},{w}) tensor on {self.device}")
+        self._rows(ins, (3, 4, 3, 3, 3, 3), n)
         if out.shape != (8, n, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"expected contiguous float32 (8,{n},3) output on {self.device}")
         key = ("comp_aos", out.data_ptr(), n)
@@ -551,8 +527,7 @@ class HydroEngine:
         if out is None:
             out = torch.empty((2,), dtype=torch.float64, device=self.device)
         if state.ndim == 3:                       # tiled (tiles,13,64): n = bodies with parameters set
-            self._check_tiled(state, nat.STATE_FIELDS, self.n)
-            self._check(self._lib.hydro_kinetic_energy_tiled(self._h, self.n, state.data_ptr(), nat.STATE_FIELDS * nat.TILE,
+            self._check(self._lib.hydro_kinetic_energy_tiled(self._h, self.n, *self._tiled(state, nat.STATE_FIELDS, self.n),
                                                              int(bool(rotational)), out.data_ptr(), self._stream(stream)))
             return out
         self._check(self._lib.hydro_kinetic_energy(self._h, state.shape[1], self._table(state, nat.STATE_FIELDS),

@@ -123,11 +123,6 @@ class KineticEnergyMonitor:
         self._pending.append((step, slot, None, done))
         self.submitted += 1
 
-    def wait_before_overwrite(self, stream=None) -> None:
-        """Kept for callers of rounds 3-4: nothing to wait for any more - `observe(sampled=...)` takes its copy of the
-        caller's buffer on the step stream itself, so a later step on that stream may overwrite the buffer at once."""
-        return None
-
     def observe(self, step: int, state: torch.Tensor | None = None, stream=None, sampled: torch.Tensor | None = None) -> bool:
         """Call after physics step `step` (1-based count of completed steps) with the state that step produced - or
         with `sampled`, the float64 pair a sampling step kernel (ke_out=) has already written on `stream`.
@@ -446,8 +441,6 @@ class ClosedLoopSim:
         with torch.cuda.stream(self.stream):
             for _ in range(steps):
                 sample = self.monitor is not None and (self.steps_done + 1) % self.monitor.every == 0
-                if sample:
-                    self.monitor.wait_before_overwrite(self.stream)
                 if self.recorder is not None:
                     self._step_recorded(1, sample)
                 else:
@@ -549,8 +542,6 @@ class ClosedLoopSim:
             while steps > 0:
                 k = min(chunk, steps)
                 sample = self.monitor is not None and k == chunk and (self.steps_done + k) % self.monitor.every == 0
-                if sample:
-                    self.monitor.wait_before_overwrite(self.stream)
                 if self.recorder is not None:
                     self._step_recorded(k, sample)
                 else:
