@@ -49,7 +49,9 @@ extern "C" {
  *        kinetic-energy reduction poison the partials they consumed; re-arming happens after the cross-stream wait and
  *        never inside a stream capture
  *        added to 0.7.1 (no existing entry changed): hydro_set_watch, hydro_watch_count, hydro_step_fused_tiled_multi_rec - a
- *        trajectory recorder inside the multi-step kernel (watched bodies' states, every `every`-th step, to a device log) */
+ *        trajectory recorder inside the multi-step kernel (watched bodies' states, every `every`-th step, to a device log)
+ *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_app, HYDRO_FRAME_* - an external force and
+ *        torque per body, world- or body-fixed, applied inside every step of the multi-step kernel */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -380,6 +382,46 @@ int hydro_step_fused_tiled_multi_rec(hydro_t *h, int64_t n, const float *state, 
                                      int rotational, double *ke_out_dev,
                                      float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
                                      int64_t row0, int64_t *rows_written_host, void *stream);
+
+/* Applied wrench: an external force and torque per body inside the closed-loop steps - a thruster, a tether, a towing force,
+ * an RL action; what PhysX adds next to the plugin's wrench in the reference (robot.py / cmd_vel), for the loop in which this
+ * library is the integrator.  Between the first and the last step of a multi-step launch the states exist in registers only,
+ * so a body-fixed thrust can be turned with the body nowhere but inside the kernel.
+ *
+ * hydro_step_fused_tiled_multi_app: hydro_step_fused_tiled_multi_rec - same arguments up to rows_written_host, same aliasing
+ * rules - with `applied`, a tiled 6-field record ([tiles][6][64] floats, tile stride applied_tile_stride >= 384, 16-byte
+ * aligned, whole tiles) of a = [Fx Fy Fz | Tx Ty Tz] per body: the force acts AT the body origin, the torque is ABOUT the
+ * body origin (a force at an offset point r: pass r x f as torque).  In every step, between the wrench and the integrator:
+ *     HYDRO_FRAME_WORLD  wrench[i] += a[i]                                      one fp32 add per component, nothing else
+ *     HYDRO_FRAME_BODY   wrench[0:3] += R a[0:3], wrench[3:6] += R a[3:6]       R: the fp32 rotation matrix of the quaternion
+ *                        of the state the step STARTS from, used as given (a non-unit quaternion is not normalised), in the
+ *                        form the integrator builds it; evaluated anew in every step of the launch
+ * Zero-order hold: `a` is read once per launch and held constant IN ITS FRAME for all `steps` steps (a world-fixed pull stays
+ * world-fixed, a body-fixed thrust turns with the body).  The safety clamp acts on the hydrodynamic wrench alone; the applied
+ * wrench is added after it, unclamped.  With implicit_drag the sum stands where the wrench stood in the implicit form.  The
+ * wrench the recorder logs (fields = 19) is the TOTAL that was integrated - the wrench that produced the state.
+ * steps = 1 is the single-step form (there is no separate entry).
+ *   log == NULL     : no recording; no watch list is needed, the other recorder arguments are ignored, *rows_written_host = 0.
+ *   log != NULL     : exactly the rules of hydro_step_fused_tiled_multi_rec.
+ *   applied == NULL : legal; the launch and its bits are those of hydro_step_fused_tiled_multi (log == NULL) or
+ *                     hydro_step_fused_tiled_multi_rec (log != NULL); applied_tile_stride and applied_frame are ignored.
+ * A zero `applied` gives the values of the unapplied step (x + 0 == x; only the sign of a zero may differ).
+ * HYDRO_E_ARG for a misaligned `applied`, a stride below 384 (or not a multiple of 4, or >= 2^24), a frame other than 0 / 1,
+ * and an `applied` whose address range [applied, applied + tiles * stride) overlaps that of state_out, prev_out or the log -
+ * besides what the neighbours refuse; all before anything is launched or written.  `applied` may be rewritten between
+ * launches on the same stream (a captured launch replays with the contents of the moment).  Asynchronous, no allocation,
+ * no synchronisation, safe to capture.
+ * New functionality; the reference leaves actuator forces to PhysX. */
+#define HYDRO_FRAME_WORLD 0
+#define HYDRO_FRAME_BODY  1
+int hydro_step_fused_tiled_multi_app(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -30,6 +30,7 @@ class Scene(ctypes.Structure):
 
 HYDRO_OK, HYDRO_E_ARG, HYDRO_E_ALLOC, HYDRO_E_LAUNCH, HYDRO_E_DEVICE, HYDRO_E_STATE = 0, -1, -2, -3, -4, -5
 HYDRO_SEM_NUMBA, HYDRO_SEM_WARP = 0, 1
+HYDRO_FRAME_WORLD, HYDRO_FRAME_BODY = 0, 1          # frame of an applied wrench (hydro_step_fused_tiled_multi_app)
 STATUS_NAMES = {v: k for k, v in list(globals().items()) if k == "HYDRO_OK" or k.startswith("HYDRO_E_")}
 
 # every symbol include/hydro.h declares: (restype, argtypes)
@@ -67,6 +68,10 @@ SIGNATURES = {
     "hydro_step_fused_tiled_multi_rec": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64), c_void_p]),
+    "hydro_step_fused_tiled_multi_app": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                 c_void_p, c_int64, c_int, c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

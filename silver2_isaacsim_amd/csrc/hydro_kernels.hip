@@ -1105,12 +1105,14 @@ __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k
 
 // One closed-loop step of a body held in registers - the loop body of the two multi-step kernels below: the wrench of
 // (s, pv), the integrator, then pv <- the velocity just used and s <- the new state.  f6 is the wrench that produced the new s.
-template <bool IMPLICIT, bool WARP>
+// `app` is the applied-wrench policy: add(s, f6) between the (clamped) hydrodynamic wrench and the integrator.
+template <bool IMPLICIT, bool WARP, typename Applied>
 __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], const float (&d)[3], const float (&c)[7], float mass,
-                                                        double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS])
+                                                        double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS], const Applied& app)
 {
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
     wrench_fields(w, f6);
+    app.add(s, f6);
     float o[HYDRO_STATE_FIELDS];
     integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
 #pragma unroll
@@ -1128,13 +1130,14 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // k_pvo may alias the velocity fields of the state this kernel READS (each lane reads its own fields first): the
 // two-buffer ping-pong of the single-step entry then carries over unchanged.
 // --------------------------------------------------------------------------
-// The body of the two kernels below.  `rec` is the recorder policy: begin(tile, lane) once the records are loaded, then
-// after_step(k, s, f6) behind every step with the state it produced and the wrench that produced it.
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder>
+// The body of the three kernels below.  `rec` is the recorder policy: begin(tile, lane) once the records are loaded, then
+// after_step(k, s, f6) behind every step with the state it produced and the wrench that produced it.  `app` is the
+// applied-wrench policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step (see AppliedWrench).
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied>
 __device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
                                                  uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec)
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app)
 {
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
@@ -1146,10 +1149,11 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
         float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
         load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
         rec.begin(tile, lane);
+        app.begin(tile, lane4);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
-            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6);
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app);
             rec.after_step(k, s, f6);
         }
         if constexpr (KE)
@@ -1164,6 +1168,10 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
 struct NoRecorder {
     __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
     __device__ __forceinline__ void after_step(uint32_t, const float (&)[HYDRO_STATE_FIELDS], const float (&)[HYDRO_WRENCH_FIELDS]) {}
+};
+struct NoApplied {
+    __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_WRENCH_FIELDS]) const {}
 };
 
 // --------------------------------------------------------------------------
@@ -1216,7 +1224,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
                                                                        double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{});
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
@@ -1230,7 +1238,78 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u});
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{});
+}
+
+// --------------------------------------------------------------------------
+// The APPLIED WRENCH in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_app): what pushes a body besides
+// water and gravity - a thruster, a tether, an RL action.  Six floats per body, a = [Fx Fy Fz | Tx Ty Tz], force at and
+// torque about the body origin, in a tiled 6-field record ([tiles][6][64], addressed like the previous-velocity record:
+// wave-uniform tile base, field offsets in the load's immediate), held constant IN ITS FRAME for all the steps of a launch:
+//   world frame : f6[i] += a[i]                               one fp32 add per component
+//   body frame  : f6[0:3] += R a[0:3], f6[3:6] += R a[3:6]    R = the fp32 matrix of the CURRENT step's quaternion, as given
+//                                                             (non-unit included), in the form integrate_body builds it -
+//                                                             a body-fixed thrust turns with the body inside the launch
+// The sum is what the integrator takes (with IMPLICIT it stands where f stood) and what the recorder logs: the wrench that
+// produced the state.  The safety clamp has already acted, on the hydrodynamic wrench alone.  `body_frame` is a kernel
+// argument, hence wave-uniform: one scalar branch per step.
+// The six values are loaded once and carried through the loop (see DESIGN.md for the register counts).
+// --------------------------------------------------------------------------
+struct AppliedWrench {
+    const float* rec; uint32_t stride; int body_frame;
+    float a[HYDRO_WRENCH_FIELDS];
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4)
+    {
+        const float* r = rec + (size_t)tile * stride;
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) a[f] = ldg<false>(at<float>(r, lane4, f * 256u));
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        if (body_frame) {
+            const float qx = s[3], qy = s[4], qz = s[5], qw = s[6];
+            const float x2 = qx + qx, y2 = qy + qy, z2 = qz + qz;
+            const float xx = qx * x2, xy = qx * y2, xz = qx * z2, yy = qy * y2, yz = qy * z2, zz = qz * z2;
+            const float sx = qw * x2, sy = qw * y2, sz = qw * z2;
+            const float r00 = 1.0f - (yy + zz), r01 = xy - sz, r02 = xz + sy;
+            const float r10 = xy + sz, r11 = 1.0f - (xx + zz), r12 = yz - sx;
+            const float r20 = xz - sy, r21 = yz + sx, r22 = 1.0f - (xx + yy);
+#pragma unroll
+            for (int h = 0; h < HYDRO_WRENCH_FIELDS; h += 3) {
+                f6[h + 0] += r00 * a[h] + r01 * a[h + 1] + r02 * a[h + 2];
+                f6[h + 1] += r10 * a[h] + r11 * a[h + 1] + r12 * a[h + 2];
+                f6[h + 2] += r20 * a[h] + r21 * a[h + 1] + r22 * a[h + 2];
+            }
+        } else {
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += a[f];
+        }
+    }
+};
+// The recorder of the applied kernel: LogRecorder, or nothing when there are no watch tables (w_mask == nullptr, a kernel
+// argument: wave-uniform) - one kernel serves "applied" and "applied + recorder".
+struct OptionalLogRecorder : LogRecorder {
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane)
+    {
+        if (w_mask) LogRecorder::begin(tile, lane);
+        else { watched = false; column = 0u; due = 0u; row = row0; }
+    }
+};
+
+// Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them, then the applied wrench's.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   AppliedWrench{applied, applied_stride, body_frame, {}});
 }
 
 }  // namespace
@@ -2066,17 +2145,30 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// hydro_step_fused_tiled_multi and its recording twin: one validation, one variant selection.  rec == nullptr launches
-// step_fused_multi_tiled_kernel, else step_fused_multi_rec_tiled_kernel with the recorder's arguments appended.
+// hydro_step_fused_tiled_multi, its recording twin and the applied-wrench entry: one validation, one variant selection.
+// rec == nullptr launches step_fused_multi_tiled_kernel, else step_fused_multi_rec_tiled_kernel with the recorder's
+// arguments appended; app != nullptr launches step_fused_multi_app_tiled_kernel, which takes both (a null watch mask: no
+// recording).
 struct RecArgs {
     const uint64_t* mask; const uint32_t* first;     // the engine's watch tables
     float* log; uint32_t stride, fields, every, phase, row0;
 };
+struct AppArgs {
+    const float* applied; int64_t stride; int frame;
+    const float* log; int64_t log_floats;            // the log as an output range `applied` must stay out of (may be null)
+};
+// [p, p + floats) and [q, q + floats_q) share an element
+inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + (uintptr_t)floats_q * 4u && b < a + (uintptr_t)floats * 4u;
+}
 int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
                                 const float* prev, int64_t prev_tile_stride, double dt, int steps,
                                 float* state_out, int64_t out_tile_stride,
                                 float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
-                                int rotational, double* ke_out_dev, const RecArgs* rec, int64_t* rows_written_host, int64_t rows, void* stream)
+                                int rotational, double* ke_out_dev, const RecArgs* rec, int64_t* rows_written_host, int64_t rows, void* stream,
+                                const AppArgs* app = nullptr)
 {
     int rc = check_common(h, n);
     if (rc) return rc;
@@ -2088,6 +2180,14 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
     if ((rc = check_tiled(h, n, prev_out, prev_out_tile_stride, HYDRO_PREV_FIELDS, "null prev_out (pass state + 7*64 to keep the two-buffer ping-pong)"))) return rc;
     if (state_out == state) return fail(h, HYDRO_E_ARG, "state_out must not alias state (it may alias the previous-state buffer)");
     if (rec && h->watch_last >= n) return fail(h, HYDRO_E_ARG, "a watched body is >= n");
+    if (app) {
+        if ((rc = check_tiled(h, n, app->applied, app->stride, HYDRO_WRENCH_FIELDS, "null applied"))) return rc;
+        if (app->frame != HYDRO_FRAME_WORLD && app->frame != HYDRO_FRAME_BODY) return fail(h, HYDRO_E_ARG, "applied_frame must be HYDRO_FRAME_WORLD or HYDRO_FRAME_BODY");
+        const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * app->stride;
+        if (ranges_overlap(app->applied, floats, state_out, tiles * out_tile_stride) || ranges_overlap(app->applied, floats, prev_out, tiles * prev_out_tile_stride)
+            || (app->log && ranges_overlap(app->applied, floats, app->log, app->log_floats)))
+            return fail(h, HYDRO_E_ARG, "applied must not overlap an output (state_out, prev_out, log)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (rows_written_host) *rows_written_host = n == 0 ? 0 : rows;
@@ -2102,10 +2202,36 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
                                (uint32_t)n, (uint32_t)steps, (float)dt, h->rho, h->g, 1.0 / dt, h->ke_partials, h->ke_stride, rotational ? 1 : 0, ke_out_dev,
                                recorder...);
         };
-        if (rec) launch(step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>, rec->mask, rec->first, rec->log, rec->stride, rec->fields, rec->every, rec->phase, rec->row0);
+        if (app) {
+            const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
+            launch(step_fused_multi_app_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
+                   app->applied, (uint32_t)app->stride, app->frame);
+        }
+        else if (rec) launch(step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>, rec->mask, rec->first, rec->log, rec->stride, rec->fields, rec->every, rec->phase, rec->row0);
         else launch(step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
     }, h->half_coeffs, streaming_fused(h, n), implicit_drag != 0, ke_out_dev != nullptr, is_warp(h));
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+// What hydro_step_fused_tiled_multi_rec checks of its recorder arguments and hands to the kernel; `rows`: the rows the launch writes.
+int check_recorder(hydro_t* h, int steps, float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase, int64_t row0,
+                   RecArgs& rec, int64_t& rows_out)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (h->watch_count == 0) return fail(h, HYDRO_E_STATE, "no watch list (call hydro_set_watch first)");
+    if (!log || !aligned_to(log, 4)) return fail(h, HYDRO_E_ARG, "null or misaligned log");
+    if (fields != HYDRO_STATE_FIELDS && fields != HYDRO_STATE_FIELDS + HYDRO_WRENCH_FIELDS) return fail(h, HYDRO_E_ARG, "fields must be 13 (state) or 19 (state + wrench)");
+    if (every < 1 || every > (1 << 30)) return fail(h, HYDRO_E_ARG, "every must be in 1 .. 2^30");
+    if (phase < 1 || phase > every) return fail(h, HYDRO_E_ARG, "phase must be in 1 .. every");
+    if (log_stride < h->watch_count || log_stride >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "log_stride must be >= the watch count (and < 2^31)");
+    if (row0 < 0 || rows_capacity < 0 || rows_capacity >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "row0 / rows_capacity out of range (0 .. 2^31)");
+    if (steps < 1 || steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
+    // the rows this launch writes: row0 .. row0 + rows - 1, all of them below rows_capacity before anything is launched
+    const int64_t rows = rows_out = phase > steps ? 0 : (int64_t)(steps - phase) / every + 1;
+    if (rows > 0 && row0 + rows > rows_capacity) return fail(h, HYDRO_E_ARG, "the launch would write past rows_capacity");
+    rec.mask = h->watch_mask; rec.first = h->watch_first; rec.log = log; rec.stride = (uint32_t)log_stride; rec.fields = (uint32_t)fields;
+    rec.every = (uint32_t)every; rec.phase = (uint32_t)phase; rec.row0 = (uint32_t)row0;
     return HYDRO_OK;
 }
 
@@ -2171,23 +2297,34 @@ int hydro_step_fused_tiled_multi_rec(hydro_t* h, int64_t n, const float* state, 
                                      float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
                                      int64_t row0, int64_t* rows_written_host, void* stream)
 {
-    if (!h) return HYDRO_E_ARG;
-    if (h->watch_count == 0) return fail(h, HYDRO_E_STATE, "no watch list (call hydro_set_watch first)");
-    if (!log || !aligned_to(log, 4)) return fail(h, HYDRO_E_ARG, "null or misaligned log");
-    if (fields != HYDRO_STATE_FIELDS && fields != HYDRO_STATE_FIELDS + HYDRO_WRENCH_FIELDS) return fail(h, HYDRO_E_ARG, "fields must be 13 (state) or 19 (state + wrench)");
-    if (every < 1 || every > (1 << 30)) return fail(h, HYDRO_E_ARG, "every must be in 1 .. 2^30");
-    if (phase < 1 || phase > every) return fail(h, HYDRO_E_ARG, "phase must be in 1 .. every");
-    if (log_stride < h->watch_count || log_stride >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "log_stride must be >= the watch count (and < 2^31)");
-    if (row0 < 0 || rows_capacity < 0 || rows_capacity >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "row0 / rows_capacity out of range (0 .. 2^31)");
-    if (steps < 1 || steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
-    // the rows this launch writes: row0 .. row0 + rows - 1, all of them below rows_capacity before anything is launched
-    const int64_t rows = phase > steps ? 0 : (int64_t)(steps - phase) / every + 1;
-    if (rows > 0 && row0 + rows > rows_capacity) return fail(h, HYDRO_E_ARG, "the launch would write past rows_capacity");
     RecArgs rec;
-    rec.mask = h->watch_mask; rec.first = h->watch_first; rec.log = log; rec.stride = (uint32_t)log_stride; rec.fields = (uint32_t)fields;
-    rec.every = (uint32_t)every; rec.phase = (uint32_t)phase; rec.row0 = (uint32_t)row0;
+    int64_t rows = 0;
+    const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
+    if (rc) return rc;
     return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
                                        prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, &rec, rows_written_host, rows, stream);
+}
+
+int hydro_step_fused_tiled_multi_app(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    RecArgs rec;
+    int64_t rows = 0;
+    if (log) {
+        const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
+        if (rc) return rc;
+    }
+    AppArgs app = {applied, applied_tile_stride, applied_frame, log, log ? rows_capacity * fields * log_stride : 0};
+    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
+                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
+                                       applied ? &app : nullptr);
 }
 
 int hydro_pack_state_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,

@@ -11,7 +11,7 @@ field f (orders in include/hydro.h).
 Each rule for turning a Python argument into C arguments is written once: `_tiled` (a tiled buffer ->
 pointer, tile stride), `_prev_velocity` (None / state buffer / 6-field buffer), `_wrench_tiled_call` and
 `_wrench_aos_call` (the direct and the prepared form of a step share one argument list), `_fused_head`
-(the three fused steps) and `_rows` / `_force_torque` (simulator tensors).  tests/test_engine_calls.py
+(the fused steps), `_fused_multi_args` and `_rec_tail` (the multi-step entries) and `_rows` / `_force_torque` (simulator tensors).  tests/test_engine_calls.py
 pins the resulting calls without a GPU.
 """
 from __future__ import annotations
@@ -28,6 +28,7 @@ from ._native import HydroError
 log = logging.getLogger("silver2_isaacsim_amd")
 _warp_mode_announced = False
 _VEL_BYTES = 7 * nat.TILE * 4          # where the six velocity fields start inside a state tile
+_FRAMES = {"world": nat.HYDRO_FRAME_WORLD, "body": nat.HYDRO_FRAME_BODY}      # frame of an applied wrench
 
 
 def _prebuilt(name: str, args, first: int = 0) -> tuple:
@@ -351,6 +352,18 @@ class HydroEngine:
                                   int(bool(implicit_drag)), int(bool(rotational)),
                                   ke_out.data_ptr() if ke_out is not None else None)
 
+    def _rec_tail(self, log, every, phase, row0):
+        """The recorder's arguments of `hydro_step_fused_tiled_multi_rec` / `_app` (log .. rows_written_host) and the
+        counter the call fills in.  `log` None (the applied entry only): no recording."""
+        written = ctypes.c_int64(0)
+        if log is None:
+            return (None, 0, 0, nat.STATE_FIELDS, 1, 1, 0, ctypes.byref(written)), written
+        if (log.dim() != 3 or log.dtype != torch.float32 or not log.is_contiguous() or log.device != self.device
+                or log.shape[1] not in (nat.STATE_FIELDS, nat.STATE_FIELDS + nat.WRENCH_FIELDS)):
+            raise ValueError("log must be a contiguous float32 (rows, 13 | 19, columns) tensor on the engine's device")
+        return (log.data_ptr(), log.shape[2], log.shape[0], log.shape[1], int(every), int(phase), int(row0),
+                ctypes.byref(written)), written
+
     def step_fused_tiled_multi(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
                                state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
                                ke_out: torch.Tensor | None = None, rotational: bool = True):
@@ -387,13 +400,29 @@ class HydroEngine:
         tensor (rows, 13 | 19, columns >= watch count) - 19 fields: the state, then the wrench that produced it.  State,
         previous-velocity and kinetic-energy bits are those of step_fused_tiled_multi.  Returns the number of rows written."""
         _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
-        if (log.dim() != 3 or log.dtype != torch.float32 or not log.is_contiguous() or log.device != self.device
-                or log.shape[1] not in (nat.STATE_FIELDS, nat.STATE_FIELDS + nat.WRENCH_FIELDS)):
-            raise ValueError("log must be a contiguous float32 (rows, 13 | 19, columns) tensor on the engine's device")
-        written = ctypes.c_int64(0)
-        self._check(self._lib.hydro_step_fused_tiled_multi_rec(
-            *args, log.data_ptr(), log.shape[2], log.shape[0], log.shape[1], int(every), int(phase), int(row0),
-            ctypes.byref(written), self._stream(stream)))
+        tail, written = self._rec_tail(log, every, phase, row0)
+        self._check(self._lib.hydro_step_fused_tiled_multi_rec(*args, *tail, self._stream(stream)))
+        return written.value
+
+    def step_fused_tiled_multi_applied(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
+                                       applied: torch.Tensor | None, frame: str = "body", log: torch.Tensor | None = None,
+                                       every: int = 1, phase: int = 1, row0: int = 0,
+                                       state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                       ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi with an external force and torque on every body (hydro_step_fused_tiled_multi_app):
+        `applied` is a tiled (tiles, 6, 64) buffer of [Fx Fy Fz | Tx Ty Tz] per body - force at, torque about the body
+        origin - added to the hydrodynamic wrench inside every one of the `steps` steps, held constant in its frame:
+        frame="world" as it stands, frame="body" turned by the body's attitude at each step (a thruster).  steps=1 is the
+        single-step form.  applied=None is the unapplied step.  `log` (with every / phase / row0, see
+        step_fused_tiled_multi_rec) also records the watched bodies; the wrench it logs is the total.  Returns the number
+        of rows written (0 without a log)."""
+        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
+        tail, written = self._rec_tail(log, every, phase, row0)
+        code = _FRAMES.get(frame)
+        if code is None:
+            raise ValueError("frame must be 'world' or 'body'")
+        a_ptr, a_stride = self._tiled(applied, nat.WRENCH_FIELDS, n) if applied is not None else (None, 0)
+        self._check(self._lib.hydro_step_fused_tiled_multi_app(*args, *tail, a_ptr, a_stride, code, self._stream(stream)))
         return written.value
 
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,

@@ -376,6 +376,11 @@ class ClosedLoopSim:
         self.ke_dev = torch.zeros(2, dtype=torch.float64, device=dev) if ke_every else None
         self._monitor_warm = self.monitor is None
         self.recorder: TrajectoryRecorder | None = None         # record()
+        # set_applied_wrench(): the tiled (tiles, 6, 64) buffer of the external wrench while one is set, its frame, and the
+        # buffer itself - made once, so that its address never changes (captured launches read it)
+        self.applied: torch.Tensor | None = None
+        self.applied_frame = "body"
+        self._applied_buf: torch.Tensor | None = None
 
     def record(self, bodies, every: int = 1, rows: int = 4096, wrench: bool = False) -> TrajectoryRecorder:
         """Watch `bodies` (any order, distinct, < n): from now on run_resident and run_eager write their state - with
@@ -402,8 +407,75 @@ class ClosedLoopSim:
             self.recorder._sim = None
             self.recorder = None
 
+    def set_applied_wrench(self, wrench, frame: str = "body", bodies=None) -> torch.Tensor:
+        """Push the bodies: from now on every physics step of run_eager, run (graph replays) and run_resident adds an external
+        force and torque to each body's hydrodynamic wrench before integrating (hydro_step_fused_tiled_multi_app) - a
+        thruster, a tether, an RL action.  `wrench`: (n, 6) rows [Fx Fy Fz | Tx Ty Tz], force at and torque about the body
+        origin - or (len(bodies), 6) for the bodies listed, all others zero; a host array or a device tensor (the copy is
+        ordered after the stream current now, and runs on `sim.stream`).  frame="body": body-fixed, turned by the body's
+        attitude at every step, also between the steps of a resident launch; frame="world": as it stands.  The wrench is
+        held until the next call.
+        Returns `sim.applied`, the tiled (tiles, 6, 64) device buffer the kernels read (`scenes.to_tiled` layout: body i,
+        field f at [i // 64, f, i % 64]).  Its address never changes: a controller on the device may write the next command
+        into it between chunks on `sim.stream`, and a graph replay sees the contents of the moment.
+        Under a process group the buffer is this rank's shard; no collective is involved."""
+        if not self.fused:
+            raise ValueError("the applied wrench lives in the fused step kernels (fused=True)")
+        if frame not in ("world", "body"):
+            raise ValueError("frame must be 'world' or 'body'")
+        dev = self.engine.device
+        w = torch.as_tensor(wrench if torch.is_tensor(wrench) else np.asarray(wrench, dtype=np.float32))
+        rows = self.n if bodies is None else len(bodies)
+        if w.ndim != 2 or tuple(w.shape) != (rows, 6):
+            raise ValueError(f"wrench: expected shape ({rows}, 6), got {tuple(w.shape)}")
+        if bodies is not None:
+            idx = torch.as_tensor(np.asarray(bodies, dtype=np.int64))
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n):
+                raise ValueError(f"bodies must be in 0 .. {self.n - 1}")
+        if self._applied_buf is None:
+            self._applied_buf = self.engine.alloc_tiled(6, self.n)
+        tiles = self._applied_buf.shape[0]
+        self.stream.wait_stream(torch.cuda.current_stream(dev))         # a device `wrench` may still be being written there
+        with torch.cuda.stream(self.stream):
+            if w.is_cuda:
+                w.record_stream(self.stream)                            # (read here, allocated on the caller's stream)
+            w = w.to(device=dev, dtype=torch.float32, non_blocking=True)
+            full = torch.zeros((tiles * 64, 6), dtype=torch.float32, device=dev)
+            if bodies is None:
+                full[:self.n] = w
+            else:
+                full[idx.to(dev)] = w
+            self._applied_buf.copy_(full.view(tiles, 64, 6).permute(0, 2, 1))
+        if self.applied is None or frame != self.applied_frame:
+            self._graph = None                                          # captured steps are of another entry / frame
+        self.applied, self.applied_frame = self._applied_buf, frame
+        return self.applied
+
+    def clear_applied_wrench(self) -> None:
+        """Back to water and gravity alone: every call the sim makes is again the one it made before set_applied_wrench."""
+        if self.applied is not None:
+            self.applied = None
+            self._graph = None
+
+    # `k` steps in one launch with the applied wrench, recording if a recorder is attached (k = 1 from run_eager and inside
+    # graph captures: the single-step form of the entry)
+    def _step_applied(self, k: int, ke_out) -> None:
+        rec = self.recorder
+        kw = {}
+        if rec is not None:
+            phase, row0, _ = rec.launch(self.steps_done, k)
+            kw = dict(log=rec.log, every=rec.every, phase=phase, row0=row0)
+        rows = self.engine.step_fused_tiled_multi_applied(self.cur, self.old, self.n, self.dt, k, self.applied, self.applied_frame,
+                                                          implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+        if rec is not None:
+            rec.rows_written += rows
+        self.cur, self.old = self.old, self.cur
+
     # `k` steps in one recording launch (k = 1 from run_eager: the bits of the single-step entry, include/hydro.h)
     def _step_recorded(self, k: int, sample: bool) -> None:
+        if self.applied is not None:
+            self._step_applied(k, self.ke_dev if sample else None)
+            return
         rec = self.recorder
         phase, row0, _ = rec.launch(self.steps_done, k)
         rec.rows_written += self.engine.step_fused_tiled_multi_rec(
@@ -425,6 +497,9 @@ class ClosedLoopSim:
     def _step_once(self, sample: bool = False, ke_out: torch.Tensor | None = None) -> None:
         e = self.engine
         ke_out = (ke_out if ke_out is not None else self.ke_dev) if sample else None
+        if self.applied is not None:
+            self._step_applied(1, ke_out)
+            return
         if self.fused:
             e.step_fused_tiled(self.cur, self.old, self.n, self.dt, implicit_drag=self.implicit_drag, ke_out=ke_out)   # new state -> old buffer
         else:
@@ -544,6 +619,8 @@ class ClosedLoopSim:
                 sample = self.monitor is not None and k == chunk and (self.steps_done + k) % self.monitor.every == 0
                 if self.recorder is not None:
                     self._step_recorded(k, sample)
+                elif self.applied is not None:
+                    self._step_applied(k, self.ke_dev if sample else None)
                 else:
                     self.engine.step_fused_tiled_multi(self.cur, self.old, self.n, self.dt, k, implicit_drag=self.implicit_drag,
                                                        ke_out=self.ke_dev if sample else None)
