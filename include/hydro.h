@@ -51,7 +51,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_set_watch, hydro_watch_count, hydro_step_fused_tiled_multi_rec - a
  *        trajectory recorder inside the multi-step kernel (watched bodies' states, every `every`-th step, to a device log)
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_app, HYDRO_FRAME_* - an external force and
- *        torque per body, world- or body-fixed, applied inside every step of the multi-step kernel */
+ *        torque per body, world- or body-fixed, applied inside every step of the multi-step kernel
+ *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_ctl, HYDRO_CTL_FIELDS - a per-body pose-hold
+ *        feedback law evaluated inside every step of the multi-step kernel */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -65,6 +67,7 @@ extern "C" {
 #define HYDRO_PREV_FIELDS    6
 #define HYDRO_PARAM_FIELDS  11
 #define HYDRO_WRENCH_FIELDS  6
+#define HYDRO_CTL_FIELDS    17   /* the control record of hydro_step_fused_tiled_multi_ctl */
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
@@ -422,6 +425,49 @@ int hydro_step_fused_tiled_multi_app(hydro_t *h, int64_t n, const float *state, 
                                      float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
                                      int64_t row0, int64_t *rows_written_host,
                                      const float *applied, int64_t applied_tile_stride, int applied_frame, void *stream);
+
+/* Pose hold: a feedback law per body INSIDE the closed-loop steps - station keeping, a depth or heading hold.  The applied
+ * wrench above is a zero-order hold over a launch; a law that is to act at the rate of the physics while the states stay in
+ * registers has to be evaluated in the loop.  This one pulls each body towards a target pose with a clamped PD law.
+ *
+ * hydro_step_fused_tiled_multi_ctl: hydro_step_fused_tiled_multi_app - same arguments up to applied_frame, same rules - with
+ * `control`, a tiled record of HYDRO_CTL_FIELDS = 17 floats per body ([tiles][17][64] floats, tile stride
+ * control_tile_stride >= 1088, 16-byte aligned, whole tiles), in field order
+ *     p*(3) | q*(4, xyzw) | kp_lin(3) | kd_lin(3) | kp_ang | kd_ang | f_max | t_max
+ * target position and attitude in the world, gains in absolute units (N/m, N s/m per world axis; N m/rad, N m s/rad),
+ * largest force and torque (+inf: unlimited; >= 0).  In EVERY step, from the state s = [p | q | v | omega] the step starts
+ * from, in fp32, in exactly this order (fma(a, b, c): a * b + c rounded once; rsqrt: hardware seed + one Newton step):
+ *     e_i = p*_i - p_i                         F_i = fma(kp_lin_i, e_i, -(kd_lin_i * v_i))                     i = x, y, z
+ *     n2  = fma(F_z, F_z, fma(F_y, F_y, F_x * F_x));       if (n2 > f_max * f_max)  F_i = F_i * (f_max * rsqrt(n2))
+ *     q_e = q* (x) conj(q), both as given (not normalised), with t = q*:
+ *           w = fma(tw, qw, fma(tx, qx, fma(ty, qy, tz * qz)))
+ *           x = fma(qw, tx, fma(-tw, qx, fma(qy, tz, -(qz * ty))))      y, z: the cyclic successors of x
+ *     h   = w < 0 ? -2 : 2                     T_i = fma(kp_ang, h * q_e_i, -(kd_ang * omega_i))
+ *     n2 of T; if (n2 > t_max * t_max)  T_i = T_i * (t_max * rsqrt(n2))
+ *     wrench[0:3] += F   (world, at the body origin)        wrench[3:6] += T   (world, about the body origin)
+ * i.e. 2 q_e.xyz is the rotation vector from the attitude to the target to first order, on the short way round (the flip at
+ * w = 0 is the law's one discontinuity); the clamps act on the norm and are continuous.  F and T are added after the safety
+ * clamp of the hydrodynamic wrench and after the applied wrench; with implicit_drag the sum stands where the wrench stood;
+ * the recorder logs the total.  |F|, |T| are expected below 2^63 (their squares are formed); f_max, t_max above that do not clamp.
+ *   control == NULL : legal; the launch and its bits are those of hydro_step_fused_tiled_multi_app with the same arguments;
+ *                     control_tile_stride is ignored.
+ *   applied == NULL : legal with or without control (applied_tile_stride and applied_frame are ignored).
+ * All-zero gains give the values of the uncontrolled step (x + 0 == x; only the sign of a zero may differ).  steps = 1 is the
+ * single-step form.  HYDRO_E_ARG for a misaligned `control`, a stride below 1088 (or not a multiple of 4, or >= 2^24) and a
+ * `control` whose range [control, control + tiles * stride) overlaps that of state_out, prev_out or the log - besides what
+ * hydro_step_fused_tiled_multi_app refuses; all before anything is launched or written.  `control` may be rewritten between
+ * launches on the same stream (a captured launch replays with the contents of the moment): a planner moves set-points
+ * between launches.  Asynchronous, no allocation, no synchronisation, safe to capture.
+ * New functionality; the reference leaves control to the simulator's articulation controllers. */
+int hydro_step_fused_tiled_multi_ctl(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libhydro.so")
 
 STATE_FIELDS, PREV_FIELDS, PARAM_FIELDS, WRENCH_FIELDS, COMP_FIELDS = 13, 6, 11, 6, 24
+CTL_FIELDS = 17                         # the control record of hydro_step_fused_tiled_multi_ctl
 TILE = 64
 BATCH_MAX = 32
 WATCH_MAX = 65536
@@ -72,6 +73,10 @@ SIGNATURES = {
                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
                                                  c_void_p, c_int64, c_int, c_void_p]),
+    "hydro_step_fused_tiled_multi_ctl": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -1312,6 +1312,109 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
                                                    AppliedWrench{applied, applied_stride, body_frame, {}});
 }
 
+// --------------------------------------------------------------------------
+// The POSE HOLD in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_ctl): a feedback law evaluated in every
+// step from the state the step starts from - between the first and the last step of a launch that state exists nowhere but
+// here.  Per body a tiled 17-field control record ([tiles][17][64], addressed like the applied record):
+//   p*(3) | q*(4) | kp_lin(3) | kd_lin(3) | kp_ang | kd_ang | f_max | t_max
+// The law, in fp32, in this order (include/hydro.h restates it; fma(a, b, c) = a * b + c rounded once):
+//   e_i  = p*_i - p_i                          F_i = fma(kp_lin_i, e_i, -(kd_lin_i * v_i))
+//   n2   = fma(F_z, F_z, fma(F_y, F_y, F_x * F_x));          if (n2 > f_max * f_max)  F_i *= f_max * rsqrt_nr(n2)
+//   q_e  = q* (x) conj(q):   w = fma(tw, qw, fma(tx, qx, fma(ty, qy, tz * qz)))                    (t = q*)
+//                            x = fma(qw, tx, fma(-tw, qx, fma(qy, tz, -(qz * ty))))   y, z: the cyclic successors
+//   h    = w < 0 ? -2 : 2                      T_i = fma(kp_ang, h * q_e_i, -(kd_ang * omega_i))
+//   n2, clamp to t_max as for F;               f6[0:3] += F, f6[3:6] += T
+// after the applied wrench, if there is one.  The sum is what the integrator takes and what the recorder logs.
+// WHERE THE 17 VALUES LIVE: the applied kernels stand at 156-168 VGPRs, at the limit of 3 waves per SIMD, so the record is
+// not carried through the loop.  Each lane parks its record - and the six applied values, which this kernel does not carry
+// either - in LDS once per launch and reads them back in every step: 23 slots per lane, [wave][23][64] floats (23 KB per
+// block; stride 1 across the lanes: no bank conflict).  A lane reads only what it wrote itself: no barrier.  The address
+// is lane4 (live anyway, for the final stores) + a wave-uniform scalar, added anew in every step - the empty asm keeps the
+// compiler from hoisting the sum into a register of its own - with the slot offsets in the instructions' immediates.
+// The kernel asks for 3 waves per SIMD (amdgpu_waves_per_eu(3)): left to itself the scheduler spends 170 VGPRs on the
+// energy-sampling instantiations - two more than three waves allow - where 160 do, without scratch (138-160 over the 32).
+// --------------------------------------------------------------------------
+constexpr uint32_t kCtlSlots = HYDRO_CTL_FIELDS + HYDRO_WRENCH_FIELDS;
+struct PoseHold {
+    const float* ctl; uint32_t ctl_stride; const float* applied; uint32_t applied_stride; int body_frame;
+    uint32_t lane4, wave_off;
+    static __device__ __forceinline__ float* slots()
+    {
+        __shared__ __attribute__((aligned(16))) float lds[kBlock * kCtlSlots];
+        return lds;
+    }
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        lane4 = lane4_;
+        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kCtlSlots * 256u);
+        float* mine = at<float>(slots(), lane4 + wave_off);
+        const float* r = ctl + (size_t)tile * ctl_stride;
+#pragma unroll
+        for (int f = 0; f < HYDRO_CTL_FIELDS; ++f) mine[f * 64] = ldg<false>(at<float>(r, lane4, f * 256u));
+        if (applied) {                                       // (a kernel argument: wave-uniform)
+            const float* a = applied + (size_t)tile * applied_stride;
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = ldg<false>(at<float>(a, lane4, f * 256u));
+        } else {
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = 0.0f;
+        }
+    }
+    static __device__ __forceinline__ void clamp_norm(float (&v)[3], float top)
+    {
+        const float n2 = __builtin_fmaf(v[2], v[2], __builtin_fmaf(v[1], v[1], v[0] * v[0]));
+        if (n2 > top * top) {
+            const float k = top * rsqrt_nr(n2);
+            v[0] *= k; v[1] *= k; v[2] *= k;
+        }
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        uint32_t w_off = wave_off;
+        asm volatile("" : "+s"(w_off));
+        const float* mine = at<float>(slots(), lane4 + w_off);
+        AppliedWrench a{nullptr, 0u, body_frame, {}};
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) a.a[f] = mine[(HYDRO_CTL_FIELDS + f) * 64];
+        a.add(s, f6);
+        {
+            float F[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) F[i] = __builtin_fmaf(mine[(7 + i) * 64], mine[i * 64] - s[i], -(mine[(10 + i) * 64] * s[7 + i]));
+            clamp_norm(F, mine[15 * 64]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) f6[i] += F[i];
+        }
+        const float tx = mine[3 * 64], ty = mine[4 * 64], tz = mine[5 * 64], tw = mine[6 * 64], qx = s[3], qy = s[4], qz = s[5], qw = s[6];
+        const float ew = __builtin_fmaf(tw, qw, __builtin_fmaf(tx, qx, __builtin_fmaf(ty, qy, tz * qz)));
+        const float ex = __builtin_fmaf(qw, tx, __builtin_fmaf(-tw, qx, __builtin_fmaf(qy, tz, -(qz * ty))));
+        const float ey = __builtin_fmaf(qw, ty, __builtin_fmaf(-tw, qy, __builtin_fmaf(qz, tx, -(qx * tz))));
+        const float ez = __builtin_fmaf(qw, tz, __builtin_fmaf(-tw, qz, __builtin_fmaf(qx, ty, -(qy * tx))));
+        const float h = ew < 0.0f ? -2.0f : 2.0f, kp = mine[13 * 64], kd = mine[14 * 64];
+        float T[3] = {__builtin_fmaf(kp, h * ex, -(kd * s[10])), __builtin_fmaf(kp, h * ey, -(kd * s[11])), __builtin_fmaf(kp, h * ez, -(kd * s[12]))};
+        clamp_norm(T, mine[16 * 64]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) f6[3 + i] += T[i];
+    }
+};
+
+// The applied kernel's arguments, then the control record's.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_ctl_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   PoseHold{control, control_stride, applied, applied_stride, body_frame, 0u, 0u});
+}
+
 }  // namespace
 
 // ==========================================================================
@@ -2145,7 +2248,8 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// hydro_step_fused_tiled_multi, its recording twin and the applied-wrench entry: one validation, one variant selection.
+// hydro_step_fused_tiled_multi, its recording twin, the applied-wrench and the pose-hold entry: one validation, one variant
+// selection.  ctl != nullptr launches step_fused_multi_ctl_tiled_kernel, which takes all three (a null `applied`: none).
 // rec == nullptr launches step_fused_multi_tiled_kernel, else step_fused_multi_rec_tiled_kernel with the recorder's
 // arguments appended; app != nullptr launches step_fused_multi_app_tiled_kernel, which takes both (a null watch mask: no
 // recording).
@@ -2157,18 +2261,29 @@ struct AppArgs {
     const float* applied; int64_t stride; int frame;
     const float* log; int64_t log_floats;            // the log as an output range `applied` must stay out of (may be null)
 };
+struct CtlArgs {
+    const float* control; int64_t stride;
+    const float* log; int64_t log_floats;            // as in AppArgs
+};
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
 {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
     return a < b + (uintptr_t)floats_q * 4u && b < a + (uintptr_t)floats * 4u;
 }
+// floats from the first to the last field of `fields`-field records in `tiles` tiles: what a kernel touches of an output.
+// (prev_out is usually the velocity fields INSIDE a state buffer: tiles * stride would reach 7 * 64 floats past its end,
+// into whatever the allocator put there)
+inline int64_t tiled_extent(int64_t tiles, int64_t stride, int fields)
+{
+    return tiles > 0 ? (tiles - 1) * stride + (int64_t)fields * HYDRO_TILE : 0;
+}
 int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
                                 const float* prev, int64_t prev_tile_stride, double dt, int steps,
                                 float* state_out, int64_t out_tile_stride,
                                 float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
                                 int rotational, double* ke_out_dev, const RecArgs* rec, int64_t* rows_written_host, int64_t rows, void* stream,
-                                const AppArgs* app = nullptr)
+                                const AppArgs* app = nullptr, const CtlArgs* ctl = nullptr)
 {
     int rc = check_common(h, n);
     if (rc) return rc;
@@ -2184,9 +2299,18 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
         if ((rc = check_tiled(h, n, app->applied, app->stride, HYDRO_WRENCH_FIELDS, "null applied"))) return rc;
         if (app->frame != HYDRO_FRAME_WORLD && app->frame != HYDRO_FRAME_BODY) return fail(h, HYDRO_E_ARG, "applied_frame must be HYDRO_FRAME_WORLD or HYDRO_FRAME_BODY");
         const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * app->stride;
-        if (ranges_overlap(app->applied, floats, state_out, tiles * out_tile_stride) || ranges_overlap(app->applied, floats, prev_out, tiles * prev_out_tile_stride)
+        if (ranges_overlap(app->applied, floats, state_out, tiled_extent(tiles, out_tile_stride, HYDRO_STATE_FIELDS))
+            || ranges_overlap(app->applied, floats, prev_out, tiled_extent(tiles, prev_out_tile_stride, HYDRO_PREV_FIELDS))
             || (app->log && ranges_overlap(app->applied, floats, app->log, app->log_floats)))
             return fail(h, HYDRO_E_ARG, "applied must not overlap an output (state_out, prev_out, log)");
+    }
+    if (ctl) {
+        if ((rc = check_tiled(h, n, ctl->control, ctl->stride, HYDRO_CTL_FIELDS, "null control"))) return rc;
+        const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * ctl->stride;
+        if (ranges_overlap(ctl->control, floats, state_out, tiled_extent(tiles, out_tile_stride, HYDRO_STATE_FIELDS))
+            || ranges_overlap(ctl->control, floats, prev_out, tiled_extent(tiles, prev_out_tile_stride, HYDRO_PREV_FIELDS))
+            || (ctl->log && ranges_overlap(ctl->control, floats, ctl->log, ctl->log_floats)))
+            return fail(h, HYDRO_E_ARG, "control must not overlap an output (state_out, prev_out, log)");
     }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2202,7 +2326,13 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
                                (uint32_t)n, (uint32_t)steps, (float)dt, h->rho, h->g, 1.0 / dt, h->ke_partials, h->ke_stride, rotational ? 1 : 0, ke_out_dev,
                                recorder...);
         };
-        if (app) {
+        if (ctl) {
+            const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
+            launch(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
+                   app ? app->applied : nullptr, app ? (uint32_t)app->stride : 0u, app ? app->frame : HYDRO_FRAME_WORLD,
+                   ctl->control, (uint32_t)ctl->stride);
+        }
+        else if (app) {
             const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
             launch(step_fused_multi_app_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
                    app->applied, (uint32_t)app->stride, app->frame);
@@ -2325,6 +2455,31 @@ int hydro_step_fused_tiled_multi_app(hydro_t* h, int64_t n, const float* state, 
     return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
                                        prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
                                        applied ? &app : nullptr);
+}
+
+int hydro_step_fused_tiled_multi_ctl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    RecArgs rec;
+    int64_t rows = 0;
+    if (log) {
+        const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
+        if (rc) return rc;
+    }
+    const int64_t log_floats = log ? rows_capacity * fields * log_stride : 0;
+    AppArgs app = {applied, applied_tile_stride, applied_frame, log, log_floats};
+    CtlArgs ctl = {control, control_tile_stride, log, log_floats};
+    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
+                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
+                                       applied ? &app : nullptr, control ? &ctl : nullptr);
 }
 
 int hydro_pack_state_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,

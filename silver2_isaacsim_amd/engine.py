@@ -425,6 +425,27 @@ class HydroEngine:
         self._check(self._lib.hydro_step_fused_tiled_multi_app(*args, *tail, a_ptr, a_stride, code, self._stream(stream)))
         return written.value
 
+    def step_fused_tiled_multi_controlled(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
+                                          control: torch.Tensor | None, applied: torch.Tensor | None = None, frame: str = "body",
+                                          log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                          state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                          ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_applied with a pose-hold feedback law on every body (hydro_step_fused_tiled_multi_ctl):
+        `control` is a tiled (tiles, 17, 64) buffer of [p*(3) | q*(4, xyzw) | kp_lin(3) | kd_lin(3) | kp_ang | kd_ang |
+        f_max | t_max] per body.  In every one of the `steps` steps the kernel forms, from the state that step starts from,
+        a clamped PD force towards p* and torque towards q* (the law and its order: include/hydro.h) and adds them to the
+        hydrodynamic wrench, after `applied` if there is one.  control=None is step_fused_tiled_multi_applied.  Returns the
+        number of rows written (0 without a log)."""
+        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
+        tail, written = self._rec_tail(log, every, phase, row0)
+        code = _FRAMES.get(frame)
+        if code is None:
+            raise ValueError("frame must be 'world' or 'body'")
+        a_ptr, a_stride = self._tiled(applied, nat.WRENCH_FIELDS, n) if applied is not None else (None, 0)
+        c_ptr, c_stride = self._tiled(control, nat.CTL_FIELDS, n) if control is not None else (None, 0)
+        self._check(self._lib.hydro_step_fused_tiled_multi_ctl(*args, *tail, a_ptr, a_stride, code, c_ptr, c_stride, self._stream(stream)))
+        return written.value
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

@@ -22,6 +22,7 @@ import time
 import numpy as np
 import torch
 
+from . import _native as nat
 from . import distributed as hd
 from . import scenes
 from .engine import HydroEngine
@@ -381,6 +382,9 @@ class ClosedLoopSim:
         self.applied: torch.Tensor | None = None
         self.applied_frame = "body"
         self._applied_buf: torch.Tensor | None = None
+        # set_pose_hold(): the tiled (tiles, 17, 64) control record while a pose hold is set, and the buffer itself (made once)
+        self.control: torch.Tensor | None = None
+        self._control_buf: torch.Tensor | None = None
 
     def record(self, bodies, every: int = 1, rows: int = 4096, wrench: bool = False) -> TrajectoryRecorder:
         """Watch `bodies` (any order, distinct, < n): from now on run_resident and run_eager write their state - with
@@ -457,23 +461,83 @@ class ClosedLoopSim:
             self.applied = None
             self._graph = None
 
-    # `k` steps in one launch with the applied wrench, recording if a recorder is attached (k = 1 from run_eager and inside
-    # graph captures: the single-step form of the entry)
+    def set_pose_hold(self, position=None, orientation_xyzw=None, kp_lin=0.0, kd_lin=0.0, kp_ang=0.0, kd_ang=0.0,
+                      f_max=float("inf"), t_max=float("inf"), bodies=None) -> torch.Tensor:
+        """Hold the bodies in place: from now on every physics step of run_eager, run (graph replays) and run_resident adds a
+        clamped PD force towards `position` and torque towards `orientation_xyzw`, evaluated INSIDE the stepping kernel from the
+        state each step starts from (hydro_step_fused_tiled_multi_ctl; the law: include/hydro.h) - a controller at the rate
+        of the physics, whatever `chunk` is.  It acts together with an applied wrench and a recorder where those are set.
+        position (., 3) and orientation_xyzw (., 4): the targets, default the current state; kp_lin, kd_lin: N/m and N s/m,
+        a scalar or per world axis (., 3) - kp_lin=(0, 0, k) is a pure depth hold; kp_ang, kd_ang: N m/rad and N m s/rad;
+        f_max, t_max: largest force and torque (inf: no limit).  Every argument is a scalar, one row, or one row per body
+        (per listed body with `bodies`); bodies that are not listed get zero gains.  The hold stays until the next call.
+        Returns `sim.control`, the tiled (tiles, 17, 64) device buffer the kernels read, fields [p* | q* | kp_lin | kd_lin |
+        kp_ang | kd_ang | f_max | t_max].  Its address never changes: a planner on the device may move the set-points in it
+        between chunks on `sim.stream`, and a graph replay sees the contents of the moment."""
+        if not self.fused:
+            raise ValueError("the pose hold lives in the fused step kernels (fused=True)")
+        idx = np.arange(self.n) if bodies is None else np.asarray(bodies, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+            raise ValueError(f"bodies must be in 0 .. {self.n - 1}")
+        rows = idx.size
+
+        def field(value, width, name):
+            a = np.asarray(value.detach().cpu() if torch.is_tensor(value) else value, dtype=np.float32)
+            if width == 1 and a.shape == (rows,):
+                a = a.reshape(rows, 1)
+            try:
+                return np.broadcast_to(a, (rows, width))
+            except ValueError:
+                raise ValueError(f"{name}: expected a scalar, ({width},) or ({rows}, {width}), got {a.shape}") from None
+
+        if position is None or orientation_xyzw is None:
+            now = self.state()[idx]
+        rec = np.zeros((self.n, nat.CTL_FIELDS), np.float32)
+        rec[:, 6] = 1.0                                                     # (an identity target where the gains are zero)
+        rec[:, 15:17] = np.inf
+        rec[idx, 0:3] = now[:, 0:3] if position is None else field(position, 3, "position")
+        rec[idx, 3:7] = now[:, 3:7] if orientation_xyzw is None else field(orientation_xyzw, 4, "orientation_xyzw")
+        rec[idx, 7:10], rec[idx, 10:13] = field(kp_lin, 3, "kp_lin"), field(kd_lin, 3, "kd_lin")
+        for col, (value, name) in enumerate(((kp_ang, "kp_ang"), (kd_ang, "kd_ang"), (f_max, "f_max"), (t_max, "t_max")), start=13):
+            rec[idx, col] = field(value, 1, name)[:, 0]
+        if np.isnan(rec).any() or (rec[:, 15:17] < 0).any():
+            raise ValueError("pose hold: NaN in an argument, or a negative f_max / t_max")
+        if self._control_buf is None:
+            self._control_buf = self.engine.alloc_tiled(nat.CTL_FIELDS, self.n)
+        with torch.cuda.stream(self.stream):
+            self._control_buf.copy_(torch.from_numpy(scenes.to_tiled(rec)))
+        if self.control is None:
+            self._graph = None                                              # captured steps are of another entry
+        self.control = self._control_buf
+        return self.control
+
+    def clear_pose_hold(self) -> None:
+        """Every call the sim makes is again the one it made before set_pose_hold."""
+        if self.control is not None:
+            self.control = None
+            self._graph = None
+
+    # `k` steps in one launch with the applied wrench and / or the pose hold, recording if a recorder is attached (k = 1
+    # from run_eager and inside graph captures: the single-step form of the entries)
     def _step_applied(self, k: int, ke_out) -> None:
         rec = self.recorder
         kw = {}
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw = dict(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        rows = self.engine.step_fused_tiled_multi_applied(self.cur, self.old, self.n, self.dt, k, self.applied, self.applied_frame,
-                                                          implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+        if self.control is not None:
+            rows = self.engine.step_fused_tiled_multi_controlled(self.cur, self.old, self.n, self.dt, k, self.control, self.applied,
+                                                                 self.applied_frame, implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+        else:
+            rows = self.engine.step_fused_tiled_multi_applied(self.cur, self.old, self.n, self.dt, k, self.applied, self.applied_frame,
+                                                              implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
         if rec is not None:
             rec.rows_written += rows
         self.cur, self.old = self.old, self.cur
 
     # `k` steps in one recording launch (k = 1 from run_eager: the bits of the single-step entry, include/hydro.h)
     def _step_recorded(self, k: int, sample: bool) -> None:
-        if self.applied is not None:
+        if self.applied is not None or self.control is not None:
             self._step_applied(k, self.ke_dev if sample else None)
             return
         rec = self.recorder
@@ -497,7 +561,7 @@ class ClosedLoopSim:
     def _step_once(self, sample: bool = False, ke_out: torch.Tensor | None = None) -> None:
         e = self.engine
         ke_out = (ke_out if ke_out is not None else self.ke_dev) if sample else None
-        if self.applied is not None:
+        if self.applied is not None or self.control is not None:
             self._step_applied(1, ke_out)
             return
         if self.fused:
@@ -619,7 +683,7 @@ class ClosedLoopSim:
                 sample = self.monitor is not None and k == chunk and (self.steps_done + k) % self.monitor.every == 0
                 if self.recorder is not None:
                     self._step_recorded(k, sample)
-                elif self.applied is not None:
+                elif self.applied is not None or self.control is not None:
                     self._step_applied(k, self.ke_dev if sample else None)
                 else:
                     self.engine.step_fused_tiled_multi(self.cur, self.old, self.n, self.dt, k, implicit_drag=self.implicit_drag,
