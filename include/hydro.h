@@ -72,6 +72,8 @@ extern "C" {
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
 #define HYDRO_WATCH_MAX  65536   /* bodies in one watch list (hydro_set_watch) */
+#define HYDRO_SEA_WAVES_MAX   8   /* regular wave components of a sea state (hydro_set_sea) */
+#define HYDRO_SEA_FIELDS      4   /* the record of hydro_sea_sample: eta, u_x, u_y, u_z */
 
 typedef struct hydro_engine hydro_t;
 
@@ -468,6 +470,89 @@ int hydro_step_fused_tiled_multi_ctl(hydro_t *h, int64_t n, const float *state, 
                                      int64_t row0, int64_t *rows_written_host,
                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
                                      const float *control, int64_t control_tile_stride, void *stream);
+
+/* Sea state: moving water for the closed-loop steps - a steady uniform current and regular deep-water waves, scene-wide like
+ * the density and gravity of hydro_set_scene.  The hydrodynamic wrench is translation-invariant in x and y and sees the water
+ * only through the depth of the body centre and the body's velocity, so moving water is the SAME wrench evaluated on a
+ * relative state: depth below the local surface, velocity against the local water.  The integrator, the applied wrench, the
+ * pose hold, the recorder and the kinetic energy keep acting on the true state.  Only hydro_step_fused_tiled_multi_sea and
+ * hydro_sea_sample know the sea: the wrench-only, array-of-structs, batch, component and plugin entries, and the other
+ * closed-loop entries, step through still water with its surface at z = 0 whatever is set here.
+ *
+ * hydro_sea_t: `current` U (m/s, world frame) and `waves` = 0 .. HYDRO_SEA_WAVES_MAX components, each an amplitude a >= 0 (m),
+ * a wave vector (kx, ky) (rad/m, world frame, kappa = |k| > 0 unless a == 0), an angular frequency omega (rad/s) and a phase
+ * phi (rad):  eta(x, y, t) = sum_j a_j cos(kx_j x + ky_j y - omega_j t + phi_j).  omega and k are taken as given: the
+ * dispersion relation (deep water: omega^2 = g kappa) is the caller's business.
+ *
+ * WATER AT A BODY.  At the start of local step k = 0 .. steps - 1 of a launch that begins at step index step0, for a body with
+ * state s = [p | q | v | omega_b], in exactly this order (fma(a, b, c): a * b + c rounded once):
+ *     t     = (step0 + k) * dt                               fp64, one rounding: (step0 + k) is an exact integer
+ *     x_j   = fma(-omega_j, t, phi_j)                        fp64
+ *     m_j   = rint(x_j * (1 / 2 pi))                         fp64, ties to even
+ *     tau_j = fma(-m_j, 2.4492935982947064e-16, fma(-m_j, 6.283185307179586, x_j))      fp64: x_j reduced to [-pi, pi];
+ *                                                            then rounded to fp32 (the same for every body)
+ *     th_j  = fma(kx_j, p_x, fma(ky_j, p_y, tau_j))          fp32 from here on
+ *     r_j   = th_j * 0.15915494 - rint(th_j * 0.15915494)    revolutions, in [-1/2, 1/2]; the subtraction is exact
+ *     c_j   = cos(2 pi r_j), s_j = sin(2 pi r_j)             the hardware's v_cos_f32 / v_sin_f32 of r_j
+ *     eta   = fma(a_j, c_j, eta)   j = 0, 1, ...             starting from +0
+ *     z_rel = p_z - eta
+ *     e_j   = exp2(kl2_j * min(z_rel, 0))                    v_exp_f32; kl2_j = kappa_j log2(e): no growth above the surface
+ *     u_x   = fma(cx_j, e_j * c_j, u_x),  u_y = fma(cy_j, e_j * c_j, u_y),  u_z = fma(aw_j, e_j * s_j, u_z)
+ *                                                            j = 0, 1, ...  starting from U
+ * with the constants kl2_j = kappa_j log2(e), cx_j = a_j omega_j kx_j / kappa_j, cy_j = a_j omega_j ky_j / kappa_j,
+ * aw_j = a_j omega_j, and a_j, kx_j, ky_j, U formed in fp64 on the host and rounded ONCE to fp32 (omega_j, phi_j stay fp64).
+ * RELATIVE STATE.  The step's hydrodynamic wrench is that of s with s[2] = z_rel and s[7:10] = v - u, and of the previous
+ * velocity pv with pv[0:3] - u (fp32 subtractions, the same u: the finite-difference acceleration stays the body's own).
+ * Everything behind the wrench takes the true s: the applied wrench, the pose hold, the integrator (the implicit-drag form
+ * needs no change: -k (v - u) removed at the old velocity and k (v' - u) added at the new one sum to -k v + k v'), the
+ * recorder, the kinetic energy, prev_out.  With implicit_drag == 0 and neither applied nor control a step is therefore, bit
+ * for bit, hydro_step_wrench_tiled of the relative state followed by hydro_integrate_tiled of the true one.
+ * NOT MODELLED: the slope of the surface; the variation of eta and u across the body (long-wave approximation: the body is
+ * small against the wavelength); dynamic pressure (Froude-Krylov force); the water's own acceleration in the added-mass term;
+ * finite depth; a vertical current U_z is accepted but is not volume-conserving.
+ *
+ * hydro_set_sea: copies the sea into an engine-owned device table (400 B, allocated by the first call, freed by
+ * hydro_destroy) on the engine's private stream and waits, like hydro_set_watch: the caller orders it after launches of this
+ * engine still in flight on other streams.  sea == NULL clears the sea.  HYDRO_E_ARG for more than HYDRO_SEA_WAVES_MAX (or
+ * fewer than 0) components, a non-finite value, a negative amplitude, kappa == 0 with a != 0, a constant beyond fp32 range -
+ * the previous sea stays in force.  A captured launch reads the table at replay time, with the number of components of the
+ * moment it was captured.
+ *
+ * hydro_sea_sample: writes the tiled HYDRO_SEA_FIELDS = 4 field record [eta, u_x, u_y, u_z] ([tiles][4][64] floats, tile
+ * stride out_tile_stride >= 256) of bodies 0 .. n - 1 - exactly the values a step that starts from `state` at step index
+ * `step_index` uses.  A small kernel of its own; asynchronous on `stream`.  HYDRO_E_STATE without a sea; HYDRO_E_ARG for
+ * dt <= 0, step_index outside 0 .. 2^52 - 1, n > capacity, a null or misaligned buffer.
+ *
+ * hydro_step_fused_tiled_multi_sea: hydro_step_fused_tiled_multi_ctl - same arguments up to control_tile_stride, same rules -
+ * through the sea, with `step0` the index of the launch's first step (the caller's running step count).
+ *   no sea set      : the launch and its bits are those of hydro_step_fused_tiled_multi_ctl with the same arguments.
+ *   a sea set       : log, applied and control are each still optional; what is added between the wrench and the integrator is
+ *                     what hydro_step_fused_tiled_multi_ctl adds for the same three pointers.
+ * A sea with no current and no waves (or waves of amplitude 0) gives the bits of the entry without a sea: x - (+0) == x, sign
+ * of zero included.  HYDRO_E_ARG for step0 < 0 or step0 + steps >= 2^52, besides what hydro_step_fused_tiled_multi_ctl
+ * refuses - all before anything is launched or written.  Asynchronous, no allocation, no synchronisation, safe to capture: a
+ * captured launch replays with the step0 it was captured with, i.e. at a frozen wave phase - capture current-only seas.
+ * Cost and registers: DESIGN.md section 17.  New functionality; the reference's water does not move. */
+typedef struct hydro_sea_wave {
+    double amplitude, kx, ky, omega, phase;
+} hydro_sea_wave_t;
+typedef struct hydro_sea {
+    double current[3];
+    int waves;
+    hydro_sea_wave_t wave[HYDRO_SEA_WAVES_MAX];
+} hydro_sea_t;
+int hydro_set_sea(hydro_t *h, const hydro_sea_t *sea);
+int hydro_sea_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
+                     float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_sea(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride, int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -19,6 +19,8 @@ CTL_FIELDS = 17                         # the control record of hydro_step_fused
 TILE = 64
 BATCH_MAX = 32
 WATCH_MAX = 65536
+SEA_WAVES_MAX = 8                       # regular wave components of a sea state (hydro_set_sea)
+SEA_FIELDS = 4                          # the record of hydro_sea_sample: eta, u_x, u_y, u_z
 
 
 class Scene(ctypes.Structure):
@@ -27,6 +29,16 @@ class Scene(ctypes.Structure):
                 ("state", c_void_p), ("state_tile_stride", c_int64),
                 ("prev", c_void_p), ("prev_tile_stride", c_int64),
                 ("wrench", c_void_p), ("wrench_tile_stride", c_int64)]
+
+
+class SeaWave(ctypes.Structure):
+    """hydro_sea_wave_t (include/hydro.h): one regular wave component."""
+    _fields_ = [("amplitude", c_double), ("kx", c_double), ("ky", c_double), ("omega", c_double), ("phase", c_double)]
+
+
+class Sea(ctypes.Structure):
+    """hydro_sea_t (include/hydro.h): the sea state hydro_set_sea takes."""
+    _fields_ = [("current", c_double * 3), ("waves", c_int), ("wave", SeaWave * SEA_WAVES_MAX)]
 
 
 HYDRO_OK, HYDRO_E_ARG, HYDRO_E_ALLOC, HYDRO_E_LAUNCH, HYDRO_E_DEVICE, HYDRO_E_STATE = 0, -1, -2, -3, -4, -5
@@ -77,6 +89,12 @@ SIGNATURES = {
                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "hydro_set_sea": (c_int, [c_void_p, POINTER(Sea)]),
+    "hydro_sea_sample": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_sea": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <dlfcn.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1106,11 +1107,17 @@ __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k
 // One closed-loop step of a body held in registers - the loop body of the two multi-step kernels below: the wrench of
 // (s, pv), the integrator, then pv <- the velocity just used and s <- the new state.  f6 is the wrench that produced the new s.
 // `app` is the applied-wrench policy: add(s, f6) between the (clamped) hydrodynamic wrench and the integrator.
-template <bool IMPLICIT, bool WARP, typename Applied>
+// `sea` is the sea-state policy: view(k, s, pv) puts the state RELATIVE to the local water in front of body_wrench (depth below
+// the local surface, velocity against the local water), restore(s, pv) brings the true one back behind it - everything
+// after the wrench acts on the true state (see SeaView; NoSea does nothing, and the kernels without a sea are unchanged).
+template <bool IMPLICIT, bool WARP, typename Applied, typename Sea>
 __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], const float (&d)[3], const float (&c)[7], float mass,
-                                                        double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS], const Applied& app)
+                                                        double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS], const Applied& app,
+                                                        uint32_t k, const Sea& sea)
 {
+    sea.view(k, s, pv);
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
+    sea.restore(s, pv);
     wrench_fields(w, f6);
     app.add(s, f6);
     float o[HYDRO_STATE_FIELDS];
@@ -1133,11 +1140,12 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // The body of the three kernels below.  `rec` is the recorder policy: begin(tile, lane) once the records are loaded, then
 // after_step(k, s, f6) behind every step with the state it produced and the wrench that produced it.  `app` is the
 // applied-wrench policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step (see AppliedWrench).
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied>
+// `sea` is the sea-state policy: begin(lane4) next to the record loads, then view / restore around every step's wrench.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea>
 __device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
                                                  uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app)
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea)
 {
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
@@ -1150,10 +1158,11 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
         load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
         rec.begin(tile, lane);
         app.begin(tile, lane4);
+        sea.begin(lane4);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
-            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app);
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea);
             rec.after_step(k, s, f6);
         }
         if constexpr (KE)
@@ -1172,6 +1181,11 @@ struct NoRecorder {
 struct NoApplied {
     __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
     __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_WRENCH_FIELDS]) const {}
+};
+struct NoSea {
+    __device__ __forceinline__ void begin(uint32_t) {}
+    __device__ __forceinline__ void view(uint32_t, float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_PREV_FIELDS]) const {}
+    __device__ __forceinline__ void restore(float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_PREV_FIELDS]) const {}
 };
 
 // --------------------------------------------------------------------------
@@ -1224,7 +1238,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
                                                                        double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{});
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
@@ -1238,7 +1252,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{});
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{});
 }
 
 // --------------------------------------------------------------------------
@@ -1309,7 +1323,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   AppliedWrench{applied, applied_stride, body_frame, {}});
+                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{});
 }
 
 // --------------------------------------------------------------------------
@@ -1412,7 +1426,184 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{control, control_stride, applied, applied_stride, body_frame, 0u, 0u});
+                                                   PoseHold{control, control_stride, applied, applied_stride, body_frame, 0u, 0u}, NoSea{});
+}
+
+// --------------------------------------------------------------------------
+// The SEA STATE in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_sea): a steady uniform current and up to
+// HYDRO_SEA_WAVES_MAX regular deep-water wave components, scene-wide like rho and g (hydro_set_sea).  The wrench is
+// translation-invariant in x, y and sees the water only through the depth of the body centre and the body's velocity, so moving
+// water is body_wrench of a RELATIVE state: p_z below the local surface, v and the previous v against the local water.  The
+// wave phase advances with every step and the states between the ends of a launch exist in registers only: the view is
+// formed here, per step.  include/hydro.h states the order of operations; sea_water below is its ONLY implementation (the
+// step kernel and hydro_sea_sample's kernel both call it).
+//   table : the engine's device copy of the sea, read through the CONSTANT address space: wave-uniform addresses, hence
+//           scalar loads (s_load) in every step - the components take no vector registers between steps
+//   time  : t = (step0 + k) * dt in fp64, tau_j = phi_j - omega_j t reduced by a two-term 2 pi in fp64 (error about
+//           1e-16 |omega_j t|: 5e-12 rad after 10^6 steps at 60 Hz), THEN rounded to fp32
+//   trig  : the hardware seeds v_sin_f32 / v_cos_f32 (argument in revolutions) behind an explicit reduction
+//           r = th / 2 pi - rint(th / 2 pi), exact but for the one product; v_exp_f32 for the depth decay
+// WHERE THE TRUE STATE LIVES while the wrench runs: the applied kernels stand at the limit of 3 waves per SIMD, so the seven
+// true values (p_z, v, pv[0:3]) are parked in LDS around body_wrench, [wave][7][64] floats (7 KB per block), and the relative
+// ones take their registers - no live range is added to the wrench.  Each lane reads only what it wrote: no barrier.  The
+// address is formed as in PoseHold (lane4 + a wave-uniform scalar, opaque to the compiler so that it neither hoists the sum
+// nor forwards the parked values through registers).
+// --------------------------------------------------------------------------
+struct SeaWave {
+    double omega, phi;                                   // rad / s, rad
+    float a, kx, ky, kl2, cx, cy, aw, pad;               // amplitude, wave vector, kappa log2(e), a omega kx / kappa, a omega ky / kappa, a omega
+};
+struct SeaTable {
+    float u[3]; uint32_t waves;
+    SeaWave w[HYDRO_SEA_WAVES_MAX];
+};
+typedef const __attribute__((address_space(4))) SeaTable* SeaTablePtr;
+__device__ __forceinline__ SeaTablePtr sea_table_ptr(const void* p) { return (SeaTablePtr)p; }
+
+// eta and u of the water at (px, py) for a body whose centre is at pz, at the start of step `step` (include/hydro.h, "sea").
+__device__ __forceinline__ void sea_water(SeaTablePtr tab, uint32_t waves, int64_t step, double dt, float px, float py, float pz,
+                                          float& eta, float (&u)[3])
+{
+    constexpr double kInv2Pi = 0.15915494309189535, kTwoPiHi = 6.283185307179586, kTwoPiLo = 2.4492935982947064e-16;
+    const double t = (double)step * dt;
+    float cs[HYDRO_SEA_WAVES_MAX], sn[HYDRO_SEA_WAVES_MAX];
+    eta = 0.0f;
+#pragma unroll
+    for (int j = 0; j < HYDRO_SEA_WAVES_MAX; ++j) {
+        if ((uint32_t)j < waves) {                           // (wave-uniform)
+            const double x = __builtin_fma(-tab->w[j].omega, t, tab->w[j].phi);
+            const double m = __builtin_rint(x * kInv2Pi);
+            const float tau = (float)__builtin_fma(-m, kTwoPiLo, __builtin_fma(-m, kTwoPiHi, x));
+            const float th = __builtin_fmaf(tab->w[j].kx, px, __builtin_fmaf(tab->w[j].ky, py, tau));
+            const float rev = th * 0.15915494309189535f;
+            const float r = rev - __builtin_rintf(rev);
+            cs[j] = __builtin_amdgcn_cosf(r);
+            sn[j] = __builtin_amdgcn_sinf(r);
+            eta = __builtin_fmaf(tab->w[j].a, cs[j], eta);
+        }
+    }
+    const float zc = __builtin_fminf(pz - eta, 0.0f);
+    u[0] = tab->u[0]; u[1] = tab->u[1]; u[2] = tab->u[2];
+#pragma unroll
+    for (int j = 0; j < HYDRO_SEA_WAVES_MAX; ++j) {
+        if ((uint32_t)j < waves) {
+            const float e = __builtin_amdgcn_exp2f(tab->w[j].kl2 * zc);
+            const float ec = e * cs[j], es = e * sn[j];
+            u[0] = __builtin_fmaf(tab->w[j].cx, ec, u[0]);
+            u[1] = __builtin_fmaf(tab->w[j].cy, ec, u[1]);
+            u[2] = __builtin_fmaf(tab->w[j].aw, es, u[2]);
+        }
+    }
+}
+
+constexpr uint32_t kSeaSlots = 7;
+struct SeaView {
+    SeaTablePtr tab; uint32_t waves; int64_t step0; double dt;
+    uint32_t lane4, wave_off;
+    static __device__ __forceinline__ float* slots()
+    {
+        __shared__ __attribute__((aligned(16))) float lds[kBlock * kSeaSlots];
+        return lds;
+    }
+    __device__ __forceinline__ void begin(uint32_t lane4_)
+    {
+        lane4 = lane4_;
+        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kSeaSlots * 256u);
+    }
+    __device__ __forceinline__ float* mine() const
+    {
+        uint32_t w_off = wave_off;
+        asm volatile("" : "+s"(w_off));
+        return at<float>(slots(), lane4 + w_off);
+    }
+    __device__ __forceinline__ void view(uint32_t k, float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        float eta, u[3];
+        sea_water(tab, waves, step0 + (int64_t)k, dt, s[0], s[1], s[2], eta, u);
+        float* m = mine();
+        m[0] = s[2];
+        s[2] = s[2] - eta;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            m[(1 + i) * 64] = s[7 + i];
+            m[(4 + i) * 64] = pv[i];
+            s[7 + i] = s[7 + i] - u[i];
+            pv[i] = pv[i] - u[i];
+        }
+    }
+    __device__ __forceinline__ void restore(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        const float* m = mine();
+        s[2] = m[0];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            s[7 + i] = m[(1 + i) * 64];
+            pv[i] = m[(4 + i) * 64];
+        }
+    }
+};
+
+// The pose hold of the sea kernel: `control` and `applied` are each optional (kernel arguments: wave-uniform branches), and
+// what is added is what the kernel the host would pick WITHOUT a sea adds - PoseHold with a control record (zeros for a
+// missing applied wrench, as there), the applied wrench alone without one, nothing without either.
+struct OptionalPoseHold : PoseHold {
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        if (ctl) { PoseHold::begin(tile, lane4_); return; }
+        lane4 = lane4_;
+        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kCtlSlots * 256u);
+        if (applied) {
+            float* mine = at<float>(slots(), lane4 + wave_off);
+            const float* a = applied + (size_t)tile * applied_stride;
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = ldg<false>(at<float>(a, lane4, f * 256u));
+        }
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        if (ctl) { PoseHold::add(s, f6); return; }
+        if (applied) {
+            uint32_t w_off = wave_off;
+            asm volatile("" : "+s"(w_off));
+            const float* mine = at<float>(slots(), lane4 + w_off);
+            AppliedWrench a{nullptr, 0u, body_frame, {}};
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) a.a[f] = mine[(HYDRO_CTL_FIELDS + f) * 64];
+            a.add(s, f6);
+        }
+    }
+};
+
+// The pose-hold kernel's arguments, then the sea's.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_sea_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{control, control_stride, applied, applied_stride, body_frame, 0u, 0u}},
+                                                   SeaView{sea_table_ptr(sea_table), sea_waves, step0, sea_dt, 0u, 0u});
+}
+
+// hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
+__global__ void __launch_bounds__(kBlock) sea_sample_kernel(const float* st, uint32_t st_stride, float* out, uint32_t out_stride, uint32_t n,
+                                                            const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float eta, u[3];
+    sea_water(sea_table_ptr(sea_table), sea_waves, step, sea_dt, *at<float>(r, lane4, 0u), *at<float>(r, lane4, 256u), *at<float>(r, lane4, 512u), eta, u);
+    const float o[HYDRO_SEA_FIELDS] = {eta, u[0], u[1], u[2]};
+    store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
 }
 
 }  // namespace
@@ -1453,6 +1644,10 @@ struct hydro_engine {
     uint32_t* watch_first = nullptr; // [tiles of capacity]
     int64_t watch_count = 0;         // 0: no watch list
     int64_t watch_last = -1;         // the largest watched body (a recording launch needs it below its n)
+    // The sea state (hydro_set_sea): the device table the sea kernels read (SeaTable), allocated by the first hydro_set_sea,
+    // kept until hydro_destroy.  sea_waves < 0: no sea.
+    void* sea_table = nullptr;
+    int sea_waves = -1;
     hipStream_t stream = nullptr;
     int vec = 0;                   // bodies per lane, 0 = default (1)
     int block = 0;                 // threads per block, 0 = by size
@@ -1896,6 +2091,7 @@ int hydro_destroy(hydro_t* h)
     if (h->ke_event) (void)hipEventDestroy(h->ke_event);
     if (h->watch_mask) (void)hipFree(h->watch_mask);
     if (h->watch_first) (void)hipFree(h->watch_first);
+    if (h->sea_table) (void)hipFree(h->sea_table);
     delete h;
     return HYDRO_OK;
 }
@@ -2248,8 +2444,9 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// hydro_step_fused_tiled_multi, its recording twin, the applied-wrench and the pose-hold entry: one validation, one variant
-// selection.  ctl != nullptr launches step_fused_multi_ctl_tiled_kernel, which takes all three (a null `applied`: none).
+// hydro_step_fused_tiled_multi, its recording twin, the applied-wrench, the pose-hold and the sea entry: one validation, one
+// variant selection.  sea != nullptr launches step_fused_multi_sea_tiled_kernel, which takes everything (each of the others
+// null: none).  Else ctl != nullptr launches step_fused_multi_ctl_tiled_kernel, which takes all three (a null `applied`: none).
 // rec == nullptr launches step_fused_multi_tiled_kernel, else step_fused_multi_rec_tiled_kernel with the recorder's
 // arguments appended; app != nullptr launches step_fused_multi_app_tiled_kernel, which takes both (a null watch mask: no
 // recording).
@@ -2265,6 +2462,7 @@ struct CtlArgs {
     const float* control; int64_t stride;
     const float* log; int64_t log_floats;            // as in AppArgs
 };
+struct SeaArgs { int64_t step0; };                   // (the table and the number of components are the engine's)
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
 {
@@ -2283,7 +2481,7 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
                                 float* state_out, int64_t out_tile_stride,
                                 float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
                                 int rotational, double* ke_out_dev, const RecArgs* rec, int64_t* rows_written_host, int64_t rows, void* stream,
-                                const AppArgs* app = nullptr, const CtlArgs* ctl = nullptr)
+                                const AppArgs* app = nullptr, const CtlArgs* ctl = nullptr, const SeaArgs* sea = nullptr)
 {
     int rc = check_common(h, n);
     if (rc) return rc;
@@ -2326,7 +2524,14 @@ int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64
                                (uint32_t)n, (uint32_t)steps, (float)dt, h->rho, h->g, 1.0 / dt, h->ke_partials, h->ke_stride, rotational ? 1 : 0, ke_out_dev,
                                recorder...);
         };
-        if (ctl) {
+        if (sea) {
+            const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
+            launch(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
+                   app ? app->applied : nullptr, app ? (uint32_t)app->stride : 0u, app ? app->frame : HYDRO_FRAME_WORLD,
+                   ctl ? ctl->control : nullptr, ctl ? (uint32_t)ctl->stride : 0u,
+                   (const void*)h->sea_table, (uint32_t)h->sea_waves, sea->step0, dt);
+        }
+        else if (ctl) {
             const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
             launch(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
                    app ? app->applied : nullptr, app ? (uint32_t)app->stride : 0u, app ? app->frame : HYDRO_FRAME_WORLD,
@@ -2480,6 +2685,99 @@ int hydro_step_fused_tiled_multi_ctl(hydro_t* h, int64_t n, const float* state, 
     return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
                                        prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
                                        applied ? &app : nullptr, control ? &ctl : nullptr);
+}
+
+int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!sea) { h->sea_waves = -1; return HYDRO_OK; }
+    if (sea->waves < 0 || sea->waves > HYDRO_SEA_WAVES_MAX) return fail(h, HYDRO_E_ARG, "sea: waves out of range (0 .. HYDRO_SEA_WAVES_MAX)");
+    for (int i = 0; i < 3; ++i)
+        if (!isfinite(sea->current[i])) return fail(h, HYDRO_E_ARG, "sea: non-finite current");
+    SeaTable tab;
+    memset(&tab, 0, sizeof tab);
+    for (int i = 0; i < 3; ++i) tab.u[i] = (float)(sea->current[i] + 0.0);      // (-0 + 0 = +0: a zero current is +0)
+    tab.waves = (uint32_t)sea->waves;
+    for (int j = 0; j < sea->waves; ++j) {
+        const hydro_sea_wave_t& w = sea->wave[j];
+        if (!isfinite(w.amplitude) || !isfinite(w.kx) || !isfinite(w.ky) || !isfinite(w.omega) || !isfinite(w.phase))
+            return fail(h, HYDRO_E_ARG, "sea: non-finite wave component");
+        if (w.amplitude < 0.0) return fail(h, HYDRO_E_ARG, "sea: negative amplitude");
+        const double kappa = sqrt(w.kx * w.kx + w.ky * w.ky);
+        if (!(kappa > 0.0)) {
+            if (w.amplitude != 0.0) return fail(h, HYDRO_E_ARG, "sea: a wave component with amplitude needs a wave vector (kappa > 0)");
+            continue;                                                          // a = 0, kappa = 0: all zeros, contributes +0
+        }
+        SeaWave& d = tab.w[j];
+        const double aw = w.amplitude * w.omega;
+        d.omega = w.omega; d.phi = w.phase;
+        d.a = (float)w.amplitude; d.kx = (float)w.kx; d.ky = (float)w.ky;
+        d.kl2 = (float)(kappa * 1.4426950408889634);
+        d.cx = (float)(aw * w.kx / kappa); d.cy = (float)(aw * w.ky / kappa); d.aw = (float)aw;
+        if (!isfinite(d.kl2) || !isfinite(d.cx) || !isfinite(d.cy) || !isfinite(d.aw) || !isfinite(d.kx) || !isfinite(d.ky) || !isfinite(d.a))
+            return fail(h, HYDRO_E_ARG, "sea: wave component out of fp32 range");
+    }
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (!h->sea_table && hipMalloc(&h->sea_table, sizeof(SeaTable)) != hipSuccess) { h->sea_table = nullptr; return fail(h, HYDRO_E_ALLOC, "sea table: allocation failed"); }
+    // from here on the device table is being rewritten: a failure leaves NO sea, never half of one
+    h->sea_waves = -1;
+    hipError_t e = hipMemcpyAsync(h->sea_table, &tab, sizeof tab, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, HYDRO_E_LAUNCH, "sea table: copy to the device", e);
+    h->sea_waves = sea->waves;
+    return HYDRO_OK;
+}
+
+int hydro_sea_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
+                     float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (n < 0 || n > h->capacity) return fail(h, HYDRO_E_ARG, "n out of range (0 <= n <= capacity)");
+    if (h->sea_waves < 0) return fail(h, HYDRO_E_STATE, "no sea (call hydro_set_sea first)");
+    if (!(dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
+    if (step_index < 0 || step_index >= ((int64_t)1 << 52)) return fail(h, HYDRO_E_ARG, "step_index must be in 0 .. 2^52 - 1");
+    int rc;
+    if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
+    if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_SEA_FIELDS, "null out"))) return rc;
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (n == 0) return HYDRO_OK;
+    hipLaunchKernelGGL(sea_sample_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
+                       out, (uint32_t)out_tile_stride, (uint32_t)n, (const void*)h->sea_table, (uint32_t)h->sea_waves, step_index, dt);
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride, int64_t step0, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (step0 < 0 || steps < 0 || step0 + (int64_t)steps >= ((int64_t)1 << 52) || step0 >= ((int64_t)1 << 52))
+        return fail(h, HYDRO_E_ARG, "step0 must be >= 0 and step0 + steps < 2^52");
+    if (h->sea_waves < 0)
+        return hydro_step_fused_tiled_multi_ctl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
+                                                prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log, log_stride, rows_capacity,
+                                                fields, every, phase, row0, rows_written_host, applied, applied_tile_stride, applied_frame,
+                                                control, control_tile_stride, stream);
+    RecArgs rec;
+    int64_t rows = 0;
+    if (log) {
+        const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
+        if (rc) return rc;
+    }
+    const int64_t log_floats = log ? rows_capacity * fields * log_stride : 0;
+    AppArgs app = {applied, applied_tile_stride, applied_frame, log, log_floats};
+    CtlArgs ctl = {control, control_tile_stride, log, log_floats};
+    SeaArgs sea = {step0};
+    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
+                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
+                                       applied ? &app : nullptr, control ? &ctl : nullptr, &sea);
 }
 
 int hydro_pack_state_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,

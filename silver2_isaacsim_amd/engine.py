@@ -11,7 +11,7 @@ field f (orders in include/hydro.h).
 Each rule for turning a Python argument into C arguments is written once: `_tiled` (a tiled buffer ->
 pointer, tile stride), `_prev_velocity` (None / state buffer / 6-field buffer), `_wrench_tiled_call` and
 `_wrench_aos_call` (the direct and the prepared form of a step share one argument list), `_fused_head`
-(the fused steps), `_fused_multi_args` and `_rec_tail` (the multi-step entries) and `_rows` / `_force_torque` (simulator tensors).  tests/test_engine_calls.py
+(the fused steps), `_fused_multi_args`, `_rec_tail` and `_applied_control` (the multi-step entries) and `_rows` / `_force_torque` (simulator tensors).  tests/test_engine_calls.py
 pins the resulting calls without a GPU.
 """
 from __future__ import annotations
@@ -70,6 +70,7 @@ class HydroEngine:
         self.coeff_dtype = "f32"
         self.semantics = "numba"
         self._tables: dict = {}
+        self.sea_waves: int | None = None            # wave components of the sea set with set_sea; None: no sea
         self.set_scene(water_density, gravity)
 
     # ------------------------------------------------------------------ utils
@@ -438,12 +439,69 @@ class HydroEngine:
         number of rows written (0 without a log)."""
         _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
         tail, written = self._rec_tail(log, every, phase, row0)
+        push = self._applied_control(applied, frame, control, n)
+        self._check(self._lib.hydro_step_fused_tiled_multi_ctl(*args, *tail, *push, self._stream(stream)))
+        return written.value
+
+    def _applied_control(self, applied, frame, control, n):
+        """The arguments `applied .. control_tile_stride` of `hydro_step_fused_tiled_multi_ctl` / `_sea`: either buffer may be
+        None (NULL, stride 0)."""
         code = _FRAMES.get(frame)
         if code is None:
             raise ValueError("frame must be 'world' or 'body'")
         a_ptr, a_stride = self._tiled(applied, nat.WRENCH_FIELDS, n) if applied is not None else (None, 0)
         c_ptr, c_stride = self._tiled(control, nat.CTL_FIELDS, n) if control is not None else (None, 0)
-        self._check(self._lib.hydro_step_fused_tiled_multi_ctl(*args, *tail, a_ptr, a_stride, code, c_ptr, c_stride, self._stream(stream)))
+        return a_ptr, a_stride, code, c_ptr, c_stride
+
+    # ------------------------------------------------------------------ sea state
+    def set_sea(self, sea) -> None:
+        """The scene's moving water (hydro_set_sea; the model: include/hydro.h): `sea` has `current` (3 floats, m/s, world
+        frame) and `waves`, up to `_native.SEA_WAVES_MAX` rows (amplitude, kx, ky, omega, phase) - a `sea.SeaState`.  None clears
+        it.  Only `step_fused_tiled_multi_sea` and `sea_sample` see the sea.  Synchronous: the copy runs on the engine's
+        stream, so launches of this engine still in flight elsewhere are the caller's to wait for."""
+        if sea is None:
+            self._check(self._lib.hydro_set_sea(self._h, None))
+            self.sea_waves = None
+            return
+        waves = [tuple(float(x) for x in w) for w in sea.waves]
+        if len(waves) > nat.SEA_WAVES_MAX or any(len(w) != 5 for w in waves):
+            raise ValueError(f"a sea has at most {nat.SEA_WAVES_MAX} wave components of (amplitude, kx, ky, omega, phase)")
+        c = nat.Sea()
+        c.current[:] = [float(x) for x in sea.current]
+        c.waves = len(waves)
+        for j, w in enumerate(waves):
+            c.wave[j] = nat.SeaWave(*w)
+        self._check(self._lib.hydro_set_sea(self._h, ctypes.byref(c)))
+        self.sea_waves = len(waves)
+
+    def sea_sample(self, state: torch.Tensor, n: int, step_index: int, dt: float, out: torch.Tensor | None = None,
+                   stream=None) -> torch.Tensor:
+        """The water each body of the tiled `state` meets at the start of step `step_index` (hydro_sea_sample): a tiled
+        (tiles, 4, 64) buffer of [eta, u_x, u_y, u_z] - surface elevation above the body and water velocity at its centre,
+        exactly the values `step_fused_tiled_multi_sea` uses for that step."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.SEA_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.SEA_FIELDS, n)
+        self._check(self._lib.hydro_sea_sample(self._h, n, s_ptr, s_stride, int(step_index), float(dt), o_ptr, o_stride,
+                                               self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_sea(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                   control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                   log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_controlled through the sea set with `set_sea` (hydro_step_fused_tiled_multi_sea): in every
+        step the hydrodynamic wrench is that of the state RELATIVE to the local water - depth below the local surface,
+        velocity against current and wave orbital velocity - while integrator, applied wrench, pose hold and recorder act
+        on the true state.  `step0`: the index of this launch's first step (the wave phase is (step0 + k) * dt inside the
+        launch).  control, applied and log are each optional; without a sea the call is step_fused_tiled_multi_controlled.
+        Returns the number of rows written (0 without a log)."""
+        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
+        tail, written = self._rec_tail(log, every, phase, row0)
+        push = self._applied_control(applied, frame, control, n)
+        self._check(self._lib.hydro_step_fused_tiled_multi_sea(*args, *tail, *push, int(step0), self._stream(stream)))
         return written.value
 
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,

@@ -385,6 +385,7 @@ class ClosedLoopSim:
         # set_pose_hold(): the tiled (tiles, 17, 64) control record while a pose hold is set, and the buffer itself (made once)
         self.control: torch.Tensor | None = None
         self._control_buf: torch.Tensor | None = None
+        self.sea = None                                         # set_sea(): the sea.SeaState the steps run through
 
     def record(self, bodies, every: int = 1, rows: int = 4096, wrench: bool = False) -> TrajectoryRecorder:
         """Watch `bodies` (any order, distinct, < n): from now on run_resident and run_eager write their state - with
@@ -517,6 +518,28 @@ class ClosedLoopSim:
             self.control = None
             self._graph = None
 
+    def set_sea(self, sea) -> None:
+        """Moving water: from now on every physics step of run_eager, run and run_resident evaluates the hydrodynamic wrench
+        on the state relative to `sea` (a `sea.SeaState`: steady current + regular waves; hydro_step_fused_tiled_multi_sea,
+        the model: include/hydro.h), with the wave phase following `steps_done` - also between the steps of a resident
+        launch.  It acts together with an applied wrench, a pose hold and a recorder where those are set.  Graph replays
+        (`run` with graph_steps) work for a current-only sea; with waves they raise ValueError - a captured launch would
+        replay a frozen time.  The sea stays until the next call or `clear_sea()`."""
+        if not self.fused:
+            raise ValueError("the sea state lives in the fused step kernels (fused=True)")
+        self.synchronize()                                      # launches in flight read the table this rewrites
+        self.engine.set_sea(sea)
+        self.sea = sea
+        self._graph = None                                      # captured steps are of another entry / another sea
+
+    def clear_sea(self) -> None:
+        """Back to still water: every call the sim makes is again the one it made before set_sea."""
+        if self.sea is not None:
+            self.synchronize()
+            self.engine.set_sea(None)
+            self.sea = None
+            self._graph = None
+
     # `k` steps in one launch with the applied wrench and / or the pose hold, recording if a recorder is attached (k = 1
     # from run_eager and inside graph captures: the single-step form of the entries)
     def _step_applied(self, k: int, ke_out) -> None:
@@ -525,7 +548,10 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw = dict(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.control is not None:
+        if self.sea is not None:
+            rows = self.engine.step_fused_tiled_multi_sea(self.cur, self.old, self.n, self.dt, k, self.steps_done, self.control, self.applied,
+                                                          self.applied_frame, implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+        elif self.control is not None:
             rows = self.engine.step_fused_tiled_multi_controlled(self.cur, self.old, self.n, self.dt, k, self.control, self.applied,
                                                                  self.applied_frame, implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
         else:
@@ -537,7 +563,7 @@ class ClosedLoopSim:
 
     # `k` steps in one recording launch (k = 1 from run_eager: the bits of the single-step entry, include/hydro.h)
     def _step_recorded(self, k: int, sample: bool) -> None:
-        if self.applied is not None or self.control is not None:
+        if self.applied is not None or self.control is not None or self.sea is not None:
             self._step_applied(k, self.ke_dev if sample else None)
             return
         rec = self.recorder
@@ -561,7 +587,7 @@ class ClosedLoopSim:
     def _step_once(self, sample: bool = False, ke_out: torch.Tensor | None = None) -> None:
         e = self.engine
         ke_out = (ke_out if ke_out is not None else self.ke_dev) if sample else None
-        if self.applied is not None or self.control is not None:
+        if self.applied is not None or self.control is not None or self.sea is not None:
             self._step_applied(1, ke_out)
             return
         if self.fused:
@@ -628,6 +654,9 @@ class ClosedLoopSim:
         if self.recorder is not None and graph_steps and steps >= graph_steps:
             raise ValueError("a trajectory recorder cannot ride in graph replays: the log row a captured launch writes to is "
                              "frozen at capture - use run_resident (or run_eager), or stop_recording() first")
+        if self.sea is not None and len(self.sea.waves) and graph_steps and steps >= graph_steps:
+            raise ValueError("a sea with waves cannot ride in graph replays: the time a captured launch steps at is frozen at "
+                             "capture - use run_resident (or run_eager); a current-only sea replays")
         self._warm_monitor()
         if graph_steps and steps >= graph_steps:
             if self.steps_done % graph_steps and self.monitor is not None:
@@ -683,7 +712,7 @@ class ClosedLoopSim:
                 sample = self.monitor is not None and k == chunk and (self.steps_done + k) % self.monitor.every == 0
                 if self.recorder is not None:
                     self._step_recorded(k, sample)
-                elif self.applied is not None or self.control is not None:
+                elif self.applied is not None or self.control is not None or self.sea is not None:
                     self._step_applied(k, self.ke_dev if sample else None)
                 else:
                     self.engine.step_fused_tiled_multi(self.cur, self.old, self.n, self.dt, k, implicit_drag=self.implicit_drag,
