@@ -47,6 +47,14 @@ with torch.cuda.stream(stream):
     print(f"engine.step_fused_tiled       host issue {d[0]:6.2f} us/call   wall {d[1]:6.2f} us/step")
     e = bench(lambda: eng.step_fused_tiled_multi(S, S2, sc.n, sc.dt, 1))
     print(f"engine.step_fused_tiled_multi host issue {e[0]:6.2f} us/call   wall {e[1]:6.2f} us/step")
+    # the resident loop's fullest call: through a sea, with pose hold, applied wrench and recorder all set (one step, row 0)
+    from silver2_isaacsim_amd.sea import SeaState
+    eng.set_sea(SeaState.regular(0.4, 8.0, 0.0, current=(0.3, 0.0, 0.0))); eng.set_watch([0, 100, sc.n - 1])
+    A, C = eng.alloc_tiled(6, sc.n), eng.alloc_tiled(nat.CTL_FIELDS, sc.n)
+    L = torch.zeros((4, 13, 3), dtype=torch.float32, device=dev)
+    g = bench(lambda: eng.step_fused_tiled_multi_sea(S, S2, sc.n, sc.dt, 1, 0, C, A, "body", log=L, every=1, phase=1, row0=0))
+    print(f"engine.step_fused_tiled_multi_sea host issue {g[0]:6.2f} us/call   wall {g[1]:6.2f} us/step")
+    eng.set_sea(None); eng.set_watch(None)
     # the plugin's call: 20 bodies on the simulator's tensors, prepared once, stream = the current one at each call
     m = 20
     eng20 = HydroEngine(m, dev, sc.rho, sc.g); eng20.set_params(sc.params[:m])

@@ -993,6 +993,19 @@ __device__ __forceinline__ float rsqrt_nr(float x)
     return __builtin_fmaf(__builtin_fmaf(-x * r, r, 1.0f), 0.5f * r, r);
 }
 
+// The fp32 rotation matrix of a quaternion as given (non-unit included), body -> world: the one form the integrator and the
+// body-frame applied wrench turn vectors with.
+struct Rotation { float r00, r01, r02, r10, r11, r12, r20, r21, r22; };
+__device__ __forceinline__ Rotation rotation_of(float qx, float qy, float qz, float qw)
+{
+    const float x2 = qx + qx, y2 = qy + qy, z2 = qz + qz;
+    const float xx = qx * x2, xy = qx * y2, xz = qx * z2, yy = qy * y2, yz = qy * z2, zz = qz * z2;
+    const float sx = qw * x2, sy = qw * y2, sz = qw * z2;
+    return {1.0f - (yy + zz), xy - sz, xz + sy,
+            xy + sz, 1.0f - (xx + zz), yz - sx,
+            xz - sy, yz + sx, 1.0f - (xx + yy)};
+}
+
 template <bool IMPLICIT>
 __device__ __forceinline__ void integrate_body(const float (&s)[HYDRO_STATE_FIELDS], const float (&f)[HYDRO_WRENCH_FIELDS],
                                                float m, float dx, float dy, float dz, float g, float dt,
@@ -1012,12 +1025,7 @@ __device__ __forceinline__ void integrate_body(const float (&s)[HYDRO_STATE_FIEL
     const float px = s[0] + dt * vx, py = s[1] + dt * vy, pz = s[2] + dt * vz;
     // angular, body frame: I w' = tau_b - w_b x (I w_b), box inertia
     const float qx = s[3], qy = s[4], qz = s[5], qw = s[6];
-    const float x2 = qx + qx, y2 = qy + qy, z2 = qz + qz;
-    const float xx = qx * x2, xy = qx * y2, xz = qx * z2, yy = qy * y2, yz = qy * z2, zz = qz * z2;
-    const float sx = qw * x2, sy = qw * y2, sz = qw * z2;
-    const float r00 = 1.0f - (yy + zz), r01 = xy - sz, r02 = xz + sy;
-    const float r10 = xy + sz, r11 = 1.0f - (xx + zz), r12 = yz - sx;
-    const float r20 = xz - sy, r21 = yz + sx, r22 = 1.0f - (xx + yy);
+    const auto [r00, r01, r02, r10, r11, r12, r20, r21, r22] = rotation_of(qx, qy, qz, qw);
     const float k = m * (1.0f / 12.0f);
     const float ix = k * (dy * dy + dz * dz), iy = k * (dx * dx + dz * dz), iz = k * (dx * dx + dy * dy);
     const float wbx = r00 * s[10] + r10 * s[11] + r20 * s[12];
@@ -1281,13 +1289,7 @@ struct AppliedWrench {
     __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
     {
         if (body_frame) {
-            const float qx = s[3], qy = s[4], qz = s[5], qw = s[6];
-            const float x2 = qx + qx, y2 = qy + qy, z2 = qz + qz;
-            const float xx = qx * x2, xy = qx * y2, xz = qx * z2, yy = qy * y2, yz = qy * z2, zz = qz * z2;
-            const float sx = qw * x2, sy = qw * y2, sz = qw * z2;
-            const float r00 = 1.0f - (yy + zz), r01 = xy - sz, r02 = xz + sy;
-            const float r10 = xy + sz, r11 = 1.0f - (xx + zz), r12 = yz - sx;
-            const float r20 = xz - sy, r21 = yz + sx, r22 = 1.0f - (xx + yy);
+            const auto [r00, r01, r02, r10, r11, r12, r20, r21, r22] = rotation_of(s[3], s[4], s[5], s[6]);
 #pragma unroll
             for (int h = 0; h < HYDRO_WRENCH_FIELDS; h += 3) {
                 f6[h + 0] += r00 * a[h] + r01 * a[h + 1] + r02 * a[h + 2];
@@ -1327,6 +1329,36 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
 }
 
 // --------------------------------------------------------------------------
+// SLOTS floats per lane PARKED IN LDS for the length of a launch, [wave][SLOTS][64] (stride 1 across the lanes: no bank
+// conflict): what a policy needs in every step and the loop has no registers for.  A lane reads only what it wrote itself: no
+// barrier.  claim(), once per launch, and parked(), in every step, give the address of the lane's slot 0; slot j is
+// [j * 64], in the instruction's immediate.  The address is lane4 (live anyway, for the final stores) + a wave-uniform
+// scalar, added anew in every step: the empty asm makes the scalar opaque, so that the compiler neither hoists the sum into
+// a register of its own nor forwards the parked values through registers.
+// --------------------------------------------------------------------------
+template <uint32_t SLOTS>
+struct LaneSlots {
+    uint32_t lane4, wave_off;
+    static __device__ __forceinline__ float* slots()
+    {
+        __shared__ __attribute__((aligned(16))) float lds[kBlock * SLOTS];
+        return lds;
+    }
+    __device__ __forceinline__ float* claim(uint32_t lane4_)
+    {
+        lane4 = lane4_;
+        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (SLOTS * 256u);
+        return at<float>(slots(), lane4 + wave_off);
+    }
+    __device__ __forceinline__ float* parked() const
+    {
+        uint32_t w_off = wave_off;
+        asm volatile("" : "+s"(w_off));
+        return at<float>(slots(), lane4 + w_off);
+    }
+};
+
+// --------------------------------------------------------------------------
 // The POSE HOLD in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_ctl): a feedback law evaluated in every
 // step from the state the step starts from - between the first and the last step of a launch that state exists nowhere but
 // here.  Per body a tiled 17-field control record ([tiles][17][64], addressed like the applied record):
@@ -1342,34 +1374,37 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
 // WHERE THE 17 VALUES LIVE: the applied kernels stand at 156-168 VGPRs, at the limit of 3 waves per SIMD, so the record is
 // not carried through the loop.  Each lane parks its record - and the six applied values, which this kernel does not carry
 // either - in LDS once per launch and reads them back in every step: 23 slots per lane, [wave][23][64] floats (23 KB per
-// block; stride 1 across the lanes: no bank conflict).  A lane reads only what it wrote itself: no barrier.  The address
-// is lane4 (live anyway, for the final stores) + a wave-uniform scalar, added anew in every step - the empty asm keeps the
-// compiler from hoisting the sum into a register of its own - with the slot offsets in the instructions' immediates.
+// block; LaneSlots, above).
 // The kernel asks for 3 waves per SIMD (amdgpu_waves_per_eu(3)): left to itself the scheduler spends 170 VGPRs on the
 // energy-sampling instantiations - two more than three waves allow - where 160 do, without scratch (138-160 over the 32).
 // --------------------------------------------------------------------------
 constexpr uint32_t kCtlSlots = HYDRO_CTL_FIELDS + HYDRO_WRENCH_FIELDS;
-struct PoseHold {
+struct PoseHold : LaneSlots<kCtlSlots> {
     const float* ctl; uint32_t ctl_stride; const float* applied; uint32_t applied_stride; int body_frame;
-    uint32_t lane4, wave_off;
-    static __device__ __forceinline__ float* slots()
+    // the six applied values: slots 17 .. 22
+    __device__ __forceinline__ void park_applied(float* mine, uint32_t tile) const
     {
-        __shared__ __attribute__((aligned(16))) float lds[kBlock * kCtlSlots];
-        return lds;
+        const float* a = applied + (size_t)tile * applied_stride;
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = ldg<false>(at<float>(a, lane4, f * 256u));
+    }
+    __device__ __forceinline__ void add_parked_applied(const float* mine, const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        // (an AppliedWrench as the carrier of the six values: handing them to a free function as a bare array computes the same
+        // and moves registers in the 64 pose-hold and sea kernels)
+        AppliedWrench a{nullptr, 0u, body_frame, {}};
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) a.a[f] = mine[(HYDRO_CTL_FIELDS + f) * 64];
+        a.add(s, f6);
     }
     __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
     {
-        lane4 = lane4_;
-        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kCtlSlots * 256u);
-        float* mine = at<float>(slots(), lane4 + wave_off);
+        float* mine = claim(lane4_);
         const float* r = ctl + (size_t)tile * ctl_stride;
 #pragma unroll
         for (int f = 0; f < HYDRO_CTL_FIELDS; ++f) mine[f * 64] = ldg<false>(at<float>(r, lane4, f * 256u));
-        if (applied) {                                       // (a kernel argument: wave-uniform)
-            const float* a = applied + (size_t)tile * applied_stride;
-#pragma unroll
-            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = ldg<false>(at<float>(a, lane4, f * 256u));
-        } else {
+        if (applied) park_applied(mine, tile);               // (a kernel argument: wave-uniform)
+        else {
 #pragma unroll
             for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = 0.0f;
         }
@@ -1384,13 +1419,8 @@ struct PoseHold {
     }
     __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
     {
-        uint32_t w_off = wave_off;
-        asm volatile("" : "+s"(w_off));
-        const float* mine = at<float>(slots(), lane4 + w_off);
-        AppliedWrench a{nullptr, 0u, body_frame, {}};
-#pragma unroll
-        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) a.a[f] = mine[(HYDRO_CTL_FIELDS + f) * 64];
-        a.add(s, f6);
+        const float* mine = parked();
+        add_parked_applied(mine, s, f6);
         {
             float F[3];
 #pragma unroll
@@ -1426,7 +1456,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{control, control_stride, applied, applied_stride, body_frame, 0u, 0u}, NoSea{});
+                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{});
 }
 
 // --------------------------------------------------------------------------
@@ -1445,9 +1475,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
 //           r = th / 2 pi - rint(th / 2 pi), exact but for the one product; v_exp_f32 for the depth decay
 // WHERE THE TRUE STATE LIVES while the wrench runs: the applied kernels stand at the limit of 3 waves per SIMD, so the seven
 // true values (p_z, v, pv[0:3]) are parked in LDS around body_wrench, [wave][7][64] floats (7 KB per block), and the relative
-// ones take their registers - no live range is added to the wrench.  Each lane reads only what it wrote: no barrier.  The
-// address is formed as in PoseHold (lane4 + a wave-uniform scalar, opaque to the compiler so that it neither hoists the sum
-// nor forwards the parked values through registers).
+// ones take their registers - no live range is added to the wrench (LaneSlots, above).
 // --------------------------------------------------------------------------
 struct SeaWave {
     double omega, phi;                                   // rad / s, rad
@@ -1497,30 +1525,14 @@ __device__ __forceinline__ void sea_water(SeaTablePtr tab, uint32_t waves, int64
 }
 
 constexpr uint32_t kSeaSlots = 7;
-struct SeaView {
+struct SeaView : LaneSlots<kSeaSlots> {
     SeaTablePtr tab; uint32_t waves; int64_t step0; double dt;
-    uint32_t lane4, wave_off;
-    static __device__ __forceinline__ float* slots()
-    {
-        __shared__ __attribute__((aligned(16))) float lds[kBlock * kSeaSlots];
-        return lds;
-    }
-    __device__ __forceinline__ void begin(uint32_t lane4_)
-    {
-        lane4 = lane4_;
-        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kSeaSlots * 256u);
-    }
-    __device__ __forceinline__ float* mine() const
-    {
-        uint32_t w_off = wave_off;
-        asm volatile("" : "+s"(w_off));
-        return at<float>(slots(), lane4 + w_off);
-    }
+    __device__ __forceinline__ void begin(uint32_t lane4_) { claim(lane4_); }
     __device__ __forceinline__ void view(uint32_t k, float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
     {
         float eta, u[3];
         sea_water(tab, waves, step0 + (int64_t)k, dt, s[0], s[1], s[2], eta, u);
-        float* m = mine();
+        float* m = parked();
         m[0] = s[2];
         s[2] = s[2] - eta;
 #pragma unroll
@@ -1533,7 +1545,7 @@ struct SeaView {
     }
     __device__ __forceinline__ void restore(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
     {
-        const float* m = mine();
+        const float* m = parked();
         s[2] = m[0];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -1550,27 +1562,13 @@ struct OptionalPoseHold : PoseHold {
     __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
     {
         if (ctl) { PoseHold::begin(tile, lane4_); return; }
-        lane4 = lane4_;
-        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kCtlSlots * 256u);
-        if (applied) {
-            float* mine = at<float>(slots(), lane4 + wave_off);
-            const float* a = applied + (size_t)tile * applied_stride;
-#pragma unroll
-            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) mine[(HYDRO_CTL_FIELDS + f) * 64] = ldg<false>(at<float>(a, lane4, f * 256u));
-        }
+        float* mine = claim(lane4_);
+        if (applied) park_applied(mine, tile);
     }
     __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
     {
         if (ctl) { PoseHold::add(s, f6); return; }
-        if (applied) {
-            uint32_t w_off = wave_off;
-            asm volatile("" : "+s"(w_off));
-            const float* mine = at<float>(slots(), lane4 + w_off);
-            AppliedWrench a{nullptr, 0u, body_frame, {}};
-#pragma unroll
-            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) a.a[f] = mine[(HYDRO_CTL_FIELDS + f) * 64];
-            a.add(s, f6);
-        }
+        if (applied) add_parked_applied(parked(), s, f6);
     }
 };
 
@@ -1589,8 +1587,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{control, control_stride, applied, applied_stride, body_frame, 0u, 0u}},
-                                                   SeaView{sea_table_ptr(sea_table), sea_waves, step0, sea_dt, 0u, 0u});
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt});
 }
 
 // hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
@@ -2444,25 +2442,21 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// hydro_step_fused_tiled_multi, its recording twin, the applied-wrench, the pose-hold and the sea entry: one validation, one
-// variant selection.  sea != nullptr launches step_fused_multi_sea_tiled_kernel, which takes everything (each of the others
-// null: none).  Else ctl != nullptr launches step_fused_multi_ctl_tiled_kernel, which takes all three (a null `applied`: none).
-// rec == nullptr launches step_fused_multi_tiled_kernel, else step_fused_multi_rec_tiled_kernel with the recorder's
-// arguments appended; app != nullptr launches step_fused_multi_app_tiled_kernel, which takes both (a null watch mask: no
-// recording).
-struct RecArgs {
-    const uint64_t* mask; const uint32_t* first;     // the engine's watch tables
-    float* log; uint32_t stride, fields, every, phase, row0;
+// hydro_step_fused_tiled_multi, its recording twin, the applied-wrench, the pose-hold and the sea entry, described ONCE: each
+// entry fills a MultiStep with what it was given and step_fused_tiled_multi_launch validates and launches it.  An option is
+// absent by its pointer: log == nullptr no recorder, applied == nullptr no applied wrench, control == nullptr no pose hold.
+struct MultiStep {
+    int64_t n; const float* state; int64_t state_tile_stride; const float* prev; int64_t prev_tile_stride; double dt; int steps;
+    float* state_out; int64_t out_tile_stride; float* prev_out; int64_t prev_out_tile_stride;
+    int implicit_drag, rotational; double* ke_out_dev; void* stream;
+    // the recorder, as the entry was given it
+    float* log = nullptr; int64_t log_stride = 0, rows_capacity = 0; int fields = HYDRO_STATE_FIELDS, every = 1, phase = 1;
+    int64_t row0 = 0; int64_t* rows_written_host = nullptr;
+    bool log_required = false;                           // the _rec entry: a null log is refused, and the recorder is checked FIRST
+    const float* applied = nullptr; int64_t applied_tile_stride = 0; int applied_frame = HYDRO_FRAME_WORLD;
+    const float* control = nullptr; int64_t control_tile_stride = 0;
+    bool sea_entry = false; int64_t step0 = 0;           // the _sea entry: step0 is checked, and the steps go through the sea if one is set
 };
-struct AppArgs {
-    const float* applied; int64_t stride; int frame;
-    const float* log; int64_t log_floats;            // the log as an output range `applied` must stay out of (may be null)
-};
-struct CtlArgs {
-    const float* control; int64_t stride;
-    const float* log; int64_t log_floats;            // as in AppArgs
-};
-struct SeaArgs { int64_t step0; };                   // (the table and the number of components are the engine's)
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
 {
@@ -2476,97 +2470,98 @@ inline int64_t tiled_extent(int64_t tiles, int64_t stride, int fields)
 {
     return tiles > 0 ? (tiles - 1) * stride + (int64_t)fields * HYDRO_TILE : 0;
 }
-int step_fused_tiled_multi_impl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
-                                const float* prev, int64_t prev_tile_stride, double dt, int steps,
-                                float* state_out, int64_t out_tile_stride,
-                                float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
-                                int rotational, double* ke_out_dev, const RecArgs* rec, int64_t* rows_written_host, int64_t rows, void* stream,
-                                const AppArgs* app = nullptr, const CtlArgs* ctl = nullptr, const SeaArgs* sea = nullptr)
+// A per-body input record (`what`: "applied" / "control"; `stride` floats per tile) must lie outside everything the launch writes.
+int check_no_overlap(hydro_t* h, const MultiStep& m, int64_t log_floats, const char* what, const float* p, int64_t stride)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if (!(dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
-    if (steps < 1 || steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
-    if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
-    if ((rc = check_tiled(h, n, prev, prev_tile_stride, HYDRO_PREV_FIELDS, "null prev (pass the previous state buffer + 7*64)"))) return rc;
-    if ((rc = check_tiled(h, n, state_out, out_tile_stride, HYDRO_STATE_FIELDS, "null state_out"))) return rc;
-    if ((rc = check_tiled(h, n, prev_out, prev_out_tile_stride, HYDRO_PREV_FIELDS, "null prev_out (pass state + 7*64 to keep the two-buffer ping-pong)"))) return rc;
-    if (state_out == state) return fail(h, HYDRO_E_ARG, "state_out must not alias state (it may alias the previous-state buffer)");
-    if (rec && h->watch_last >= n) return fail(h, HYDRO_E_ARG, "a watched body is >= n");
-    if (app) {
-        if ((rc = check_tiled(h, n, app->applied, app->stride, HYDRO_WRENCH_FIELDS, "null applied"))) return rc;
-        if (app->frame != HYDRO_FRAME_WORLD && app->frame != HYDRO_FRAME_BODY) return fail(h, HYDRO_E_ARG, "applied_frame must be HYDRO_FRAME_WORLD or HYDRO_FRAME_BODY");
-        const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * app->stride;
-        if (ranges_overlap(app->applied, floats, state_out, tiled_extent(tiles, out_tile_stride, HYDRO_STATE_FIELDS))
-            || ranges_overlap(app->applied, floats, prev_out, tiled_extent(tiles, prev_out_tile_stride, HYDRO_PREV_FIELDS))
-            || (app->log && ranges_overlap(app->applied, floats, app->log, app->log_floats)))
-            return fail(h, HYDRO_E_ARG, "applied must not overlap an output (state_out, prev_out, log)");
-    }
-    if (ctl) {
-        if ((rc = check_tiled(h, n, ctl->control, ctl->stride, HYDRO_CTL_FIELDS, "null control"))) return rc;
-        const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * ctl->stride;
-        if (ranges_overlap(ctl->control, floats, state_out, tiled_extent(tiles, out_tile_stride, HYDRO_STATE_FIELDS))
-            || ranges_overlap(ctl->control, floats, prev_out, tiled_extent(tiles, prev_out_tile_stride, HYDRO_PREV_FIELDS))
-            || (ctl->log && ranges_overlap(ctl->control, floats, ctl->log, ctl->log_floats)))
-            return fail(h, HYDRO_E_ARG, "control must not overlap an output (state_out, prev_out, log)");
-    }
-    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (rows_written_host) *rows_written_host = n == 0 ? 0 : rows;
-    if (n == 0) return ke_out_dev ? ke_of_nothing(h, ke_out_dev, s) : HYDRO_OK;
-    const dim3 grid(grid_for(n, kBlock)), blk(kBlock);
-    if (ke_out_dev && (rc = ke_prepare(h, s))) return rc;
-    dispatch_flags([&](auto HALF, auto NT, auto IMPL, auto KE, auto WARP) {
-        // the arguments both kernels take, then the launch of one of them
-        const auto launch = [&](auto kernel, auto... recorder) {
-            hipLaunchKernelGGL(kernel, grid, blk, 0, s, state, prev, h->params_tiled, state_out, prev_out,
-                               (uint32_t)state_tile_stride, (uint32_t)prev_tile_stride, (uint32_t)out_tile_stride, (uint32_t)prev_out_tile_stride,
-                               (uint32_t)n, (uint32_t)steps, (float)dt, h->rho, h->g, 1.0 / dt, h->ke_partials, h->ke_stride, rotational ? 1 : 0, ke_out_dev,
-                               recorder...);
-        };
-        if (sea) {
-            const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
-            launch(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
-                   app ? app->applied : nullptr, app ? (uint32_t)app->stride : 0u, app ? app->frame : HYDRO_FRAME_WORLD,
-                   ctl ? ctl->control : nullptr, ctl ? (uint32_t)ctl->stride : 0u,
-                   (const void*)h->sea_table, (uint32_t)h->sea_waves, sea->step0, dt);
-        }
-        else if (ctl) {
-            const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
-            launch(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
-                   app ? app->applied : nullptr, app ? (uint32_t)app->stride : 0u, app ? app->frame : HYDRO_FRAME_WORLD,
-                   ctl->control, (uint32_t)ctl->stride);
-        }
-        else if (app) {
-            const RecArgs none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u}, &r = rec ? *rec : none;
-            launch(step_fused_multi_app_tiled_kernel<HALF, NT, IMPL, KE, WARP>, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0,
-                   app->applied, (uint32_t)app->stride, app->frame);
-        }
-        else if (rec) launch(step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>, rec->mask, rec->first, rec->log, rec->stride, rec->fields, rec->every, rec->phase, rec->row0);
-        else launch(step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
-    }, h->half_coeffs, streaming_fused(h, n), implicit_drag != 0, ke_out_dev != nullptr, is_warp(h));
-    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * stride;
+    if (!ranges_overlap(p, floats, m.state_out, tiled_extent(tiles, m.out_tile_stride, HYDRO_STATE_FIELDS))
+        && !ranges_overlap(p, floats, m.prev_out, tiled_extent(tiles, m.prev_out_tile_stride, HYDRO_PREV_FIELDS))
+        && !(m.log && ranges_overlap(p, floats, m.log, log_floats)))
+        return HYDRO_OK;
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s must not overlap an output (state_out, prev_out, log)", what);
+    return fail(h, HYDRO_E_ARG, msg);
+}
+
+// What a recording launch checks of its recorder arguments; `rows`: the rows the launch writes.
+int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
+{
+    if (h->watch_count == 0) return fail(h, HYDRO_E_STATE, "no watch list (call hydro_set_watch first)");
+    if (!m.log || !aligned_to(m.log, 4)) return fail(h, HYDRO_E_ARG, "null or misaligned log");
+    if (m.fields != HYDRO_STATE_FIELDS && m.fields != HYDRO_STATE_FIELDS + HYDRO_WRENCH_FIELDS) return fail(h, HYDRO_E_ARG, "fields must be 13 (state) or 19 (state + wrench)");
+    if (m.every < 1 || m.every > (1 << 30)) return fail(h, HYDRO_E_ARG, "every must be in 1 .. 2^30");
+    if (m.phase < 1 || m.phase > m.every) return fail(h, HYDRO_E_ARG, "phase must be in 1 .. every");
+    if (m.log_stride < h->watch_count || m.log_stride >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "log_stride must be >= the watch count (and < 2^31)");
+    if (m.row0 < 0 || m.rows_capacity < 0 || m.rows_capacity >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "row0 / rows_capacity out of range (0 .. 2^31)");
+    if (m.steps < 1 || m.steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
+    // the rows this launch writes: row0 .. row0 + rows - 1, all of them below rows_capacity before anything is launched
+    const int64_t rows = rows_out = m.phase > m.steps ? 0 : (int64_t)(m.steps - m.phase) / m.every + 1;
+    if (rows > 0 && m.row0 + rows > m.rows_capacity) return fail(h, HYDRO_E_ARG, "the launch would write past rows_capacity");
     return HYDRO_OK;
 }
 
-// What hydro_step_fused_tiled_multi_rec checks of its recorder arguments and hands to the kernel; `rows`: the rows the launch writes.
-int check_recorder(hydro_t* h, int steps, float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase, int64_t row0,
-                   RecArgs& rec, int64_t& rows_out)
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the sea kernel takes
+// everything, the pose-hold kernel everything but the sea, the applied kernel recorder and applied wrench, the recording
+// kernel the recorder - and a launch is handed the options it goes without as absent ones.
+int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
     if (!h) return HYDRO_E_ARG;
-    if (h->watch_count == 0) return fail(h, HYDRO_E_STATE, "no watch list (call hydro_set_watch first)");
-    if (!log || !aligned_to(log, 4)) return fail(h, HYDRO_E_ARG, "null or misaligned log");
-    if (fields != HYDRO_STATE_FIELDS && fields != HYDRO_STATE_FIELDS + HYDRO_WRENCH_FIELDS) return fail(h, HYDRO_E_ARG, "fields must be 13 (state) or 19 (state + wrench)");
-    if (every < 1 || every > (1 << 30)) return fail(h, HYDRO_E_ARG, "every must be in 1 .. 2^30");
-    if (phase < 1 || phase > every) return fail(h, HYDRO_E_ARG, "phase must be in 1 .. every");
-    if (log_stride < h->watch_count || log_stride >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "log_stride must be >= the watch count (and < 2^31)");
-    if (row0 < 0 || rows_capacity < 0 || rows_capacity >= ((int64_t)1 << 31)) return fail(h, HYDRO_E_ARG, "row0 / rows_capacity out of range (0 .. 2^31)");
-    if (steps < 1 || steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
-    // the rows this launch writes: row0 .. row0 + rows - 1, all of them below rows_capacity before anything is launched
-    const int64_t rows = rows_out = phase > steps ? 0 : (int64_t)(steps - phase) / every + 1;
-    if (rows > 0 && row0 + rows > rows_capacity) return fail(h, HYDRO_E_ARG, "the launch would write past rows_capacity");
-    rec.mask = h->watch_mask; rec.first = h->watch_first; rec.log = log; rec.stride = (uint32_t)log_stride; rec.fields = (uint32_t)fields;
-    rec.every = (uint32_t)every; rec.phase = (uint32_t)phase; rec.row0 = (uint32_t)row0;
+    int rc;
+    if (m.sea_entry && (m.step0 < 0 || m.steps < 0 || m.step0 + (int64_t)m.steps >= ((int64_t)1 << 52) || m.step0 >= ((int64_t)1 << 52)))
+        return fail(h, HYDRO_E_ARG, "step0 must be >= 0 and step0 + steps < 2^52");
+    const bool rec = m.log || m.log_required, sea = m.sea_entry && h->sea_waves >= 0;
+    int64_t rows = 0;
+    if (rec && (rc = check_recorder(h, m, rows))) return rc;
+    if ((rc = check_common(h, m.n))) return rc;
+    if (!(m.dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
+    if (m.steps < 1 || m.steps > (1 << 20)) return fail(h, HYDRO_E_ARG, "steps must be in 1 .. 2^20");
+    if ((rc = check_tiled(h, m.n, m.state, m.state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
+    if ((rc = check_tiled(h, m.n, m.prev, m.prev_tile_stride, HYDRO_PREV_FIELDS, "null prev (pass the previous state buffer + 7*64)"))) return rc;
+    if ((rc = check_tiled(h, m.n, m.state_out, m.out_tile_stride, HYDRO_STATE_FIELDS, "null state_out"))) return rc;
+    if ((rc = check_tiled(h, m.n, m.prev_out, m.prev_out_tile_stride, HYDRO_PREV_FIELDS, "null prev_out (pass state + 7*64 to keep the two-buffer ping-pong)"))) return rc;
+    if (m.state_out == m.state) return fail(h, HYDRO_E_ARG, "state_out must not alias state (it may alias the previous-state buffer)");
+    if (rec && h->watch_last >= m.n) return fail(h, HYDRO_E_ARG, "a watched body is >= n");
+    const int64_t log_floats = m.log ? m.rows_capacity * m.fields * m.log_stride : 0;      // the log as an output range the inputs must stay out of
+    if (m.applied) {
+        if ((rc = check_tiled(h, m.n, m.applied, m.applied_tile_stride, HYDRO_WRENCH_FIELDS, "null applied"))) return rc;
+        if (m.applied_frame != HYDRO_FRAME_WORLD && m.applied_frame != HYDRO_FRAME_BODY) return fail(h, HYDRO_E_ARG, "applied_frame must be HYDRO_FRAME_WORLD or HYDRO_FRAME_BODY");
+        if ((rc = check_no_overlap(h, m, log_floats, "applied", m.applied, m.applied_tile_stride))) return rc;
+    }
+    if (m.control) {
+        if ((rc = check_tiled(h, m.n, m.control, m.control_tile_stride, HYDRO_CTL_FIELDS, "null control"))) return rc;
+        if ((rc = check_no_overlap(h, m, log_floats, "control", m.control, m.control_tile_stride))) return rc;
+    }
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    hipStream_t s = static_cast<hipStream_t>(m.stream);
+    if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
+    if (m.n == 0) return m.ke_out_dev ? ke_of_nothing(h, m.ke_out_dev, s) : HYDRO_OK;
+    const dim3 grid(grid_for(m.n, kBlock)), blk(kBlock);
+    if (m.ke_out_dev && (rc = ke_prepare(h, s))) return rc;
+    // the kernels' recorder arguments: the engine's watch tables and the log, or the absent recorder
+    struct Recorder { const uint64_t* mask; const uint32_t* first; float* log; uint32_t stride, fields, every, phase, row0; };
+    const Recorder none = {nullptr, nullptr, nullptr, 0u, (uint32_t)HYDRO_STATE_FIELDS, 1u, 1u, 0u};
+    const Recorder r = !rec ? none : Recorder{h->watch_mask, h->watch_first, m.log, (uint32_t)m.log_stride, (uint32_t)m.fields,
+                                              (uint32_t)m.every, (uint32_t)m.phase, (uint32_t)m.row0};
+    const uint32_t applied_stride = m.applied ? (uint32_t)m.applied_tile_stride : 0u, control_stride = m.control ? (uint32_t)m.control_tile_stride : 0u;
+    const int frame = m.applied ? m.applied_frame : HYDRO_FRAME_WORLD;
+    dispatch_flags([&](auto HALF, auto NT, auto IMPL, auto KE, auto WARP) {
+        // the arguments every kernel takes, then the recorder's, then the applied wrench's, then the family's own
+        const auto plain = [&](auto kernel, auto... tail) {
+            hipLaunchKernelGGL(kernel, grid, blk, 0, s, m.state, m.prev, h->params_tiled, m.state_out, m.prev_out,
+                               (uint32_t)m.state_tile_stride, (uint32_t)m.prev_tile_stride, (uint32_t)m.out_tile_stride, (uint32_t)m.prev_out_tile_stride,
+                               (uint32_t)m.n, (uint32_t)m.steps, (float)m.dt, h->rho, h->g, 1.0 / m.dt, h->ke_partials, h->ke_stride, m.rotational ? 1 : 0, m.ke_out_dev,
+                               tail...);
+        };
+        const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
+        const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
+        if (sea) pushed(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        (const void*)h->sea_table, (uint32_t)h->sea_waves, m.step0, m.dt);
+        else if (m.control) pushed(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride);
+        else if (m.applied) pushed(step_fused_multi_app_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (rec) recording(step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else plain(step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+    }, h->half_coeffs, streaming_fused(h, m.n), m.implicit_drag != 0, m.ke_out_dev != nullptr, is_warp(h));
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }
 
@@ -2580,8 +2575,9 @@ int hydro_step_fused_tiled_multi(hydro_t* h, int64_t n, const float* state, int6
                                  float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
                                  int rotational, double* ke_out_dev, void* stream)
 {
-    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
-                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, nullptr, nullptr, 0, stream);
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    return step_fused_tiled_multi_launch(h, m);
 }
 
 int hydro_set_watch(hydro_t* h, int64_t count, const int64_t* bodies_host)
@@ -2632,12 +2628,12 @@ int hydro_step_fused_tiled_multi_rec(hydro_t* h, int64_t n, const float* state, 
                                      float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
                                      int64_t row0, int64_t* rows_written_host, void* stream)
 {
-    RecArgs rec;
-    int64_t rows = 0;
-    const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
-    if (rc) return rc;
-    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
-                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, &rec, rows_written_host, rows, stream);
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.log_required = true;
+    return step_fused_tiled_multi_launch(h, m);
 }
 
 int hydro_step_fused_tiled_multi_app(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -2649,17 +2645,12 @@ int hydro_step_fused_tiled_multi_app(hydro_t* h, int64_t n, const float* state, 
                                      int64_t row0, int64_t* rows_written_host,
                                      const float* applied, int64_t applied_tile_stride, int applied_frame, void* stream)
 {
-    if (!h) return HYDRO_E_ARG;
-    RecArgs rec;
-    int64_t rows = 0;
-    if (log) {
-        const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
-        if (rc) return rc;
-    }
-    AppArgs app = {applied, applied_tile_stride, applied_frame, log, log ? rows_capacity * fields * log_stride : 0};
-    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
-                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
-                                       applied ? &app : nullptr);
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    return step_fused_tiled_multi_launch(h, m);
 }
 
 int hydro_step_fused_tiled_multi_ctl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -2672,19 +2663,13 @@ int hydro_step_fused_tiled_multi_ctl(hydro_t* h, int64_t n, const float* state, 
                                      const float* applied, int64_t applied_tile_stride, int applied_frame,
                                      const float* control, int64_t control_tile_stride, void* stream)
 {
-    if (!h) return HYDRO_E_ARG;
-    RecArgs rec;
-    int64_t rows = 0;
-    if (log) {
-        const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
-        if (rc) return rc;
-    }
-    const int64_t log_floats = log ? rows_capacity * fields * log_stride : 0;
-    AppArgs app = {applied, applied_tile_stride, applied_frame, log, log_floats};
-    CtlArgs ctl = {control, control_tile_stride, log, log_floats};
-    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
-                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
-                                       applied ? &app : nullptr, control ? &ctl : nullptr);
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    return step_fused_tiled_multi_launch(h, m);
 }
 
 int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
@@ -2757,27 +2742,14 @@ int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, 
                                      const float* applied, int64_t applied_tile_stride, int applied_frame,
                                      const float* control, int64_t control_tile_stride, int64_t step0, void* stream)
 {
-    if (!h) return HYDRO_E_ARG;
-    if (step0 < 0 || steps < 0 || step0 + (int64_t)steps >= ((int64_t)1 << 52) || step0 >= ((int64_t)1 << 52))
-        return fail(h, HYDRO_E_ARG, "step0 must be >= 0 and step0 + steps < 2^52");
-    if (h->sea_waves < 0)
-        return hydro_step_fused_tiled_multi_ctl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
-                                                prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log, log_stride, rows_capacity,
-                                                fields, every, phase, row0, rows_written_host, applied, applied_tile_stride, applied_frame,
-                                                control, control_tile_stride, stream);
-    RecArgs rec;
-    int64_t rows = 0;
-    if (log) {
-        const int rc = check_recorder(h, steps, log, log_stride, rows_capacity, fields, every, phase, row0, rec, rows);
-        if (rc) return rc;
-    }
-    const int64_t log_floats = log ? rows_capacity * fields * log_stride : 0;
-    AppArgs app = {applied, applied_tile_stride, applied_frame, log, log_floats};
-    CtlArgs ctl = {control, control_tile_stride, log, log_floats};
-    SeaArgs sea = {step0};
-    return step_fused_tiled_multi_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride,
-                                       prev_out, prev_out_tile_stride, implicit_drag, rotational, ke_out_dev, log ? &rec : nullptr, rows_written_host, rows, stream,
-                                       applied ? &app : nullptr, control ? &ctl : nullptr, &sea);
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    return step_fused_tiled_multi_launch(h, m);
 }
 
 int hydro_pack_state_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,

@@ -365,6 +365,15 @@ class HydroEngine:
         return (log.data_ptr(), log.shape[2], log.shape[0], log.shape[1], int(every), int(phase), int(row0),
                 ctypes.byref(written)), written
 
+    def _recorded_multi(self, entry, multi, rec, stream, extra=lambda: ()) -> int:
+        """One call of a multi-step entry that can record: `multi` are `_fused_multi_args`' arguments, `rec` `_rec_tail`'s,
+        `extra()` gives what the entry takes between `rows_written_host` and `stream` (built, and so validated, after the
+        other two).  Returns the number of rows written."""
+        _, args = self._fused_multi_args(*multi)
+        tail, written = self._rec_tail(*rec)
+        self._check(entry(*args, *tail, *extra(), self._stream(stream)))
+        return written.value
+
     def step_fused_tiled_multi(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
                                state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
                                ke_out: torch.Tensor | None = None, rotational: bool = True):
@@ -400,10 +409,9 @@ class HydroEngine:
         k = phase, phase + every, ... of this launch, into rows row0, row0 + 1, ... of `log`, a contiguous float32 device
         tensor (rows, 13 | 19, columns >= watch count) - 19 fields: the state, then the wrench that produced it.  State,
         previous-velocity and kinetic-energy bits are those of step_fused_tiled_multi.  Returns the number of rows written."""
-        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
-        tail, written = self._rec_tail(log, every, phase, row0)
-        self._check(self._lib.hydro_step_fused_tiled_multi_rec(*args, *tail, self._stream(stream)))
-        return written.value
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_rec,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream)
 
     def step_fused_tiled_multi_applied(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
                                        applied: torch.Tensor | None, frame: str = "body", log: torch.Tensor | None = None,
@@ -417,14 +425,10 @@ class HydroEngine:
         single-step form.  applied=None is the unapplied step.  `log` (with every / phase / row0, see
         step_fused_tiled_multi_rec) also records the watched bodies; the wrench it logs is the total.  Returns the number
         of rows written (0 without a log)."""
-        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
-        tail, written = self._rec_tail(log, every, phase, row0)
-        code = _FRAMES.get(frame)
-        if code is None:
-            raise ValueError("frame must be 'world' or 'body'")
-        a_ptr, a_stride = self._tiled(applied, nat.WRENCH_FIELDS, n) if applied is not None else (None, 0)
-        self._check(self._lib.hydro_step_fused_tiled_multi_app(*args, *tail, a_ptr, a_stride, code, self._stream(stream)))
-        return written.value
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_app,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._applied_control(applied, frame, None, n)[:3])
 
     def step_fused_tiled_multi_controlled(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int,
                                           control: torch.Tensor | None, applied: torch.Tensor | None = None, frame: str = "body",
@@ -437,15 +441,14 @@ class HydroEngine:
         a clamped PD force towards p* and torque towards q* (the law and its order: include/hydro.h) and adds them to the
         hydrodynamic wrench, after `applied` if there is one.  control=None is step_fused_tiled_multi_applied.  Returns the
         number of rows written (0 without a log)."""
-        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
-        tail, written = self._rec_tail(log, every, phase, row0)
-        push = self._applied_control(applied, frame, control, n)
-        self._check(self._lib.hydro_step_fused_tiled_multi_ctl(*args, *tail, *push, self._stream(stream)))
-        return written.value
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_ctl,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._applied_control(applied, frame, control, n))
 
     def _applied_control(self, applied, frame, control, n):
-        """The arguments `applied .. control_tile_stride` of `hydro_step_fused_tiled_multi_ctl` / `_sea`: either buffer may be
-        None (NULL, stride 0)."""
+        """The arguments `applied .. control_tile_stride` of `hydro_step_fused_tiled_multi_ctl` / `_sea` (the first three:
+        `_app`'s): either buffer may be None (NULL, stride 0)."""
         code = _FRAMES.get(frame)
         if code is None:
             raise ValueError("frame must be 'world' or 'body'")
@@ -498,11 +501,10 @@ class HydroEngine:
         on the true state.  `step0`: the index of this launch's first step (the wave phase is (step0 + k) * dt inside the
         launch).  control, applied and log are each optional; without a sea the call is step_fused_tiled_multi_controlled.
         Returns the number of rows written (0 without a log)."""
-        _, args = self._fused_multi_args(state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational)
-        tail, written = self._rec_tail(log, every, phase, row0)
-        push = self._applied_control(applied, frame, control, n)
-        self._check(self._lib.hydro_step_fused_tiled_multi_sea(*args, *tail, *push, int(step0), self._stream(stream)))
-        return written.value
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_sea,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: (*self._applied_control(applied, frame, control, n), int(step0)))
 
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:

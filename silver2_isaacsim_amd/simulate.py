@@ -540,37 +540,39 @@ class ClosedLoopSim:
             self.sea = None
             self._graph = None
 
-    # `k` steps in one launch with the applied wrench and / or the pose hold, recording if a recorder is attached (k = 1
-    # from run_eager and inside graph captures: the single-step form of the entries)
-    def _step_applied(self, k: int, ke_out) -> None:
-        rec = self.recorder
-        kw = {}
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
+    # the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
+    # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
+    # graph captures: the single-step form of the entries, the bits of the single-step entry, include/hydro.h).  The plain
+    # step has two forms: single_step=True is one hydro_step_fused_tiled (or the two-kernel path, fused=False), else one
+    # hydro_step_fused_tiled_multi of k steps.  ke_out: the last step also leaves the kinetic energy of its state there.
+    def _advance(self, k: int, ke_out, single_step: bool = False) -> None:
+        e, rec = self.engine, self.recorder
+        args = (self.cur, self.old, self.n, self.dt)
+        kw = dict(implicit_drag=self.implicit_drag, ke_out=ke_out)
+        rows = 0
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
-            kw = dict(log=rec.log, every=rec.every, phase=phase, row0=row0)
+            kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
         if self.sea is not None:
-            rows = self.engine.step_fused_tiled_multi_sea(self.cur, self.old, self.n, self.dt, k, self.steps_done, self.control, self.applied,
-                                                          self.applied_frame, implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+            rows = e.step_fused_tiled_multi_sea(*args, k, self.steps_done, self.control, self.applied, self.applied_frame, **kw)
         elif self.control is not None:
-            rows = self.engine.step_fused_tiled_multi_controlled(self.cur, self.old, self.n, self.dt, k, self.control, self.applied,
-                                                                 self.applied_frame, implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+            rows = e.step_fused_tiled_multi_controlled(*args, k, self.control, self.applied, self.applied_frame, **kw)
+        elif self.applied is not None:
+            rows = e.step_fused_tiled_multi_applied(*args, k, self.applied, self.applied_frame, **kw)
+        elif rec is not None:
+            rows = e.step_fused_tiled_multi_rec(*args, k, **kw)
+        elif not single_step:
+            e.step_fused_tiled_multi(*args, k, **kw)
+        elif self.fused:
+            e.step_fused_tiled(*args, **kw)                     # new state -> old buffer
         else:
-            rows = self.engine.step_fused_tiled_multi_applied(self.cur, self.old, self.n, self.dt, k, self.applied, self.applied_frame,
-                                                              implicit_drag=self.implicit_drag, ke_out=ke_out, **kw)
+            e.step_wrench_tiled(self.cur, self.n, self.dt, out=self.wrench, prev=self.old)
+            e.integrate_tiled(self.cur, self.wrench, self.n, self.dt, state_out=self.old)   # overwrite the old buffer
+            if ke_out is not None:
+                e.kinetic_energy(self.old, True, out=ke_out)
         if rec is not None:
             rec.rows_written += rows
-        self.cur, self.old = self.old, self.cur
-
-    # `k` steps in one recording launch (k = 1 from run_eager: the bits of the single-step entry, include/hydro.h)
-    def _step_recorded(self, k: int, sample: bool) -> None:
-        if self.applied is not None or self.control is not None or self.sea is not None:
-            self._step_applied(k, self.ke_dev if sample else None)
-            return
-        rec = self.recorder
-        phase, row0, _ = rec.launch(self.steps_done, k)
-        rec.rows_written += self.engine.step_fused_tiled_multi_rec(
-            self.cur, self.old, self.n, self.dt, k, rec.log, rec.every, phase, row0, implicit_drag=self.implicit_drag,
-            ke_out=self.ke_dev if sample else None)
         self.cur, self.old = self.old, self.cur
 
     def _warm_monitor(self) -> None:
@@ -582,23 +584,6 @@ class ClosedLoopSim:
             with torch.cuda.stream(self.stream):
                 self.monitor.warm_up(self.stream)
 
-    # one physics step on the current stream context; sample=True: the step also leaves the kinetic energy of the state it
-    # produces in self.ke_dev (fused step: inside the kernel; two-kernel path: the stand-alone reduction afterwards)
-    def _step_once(self, sample: bool = False, ke_out: torch.Tensor | None = None) -> None:
-        e = self.engine
-        ke_out = (ke_out if ke_out is not None else self.ke_dev) if sample else None
-        if self.applied is not None or self.control is not None or self.sea is not None:
-            self._step_applied(1, ke_out)
-            return
-        if self.fused:
-            e.step_fused_tiled(self.cur, self.old, self.n, self.dt, implicit_drag=self.implicit_drag, ke_out=ke_out)   # new state -> old buffer
-        else:
-            e.step_wrench_tiled(self.cur, self.n, self.dt, out=self.wrench, prev=self.old)
-            e.integrate_tiled(self.cur, self.wrench, self.n, self.dt, state_out=self.old)   # overwrite the old buffer
-            if sample:
-                e.kinetic_energy(self.old, True, out=ke_out)
-        self.cur, self.old = self.old, self.cur
-
     def run_eager(self, steps: int) -> None:
         if self.recorder is not None:
             self.recorder.launch(self.steps_done, steps)        # room for the whole run, before anything is launched
@@ -606,10 +591,7 @@ class ClosedLoopSim:
         with torch.cuda.stream(self.stream):
             for _ in range(steps):
                 sample = self.monitor is not None and (self.steps_done + 1) % self.monitor.every == 0
-                if self.recorder is not None:
-                    self._step_recorded(1, sample)
-                else:
-                    self._step_once(sample)
+                self._advance(1, self.ke_dev if sample else None, single_step=True)
                 self.steps_done += 1
                 if sample:
                     self.monitor.observe(self.steps_done, stream=self.stream, sampled=self.ke_dev)
@@ -631,7 +613,7 @@ class ClosedLoopSim:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
                 for k in range(graph_steps):
-                    self._step_once(sample=sample_into is not None and k == graph_steps - 1, ke_out=sample_into)
+                    self._advance(1, sample_into if k == graph_steps - 1 else None, single_step=True)
                 if slot is not None:
                     self.monitor.capture_sample(slot)
             return g
@@ -710,14 +692,7 @@ class ClosedLoopSim:
             while steps > 0:
                 k = min(chunk, steps)
                 sample = self.monitor is not None and k == chunk and (self.steps_done + k) % self.monitor.every == 0
-                if self.recorder is not None:
-                    self._step_recorded(k, sample)
-                elif self.applied is not None or self.control is not None or self.sea is not None:
-                    self._step_applied(k, self.ke_dev if sample else None)
-                else:
-                    self.engine.step_fused_tiled_multi(self.cur, self.old, self.n, self.dt, k, implicit_drag=self.implicit_drag,
-                                                       ke_out=self.ke_dev if sample else None)
-                    self.cur, self.old = self.old, self.cur
+                self._advance(k, self.ke_dev if sample else None)
                 self.steps_done += k
                 steps -= k
                 if sample:
