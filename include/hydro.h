@@ -554,6 +554,95 @@ int hydro_step_fused_tiled_multi_sea(hydro_t *h, int64_t n, const float *state, 
                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
                                      const float *control, int64_t control_tile_stride, int64_t step0, void *stream);
 
+/* Seabed: a floor under the water for the closed-loop steps - the horizontal plane z = z_b, scene-wide like the density, the
+ * gravity and the sea.  A body touches it through the EIGHT CORNERS of the box the buoyancy already uses (x/y/zDimension),
+ * each a penalty contact: a spring and a damper along z that never pull (no adhesion) and a Coulomb friction with a
+ * regularised direction and a capped tangential damping.  Bodies stay independent: nothing couples two of them.  Only
+ * hydro_step_fused_tiled_multi_bed and hydro_seabed_wrench know the bed: the wrench-only, array-of-structs, batch, component
+ * and plugin entries, and the other five closed-loop entries (hydro_step_fused_tiled, _multi, _multi_rec, _multi_app,
+ * _multi_ctl, _multi_sea), ignore it whatever is set here - their bodies sink for ever.
+ *
+ * hydro_seabed_t.  The five contact constants are MASS-NORMALISED - the force is the constant times the body's mass - so one
+ * set serves a 2 kg link and a 500 kg buoy:
+ *     z              z_b, height of the plane (m).  Finite; may be above 0.
+ *     stiffness      kappa >= 0, normal spring per corner and unit of the body's mass (1/s^2)
+ *     damping        beta >= 0, normal damper per corner and unit mass (1/s)
+ *     friction       mu >= 0, Coulomb coefficient
+ *     slip_speed     v_s > 0, regularisation of the friction direction (m/s)
+ *     friction_rate  gamma >= 0, cap on the tangential damping the friction may amount to, per corner and unit mass (1/s)
+ * RULE OF THUMB for a step dt, per corner: kappa dt^2 <= 0.04 and beta dt, gamma dt <= 0.04 - explicit penalty forces
+ * overshoot inside one step beyond that (without the cap the friction's slope mu N / v_s does, whatever kappa and beta are:
+ * DESIGN.md section 18).  kappa = (0.2 / dt)^2, beta = gamma = 0.04 / dt, mu = 0.5, v_s = 0.01 bring boxes of 1.05 to 7.8 times
+ * the water's density to rest on four corners at dt = 1/60 and 1/120 with implicit drag; a box at rest stands
+ * g (1 - rho / rho_body) / (4 kappa) below z_b.
+ *
+ * THE CONTACT WRENCH of a body with state s = [p | q | v | omega] (the TRUE state the step starts from), box (dx, dy, dz) and
+ * mass m, in fp32, in exactly this order (fma(a, b, c): a * b + c rounded once; the six constants are rounded ONCE from
+ * double to fp32 by hydro_set_seabed):
+ *     R            the fp32 matrix of q as given, non-unit included - the form the integrator and the body-frame applied
+ *                  wrench use: with x2 = q_x + q_x ..., R_00 = 1 - (q_y y2 + q_z z2), R_01 = q_x y2 - q_w z2, ...
+ *     A_k = 0.5 * (R_k0 * dx),  B_k = 0.5 * (R_k1 * dy),  C_k = 0.5 * (R_k2 * dz)          k = x, y, z
+ *   for corner i = 0 .. 7 with signs (s_x, s_y, s_z) = (i & 1 ? + : -, i & 2 ? + : -, i & 4 ? + : -), in ascending i:
+ *     r_k     = (s_x A_k + s_y B_k) + s_z C_k                          two fp32 additions per component
+ *     delta   = z_b - (p_z + r_z)                                      the corner contributes only if delta > 0
+ *     u_x     = fma(omega_y, r_z, fma(-omega_z, r_y, v_x))             u = v + omega x r, world frame;
+ *     u_y     = fma(omega_z, r_x, fma(-omega_x, r_z, v_y)),  u_z = fma(omega_x, r_y, fma(-omega_y, r_x, v_z))
+ *     a       = max(0, fma(kappa, delta, -(beta * u_z))),  N = m * a   no adhesion
+ *     c       = m * min((mu * a) * rsqrt(fma(v_s, v_s, fma(u_y, u_y, u_x * u_x))), gamma)
+ *                                                                      = min(mu N / sqrt(u_x^2 + u_y^2 + v_s^2), m gamma);
+ *                                                                      rsqrt: hardware seed + one Newton step,
+ *                                                                      y = seed; y = fma(fma(-x * y, y, 1), 0.5 * y, y)
+ *     t_x = c * u_x,  t_y = c * u_y                                    F = (-t_x, -t_y, N)
+ *     W_0 = W_0 - t_x,  W_1 = W_1 - t_y,  W_2 = W_2 + N                W starts from +0
+ *     W_3 = fma(r_y, N, fma(r_z, t_y, W_3))                            r x F
+ *     W_4 = fma(-r_z, t_x, fma(-r_x, N, W_4)),  W_5 = fma(r_y, t_x, fma(-r_x, t_y, W_5))
+ * W = [force at | torque about] the body origin, world frame.  IN A STEP it is added to the step's wrench with one fp32 add
+ * per component - after the clamped hydrodynamic wrench, after the applied wrench and the pose hold, before the integrator.
+ * The sum is what the integrator takes (with implicit_drag it stands where f stood) and what the recorder logs.  A body with
+ * no contributing corner has its wrench left untouched: +0 is NOT added, the sign of a zero survives.  Whole wavefronts of
+ * bodies whose lowest corner, p_z - ((|A_z| + |B_z|) + |C_z|), is not below z_b skip the contact altogether; that value is,
+ * bit for bit, the smallest p_z + r_z, so skipping changes no bit.
+ * THE SEA DOES NOT TOUCH THE BED: the bed sees the true state, never the state relative to the water, and the wave field
+ * stays the deep-water one however shallow z_b makes the scene.
+ * NOT MODELLED: slope and terrain; rolling and spinning friction; face or edge contact other than through the corners (a box
+ * lying flat is held by its four lower corners); body-to-body contact.
+ *
+ * hydro_set_seabed: bed == NULL clears the bed.  HYDRO_E_ARG for a non-finite value, a negative stiffness, damping, friction
+ * or friction_rate, slip_speed <= 0, a constant beyond fp32 range (a slip speed whose fp32 square is 0 or infinite
+ * included) - the previous bed stays in force.  Host-side only: no device memory, no synchronisation; the constants travel as
+ * kernel arguments, so a captured launch replays with the bed of the moment it was captured.
+ *
+ * hydro_seabed_wrench: writes the tiled 6-field W ([tiles][6][64] floats, tile stride out_tile_stride >= 384) of bodies
+ * 0 .. n - 1 in `state` - exactly what a step that starts from `state` adds; +0 in all six fields for a body that does not
+ * touch.  Uses the engine's parameters (dimensions, mass).  A small kernel of its own; asynchronous on `stream`.
+ * HYDRO_E_STATE without a bed or without parameters; HYDRO_E_ARG for n > capacity, a null or misaligned buffer.
+ *
+ * hydro_step_fused_tiled_multi_bed: exactly the signature and the rules of hydro_step_fused_tiled_multi_sea.
+ *   no bed set      : the launch and its bits are those of hydro_step_fused_tiled_multi_sea with the same arguments (which
+ *                     without a sea are those of hydro_step_fused_tiled_multi_ctl).
+ *   a bed set       : log, applied, control and the sea are each still optional; the hydrodynamic wrench is taken through
+ *                     the sea if one is set (without one no view is formed: the bits of the entries without a sea), what is
+ *                     added for the three pointers is what hydro_step_fused_tiled_multi_ctl adds, then W.
+ * The refusals are those of hydro_step_fused_tiled_multi_sea, in its order; the bed adds none at launch time.  Asynchronous,
+ * no allocation, no synchronisation, safe to capture (the bed does not depend on time; waves in a replay stay frozen).
+ * Cost and registers: DESIGN.md section 18.  New functionality; the reference has no seabed of its own (its floor is the
+ * simulator's rigid-body contact). */
+typedef struct hydro_seabed {
+    double z, stiffness, damping, friction, slip_speed, friction_rate;
+} hydro_seabed_t;
+int hydro_set_seabed(hydro_t *h, const hydro_seabed_t *bed);
+int hydro_seabed_wrench(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                        float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_bed(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride, int64_t step0, void *stream);
+
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per
  * SIMD of the tiled wrench kernel (-1 = chosen by size, 0 = whatever the registers allow, 1..8 = cap,

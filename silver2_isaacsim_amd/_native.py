@@ -41,6 +41,12 @@ class Sea(ctypes.Structure):
     _fields_ = [("current", c_double * 3), ("waves", c_int), ("wave", SeaWave * SEA_WAVES_MAX)]
 
 
+class Seabed(ctypes.Structure):
+    """hydro_seabed_t (include/hydro.h): the plane and the five mass-normalised contact constants hydro_set_seabed takes."""
+    _fields_ = [("z", c_double), ("stiffness", c_double), ("damping", c_double), ("friction", c_double),
+                ("slip_speed", c_double), ("friction_rate", c_double)]
+
+
 HYDRO_OK, HYDRO_E_ARG, HYDRO_E_ALLOC, HYDRO_E_LAUNCH, HYDRO_E_DEVICE, HYDRO_E_STATE = 0, -1, -2, -3, -4, -5
 HYDRO_SEM_NUMBA, HYDRO_SEM_WARP = 0, 1
 HYDRO_FRAME_WORLD, HYDRO_FRAME_BODY = 0, 1          # frame of an applied wrench (hydro_step_fused_tiled_multi_app)
@@ -92,6 +98,12 @@ SIGNATURES = {
     "hydro_set_sea": (c_int, [c_void_p, POINTER(Sea)]),
     "hydro_sea_sample": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]),
     "hydro_step_fused_tiled_multi_sea": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_set_seabed": (c_int, [c_void_p, POINTER(Seabed)]),
+    "hydro_seabed_wrench": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_bed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),

@@ -1118,16 +1118,18 @@ __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k
 // `sea` is the sea-state policy: view(k, s, pv) puts the state RELATIVE to the local water in front of body_wrench (depth below
 // the local surface, velocity against the local water), restore(s, pv) brings the true one back behind it - everything
 // after the wrench acts on the true state (see SeaView; NoSea does nothing, and the kernels without a sea are unchanged).
-template <bool IMPLICIT, bool WARP, typename Applied, typename Sea>
+// `bed` is the seabed policy: add(s, d, mass, f6) behind app.add, before the integrator (see SeabedContact; NoBed does nothing).
+template <bool IMPLICIT, bool WARP, typename Applied, typename Sea, typename Bed>
 __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], const float (&d)[3], const float (&c)[7], float mass,
                                                         double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS], const Applied& app,
-                                                        uint32_t k, const Sea& sea)
+                                                        uint32_t k, const Sea& sea, const Bed& bed)
 {
     sea.view(k, s, pv);
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
     sea.restore(s, pv);
     wrench_fields(w, f6);
     app.add(s, f6);
+    bed.add(s, d, mass, f6);
     float o[HYDRO_STATE_FIELDS];
     integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
 #pragma unroll
@@ -1149,11 +1151,12 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // after_step(k, s, f6) behind every step with the state it produced and the wrench that produced it.  `app` is the
 // applied-wrench policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step (see AppliedWrench).
 // `sea` is the sea-state policy: begin(lane4) next to the record loads, then view / restore around every step's wrench.
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea>
+// `bed` is the seabed policy: add(s, d, mass, f6) inside every step; it carries scene constants only and has no begin.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed>
 __device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
                                                  uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea)
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed)
 {
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
@@ -1170,7 +1173,7 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
-            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea);
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea, bed);
             rec.after_step(k, s, f6);
         }
         if constexpr (KE)
@@ -1194,6 +1197,9 @@ struct NoSea {
     __device__ __forceinline__ void begin(uint32_t) {}
     __device__ __forceinline__ void view(uint32_t, float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_PREV_FIELDS]) const {}
     __device__ __forceinline__ void restore(float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_PREV_FIELDS]) const {}
+};
+struct NoBed {
+    __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], const float (&)[3], float, float (&)[HYDRO_WRENCH_FIELDS]) const {}
 };
 
 // --------------------------------------------------------------------------
@@ -1246,7 +1252,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
                                                                        double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{});
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
@@ -1260,7 +1266,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{});
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{});
 }
 
 // --------------------------------------------------------------------------
@@ -1325,7 +1331,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{});
+                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{});
 }
 
 // --------------------------------------------------------------------------
@@ -1456,7 +1462,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{});
+                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{});
 }
 
 // --------------------------------------------------------------------------
@@ -1588,7 +1594,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt});
+                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{});
 }
 
 // hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
@@ -1602,6 +1608,148 @@ __global__ void __launch_bounds__(kBlock) sea_sample_kernel(const float* st, uin
     sea_water(sea_table_ptr(sea_table), sea_waves, step, sea_dt, *at<float>(r, lane4, 0u), *at<float>(r, lane4, 256u), *at<float>(r, lane4, 512u), eta, u);
     const float o[HYDRO_SEA_FIELDS] = {eta, u[0], u[1], u[2]};
     store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
+}
+
+// --------------------------------------------------------------------------
+// The SEABED in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_bed): the horizontal plane z = z_b under the
+// water, scene-wide like rho, g and the sea (hydro_set_seabed).  A body touches it through the eight corners of the box the
+// buoyancy already uses: per corner below the plane a mass-normalised spring and damper along z (no adhesion) and a Coulomb
+// friction whose direction is regularised by a slip speed and whose tangential damping is capped.  include/hydro.h states
+// the model and the order of operations ("Seabed"); seabed_wrench below is its ONLY implementation (the step kernel and
+// hydro_seabed_wrench's kernel both call it).  The bed sees the TRUE state - never the one relative to the water - and adds
+// its wrench behind the applied wrench and the pose hold, in front of the integrator: one fp32 add per component.
+//   constants   : six floats, rounded once on the host, kernel arguments (SGPRs) - no table
+//   broad phase : the lowest corner stands at p_z - ((|A_z| + |B_z|) + |C_z|), A_z = R_20 dx/2 ... - and that is, bit for
+//                 bit, the t_i of the corner whose signs oppose those of A_z, B_z, C_z: fp32 rounding is monotone and
+//                 symmetric, so no other corner's t_i lies below it.  delta_max = z_b - that value is therefore EXACTLY the
+//                 largest delta_i (margin 0 is conservative), and a lane whose delta_max is not > 0 has no contributing
+//                 corner.  If that holds for every lane of the wavefront (ballot == 0) the wave branches round the contact:
+//                 a scene far from the bed pays the rotation's third row, three products, three adds, a compare and the branch
+//   the skip    : a lane without a contributing corner leaves f6 untouched (it does not add +0: the sign of a zero
+//                 survives), whether its wave took the branch or not - skipped and evaluated give the same bits
+// It runs behind the fp64 wrench, where that wrench's registers are free again; nothing is parked for it.
+// --------------------------------------------------------------------------
+struct Seabed { float z, stiffness, damping, friction, slip_speed, friction_rate; };
+
+// W (force at, torque about the body origin, world frame) of the bed on a body in state s with box d and mass m.  Returns
+// whether any corner contributed; W is meaningful (and complete) only then.
+__device__ __forceinline__ bool seabed_wrench(const Seabed& b, const float (&s)[HYDRO_STATE_FIELDS], const float (&d)[3], float m,
+                                              float (&W)[HYDRO_WRENCH_FIELDS])
+{
+    const auto [r00, r01, r02, r10, r11, r12, r20, r21, r22] = rotation_of(s[3], s[4], s[5], s[6]);
+    // (0.5 * (R d), not R (0.5 d) - the same value, and nothing in it that is constant over the steps of a launch: the compiler
+    // would carry such a value through the loop in a register of its own, and the loop has none to spare)
+    const float pz0 = r20 * d[0], pz1 = r21 * d[1], pz2 = r22 * d[2];
+    const float az = 0.5f * pz0, bz = 0.5f * pz1, cz = 0.5f * pz2;
+    const float reach = (__builtin_fabsf(az) + __builtin_fabsf(bz)) + __builtin_fabsf(cz);
+    const float lowest = s[2] - reach;
+    const bool can_touch = b.z - lowest > 0.0f;
+    if (__builtin_amdgcn_ballot_w64(can_touch) == 0) return false;        // (scalar branch: nobody in this wave is near the bed)
+    const float px0 = r00 * d[0], px1 = r01 * d[1], px2 = r02 * d[2];
+    const float py0 = r10 * d[0], py1 = r11 * d[1], py2 = r12 * d[2];
+    const float ax = 0.5f * px0, bx = 0.5f * px1, cx = 0.5f * px2;
+    const float ay = 0.5f * py0, by = 0.5f * py1, cy = 0.5f * py2;
+    bool any = false;
+#pragma unroll
+    for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) W[f] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float sx = (i & 1) ? 1.0f : -1.0f, sy = (i & 2) ? 1.0f : -1.0f, sz = (i & 4) ? 1.0f : -1.0f;
+        const float rx = __builtin_fmaf(sz, cx, __builtin_fmaf(sy, bx, sx * ax));
+        const float ry = __builtin_fmaf(sz, cy, __builtin_fmaf(sy, by, sx * ay));
+        const float rz = __builtin_fmaf(sz, cz, __builtin_fmaf(sy, bz, sx * az));
+        const float t = s[2] + rz;
+        const float delta = b.z - t;
+        if (delta > 0.0f) {
+            any = true;
+            const float ux = __builtin_fmaf(s[11], rz, __builtin_fmaf(-s[12], ry, s[7]));
+            const float uy = __builtin_fmaf(s[12], rx, __builtin_fmaf(-s[10], rz, s[8]));
+            const float uz = __builtin_fmaf(s[10], ry, __builtin_fmaf(-s[11], rx, s[9]));
+            const float bu = b.damping * uz;
+            const float a = __builtin_fmaf(b.stiffness, delta, -bu);
+            const float ap = __builtin_fmaxf(0.0f, a);
+            const float N = m * ap;
+            const float mua = b.friction * ap;
+            const float ux2 = ux * ux;
+            const float ut2 = __builtin_fmaf(b.slip_speed, b.slip_speed, __builtin_fmaf(uy, uy, ux2));
+            const float q = mua * rsqrt_nr(ut2);
+            const float c = m * __builtin_fminf(q, b.friction_rate);
+            const float tx = c * ux, ty = c * uy;                             // F = (-tx, -ty, N)
+            W[0] = W[0] - tx;
+            W[1] = W[1] - ty;
+            W[2] = W[2] + N;
+            W[3] = __builtin_fmaf(ry, N, __builtin_fmaf(rz, ty, W[3]));
+            W[4] = __builtin_fmaf(-rz, tx, __builtin_fmaf(-rx, N, W[4]));
+            W[5] = __builtin_fmaf(ry, tx, __builtin_fmaf(-rx, ty, W[5]));
+        }
+    }
+    return any;
+}
+
+struct SeabedContact {
+    Seabed b;
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], const float (&d)[3], float mass, float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        float W[HYDRO_WRENCH_FIELDS];
+        if (seabed_wrench(b, s, d, mass, W)) {
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+        }
+    }
+};
+
+// The sea of the bed kernel: optional (a null table - a kernel argument: wave-uniform); an absent sea forms no view and
+// parks nothing, so the wrench takes the true state as in the kernels without a sea.
+struct OptionalSeaView : SeaView {
+    __device__ __forceinline__ void view(uint32_t k, float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        if (tab) SeaView::view(k, s, pv);
+    }
+    __device__ __forceinline__ void restore(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        if (tab) SeaView::restore(s, pv);
+    }
+};
+
+// The sea kernel's arguments, then the bed's six constants.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_bed_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
+                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
+                                                                           float bed_slip_speed, float bed_friction_rate)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
+                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}});
+}
+
+// hydro_seabed_wrench: the bed's W per body for the tiled state `st` (zeros for a body no corner of which is below the plane).
+__global__ void __launch_bounds__(kBlock) seabed_wrench_kernel(const float* st, uint32_t st_stride, const float* prm, uint32_t prm_tile_floats, uint32_t mass_field,
+                                                               float* out, uint32_t out_stride, uint32_t n, Seabed bed)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    const float* q = prm + (size_t)tile * prm_tile_floats + lane;
+    float s[HYDRO_STATE_FIELDS], W[HYDRO_WRENCH_FIELDS];
+#pragma unroll
+    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = *at<float>(r, lane4, f * 256u);
+    const float d[3] = {q[0], q[64], q[128]};
+    if (!seabed_wrench(bed, s, d, q[mass_field * 64u], W)) {
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) W[f] = 0.0f;
+    }
+    store_record<HYDRO_WRENCH_FIELDS, false>(out + (size_t)tile * out_stride, lane4, W);
 }
 
 }  // namespace
@@ -1646,6 +1794,9 @@ struct hydro_engine {
     // kept until hydro_destroy.  sea_waves < 0: no sea.
     void* sea_table = nullptr;
     int sea_waves = -1;
+    // The seabed (hydro_set_seabed): the plane and the five contact constants, already rounded to fp32 - kernel arguments.
+    Seabed bed = {};
+    bool has_bed = false;
     hipStream_t stream = nullptr;
     int vec = 0;                   // bodies per lane, 0 = default (1)
     int block = 0;                 // threads per block, 0 = by size
@@ -2456,6 +2607,7 @@ struct MultiStep {
     const float* applied = nullptr; int64_t applied_tile_stride = 0; int applied_frame = HYDRO_FRAME_WORLD;
     const float* control = nullptr; int64_t control_tile_stride = 0;
     bool sea_entry = false; int64_t step0 = 0;           // the _sea entry: step0 is checked, and the steps go through the sea if one is set
+    bool bed_entry = false;                              // the _bed entry: the _sea entry, and the steps meet the seabed if one is set
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -2500,8 +2652,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
     return HYDRO_OK;
 }
 
-// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the sea kernel takes
-// everything, the pose-hold kernel everything but the sea, the applied kernel recorder and applied wrench, the recording
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the bed kernel takes
+// everything, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
 // kernel the recorder - and a launch is handed the options it goes without as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
@@ -2509,7 +2661,7 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
     int rc;
     if (m.sea_entry && (m.step0 < 0 || m.steps < 0 || m.step0 + (int64_t)m.steps >= ((int64_t)1 << 52) || m.step0 >= ((int64_t)1 << 52)))
         return fail(h, HYDRO_E_ARG, "step0 must be >= 0 and step0 + steps < 2^52");
-    const bool rec = m.log || m.log_required, sea = m.sea_entry && h->sea_waves >= 0;
+    const bool rec = m.log || m.log_required, sea = m.sea_entry && h->sea_waves >= 0, bed = m.bed_entry && h->has_bed;
     int64_t rows = 0;
     if (rec && (rc = check_recorder(h, m, rows))) return rc;
     if ((rc = check_common(h, m.n))) return rc;
@@ -2554,7 +2706,10 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (sea) pushed(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+        if (bed) pushed(step_fused_multi_bed_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
+                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate);
+        else if (sea) pushed(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
                         (const void*)h->sea_table, (uint32_t)h->sea_waves, m.step0, m.dt);
         else if (m.control) pushed(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride);
         else if (m.applied) pushed(step_fused_multi_app_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
@@ -2749,6 +2904,64 @@ int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, 
     m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
     m.control = control; m.control_tile_stride = control_tile_stride;
     m.sea_entry = true; m.step0 = step0;
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_set_seabed(hydro_t* h, const hydro_seabed_t* bed)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!bed) { h->has_bed = false; return HYDRO_OK; }
+    const double v[6] = {bed->z, bed->stiffness, bed->damping, bed->friction, bed->slip_speed, bed->friction_rate};
+    for (int i = 0; i < 6; ++i)
+        if (!isfinite(v[i])) return fail(h, HYDRO_E_ARG, "seabed: non-finite value");
+    if (bed->stiffness < 0.0 || bed->damping < 0.0 || bed->friction < 0.0 || bed->friction_rate < 0.0)
+        return fail(h, HYDRO_E_ARG, "seabed: stiffness, damping, friction and friction_rate must be >= 0");
+    if (!(bed->slip_speed > 0.0)) return fail(h, HYDRO_E_ARG, "seabed: slip_speed must be > 0");
+    // rounded ONCE; the slip speed must stay positive in fp32, and its square too (it is what keeps the friction's 1/sqrt finite)
+    const Seabed b = {(float)(bed->z + 0.0), (float)(bed->stiffness + 0.0), (float)(bed->damping + 0.0), (float)(bed->friction + 0.0),
+                      (float)bed->slip_speed, (float)(bed->friction_rate + 0.0)};
+    if (!isfinite(b.z) || !isfinite(b.stiffness) || !isfinite(b.damping) || !isfinite(b.friction) || !isfinite(b.slip_speed)
+        || !isfinite(b.friction_rate) || !(b.slip_speed * b.slip_speed > 0.0f) || !isfinite(b.slip_speed * b.slip_speed))
+        return fail(h, HYDRO_E_ARG, "seabed: constant out of fp32 range");
+    h->bed = b;
+    h->has_bed = true;
+    return HYDRO_OK;
+}
+
+int hydro_seabed_wrench(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!h->has_bed) return fail(h, HYDRO_E_STATE, "no seabed (call hydro_set_seabed first)");
+    int rc;
+    if ((rc = check_common(h, n))) return rc;
+    if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
+    if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_WRENCH_FIELDS, "null out"))) return rc;
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (n == 0) return HYDRO_OK;
+    hipLaunchKernelGGL(seabed_wrench_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
+                       (const float*)h->params_tiled, prm_tile_floats(h), prm_mass_field(h), out, (uint32_t)out_tile_stride, (uint32_t)n, h->bed);
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+int hydro_step_fused_tiled_multi_bed(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    m.bed_entry = true;
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -71,6 +71,7 @@ class HydroEngine:
         self.semantics = "numba"
         self._tables: dict = {}
         self.sea_waves: int | None = None            # wave components of the sea set with set_sea; None: no sea
+        self.seabed = None                           # the seabed.Seabed set with set_seabed; None: no bed
         self.set_scene(water_density, gravity)
 
     # ------------------------------------------------------------------ utils
@@ -447,7 +448,7 @@ class HydroEngine:
                                     lambda: self._applied_control(applied, frame, control, n))
 
     def _applied_control(self, applied, frame, control, n):
-        """The arguments `applied .. control_tile_stride` of `hydro_step_fused_tiled_multi_ctl` / `_sea` (the first three:
+        """The arguments `applied .. control_tile_stride` of `hydro_step_fused_tiled_multi_ctl` / `_sea` / `_bed` (the first three:
         `_app`'s): either buffer may be None (NULL, stride 0)."""
         code = _FRAMES.get(frame)
         if code is None:
@@ -502,6 +503,46 @@ class HydroEngine:
         launch).  control, applied and log are each optional; without a sea the call is step_fused_tiled_multi_controlled.
         Returns the number of rows written (0 without a log)."""
         return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_sea,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: (*self._applied_control(applied, frame, control, n), int(step0)))
+
+    # ------------------------------------------------------------------ seabed
+    def set_seabed(self, bed) -> None:
+        """The scene's floor (hydro_set_seabed; the model: include/hydro.h, "Seabed"): `bed` has `z`, `stiffness`, `damping`,
+        `friction`, `slip_speed` and `friction_rate` - a `seabed.Seabed`.  None clears it.  Only `step_fused_tiled_multi_bed`
+        and `seabed_wrench` see the bed.  Host-side only: the constants travel with every launch."""
+        if bed is None:
+            self._check(self._lib.hydro_set_seabed(self._h, None))
+            self.seabed = None
+            return
+        c = nat.Seabed(float(bed.z), float(bed.stiffness), float(bed.damping), float(bed.friction), float(bed.slip_speed),
+                       float(bed.friction_rate))
+        self._check(self._lib.hydro_set_seabed(self._h, ctypes.byref(c)))
+        self.seabed = bed
+
+    def seabed_wrench(self, state: torch.Tensor, n: int, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The bed's contact wrench on each body of the tiled `state` (hydro_seabed_wrench): a tiled (tiles, 6, 64) buffer of
+        [Fx Fy Fz | Tx Ty Tz], world frame, force at and torque about the body origin - exactly what a step of
+        `step_fused_tiled_multi_bed` that starts from `state` adds; zeros for a body that does not touch."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
+        self._check(self._lib.hydro_seabed_wrench(self._h, n, s_ptr, s_stride, o_ptr, o_stride, self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_bed(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                   control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                   log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_sea over the seabed set with `set_seabed` (hydro_step_fused_tiled_multi_bed): in every step
+        the corners of each body's box that are below the plane add a spring, damper and friction wrench, formed from the
+        true state the step starts from, behind the applied wrench and the pose hold and in front of the integrator.
+        control, applied, log and the sea are each optional; without a bed the call is step_fused_tiled_multi_sea.
+        Returns the number of rows written (0 without a log)."""
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_bed,
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream,
                                     lambda: (*self._applied_control(applied, frame, control, n), int(step0)))

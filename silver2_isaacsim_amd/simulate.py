@@ -331,6 +331,8 @@ class TrajectoryRecorder:
 
 
 class ClosedLoopSim:
+    seabed = None               # set_seabed(): the seabed.Seabed under the bodies (a class default: a sim has none until one is set)
+
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
                  sample_timeout_s: float | None = 300.0):
@@ -540,8 +542,28 @@ class ClosedLoopSim:
             self.sea = None
             self._graph = None
 
-    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
-    # the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
+    def set_seabed(self, bed) -> None:
+        """A floor under the water: from now on every physics step of run_eager, run (graph replays included) and run_resident
+        lets the corners of each body's box meet the plane z = `bed.z` (a `seabed.Seabed`, e.g. `Seabed.for_step(z, sim.dt)`;
+        hydro_step_fused_tiled_multi_bed, the model: include/hydro.h) - a spring, a damper and friction per corner below the
+        plane, evaluated INSIDE the stepping kernel from the state each step starts from.  It acts together with a sea, an
+        applied wrench, a pose hold and a recorder where those are set.  The bed does not depend on time, so it replays; a
+        sea with waves still does not.  The bed stays until the next call or `clear_seabed()`."""
+        if not self.fused:
+            raise ValueError("the seabed lives in the fused step kernels (fused=True)")
+        self.engine.set_seabed(bed)                             # (kernel arguments: launches in flight keep the bed they took)
+        self.seabed = bed
+        self._graph = None                                      # captured steps are of another entry / another bed
+
+    def clear_seabed(self) -> None:
+        """Bottomless water again: every call the sim makes is again the one it made before set_seabed."""
+        if self.seabed is not None:
+            self.engine.set_seabed(None)
+            self.seabed = None
+            self._graph = None
+
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: over
+    # the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
     # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
     # graph captures: the single-step form of the entries, the bits of the single-step entry, include/hydro.h).  The plain
     # step has two forms: single_step=True is one hydro_step_fused_tiled (or the two-kernel path, fused=False), else one
@@ -554,7 +576,9 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.sea is not None:
+        if self.seabed is not None:
+            rows = e.step_fused_tiled_multi_bed(*args, k, self.steps_done, self.control, self.applied, self.applied_frame, **kw)
+        elif self.sea is not None:
             rows = e.step_fused_tiled_multi_sea(*args, k, self.steps_done, self.control, self.applied, self.applied_frame, **kw)
         elif self.control is not None:
             rows = e.step_fused_tiled_multi_controlled(*args, k, self.control, self.applied, self.applied_frame, **kw)
