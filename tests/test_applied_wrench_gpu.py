@@ -33,6 +33,9 @@ RHO, G, DT = populations.RHO, populations.G, populations.DT
 NAN = float("nan")
 COEFFS = pytest.mark.parametrize("coeff", ["f32", "f16"])
 DRAG = pytest.mark.parametrize("implicit", [False, True], ids=["explicit", "implicit"])
+# the chain tests (device against device, bit for bit) hold in either semantics: the Numba cases keep their ids
+COEFFS_SEMANTICS = pytest.mark.parametrize("coeff,semantics", [("f32", "numba"), ("f16", "numba"), ("f32", "warp"), ("f16", "warp")],
+                                           ids=["f32", "f16", "f32-warp", "f16-warp"])
 
 
 @pytest.fixture(scope="module")
@@ -60,9 +63,11 @@ def _tiled(x):
     return torch.from_numpy(scenes.to_tiled(x)).to(DEV)
 
 
-def _engine(n, params, coeff):
+def _engine(n, params, coeff, semantics="numba"):
     eng = HydroEngine(n, DEV, RHO, G)
     eng.set_params(params[:n], coeff)
+    if semantics != "numba":
+        eng.set_semantics(semantics)
     return eng
 
 
@@ -156,11 +161,11 @@ def test_zero_wrench_is_the_plain_step(coeff, implicit, pop, native_built):
 
 
 # ---- 2. world frame = wrench kernel, fp32 add, integrator kernel ---------------------------------------------------------------
-@COEFFS
-def test_world_frame_is_the_two_kernel_path_bit_for_bit(coeff, pop, native_built):
+@COEFFS_SEMANTICS
+def test_world_frame_is_the_two_kernel_path_bit_for_bit(coeff, semantics, pop, native_built):
     st, pv, params, applied, _ = pop
     for n in SIZES:
-        eng = _engine(n, params[coeff], coeff)
+        eng = _engine(n, params[coeff], coeff, semantics)
         a = _tiled(applied[:n])
         cur, old = _buffers(st, pv, n)
         total = _hydro_wrench(eng, cur, old, n) + a                 # torch: one fp32 add per component

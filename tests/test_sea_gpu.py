@@ -29,7 +29,7 @@ from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import (B, COEFFS, DEV, DRAG, DT, G, NAN, RHO, SIZES, STEPS, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers,
+from test_applied_wrench_gpu import (B, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, G, NAN, RHO, SIZES, STEPS, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers,
                                      _engine, _k, _ke, _report, _same, _tiled)
 from test_integrator_gpu import _guarded, _unguard, _untouched
 from test_pose_hold_gpu import S_C, _fp64_errors
@@ -145,11 +145,11 @@ def _relative(eng, st, pv, n, step):
     return sr.relative(st[:n], pv[:n], w[:, 0], w[:, 1:4])
 
 
-@COEFFS
-def test_explicit_step_is_wrench_of_the_relative_state_then_integrator_of_the_true_one(coeff, pop, native_built):
+@COEFFS_SEMANTICS
+def test_explicit_step_is_wrench_of_the_relative_state_then_integrator_of_the_true_one(coeff, semantics, pop, native_built):
     st, pv, params, _, _ = pop
     for n in SIZES:
-        eng = _engine(n, params[coeff], coeff)
+        eng = _engine(n, params[coeff], coeff, semantics)
         eng.set_sea(SEA)
         watched = _watched(n)
         eng.set_watch(watched)

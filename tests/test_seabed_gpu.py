@@ -36,7 +36,7 @@ from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.seabed import Seabed
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import B, COEFFS, DEV, DRAG, DT, G, NAN, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers, _engine, _k, _ke, _same, _tiled
+from test_applied_wrench_gpu import B, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, G, NAN, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers, _engine, _k, _ke, _same, _tiled
 from test_integrator_gpu import _guarded, _unguard, _untouched
 from test_pose_hold_gpu import S_C, _surrogate
 from test_pose_hold_gpu import pop as hold_pop                    # noqa: F401  (fixture: the designed population with its control record)
@@ -219,14 +219,14 @@ def test_probe_against_the_fp64_restatement(coeff, pop, native_built):
 
 
 # ---- 3. a bed step is the sea entry's step with the probe's wrench applied ---------------------------------------------------------------
-@COEFFS
+@COEFFS_SEMANTICS
 @DRAG
 @pytest.mark.parametrize("moving", [False, True], ids=["still", "sea"])
-def test_bed_step_is_the_sea_step_with_the_probe_wrench_applied(coeff, implicit, moving, pop, native_built):
+def test_bed_step_is_the_sea_step_with_the_probe_wrench_applied(coeff, semantics, implicit, moving, pop, native_built):
     st, pv, params, _, _ = pop
     sea = SeaState((0.5, -0.2, 0.05)).add_wave(*SEA.waves[0]).add_wave(*SEA.waves[1]) if moving else None
     for n in SIZES:
-        eng = _engine(n, params[coeff], coeff)
+        eng = _engine(n, params[coeff], coeff, semantics)
         eng.set_seabed(BED)
         eng.set_sea(sea)
         watched = _watched(n)
