@@ -53,7 +53,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_app, HYDRO_FRAME_* - an external force and
  *        torque per body, world- or body-fixed, applied inside every step of the multi-step kernel
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_ctl, HYDRO_CTL_FIELDS - a per-body pose-hold
- *        feedback law evaluated inside every step of the multi-step kernel */
+ *        feedback law evaluated inside every step of the multi-step kernel
+ *        added to 0.7.1 (no existing entry changed): hydro_mooring_wrench, hydro_step_fused_tiled_multi_moor,
+ *        HYDRO_MOOR_FIELDS - one tension-only mooring line per body, evaluated inside every step of the multi-step kernel */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -68,6 +70,7 @@ extern "C" {
 #define HYDRO_PARAM_FIELDS  11
 #define HYDRO_WRENCH_FIELDS  6
 #define HYDRO_CTL_FIELDS    17   /* the control record of hydro_step_fused_tiled_multi_ctl */
+#define HYDRO_MOOR_FIELDS    9   /* the mooring record of hydro_step_fused_tiled_multi_moor */
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
@@ -642,6 +645,79 @@ int hydro_step_fused_tiled_multi_bed(hydro_t *h, int64_t n, const float *state, 
                                      int64_t row0, int64_t *rows_written_host,
                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
                                      const float *control, int64_t control_tile_stride, int64_t step0, void *stream);
+
+/* Mooring: something to tie a body down with in the closed-loop steps - per body ONE line from an anchor fixed in the world
+ * to a fairlead fixed in the body: a spring and a damper along the line that act only while the line is stretched and never
+ * push.  A buoy moored to the seabed and an ROV on a tether are the same model.  Bodies stay independent: a line joins one
+ * body to a fixed point, never two bodies.  Only hydro_step_fused_tiled_multi_moor and hydro_mooring_wrench know lines; every
+ * other entry ignores them.
+ *
+ * THE RECORD `mooring`: HYDRO_MOOR_FIELDS = 9 floats per body, tiled ([tiles][9][64] floats, tile stride
+ * mooring_tile_stride >= 576, 16-byte aligned, whole tiles, addressed like `control`), in this order:
+ *     a(3)   anchor, world frame (m)
+ *     b(3)   fairlead, body frame (m)
+ *     L0     unstretched length (m), >= 0
+ *     k      stiffness (N/m), >= 0
+ *     c      damping along the line (N s/m), >= 0
+ * It is the caller's device buffer and is READ AT EVERY LAUNCH, like `applied` and `control`: a device-side winch may
+ * rewrite L0 between launches.  A body without a line has k = c = 0.  The contents are the caller's and are not validated on
+ * the device: a lane HAS A LINE if k > 0 or c > 0 (a NaN is neither); with a line, negative or non-finite values are
+ * computed as given (k < 0 gives a tension that is clamped to 0 while the line is stretched, c < 0 a negative damper).
+ * RULE OF THUMB for a step dt and a body of mass m: k dt^2 / m <= 0.04 and c dt / m <= 0.04 - an explicit spring overshoots
+ * inside one step beyond that, and at k dt^2 / m = 0.25 the tension chatters to zero.
+ * k = 0.004 m / dt^2, c = 0.02 m / dt hold a 500 kg buoy in a 0.5 m/s current at dt = 1/60.
+ *
+ * THE LINE'S WRENCH on a body with state s = [p | q | v | omega] (the TRUE state the step starts from, never the one
+ * relative to the water), in fp32, in exactly this order (fma(a, b, c): a * b + c rounded once; rsqrt: hardware seed + one
+ * Newton step, as for the seabed):
+ *     R      the fp32 matrix of q as given, non-unit included (the form the seabed and the integrator use)
+ *     r_i    = fma(R_i2, b_z, fma(R_i1, b_y, R_i0 * b_x))              the fairlead's arm, world frame
+ *     e_i    = (a_i - p_i) - r_i                                       two subtractions: fairlead -> anchor
+ *     l2     = fma(e_z, e_z, fma(e_y, e_y, e_x * e_x)),  inv = rsqrt(l2),  l = l2 * inv
+ *     x      = l - L0                                                  the line is TAUT only if x > 0 (l2 = 0 gives NaN: not taut)
+ *     u_x    = fma(omega_y, r_z, fma(-omega_z, r_y, v_x))              u = v + omega x r, the seabed's corner velocity;
+ *     u_y    = fma(omega_z, r_x, fma(-omega_x, r_z, v_y)),  u_z = fma(omega_x, r_y, fma(-omega_y, r_x, v_z))
+ *     un     = fma(u_z, e_z, fma(u_y, e_y, u_x * e_x)) * inv           > 0: the fairlead approaches the anchor
+ *     T      = max(0, fma(k, x, -(c * un)))                            tension; a line cannot push
+ *     F_i    = (T * inv) * e_i
+ *     M_x    = fma(r_y, F_z, -(r_z * F_y)),  M_y = fma(r_z, F_x, -(r_x * F_z)),  M_z = fma(r_x, F_y, -(r_y * F_x))
+ * W = [F | M]: force at, torque about the body origin, world frame.  IN A STEP it is added to the step's wrench with one
+ * fp32 add per component - after the clamped hydrodynamic wrench, the applied wrench, the pose hold and the seabed, before
+ * the integrator.  The sum is what the integrator takes (with implicit_drag it stands where f stood) and what the recorder
+ * logs.  A body without a line, with a line that is not taut, or with a T that is not > 0 has its wrench left untouched:
+ * +0 is NOT added, the sign of a zero survives.  Whole wavefronts without a line skip the evaluation; that changes no bit.
+ * NOT MODELLED: the line's mass and catenary sag; drag on the line; the line lying on the bed; more than one line per
+ * body; a line between two bodies.
+ *
+ * hydro_mooring_wrench: writes the tiled 6-field W ([tiles][6][64] floats, tile stride out_tile_stride >= 384) of bodies
+ * 0 .. n - 1 in `state` - exactly what a step that starts from `state` adds; +0 in all six fields for a body whose line adds
+ * nothing.  A small kernel of its own; asynchronous on `stream`.  HYDRO_E_STATE without parameters; HYDRO_E_ARG for
+ * n > capacity, a null or misaligned buffer, a stride below 832 (state) / 576 (mooring) / 384 (out), or `out` overlapping
+ * an input.
+ *
+ * hydro_step_fused_tiled_multi_moor: the signature and the rules of hydro_step_fused_tiled_multi_bed, with `mooring` and its
+ * stride in front of step0.
+ *   mooring == NULL : the launch and its bits are those of hydro_step_fused_tiled_multi_bed with the same arguments.
+ *   mooring != NULL : log, applied, control, the sea (hydro_set_sea) and the bed (hydro_set_seabed) are each still optional,
+ *                     and what they add is what the entries without lines add (no sea: no view is formed; no bed: no broad
+ *                     phase); then W.  Like hydro_step_fused_tiled_multi_bed, this entry knows the sea and the bed.
+ * The refusals are those of hydro_step_fused_tiled_multi_bed, in its order, then the mooring's, behind `control`'s: a stride
+ * below 576 or misaligned buffer, a record that overlaps an output (state_out, prev_out, log) - HYDRO_E_ARG, and nothing is
+ * launched or written.  Asynchronous, no allocation, no synchronisation, safe to capture (a line does not depend on time).
+ * Cost and registers: DESIGN.md section 19.  New functionality; the reference has no mooring of its own. */
+int hydro_mooring_wrench(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                         const float *mooring, int64_t mooring_tile_stride,
+                         float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_moor(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                      const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float *state_out, int64_t out_tile_stride,
+                                      float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double *ke_out_dev,
+                                      float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t *rows_written_host,
+                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float *control, int64_t control_tile_stride,
+                                      const float *mooring, int64_t mooring_tile_stride, int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

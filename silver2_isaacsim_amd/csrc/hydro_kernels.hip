@@ -1119,10 +1119,11 @@ __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k
 // the local surface, velocity against the local water), restore(s, pv) brings the true one back behind it - everything
 // after the wrench acts on the true state (see SeaView; NoSea does nothing, and the kernels without a sea are unchanged).
 // `bed` is the seabed policy: add(s, d, mass, f6) behind app.add, before the integrator (see SeabedContact; NoBed does nothing).
-template <bool IMPLICIT, bool WARP, typename Applied, typename Sea, typename Bed>
+// `moor` is the mooring policy: add(s, f6) behind bed.add, before the integrator (see MooringLine; NoMooring does nothing).
+template <bool IMPLICIT, bool WARP, typename Applied, typename Sea, typename Bed, typename Moor>
 __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], const float (&d)[3], const float (&c)[7], float mass,
                                                         double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS], const Applied& app,
-                                                        uint32_t k, const Sea& sea, const Bed& bed)
+                                                        uint32_t k, const Sea& sea, const Bed& bed, const Moor& moor)
 {
     sea.view(k, s, pv);
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
@@ -1130,6 +1131,7 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
     wrench_fields(w, f6);
     app.add(s, f6);
     bed.add(s, d, mass, f6);
+    moor.add(s, f6);
     float o[HYDRO_STATE_FIELDS];
     integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
 #pragma unroll
@@ -1152,11 +1154,13 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // applied-wrench policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step (see AppliedWrench).
 // `sea` is the sea-state policy: begin(lane4) next to the record loads, then view / restore around every step's wrench.
 // `bed` is the seabed policy: add(s, d, mass, f6) inside every step; it carries scene constants only and has no begin.
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed>
+// `moor` is the mooring policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step, and end(d)
+// behind the last step of a kernel that samples the kinetic energy (see MooringLine).
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed, typename Moor>
 __device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
                                                  uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed)
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed, Moor moor)
 {
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
@@ -1170,15 +1174,18 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
         rec.begin(tile, lane);
         app.begin(tile, lane4);
         sea.begin(lane4);
+        moor.begin(tile, lane4);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
-            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea, bed);
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea, bed, moor);
             rec.after_step(k, s, f6);
         }
-        if constexpr (KE)
+        if constexpr (KE) {
+            moor.end(d);
             hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
                                   ke_rotational != 0, ke_lin, ke_rot);
+        }
         store_record<HYDRO_PREV_FIELDS, NT>(k_pvo + (size_t)tile * pvo_stride, lane4, pv);
         store_record<HYDRO_STATE_FIELDS, NT>(k_so + (size_t)tile * so_stride, lane4, s);
     }
@@ -1200,6 +1207,11 @@ struct NoSea {
 };
 struct NoBed {
     __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], const float (&)[3], float, float (&)[HYDRO_WRENCH_FIELDS]) const {}
+};
+struct NoMooring {
+    __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void end(float (&)[3]) const {}
+    __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_WRENCH_FIELDS]) const {}
 };
 
 // --------------------------------------------------------------------------
@@ -1252,7 +1264,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
                                                                        double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{});
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
@@ -1266,7 +1278,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{});
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{});
 }
 
 // --------------------------------------------------------------------------
@@ -1331,7 +1343,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{});
+                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{}, NoMooring{});
 }
 
 // --------------------------------------------------------------------------
@@ -1462,7 +1474,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{});
+                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{}, NoMooring{});
 }
 
 // --------------------------------------------------------------------------
@@ -1594,7 +1606,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{});
+                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{}, NoMooring{});
 }
 
 // hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
@@ -1730,7 +1742,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
                                                    OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}});
+                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, NoMooring{});
 }
 
 // hydro_seabed_wrench: the bed's W per body for the tiled state `st` (zeros for a body no corner of which is below the plane).
@@ -1746,6 +1758,133 @@ __global__ void __launch_bounds__(kBlock) seabed_wrench_kernel(const float* st, 
     for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = *at<float>(r, lane4, f * 256u);
     const float d[3] = {q[0], q[64], q[128]};
     if (!seabed_wrench(bed, s, d, q[mass_field * 64u], W)) {
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) W[f] = 0.0f;
+    }
+    store_record<HYDRO_WRENCH_FIELDS, false>(out + (size_t)tile * out_stride, lane4, W);
+}
+
+// --------------------------------------------------------------------------
+// MOORING LINES in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_moor): per body ONE tension-only line
+// from an anchor fixed in the world to a fairlead fixed in the body - a spring and a damper along the line that never push.
+// Per body a tiled 9-field record ([tiles][9][64], addressed like the control record):
+//   a(3) | b(3) | L0 | k | c
+// include/hydro.h states the model and the order of operations ("Mooring"); mooring_wrench below is its ONLY implementation
+// (the step kernel and hydro_mooring_wrench's kernel both call it).  The line sees the TRUE state - never the one relative
+// to the water - and adds its wrench behind the bed, in front of the integrator: one fp32 add per component.
+//   the record  : the caller's device buffer, read at every launch.  The bed kernels stand at 161-167 VGPRs against the 168
+//                 of three waves per SIMD, so the nine values are not carried through the loop: each lane parks them in LDS
+//                 once per launch, [wave][9][64] floats (9 KB per block; LaneSlots, above), and reads them back in every step
+//   the skip    : a lane has a line if k > 0 or c > 0.  If no lane of the wavefront has one (ballot == 0) the wave branches
+//                 round the evaluation: an unmoored scene pays two LDS reads, two compares and the branch
+//   no +0       : a lane whose line adds nothing (no line, slack, or a tension that is not > 0) leaves f6 untouched, whether
+//                 its wave took the branch or not - skipped and evaluated give the same bits
+// It runs behind the fp64 wrench and the bed, where their registers are free again.
+// --------------------------------------------------------------------------
+// W (force at, torque about the body origin, world frame) of the line whose record is m[j * 64], j = 0 .. 8, on a body in
+// state s.  Returns whether the line pulls; W is meaningful (and complete) only then.
+__device__ __forceinline__ bool mooring_wrench(const float* m, const float (&s)[HYDRO_STATE_FIELDS], float (&W)[HYDRO_WRENCH_FIELDS])
+{
+    const float k = m[7 * 64], c = m[8 * 64];
+    const bool has_line = k > 0.0f || c > 0.0f;
+    if (__builtin_amdgcn_ballot_w64(has_line) == 0) return false;         // (scalar branch: nobody in this wave is moored)
+    const auto [r00, r01, r02, r10, r11, r12, r20, r21, r22] = rotation_of(s[3], s[4], s[5], s[6]);
+    const float bx = m[3 * 64], by = m[4 * 64], bz = m[5 * 64];
+    const float rx = __builtin_fmaf(r02, bz, __builtin_fmaf(r01, by, r00 * bx));
+    const float ry = __builtin_fmaf(r12, bz, __builtin_fmaf(r11, by, r10 * bx));
+    const float rz = __builtin_fmaf(r22, bz, __builtin_fmaf(r21, by, r20 * bx));
+    const float ex = (m[0 * 64] - s[0]) - rx, ey = (m[1 * 64] - s[1]) - ry, ez = (m[2 * 64] - s[2]) - rz;
+    const float l2 = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+    const float inv = rsqrt_nr(l2);
+    const float l = l2 * inv;
+    const float x = l - m[6 * 64];
+    const float ux = __builtin_fmaf(s[11], rz, __builtin_fmaf(-s[12], ry, s[7]));
+    const float uy = __builtin_fmaf(s[12], rx, __builtin_fmaf(-s[10], rz, s[8]));
+    const float uz = __builtin_fmaf(s[10], ry, __builtin_fmaf(-s[11], rx, s[9]));
+    const float un = __builtin_fmaf(uz, ez, __builtin_fmaf(uy, ey, ux * ex)) * inv;
+    const float cu = c * un;
+    const float T = __builtin_fmaxf(0.0f, __builtin_fmaf(k, x, -cu));
+    const float ti = T * inv;
+    W[0] = ti * ex; W[1] = ti * ey; W[2] = ti * ez;
+    W[3] = __builtin_fmaf(ry, W[2], -(rz * W[1]));
+    W[4] = __builtin_fmaf(rz, W[0], -(rx * W[2]));
+    W[5] = __builtin_fmaf(rx, W[1], -(ry * W[0]));
+    return has_line && x > 0.0f && T > 0.0f;                              // (l2 = 0: x is NaN, not taut)
+}
+
+constexpr uint32_t kMoorSlots = HYDRO_MOOR_FIELDS;
+struct MooringLine : LaneSlots<kMoorSlots> {
+    const float* rec; uint32_t stride;
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        float* mine = claim(lane4_);
+        const float* r = rec + (size_t)tile * stride;
+#pragma unroll
+        for (int f = 0; f < HYDRO_MOOR_FIELDS; ++f) mine[f * 64] = ldg<false>(at<float>(r, lane4, f * 256u));
+    }
+    // Behind the loop of a kernel that samples the kinetic energy: the box as the energy sees it is made opaque.  The energy
+    // takes (double)d, which the fp64 wrench forms in front of the loop too; left to itself the compiler keeps those doubles
+    // alive across the loop for the energy's sake - four VGPRs the loop does not have (it spilled them to scratch).  Behind
+    // the empty asm the conversions are made anew from the floats, which are live anyway.  Same values, same bits.
+    __device__ __forceinline__ void end(float (&d)[3]) const
+    {
+        asm volatile("" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]));
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        float W[HYDRO_WRENCH_FIELDS];
+        if (mooring_wrench(parked(), s, W)) {
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+        }
+    }
+};
+
+// The bed of the mooring kernel: optional (`present` - a kernel argument: wave-uniform); an absent bed runs no broad phase
+// and adds nothing, the bits of the kernels without one.
+struct OptionalSeabedContact : SeabedContact {
+    int present;
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], const float (&d)[3], float mass, float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        if (present) SeabedContact::add(s, d, mass, f6);
+    }
+};
+
+// The bed kernel's arguments, then the bed's presence, then the mooring record's.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_moor_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
+                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
+                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
+                                                                           const float* mooring, uint32_t mooring_stride)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
+                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
+                                                   MooringLine{{0u, 0u}, mooring, mooring_stride});
+}
+
+// hydro_mooring_wrench: the line's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds nothing).
+__global__ void __launch_bounds__(kBlock) mooring_wrench_kernel(const float* st, uint32_t st_stride, const float* moor, uint32_t moor_stride,
+                                                                float* out, uint32_t out_stride, uint32_t n)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float s[HYDRO_STATE_FIELDS], W[HYDRO_WRENCH_FIELDS];
+#pragma unroll
+    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = *at<float>(r, lane4, f * 256u);
+    if (!mooring_wrench(moor + (size_t)tile * moor_stride + lane, s, W)) {
 #pragma unroll
         for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) W[f] = 0.0f;
     }
@@ -2608,6 +2747,7 @@ struct MultiStep {
     const float* control = nullptr; int64_t control_tile_stride = 0;
     bool sea_entry = false; int64_t step0 = 0;           // the _sea entry: step0 is checked, and the steps go through the sea if one is set
     bool bed_entry = false;                              // the _bed entry: the _sea entry, and the steps meet the seabed if one is set
+    const float* mooring = nullptr; int64_t mooring_tile_stride = 0;      // the _moor entry: the _bed entry, and a line per body if a record is given
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -2622,7 +2762,7 @@ inline int64_t tiled_extent(int64_t tiles, int64_t stride, int fields)
 {
     return tiles > 0 ? (tiles - 1) * stride + (int64_t)fields * HYDRO_TILE : 0;
 }
-// A per-body input record (`what`: "applied" / "control"; `stride` floats per tile) must lie outside everything the launch writes.
+// A per-body input record (`what`: "applied" / "control" / "mooring"; `stride` floats per tile) must lie outside everything the launch writes.
 int check_no_overlap(hydro_t* h, const MultiStep& m, int64_t log_floats, const char* what, const float* p, int64_t stride)
 {
     const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiles * stride;
@@ -2652,8 +2792,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
     return HYDRO_OK;
 }
 
-// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the bed kernel takes
-// everything, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the mooring kernel takes
+// everything, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
 // kernel the recorder - and a launch is handed the options it goes without as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
@@ -2683,6 +2823,10 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         if ((rc = check_tiled(h, m.n, m.control, m.control_tile_stride, HYDRO_CTL_FIELDS, "null control"))) return rc;
         if ((rc = check_no_overlap(h, m, log_floats, "control", m.control, m.control_tile_stride))) return rc;
     }
+    if (m.mooring) {
+        if ((rc = check_tiled(h, m.n, m.mooring, m.mooring_tile_stride, HYDRO_MOOR_FIELDS, "null mooring"))) return rc;
+        if ((rc = check_no_overlap(h, m, log_floats, "mooring", m.mooring, m.mooring_tile_stride))) return rc;
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -2706,7 +2850,11 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (bed) pushed(step_fused_multi_bed_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+        if (m.mooring) pushed(step_fused_multi_moor_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
+                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
+                        m.mooring, (uint32_t)m.mooring_tile_stride);
+        else if (bed) pushed(step_fused_multi_bed_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
                         sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
                         h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate);
         else if (sea) pushed(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
@@ -2962,6 +3110,50 @@ int hydro_step_fused_tiled_multi_bed(hydro_t* h, int64_t n, const float* state, 
     m.control = control; m.control_tile_stride = control_tile_stride;
     m.sea_entry = true; m.step0 = step0;
     m.bed_entry = true;
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_mooring_wrench(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, const float* mooring, int64_t mooring_tile_stride,
+                         float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    int rc;
+    if ((rc = check_common(h, n))) return rc;
+    if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
+    if ((rc = check_tiled(h, n, mooring, mooring_tile_stride, HYDRO_MOOR_FIELDS, "null mooring"))) return rc;
+    if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_WRENCH_FIELDS, "null out"))) return rc;
+    const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, out_floats = tiled_extent(tiles, out_tile_stride, HYDRO_WRENCH_FIELDS);
+    if (ranges_overlap(state, tiled_extent(tiles, state_tile_stride, HYDRO_STATE_FIELDS), out, out_floats)
+        || ranges_overlap(mooring, tiled_extent(tiles, mooring_tile_stride, HYDRO_MOOR_FIELDS), out, out_floats))
+        return fail(h, HYDRO_E_ARG, "out must not overlap an input (state, mooring)");
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (n == 0) return HYDRO_OK;
+    hipLaunchKernelGGL(mooring_wrench_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
+                       mooring, (uint32_t)mooring_tile_stride, out, (uint32_t)out_tile_stride, (uint32_t)n);
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+int hydro_step_fused_tiled_multi_moor(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                      const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float* state_out, int64_t out_tile_stride,
+                                      float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double* ke_out_dev,
+                                      float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t* rows_written_host,
+                                      const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float* control, int64_t control_tile_stride,
+                                      const float* mooring, int64_t mooring_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    m.bed_entry = true;
+    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
     return step_fused_tiled_multi_launch(h, m);
 }
 

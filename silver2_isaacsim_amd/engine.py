@@ -547,6 +547,42 @@ class HydroEngine:
                                     (log, every, phase, row0), stream,
                                     lambda: (*self._applied_control(applied, frame, control, n), int(step0)))
 
+    # ------------------------------------------------------------------ mooring lines
+    def mooring_wrench(self, state: torch.Tensor, mooring: torch.Tensor, n: int, out: torch.Tensor | None = None,
+                       stream=None) -> torch.Tensor:
+        """The wrench of each body's mooring line on the tiled `state` (hydro_mooring_wrench; the model: include/hydro.h,
+        "Mooring"): `mooring` is a tiled (tiles, 9, 64) buffer of [a(3) | b(3) | L0 | k | c] per body; the result a tiled
+        (tiles, 6, 64) buffer of [Fx Fy Fz | Tx Ty Tz], world frame, force at and torque about the body origin - exactly
+        what a step of `step_fused_tiled_multi_moor` that starts from `state` adds; zeros where the line adds nothing."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        m_ptr, m_stride = self._tiled(mooring, nat.MOOR_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
+        self._check(self._lib.hydro_mooring_wrench(self._h, n, s_ptr, s_stride, m_ptr, m_stride, o_ptr, o_stride,
+                                                   self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_moor(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                    mooring: torch.Tensor | None,
+                                    control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                    log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                    state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                    ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_bed with one tension-only mooring line per body (hydro_step_fused_tiled_multi_moor):
+        `mooring` is the tiled (tiles, 9, 64) record of `mooring_wrench`, read at every launch.  In every step a taut line
+        adds a spring and damper force along itself at the fairlead, formed from the true state the step starts from,
+        behind the applied wrench, the pose hold and the bed and in front of the integrator.  control, applied, log, the
+        sea and the bed are each optional; mooring=None is step_fused_tiled_multi_bed.  Returns the number of rows written
+        (0 without a log)."""
+        def extra():
+            tail = self._applied_control(applied, frame, control, n)
+            m_ptr, m_stride = self._tiled(mooring, nat.MOOR_FIELDS, n) if mooring is not None else (None, 0)
+            return (*tail, m_ptr, m_stride, int(step0))
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_moor,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

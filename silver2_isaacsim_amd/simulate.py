@@ -26,6 +26,7 @@ from . import _native as nat
 from . import distributed as hd
 from . import scenes
 from .engine import HydroEngine
+from .mooring import Mooring
 
 
 class KineticEnergyMonitor:
@@ -332,6 +333,8 @@ class TrajectoryRecorder:
 
 class ClosedLoopSim:
     seabed = None               # set_seabed(): the seabed.Seabed under the bodies (a class default: a sim has none until one is set)
+    mooring = None              # set_mooring(): the tiled (tiles, 9, 64) record of the bodies' mooring lines while lines are set
+    _mooring_buf = None         # the buffer itself (made once)
 
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
@@ -562,8 +565,48 @@ class ClosedLoopSim:
             self.seabed = None
             self._graph = None
 
-    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: over
-    # the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
+    def set_mooring(self, anchor, fairlead=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0, bodies=None) -> torch.Tensor:
+        """Tie the bodies down: from now on every physics step of run_eager, run (graph replays included) and run_resident
+        lets one tension-only line per body pull its fairlead towards its anchor (hydro_step_fused_tiled_multi_moor; the
+        model: include/hydro.h, "Mooring"), evaluated INSIDE the stepping kernel from the state each step starts from.  It
+        acts together with a sea, a seabed, an applied wrench, a pose hold and a recorder where those are set.
+        anchor (., 3): world frame; fairlead (., 3): body frame; length: unstretched, m; stiffness: N/m; damping: N s/m -
+        each a scalar / one row, or one row per body (per listed body with `bodies`); bodies that are not listed have no
+        line.  `mooring.Mooring` validates them, and its rule of thumb (k dt^2 / m, c dt / m <= 0.04) is enforced for the
+        bodies' masses: `Mooring.for_body(mass, sim.dt)` gives stable defaults.  The lines stay until the next call or
+        `clear_mooring()`.
+        Returns `sim.mooring`, the tiled (tiles, 9, 64) device buffer the kernels read, fields [a | b | L0 | k | c].  Its
+        address never changes: a winch on the device may rewrite L0 in it between chunks on `sim.stream`, and a graph replay
+        sees the contents of the moment."""
+        if not self.fused:
+            raise ValueError("mooring lines live in the fused step kernels (fused=True)")
+        idx = np.arange(self.n) if bodies is None else np.asarray(bodies, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+            raise ValueError(f"bodies must be in 0 .. {self.n - 1}")
+        lines = Mooring(anchor, fairlead, length=length, stiffness=stiffness, damping=damping, n=idx.size)
+        lines.check_stable(np.asarray(self.scene.params, np.float64)[idx, 10], self.dt)
+        rec = np.zeros((self.n, nat.MOOR_FIELDS), np.float32)
+        with np.errstate(over="ignore"):
+            rec[idx] = lines.record
+        if not np.isfinite(rec).all():
+            raise ValueError("mooring: a value is out of fp32 range")
+        if self._mooring_buf is None:
+            self._mooring_buf = self.engine.alloc_tiled(nat.MOOR_FIELDS, self.n)
+        with torch.cuda.stream(self.stream):
+            self._mooring_buf.copy_(torch.from_numpy(scenes.to_tiled(rec)))
+        if self.mooring is None:
+            self._graph = None                                              # captured steps are of another entry
+        self.mooring = self._mooring_buf
+        return self.mooring
+
+    def clear_mooring(self) -> None:
+        """Cast off: every call the sim makes is again the one it made before set_mooring."""
+        if self.mooring is not None:
+            self.mooring = None
+            self._graph = None
+
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
     # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
     # graph captures: the single-step form of the entries, the bits of the single-step entry, include/hydro.h).  The plain
     # step has two forms: single_step=True is one hydro_step_fused_tiled (or the two-kernel path, fused=False), else one
@@ -576,7 +619,9 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.seabed is not None:
+        if self.mooring is not None:
+            rows = e.step_fused_tiled_multi_moor(*args, k, self.steps_done, self.mooring, self.control, self.applied, self.applied_frame, **kw)
+        elif self.seabed is not None:
             rows = e.step_fused_tiled_multi_bed(*args, k, self.steps_done, self.control, self.applied, self.applied_frame, **kw)
         elif self.sea is not None:
             rows = e.step_fused_tiled_multi_sea(*args, k, self.steps_done, self.control, self.applied, self.applied_frame, **kw)
