@@ -116,9 +116,12 @@ int hydro_set_scene(hydro_t *h, double water_density, double gravity);
  * Everything else is common (same matrix from the quaternion - Warp's quat_rotate differs from it by
  * 2(|q|^2-1), 2.4e-7 for an fp32-rounded unit quaternion; lift with a degenerate axis and the pressure
  * centre at rest, which the Warp source leaves unassigned, follow Numba / the N1 completion).
- * PARITY UNPINNED for HYDRO_SEM_WARP: the mode restates warp_hydrodynamics.py from its source text - the reference
- * holds no outputs of its Warp calculator and `warp` cannot be imported where this library is built.  The first call
- * that selects it says so once on stderr (HYDRO_QUIET=1 in the environment silences it). */
+ * What pins HYDRO_SEM_WARP: the reference's warp_hydrodynamics.py and its wrapper EXECUTED under a stand-in for the Warp
+ * runtime (fp64, Warp's zero-initialised locals modelled, quat_rotate bound to the matrix form), whose outputs the tests
+ * hold every entry to (tests/test_warp_semantics.py).  Not NVIDIA's runtime, not its fp32 rounding, and not Warp's own
+ * quat_rotate: against that the net wrench moves by up to 1.0e-5 on fp32-rounded unit quaternions and at order one on
+ * non-unit ones.  The first call that selects the mode says so once on stderr (HYDRO_QUIET=1 in the
+ * environment silences it). */
 #define HYDRO_SEM_NUMBA 0
 #define HYDRO_SEM_WARP  1
 int hydro_set_semantics(hydro_t *h, int semantics);

@@ -28,10 +28,16 @@ Documented completion: the reference's
 :113-115 - is `(center_of_buoyancy, 0.0)`; this oracle, the golden generator
 and the HIP kernels all apply that completion.
 
-Warp twin (`semantics="warp"`): the two places where warp_hydrodynamics.py:233-335 differs from the
-Numba path (added-mass rotation, centres of a dry body) are restated from its source text.  PARITY
-UNPINNED for that mode: `warp` is not importable in the build container and the reference holds no
-outputs of it, so nothing executes or pins the Warp path; the Numba mode is unaffected.
+Warp twin (`semantics="warp"`): the places where warp_hydrodynamics.py:233-335 differs from the Numba
+path (added-mass rotation, centres of a dry body, centre of buoyancy when the top keypoints are exactly
+on the surface) are restated here.  Pinned the same way as the Numba mode:
+`tests/golden/make_golden_warp.py` executes the reference's Warp source and its wrapper under a stand-in
+for the Warp runtime (`tests/tools/warp_standin.py`: float64, Warp's zero-initialised locals modelled,
+`quat_rotate` bound to the matrix form) through the reference's `_apply_behavior`, and
+`tests/test_warp_semantics.py` holds this module to those outputs at 1e-9.  Not pinned: NVIDIA's runtime
+and its fp32 rounding.  Warp's own `quat_rotate(q, v)` equals R(q) v + 2 (|q|^2 - 1) v; this module and
+the kernels use R(q) v in both modes (up to 1.0e-5 of the wrench on fp32-rounded unit
+quaternions, order one on non-unit ones).  The Numba mode is unaffected.
 
 Field orders used everywhere in this repo
   state  (13): px py pz | qx qy qz qw | vx vy vz | wx wy wz     (quat xyzw)
@@ -324,7 +330,10 @@ def solve_components(state, accel, params, rho, g, semantics="numba", dtype=np.f
 
     # A2/A3: world keypoints, extent ratio, CoB
     local = _LATTICE_IJK[None, :, :] * half[:, None, :]              # (N,27,3)
-    world = np.einsum("nab,nkb->nka", rot, local) + p[:, None, :]     # (N,27,3)
+    # R k summed in the order written, x then y then z, as any sequential evaluation of the reference's source does:
+    # einsum's order is numpy's choice, and a body within 1e-8 of the dry threshold sees one ulp of a keypoint height
+    world = (rot[:, None, :, 0] * local[:, :, None, 0] + rot[:, None, :, 1] * local[:, :, None, 1]
+             + rot[:, None, :, 2] * local[:, :, None, 2]) + p[:, None, :]                      # (N,27,3)
     if "heights_f32" in mutate:
         world[:, :, 2] = _f32(world[:, :, 2])
     z = world[:, :, 2]

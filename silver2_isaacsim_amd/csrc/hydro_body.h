@@ -226,7 +226,7 @@ struct Body {
 // added-mass factors instead of six products), component mode passes accelerations and 1.  rho, g: scene scalars
 // (hydrodynamics_config.json:2-5 "globals"), doubles as the reference passes Python floats.
 // `warp` (uniform over a launch) selects the semantics of the reference's Warp twin where it differs from the Numba
-// path (include/hydro.h HYDRO_SEM_WARP - PARITY UNPINNED for that mode); the default is Numba.
+// path (include/hydro.h HYDRO_SEM_WARP says what pins that mode); the default is Numba.
 //
 // Instruction count matters as much as bytes here: under the combined load of this kernel the chip holds ~2.0 GHz
 // (2.4 for its memory traffic or its arithmetic alone) and at that clock the ~500 VALU instructions of a body take as

@@ -3472,13 +3472,13 @@ int hydro_set_semantics(hydro_t* h, int semantics)
     if (semantics != HYDRO_SEM_NUMBA && semantics != HYDRO_SEM_WARP)
         return fail(h, HYDRO_E_ARG, "semantics must be HYDRO_SEM_NUMBA (0) or HYDRO_SEM_WARP (1)");
     if (semantics == HYDRO_SEM_WARP) {
-        // said once per process: this mode restates warp_hydrodynamics.py from its source text; the reference holds no
-        // outputs of its Warp calculator and `warp` cannot be imported where this library is built - PARITY UNPINNED
+        // said once per process: what pins this mode is warp_hydrodynamics.py executed under a stand-in for the Warp runtime
+        // (tests/test_warp_semantics.py), not NVIDIA's runtime, its fp32 rounding or its own quat_rotate (include/hydro.h)
         static std::once_flag told;               // (handles are independent across host threads)
         if (!getenv("HYDRO_QUIET"))
             std::call_once(told, [] {
-                fprintf(stderr, "[libhydro] HYDRO_SEM_WARP: restated from the source text of warp_hydrodynamics.py, no reference "
-                                "outputs behind it (parity unpinned); HYDRO_SEM_NUMBA is the verified mode\n");
+                fprintf(stderr, "[libhydro] HYDRO_SEM_WARP: pinned on warp_hydrodynamics.py executed under an fp64 stand-in for the "
+                                "Warp runtime (matrix quat_rotate), not on NVIDIA's runtime; HYDRO_SEM_NUMBA is the parity target\n");
             });
     }
     h->semantics = semantics;

@@ -108,17 +108,18 @@ class HydroEngine:
     def set_semantics(self, semantics: str = "numba") -> None:
         """'numba' (default, the parity target) or 'warp': follow the reference's Warp twin where the two
         calculators differ (added-mass rotation, centres of a dry body; include/hydro.h).
-        PARITY UNPINNED for 'warp': that mode restates warp_hydrodynamics.py from its source text; the reference holds
-        no outputs of its Warp calculator and `warp` is not importable where this package is built.  Said once per
-        process through the package logger."""
+        What pins 'warp': the reference's warp_hydrodynamics.py and its wrapper executed under a stand-in for the Warp
+        runtime (fp64, zero-initialised locals modelled, quat_rotate = the matrix form; tests/test_warp_semantics.py) -
+        not NVIDIA's runtime, its fp32 rounding or its own quat_rotate, against which the wrench moves by up to 1.0e-5 on
+        fp32-rounded unit quaternions and at order one on non-unit ones.  Said once per process through the package logger."""
         global _warp_mode_announced
         code = {"numba": nat.HYDRO_SEM_NUMBA, "warp": nat.HYDRO_SEM_WARP}.get(semantics)
         if code is None:
             raise ValueError("semantics must be 'numba' or 'warp'")
         if semantics == "warp" and not _warp_mode_announced:
             _warp_mode_announced = True
-            log.warning("semantics='warp': restated from the source text of the reference's warp_hydrodynamics.py, no "
-                        "reference outputs behind it (parity unpinned); 'numba' is the verified mode")
+            log.warning("semantics='warp': pinned on the reference's warp_hydrodynamics.py executed under an fp64 stand-in for "
+                        "the Warp runtime (matrix quat_rotate), not on NVIDIA's runtime; 'numba' is the parity target")
         self._check(self._lib.hydro_set_semantics(self._h, code))
         self.semantics = semantics
 

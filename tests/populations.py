@@ -205,6 +205,28 @@ def integrator_population(n=20000, seed=31, margin=1e-4):
     return state, prev, params
 
 
+WARP_FUZZ = (2048, 20251)          # (bodies, seed) of the fuzz population behind tests/golden/warp_reference.npz
+
+
+def warp_reference_populations():
+    """name -> (state, prev, params, rho, g, dt), fp32 inputs: the populations on which tests/golden/make_golden_warp.py
+    executes the reference's Warp calculator (tests/golden/warp_reference.npz holds the outputs and a digest of each)."""
+    import os
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    if os.path.join(here, "tools") not in sys.path:
+        sys.path.insert(0, os.path.join(here, "tools"))
+    import edge_cases as ec
+    import reference_fuzz as rf
+    out = {}
+    for name, head in (("c4", 1024), ("c2", 512), ("ties", 2048)):
+        z = np.load(os.path.join(here, "golden", f"{name}.npz"))
+        out[name] = (z["state"][:head], z["prev"][:head], z["params"][:head], float(z["rho"]), float(z["g"]), float(z["dt"]))
+    out["edge"] = (ec.STATE, ec.PREV, ec.PARAMS, ec.RHO, ec.G, ec.DT)
+    out["fuzz"] = rf.population(*WARP_FUZZ)[:6]
+    return out
+
+
 def tie_census(state, params):
     """How many bodies have which exact tie (evaluated in fp64 as the oracle does: R @ k + p)."""
     q = state[:, 3:7].astype(np.float64)
