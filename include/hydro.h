@@ -55,7 +55,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_ctl, HYDRO_CTL_FIELDS - a per-body pose-hold
  *        feedback law evaluated inside every step of the multi-step kernel
  *        added to 0.7.1 (no existing entry changed): hydro_mooring_wrench, hydro_step_fused_tiled_multi_moor,
- *        HYDRO_MOOR_FIELDS - one tension-only mooring line per body, evaluated inside every step of the multi-step kernel */
+ *        HYDRO_MOOR_FIELDS - one tension-only mooring line per body, evaluated inside every step of the multi-step kernel
+ *        added to 0.7.1 (no existing entry changed): hydro_extremes_reset, hydro_step_fused_tiled_multi_ext,
+ *        HYDRO_EXT_FIELDS - running per-body extremes (position box, speed, line tension) updated inside every step */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -71,6 +73,7 @@ extern "C" {
 #define HYDRO_WRENCH_FIELDS  6
 #define HYDRO_CTL_FIELDS    17   /* the control record of hydro_step_fused_tiled_multi_ctl */
 #define HYDRO_MOOR_FIELDS    9   /* the mooring record of hydro_step_fused_tiled_multi_moor */
+#define HYDRO_EXT_FIELDS     8   /* the extremes record of hydro_step_fused_tiled_multi_ext */
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
@@ -721,6 +724,63 @@ int hydro_step_fused_tiled_multi_moor(hydro_t *h, int64_t n, const float *state,
                                       const float *applied, int64_t applied_tile_stride, int applied_frame,
                                       const float *control, int64_t control_tile_stride,
                                       const float *mooring, int64_t mooring_tile_stride, int64_t step0, void *stream);
+
+/* Extremes: what a design-load study asks of a long resident run - the peak line tension, how far the body wandered, how
+ * deep or how high it got - as a running record per body that the kernel updates in every step.  Between the first and the
+ * last step of a launch the states exist in registers only, and the line tension T is never visible at all; the record
+ * costs eight floats per body and launch to read and to write, whatever the number of steps.  Only
+ * hydro_step_fused_tiled_multi_ext and hydro_extremes_reset know it.  Bodies stay independent.
+ *
+ * THE RECORD `extremes`: HYDRO_EXT_FIELDS = 8 floats per body, tiled ([tiles][8][64] floats, tile stride
+ * extremes_tile_stride >= 512, 16-byte aligned, whole tiles, addressed like `mooring`), in this order:
+ *     x_min x_max | y_min y_max | z_min z_max | speed2_max | tension_max
+ * It is the caller's device buffer.  Unlike `applied`, `control` and `mooring` it is READ AT THE START OF A LAUNCH AND
+ * WRITTEN AT ITS END: the extremes accumulate across launches, chunks and graph replays until the caller resets them.
+ * Lanes >= n of the last tile are never written.
+ *
+ * THE SAMPLE, after every step k of the launch, is the state the step produced - the values a recorder row with
+ * fields = 19 holds for that step:
+ *     x, y, z   s[0..2] after the step
+ *     speed2    fma(v_z, v_z, fma(v_y, v_y, v_x * v_x)) of s[7..9] after the step, in fp32 (fma: rounded once)
+ *     tension   the T the mooring formed IN that step, from the state the step started from ("Mooring", above); +0 where
+ *               the line adds nothing: no line, a slack line, a T that is not > 0, or no mooring record at all
+ * THE UPDATE is an explicit compare-and-select, never fminf / fmaxf:
+ *     m = (x < m) ? x : m            M = (x > M) ? x : M
+ * so a NaN sample never enters, a NaN accumulator stays NaN, and an equal value (+0 against -0 included) leaves the
+ * accumulator's bits as they are.
+ * NOT PROVIDED: means and variances; the step at which an extreme occurred; the extremes of the launch's INITIAL state (seed
+ * the record from it with hydro_extremes_reset if it is to count); extremes of the wrench.
+ *
+ * hydro_extremes_reset: state == NULL writes [+inf, -inf, +inf, -inf, +inf, -inf, +0, +0] for bodies 0 .. n - 1; with a
+ * tiled state it writes the record of that one sample: min = max = p, speed2 of its v, tension +0.  A small kernel of its
+ * own; asynchronous on `stream`; needs no parameters.  HYDRO_E_ARG for n > capacity, a null or misaligned buffer, a stride
+ * below 832 (state) / 512 (extremes), or the two overlapping.
+ *
+ * hydro_step_fused_tiled_multi_ext: the signature and the rules of hydro_step_fused_tiled_multi_moor, with `extremes` and
+ * its stride in front of step0.
+ *   extremes == NULL : the launch and its bits are those of hydro_step_fused_tiled_multi_moor with the same arguments.
+ *   extremes != NULL : log, applied, control, the sea, the bed AND `mooring` are each optional, and each adds exactly what
+ *                      it adds in the entries without extremes; state_out, prev_out, the kinetic-energy pair and the log
+ *                      are bit for bit those of hydro_step_fused_tiled_multi_moor with the same arguments - nothing the
+ *                      record computes feeds back.
+ * The refusals are those of hydro_step_fused_tiled_multi_moor, in its order, then the extremes', behind the mooring's: a
+ * stride below 512 or a misaligned buffer, a record that overlaps an output (state_out, prev_out, log) or - since it is
+ * written - an input of the launch (state, prev, applied, control, mooring): HYDRO_E_ARG, and nothing is launched or
+ * written.  Asynchronous, no allocation, no synchronisation, safe to capture: a replay accumulates.
+ * Cost and registers: DESIGN.md section 20.  New functionality; the reference keeps no extremes. */
+int hydro_extremes_reset(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                         float *extremes, int64_t extremes_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_ext(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride,
+                                     const float *mooring, int64_t mooring_tile_stride,
+                                     float *extremes, int64_t extremes_tile_stride, int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

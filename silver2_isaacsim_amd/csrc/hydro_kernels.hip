@@ -1156,11 +1156,14 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // `bed` is the seabed policy: add(s, d, mass, f6) inside every step; it carries scene constants only and has no begin.
 // `moor` is the mooring policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step, and end(d)
 // behind the last step of a kernel that samples the kinetic energy (see MooringLine).
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed, typename Moor>
+// `ext` is the extremes policy: begin(tile, lane4) next to the record loads, after_step(s, T) behind rec.after_step with the
+// state the step produced and the tension moor.add formed in it, end(tile, lane4) in front of the final stores (see
+// ExtremesTrack; NoExtremes does nothing).
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed, typename Moor, typename Ext>
 __device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
                                                  uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed, Moor moor)
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed, Moor moor, Ext ext)
 {
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
@@ -1175,17 +1178,20 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
         app.begin(tile, lane4);
         sea.begin(lane4);
         moor.begin(tile, lane4);
+        ext.begin(tile, lane4);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
             fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea, bed, moor);
             rec.after_step(k, s, f6);
+            ext.after_step(s, moor.tension());
         }
         if constexpr (KE) {
             moor.end(d);
             hydro::kinetic_energy(s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], s[11], s[12], d[0], d[1], d[2], mass,
                                   ke_rotational != 0, ke_lin, ke_rot);
         }
+        ext.end(tile, lane4);
         store_record<HYDRO_PREV_FIELDS, NT>(k_pvo + (size_t)tile * pvo_stride, lane4, pv);
         store_record<HYDRO_STATE_FIELDS, NT>(k_so + (size_t)tile * so_stride, lane4, s);
     }
@@ -1212,6 +1218,12 @@ struct NoMooring {
     __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
     __device__ __forceinline__ void end(float (&)[3]) const {}
     __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_WRENCH_FIELDS]) const {}
+    __device__ __forceinline__ float tension() const { return 0.0f; }
+};
+struct NoExtremes {
+    __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void after_step(const float (&)[HYDRO_STATE_FIELDS], float) const {}
+    __device__ __forceinline__ void end(uint32_t, uint32_t) const {}
 };
 
 // --------------------------------------------------------------------------
@@ -1264,7 +1276,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
                                                                        double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{});
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
@@ -1278,7 +1290,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{});
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
 }
 
 // --------------------------------------------------------------------------
@@ -1343,7 +1355,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{}, NoMooring{});
+                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
 }
 
 // --------------------------------------------------------------------------
@@ -1474,7 +1486,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{}, NoMooring{});
+                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
 }
 
 // --------------------------------------------------------------------------
@@ -1606,7 +1618,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{}, NoMooring{});
+                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{}, NoMooring{}, NoExtremes{});
 }
 
 // hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
@@ -1742,7 +1754,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
                                                    OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, NoMooring{});
+                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, NoMooring{}, NoExtremes{});
 }
 
 // hydro_seabed_wrench: the bed's W per body for the tiled state `st` (zeros for a body no corner of which is below the plane).
@@ -1782,8 +1794,9 @@ __global__ void __launch_bounds__(kBlock) seabed_wrench_kernel(const float* st, 
 // It runs behind the fp64 wrench and the bed, where their registers are free again.
 // --------------------------------------------------------------------------
 // W (force at, torque about the body origin, world frame) of the line whose record is m[j * 64], j = 0 .. 8, on a body in
-// state s.  Returns whether the line pulls; W is meaningful (and complete) only then.
-__device__ __forceinline__ bool mooring_wrench(const float* m, const float (&s)[HYDRO_STATE_FIELDS], float (&W)[HYDRO_WRENCH_FIELDS])
+// state s.  Returns whether the line pulls; W is meaningful (and complete) only then, and so is `tension`, the T W was
+// formed from (the extremes record keeps its maximum; a wave that skips leaves it untouched).
+__device__ __forceinline__ bool mooring_wrench(const float* m, const float (&s)[HYDRO_STATE_FIELDS], float (&W)[HYDRO_WRENCH_FIELDS], float& tension)
 {
     const float k = m[7 * 64], c = m[8 * 64];
     const bool has_line = k > 0.0f || c > 0.0f;
@@ -1805,11 +1818,17 @@ __device__ __forceinline__ bool mooring_wrench(const float* m, const float (&s)[
     const float cu = c * un;
     const float T = __builtin_fmaxf(0.0f, __builtin_fmaf(k, x, -cu));
     const float ti = T * inv;
+    tension = T;
     W[0] = ti * ex; W[1] = ti * ey; W[2] = ti * ez;
     W[3] = __builtin_fmaf(ry, W[2], -(rz * W[1]));
     W[4] = __builtin_fmaf(rz, W[0], -(rx * W[2]));
     W[5] = __builtin_fmaf(rx, W[1], -(ry * W[0]));
     return has_line && x > 0.0f && T > 0.0f;                              // (l2 = 0: x is NaN, not taut)
+}
+__device__ __forceinline__ bool mooring_wrench(const float* m, const float (&s)[HYDRO_STATE_FIELDS], float (&W)[HYDRO_WRENCH_FIELDS])
+{
+    float tension;
+    return mooring_wrench(m, s, W, tension);
 }
 
 constexpr uint32_t kMoorSlots = HYDRO_MOOR_FIELDS;
@@ -1838,6 +1857,7 @@ struct MooringLine : LaneSlots<kMoorSlots> {
             for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
         }
     }
+    __device__ __forceinline__ float tension() const { return 0.0f; }        // (nobody asks: the mooring kernels track no extremes)
 };
 
 // The bed of the mooring kernel: optional (`present` - a kernel argument: wave-uniform); an absent bed runs no broad phase
@@ -1871,7 +1891,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
                                                    OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
                                                    OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   MooringLine{{0u, 0u}, mooring, mooring_stride});
+                                                   MooringLine{{0u, 0u}, mooring, mooring_stride}, NoExtremes{});
 }
 
 // hydro_mooring_wrench: the line's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds nothing).
@@ -1889,6 +1909,130 @@ __global__ void __launch_bounds__(kBlock) mooring_wrench_kernel(const float* st,
         for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) W[f] = 0.0f;
     }
     store_record<HYDRO_WRENCH_FIELDS, false>(out + (size_t)tile * out_stride, lane4, W);
+}
+
+// --------------------------------------------------------------------------
+// EXTREMES in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_ext): what a design-load study asks of a long
+// resident run - how far, how deep, how fast, how hard did the line pull - without a trajectory.  Per body a tiled 8-field
+// record ([tiles][8][64], addressed like the mooring record):
+//   x_min x_max | y_min y_max | z_min z_max | speed2_max | tension_max
+// include/hydro.h states the sample and the update ("Extremes").  Unlike every other record it is READ at the start of a
+// launch and WRITTEN at its end: the extremes accumulate across launches until hydro_extremes_reset.
+//   the sample  : after every step, the state the step produced (a recorder row's values) and the tension T that
+//                 mooring_wrench formed in that step - handed over by TrackedMooringLine, +0 where the line adds nothing
+//   the update  : extreme_min / extreme_max, an explicit compare-and-select (v_cmp + v_cndmask), never fminf / fmaxf: a NaN
+//                 sample never enters, a NaN accumulator stays, an equal value (+-0 included) leaves the accumulator's bits
+//   the record  : the mooring kernels stand at 161-165 VGPRs of 168, so the eight accumulators are not carried through the
+//                 loop: each lane parks them in LDS, [wave][8][64] floats (8 KB per block; LaneSlots), and reads, updates
+//                 and writes them behind the integrator, where the fp64 wrench's registers are free
+// Nothing the policy computes feeds back: state, prev_out, energy and log are the mooring kernel's bits.
+// --------------------------------------------------------------------------
+__device__ __forceinline__ float extreme_min(float m, float x) { return (x < m) ? x : m; }
+__device__ __forceinline__ float extreme_max(float M, float x) { return (x > M) ? x : M; }
+
+// The line that remembers the tension of its last add: T if the line pulled, +0 if it added nothing.
+struct TrackedMooringLine : MooringLine {
+    mutable float last;
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        float W[HYDRO_WRENCH_FIELDS], T = 0.0f;
+        const bool pulls = mooring_wrench(parked(), s, W, T);
+        if (pulls) {
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+        }
+        last = pulls ? T : 0.0f;
+    }
+    __device__ __forceinline__ float tension() const { return last; }
+};
+// The lines of the extremes kernel: optional (`rec` - a kernel argument: wave-uniform); an absent record parks nothing,
+// evaluates nothing and reports a tension of +0.
+struct OptionalMooringLine : TrackedMooringLine {
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        if (rec) MooringLine::begin(tile, lane4_);
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        if (rec) TrackedMooringLine::add(s, f6);
+        else last = 0.0f;
+    }
+};
+
+constexpr uint32_t kExtSlots = HYDRO_EXT_FIELDS;
+struct ExtremesTrack : LaneSlots<kExtSlots> {
+    float* rec; uint32_t stride;
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        float* mine = claim(lane4_);
+        const float* r = rec + (size_t)tile * stride;
+#pragma unroll
+        for (int f = 0; f < HYDRO_EXT_FIELDS; ++f) mine[f * 64] = ldg<false>(at<float>(r, lane4, f * 256u));
+    }
+    __device__ __forceinline__ void after_step(const float (&s)[HYDRO_STATE_FIELDS], float T) const
+    {
+        float* e = parked();
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            e[(2 * a) * 64] = extreme_min(e[(2 * a) * 64], s[a]);
+            e[(2 * a + 1) * 64] = extreme_max(e[(2 * a + 1) * 64], s[a]);
+        }
+        const float speed2 = __builtin_fmaf(s[9], s[9], __builtin_fmaf(s[8], s[8], s[7] * s[7]));
+        e[6 * 64] = extreme_max(e[6 * 64], speed2);
+        e[7 * 64] = extreme_max(e[7 * 64], T);
+    }
+    // Only live lanes come here (fused_multi_body): the padding lanes of the last tile are never written.
+    __device__ __forceinline__ void end(uint32_t tile, uint32_t lane4_) const
+    {
+        const float* e = parked();
+        float v[HYDRO_EXT_FIELDS];
+#pragma unroll
+        for (int f = 0; f < HYDRO_EXT_FIELDS; ++f) v[f] = e[f * 64];
+        store_record<HYDRO_EXT_FIELDS, false>(rec + (size_t)tile * stride, lane4_, v);
+    }
+};
+
+// The mooring kernel's arguments, then the extremes record's.  `mooring` may be null.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_ext_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
+                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
+                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
+                                                                           const float* mooring, uint32_t mooring_stride,
+                                                                           float* extremes, uint32_t extremes_stride)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
+                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
+                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
+                                                   ExtremesTrack{{0u, 0u}, extremes, extremes_stride});
+}
+
+// hydro_extremes_reset: the empty record, or (st != nullptr) the record of the one sample `st`.
+__global__ void __launch_bounds__(kBlock) extremes_reset_kernel(const float* st, uint32_t st_stride, float* ext, uint32_t ext_stride, uint32_t n)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float inf = __builtin_inff();
+    float v[HYDRO_EXT_FIELDS] = {inf, -inf, inf, -inf, inf, -inf, 0.0f, 0.0f};
+    if (st) {                                                            // (a kernel argument: wave-uniform)
+        const float* r = st + (size_t)tile * st_stride;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) v[2 * a] = v[2 * a + 1] = *at<float>(r, lane4, a * 256u);
+        const float vx = *at<float>(r, lane4, 7 * 256u), vy = *at<float>(r, lane4, 8 * 256u), vz = *at<float>(r, lane4, 9 * 256u);
+        v[6] = __builtin_fmaf(vz, vz, __builtin_fmaf(vy, vy, vx * vx));
+    }
+    store_record<HYDRO_EXT_FIELDS, false>(ext + (size_t)tile * ext_stride, lane4, v);
 }
 
 }  // namespace
@@ -2748,6 +2892,7 @@ struct MultiStep {
     bool sea_entry = false; int64_t step0 = 0;           // the _sea entry: step0 is checked, and the steps go through the sea if one is set
     bool bed_entry = false;                              // the _bed entry: the _sea entry, and the steps meet the seabed if one is set
     const float* mooring = nullptr; int64_t mooring_tile_stride = 0;      // the _moor entry: the _bed entry, and a line per body if a record is given
+    float* extremes = nullptr; int64_t extremes_tile_stride = 0;          // the _ext entry: the _moor entry, and the running extremes if a record is given
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -2792,8 +2937,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
     return HYDRO_OK;
 }
 
-// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the mooring kernel takes
-// everything, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the extremes kernel takes
+// everything, the mooring kernel everything but the extremes, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
 // kernel the recorder - and a launch is handed the options it goes without as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
@@ -2827,6 +2972,19 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         if ((rc = check_tiled(h, m.n, m.mooring, m.mooring_tile_stride, HYDRO_MOOR_FIELDS, "null mooring"))) return rc;
         if ((rc = check_no_overlap(h, m, log_floats, "mooring", m.mooring, m.mooring_tile_stride))) return rc;
     }
+    if (m.extremes) {
+        if ((rc = check_tiled(h, m.n, m.extremes, m.extremes_tile_stride, HYDRO_EXT_FIELDS, "null extremes"))) return rc;
+        if ((rc = check_no_overlap(h, m, log_floats, "extremes", m.extremes, m.extremes_tile_stride))) return rc;
+        // it is written: it must stay out of what the launch reads as well
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiled_extent(tiles, m.extremes_tile_stride, HYDRO_EXT_FIELDS);
+        const auto reads = [&](const float* p, int64_t stride, int fields) {
+            return p && ranges_overlap(m.extremes, floats, p, tiled_extent(tiles, stride, fields));
+        };
+        if (reads(m.state, m.state_tile_stride, HYDRO_STATE_FIELDS) || reads(m.prev, m.prev_tile_stride, HYDRO_PREV_FIELDS)
+            || reads(m.applied, m.applied_tile_stride, HYDRO_WRENCH_FIELDS) || reads(m.control, m.control_tile_stride, HYDRO_CTL_FIELDS)
+            || reads(m.mooring, m.mooring_tile_stride, HYDRO_MOOR_FIELDS))
+            return fail(h, HYDRO_E_ARG, "extremes must not overlap an input (state, prev, applied, control, mooring)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -2850,7 +3008,11 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (m.mooring) pushed(step_fused_multi_moor_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+        if (m.extremes) pushed(step_fused_multi_ext_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
+                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
+                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, (uint32_t)m.extremes_tile_stride);
+        else if (m.mooring) pushed(step_fused_multi_moor_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
                         sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
                         h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
                         m.mooring, (uint32_t)m.mooring_tile_stride);
@@ -3154,6 +3316,50 @@ int hydro_step_fused_tiled_multi_moor(hydro_t* h, int64_t n, const float* state,
     m.sea_entry = true; m.step0 = step0;
     m.bed_entry = true;
     m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_extremes_reset(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                         float* extremes, int64_t extremes_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    int rc;
+    if (n < 0 || n > h->capacity) return fail(h, HYDRO_E_ARG, "n out of range (0 .. capacity)");
+    if (state && (rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
+    if ((rc = check_tiled(h, n, extremes, extremes_tile_stride, HYDRO_EXT_FIELDS, "null extremes"))) return rc;
+    const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE;
+    if (state && ranges_overlap(state, tiled_extent(tiles, state_tile_stride, HYDRO_STATE_FIELDS), extremes, tiled_extent(tiles, extremes_tile_stride, HYDRO_EXT_FIELDS)))
+        return fail(h, HYDRO_E_ARG, "extremes must not overlap state");
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (n == 0) return HYDRO_OK;
+    hipLaunchKernelGGL(extremes_reset_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       state, state ? (uint32_t)state_tile_stride : 0u, extremes, (uint32_t)extremes_tile_stride, (uint32_t)n);
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+int hydro_step_fused_tiled_multi_ext(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride,
+                                     const float* mooring, int64_t mooring_tile_stride,
+                                     float* extremes, int64_t extremes_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    m.bed_entry = true;
+    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
+    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
     return step_fused_tiled_multi_launch(h, m);
 }
 

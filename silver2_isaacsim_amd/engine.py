@@ -584,6 +584,37 @@ class HydroEngine:
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream, extra)
 
+    # ------------------------------------------------------------------ extremes
+    def extremes_reset(self, extremes: torch.Tensor, n: int, state: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """Empty the tiled (tiles, 8, 64) extremes record of bodies 0 .. n - 1 (hydro_extremes_reset; the record:
+        include/hydro.h, "Extremes"): [+inf, -inf] for the three position pairs, +0 for speed2_max and tension_max - or,
+        with a tiled `state`, the record of that one sample, so that a run's initial state counts."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n) if state is not None else (None, 0)
+        e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n)
+        self._check(self._lib.hydro_extremes_reset(self._h, n, s_ptr, s_stride, e_ptr, e_stride, self._stream(stream)))
+        return extremes
+
+    def step_fused_tiled_multi_ext(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                   extremes: torch.Tensor | None, mooring: torch.Tensor | None = None,
+                                   control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                   log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_moor that also keeps each body's running extremes (hydro_step_fused_tiled_multi_ext):
+        `extremes` is the tiled (tiles, 8, 64) record of `extremes_reset`, read at the start of the launch and written at
+        its end, so it accumulates over launches.  After every step the position the step produced, its squared speed and
+        the line tension formed in the step enter by compare-and-select.  Nothing feeds back: states, energy and log are
+        those of step_fused_tiled_multi_moor.  mooring, control, applied, log, the sea and the bed are each optional;
+        extremes=None is step_fused_tiled_multi_moor.  Returns the number of rows written (0 without a log)."""
+        def extra():
+            tail = self._applied_control(applied, frame, control, n)
+            m_ptr, m_stride = self._tiled(mooring, nat.MOOR_FIELDS, n) if mooring is not None else (None, 0)
+            e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
+            return (*tail, m_ptr, m_stride, e_ptr, e_stride, int(step0))
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_ext,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

@@ -26,6 +26,7 @@ from . import _native as nat
 from . import distributed as hd
 from . import scenes
 from .engine import HydroEngine
+from .extremes import Extremes
 from .mooring import Mooring
 
 
@@ -335,6 +336,8 @@ class ClosedLoopSim:
     seabed = None               # set_seabed(): the seabed.Seabed under the bodies (a class default: a sim has none until one is set)
     mooring = None              # set_mooring(): the tiled (tiles, 9, 64) record of the bodies' mooring lines while lines are set
     _mooring_buf = None         # the buffer itself (made once)
+    extremes = None             # track_extremes(): the extremes.Extremes view over the bodies' running extremes while they are tracked
+    _extremes_view = None       # the view and its buffer (made once)
 
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
@@ -605,8 +608,35 @@ class ClosedLoopSim:
             self.mooring = None
             self._graph = None
 
+    def track_extremes(self, from_state: bool = True) -> Extremes:
+        """Keep each body's running extremes: from now on every physics step of run_eager, run (graph replays included) and
+        run_resident updates, INSIDE the stepping kernel, the box the body stayed in, its largest squared speed and the
+        largest tension of its mooring line (hydro_step_fused_tiled_multi_ext; the record: include/hydro.h, "Extremes") -
+        eight floats per body, read and written once per launch whatever the chunk.  Nothing feeds back: the states are
+        bit for bit those of a run that tracks nothing.  It rides with a sea, a seabed, lines, an applied wrench, a pose
+        hold and a recorder where those are set.
+        from_state=True seeds the record from the current state (it counts as the first sample), False starts from the
+        empty record.  Calling it again resets the record.  Returns `sim.extremes`, an `extremes.Extremes` view; the
+        address of its buffer never changes, and `view.reset()` starts over without leaving the entry."""
+        if not self.fused:
+            raise ValueError("extremes are tracked in the fused step kernels (fused=True)")
+        if self._extremes_view is None:
+            self._extremes_view = Extremes(self, self.engine.alloc_tiled(nat.EXT_FIELDS, self.n))
+        self._extremes_view.reset(from_state)
+        if self.extremes is None:
+            self._graph = None                                              # captured steps are of another entry
+        self.extremes = self._extremes_view
+        return self.extremes
+
+    def clear_extremes(self) -> None:
+        """Stop tracking: every call the sim makes is again the one it made before track_extremes.  The record keeps its
+        contents (the view returned by track_extremes still reads them)."""
+        if self.extremes is not None:
+            self.extremes = None
+            self._graph = None
+
     # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
-    # the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
+    # the extremes if they are tracked, else with the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
     # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
     # graph captures: the single-step form of the entries, the bits of the single-step entry, include/hydro.h).  The plain
     # step has two forms: single_step=True is one hydro_step_fused_tiled (or the two-kernel path, fused=False), else one
@@ -619,7 +649,10 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.mooring is not None:
+        if self.extremes is not None:
+            rows = e.step_fused_tiled_multi_ext(*args, k, self.steps_done, self.extremes.buffer, self.mooring, self.control, self.applied,
+                                                self.applied_frame, **kw)
+        elif self.mooring is not None:
             rows = e.step_fused_tiled_multi_moor(*args, k, self.steps_done, self.mooring, self.control, self.applied, self.applied_frame, **kw)
         elif self.seabed is not None:
             rows = e.step_fused_tiled_multi_bed(*args, k, self.steps_done, self.control, self.applied, self.applied_frame, **kw)
