@@ -28,6 +28,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <type_traits>
@@ -2034,6 +2035,19 @@ __global__ void __launch_bounds__(kBlock) extremes_reset_kernel(const float* st,
     }
     store_record<HYDRO_EXT_FIELDS, false>(ext + (size_t)tile * ext_stride, lane4, v);
 }
+
+// LaneSlots<SLOTS>::slots() is ONE __shared__ array per value of SLOTS: two policies of the same count that meet in one kernel
+// (pose hold, sea view, mooring line and extremes all do, in step_fused_multi_ext_tiled_kernel) would park their values on top
+// of each other without a message.  A new policy takes a count of its own (or LaneSlots grows a tag type).
+constexpr bool lane_slot_counts_distinct(std::initializer_list<uint32_t> counts)
+{
+    for (auto a = counts.begin(); a != counts.end(); ++a)
+        for (auto b = a + 1; b != counts.end(); ++b)
+            if (*a == *b) return false;
+    return true;
+}
+static_assert(lane_slot_counts_distinct({kCtlSlots, kSeaSlots, kMoorSlots, kExtSlots}),
+              "two LaneSlots policies of one kernel share a slot count, hence one LDS array");
 
 }  // namespace
 

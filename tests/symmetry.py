@@ -1,0 +1,116 @@
+"""The three maps under which the model is EXACTLY symmetric, and the predicate the symmetry tests share
+(tests/test_symmetry.py, tests/test_symmetry_gpu.py; DESIGN.md, "Sign symmetry").
+
+The water surface, gravity and the bed are horizontal, so a mirror in the plane y = 0, a mirror in x = 0 and their product,
+a half turn about z, map a scene onto an equally valid one.  Each of them only changes signs of inputs, and IEEE arithmetic
+is exactly odd - fl(-a) = -fl(a), fma(-a, b, -c) = -fma(a, b, c) - so an evaluation in which every term of every sum has the
+same parity returns the same bits with the predicted signs.  The table, stated once:
+
+    map         polar vector    axial vector    quaternion (x, y, z, w)
+    mirror_y    (+, -, +)       (-, +, -)       (-, +, -, +)
+    mirror_x    (-, +, +)       (+, -, -)       (+, -, -, +)
+    half_turn   (-, -, +)       (-, -, +)       (-, -, +, +)
+
+polar: positions, linear velocities, forces, anchors, fairleads, the current, the wave vector, centres; axial: angular
+velocities and torques; a mirrored body's frame is the mirrored frame, so body-frame records transform like world-frame
+ones.  Scalars (dimensions, coefficients, mass, gains, limits, lengths, the bed's constants, amplitudes, frequencies,
+phases, eta, the submersion ratio, energies, tensions) do not change.  An extremes record swaps min and max of a flipped
+axis: min' = -max, max' = -min.
+
+One function per record kind; each returns the IMAGE of a record (the maps are involutions: the image of the image is the
+record).  `equal` is the predicate: float equality with NaN == NaN, so -0 == +0 (a dry body returns +0 and the image of +0
+is -0) - no tolerance.
+"""
+import numpy as np
+
+MAPS = ("mirror_y", "mirror_x", "half_turn")
+POLAR = {"mirror_y": (1, -1, 1), "mirror_x": (-1, 1, 1), "half_turn": (-1, -1, 1)}
+AXIAL = {"mirror_y": (-1, 1, -1), "mirror_x": (1, -1, -1), "half_turn": (-1, -1, 1)}
+QUAT = {"mirror_y": (-1, 1, -1, 1), "mirror_x": (1, -1, -1, 1), "half_turn": (-1, -1, 1, 1)}
+SAME3 = (1, 1, 1)
+# the bed's corner i has the signs of (i & 1, i & 2, i & 4) along the body's x, y, z: the image of corner i is corner i ^ this
+CORNER_XOR = {"mirror_y": 2, "mirror_x": 1, "half_turn": 3}
+# the components of hydro_step_components, in the reference's order: buoyancy F, drag F, lift F, drag T, added-mass F,
+# added-mass T, centre of buoyancy, centre of pressure
+COMPONENT_KINDS = (POLAR, POLAR, POLAR, AXIAL, POLAR, AXIAL, POLAR, POLAR)
+
+
+def _times(x, signs):
+    x = np.asarray(x)
+    return x * np.asarray(signs, dtype=x.dtype)
+
+
+def state(g, s):
+    """(n, 13) [p | q xyzw | v | omega]."""
+    return _times(s, POLAR[g] + QUAT[g] + POLAR[g] + AXIAL[g])
+
+
+def prev(g, pv):
+    """(n, 6) previous velocity [v | omega]."""
+    return _times(pv, POLAR[g] + AXIAL[g])
+
+
+def wrench(g, w):
+    """(n, 6) [F | T], world frame."""
+    return _times(w, POLAR[g] + AXIAL[g])
+
+
+def applied(g, a):
+    """(n, 6) applied [F | T], in either frame: the mirrored body's frame is the mirrored frame."""
+    return wrench(g, a)
+
+
+def control(g, c):
+    """(n, 17) pose-hold record [p* | q* | kp_lin(3) | kd_lin(3) | kp_ang | kd_ang | f_max | t_max]."""
+    return _times(c, POLAR[g] + QUAT[g] + (1,) * 10)
+
+
+def mooring(g, m):
+    """(n, 9) line record [anchor (world) | fairlead (body) | L0 | k | c]."""
+    return _times(m, POLAR[g] + POLAR[g] + SAME3)
+
+
+def extremes(g, e):
+    """(n, 8) [x_min x_max | y_min y_max | z_min z_max | speed2_max | tension_max]: a flipped axis swaps its pair."""
+    e = np.asarray(e)
+    out = e.copy()
+    for a, sign in enumerate(POLAR[g]):
+        if sign < 0:
+            out[:, 2 * a], out[:, 2 * a + 1] = -e[:, 2 * a + 1], -e[:, 2 * a]
+    return out
+
+
+def sea(g, s):
+    """A sea.SeaState: the current and the wave vector (kx, ky) are polar - never a heading angle."""
+    sx, sy, sz = POLAR[g]
+    out = type(s)((sx * s.current[0], sy * s.current[1], sz * s.current[2]))
+    for a, kx, ky, om, ph in s.waves:
+        out.add_wave(a, sx * kx, sy * ky, om, ph)
+    return out
+
+
+def sea_sample(g, w):
+    """(n, 4) [eta | u] of hydro_sea_sample."""
+    return _times(w, (1,) + POLAR[g])
+
+
+def components(g, c):
+    """(n, 8, 3) in the order of COMPONENT_KINDS."""
+    return _times(c, np.array([kind[g] for kind in COMPONENT_KINDS]))
+
+
+def log_row(g, row):
+    """(..., n, 19) recorded rows: the state, then the wrench that produced it."""
+    return _times(row, POLAR[g] + QUAT[g] + POLAR[g] + AXIAL[g] + POLAR[g] + AXIAL[g])
+
+
+def equal(a, b):
+    """Equal under g: the image computed equals the image predicted, by float equality (a NaN equals a NaN)."""
+    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
+
+
+def differing(a, b):
+    """(n,) bool: the bodies (leading axis) on which `equal` fails."""
+    a, b = np.asarray(a), np.asarray(b)
+    same = (a == b) | (np.isnan(a) & np.isnan(b))
+    return ~same.reshape(len(a), -1).all(axis=1)

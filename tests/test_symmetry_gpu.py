@@ -1,0 +1,560 @@
+"""Exact sign symmetry of every device entry under mirror_y, mirror_x and the half turn about z (tests/symmetry.py states the
+maps and the predicate; DESIGN.md, "Sign symmetry"; the CPU half is tests/test_symmetry.py).
+
+Each test runs an entry on a population and on its image and demands that the image's outputs are the images of the outputs,
+by float equality - state, prev_out, wrench, components, ratio, every recorded row, the extremes record (min and max of a
+flipped axis swapped) - and that scalars (energy pair, eta, tension) keep their bits.  No tolerance: the maps change signs
+only, and a kernel in which every term of every sum has the same parity cannot tell a scene from its image.  The references
+of the other GPU tests were written from the same reading of the model as the kernels; this one was written by neither.
+
+THE ONE EXCEPTION is the bed: seabed_wrench accumulates the corners i = 0 .. 7 in index order and the maps permute them
+(mirror_y i <-> i ^ 2, mirror_x i <-> i ^ 1, half turn i <-> i ^ 3), so with two or more contributing corners the fp32 sums
+run in another order - a sum of more than two terms whose order the map permutes, not a term of the wrong hand.  A body is
+ORDER-SENSITIVE from the first step whose input state has two or more contributing corners by seabed_reference (decided in
+fp64 or as the kernel decides, whichever counts more; on the recorded states of either run - the reference decides, not the
+kernel under test).  Before that step its rows are compared exactly; from it on they are left out and must be finite; the
+probe's wrench of such a body is held to 2 x PROBE_BOUND of tests/test_seabed_gpu.py in that test's metric and its one-step
+result to 2 x integrator_oracle.STEP_ULP_BOUND in the metric of tests/test_integrator_gpu.py (each run is within one bound
+of fp64, and fp64 is symmetric to 1e-12: tests/test_symmetry.py).
+
+THE RESIDENT POPULATIONS.  `designed` is the mooring tests' population (the bed population with line_population's unmoored,
+all-taut and mixed tiles).  A quarter of it and more stands on four to eight corners by design (test_population_meets_the_bed),
+so more than 25 % of it is order-sensitive from the first step; `reseated` is the same population with most of those bodies
+moved, in z only, onto ONE corner and the lines drawn anew for the moved bodies: on it the share left out after 7 steps is
+asserted to be at most 25 %.  Both are run; the tests print, per entry, the bodies compared exactly and the bodies left out.
+EXPLICIT DRAG.  The population's |k| dt / m reaches 50, far beyond the explicit form's stability: in the fp64 closed loop 249
+of the 321 bodies have left the fp32 range after seven explicit steps (tests/test_step_variants_gpu.py: "seven explicit steps
+may carry a light body out of range"), and a body on its way out counts eight corners far below the plane.  With explicit drag
+the comparisons are the same (a NaN equals a NaN), but "finite" and the 25 % share are asserted under implicit drag only; the
+explicit share is printed.
+
+Sizes: n = 200 (one block: three full tiles and 8 lanes) and n = 321 (two blocks, the last wave with one live lane); the
+wrench entries: 81, 4 096 and 4 097 bodies.  One engine per population, size and coefficient format, switched with
+set_semantics / set_sea / set_seabed / set_tuning / set_watch.
+
+ON AN MI355X (f32 and f16 coefficients, both semantics, explicit and implicit drag alike unless said):
+  wrench entries        edge_cases 81 (72 wet), ties 4 096 (2 923 wet), config 4 4 097 (3 060 wet) bodies x 3 maps x 8 entries
+                        (ext, tiled, tiled + ke, aos wxyz, aos xyzw, batch, components, components_aos): 0 bodies differ; the
+                        energy pair keeps its bits
+  integrator, fused     321 bodies x 3 maps x 6 entries (4 with implicit drag): 0 differ; the wrong hand is told apart
+  probes                hydro_sea_sample at steps 0 and 10^6 and hydro_mooring_wrench: 0 differ
+  hydro_seabed_wrench   1 356 bodies x maps with at most one corner: 0 differ; 207 with two or more: largest difference 1.82
+                        units of 2^-24 of the scale (bound 2 x 4)
+  resident policies     rec, app (world, body), ctl, ctl + app, sea, all-far: every body exact at 1 and 7 steps, n = 200 and 321.
+                        bed, moor, ext, all on `reseated`: 175 / 277 exact and 25 / 44 left out (12 % / 14 %) after one step,
+                        the one step of those left out within 7.67 ulps of its image (bound 2 x 24); after 7 implicit steps
+                        32 .. 43 of 200 (16 .. 22 %) and 59 .. 72 of 321 (18 .. 22 %) left out, after 7 explicit steps 36 .. 39 %;
+                        on `designed` 57 .. 60 % are left out from the first step.  Not one body the reference calls
+                        order-insensitive differs in any row.
+  everything on         with non_temporal = 1 and under Warp semantics: as above (69 .. 72 of 321 left out after 7 implicit steps)
+  ClosedLoopSim         64 moored buoys and their mirror_y image, 20 steps in chunks of 7: 0 bodies differ
+So every device entry is exactly sign-symmetric under all three maps, but for the bed's corner sum - an order asymmetry, not
+a term of the wrong hand: no body with fewer than two contributing corners ever differs."""
+import numpy as np
+import pytest
+import torch
+
+import populations
+import sea_reference as sr
+import seabed_reference as br
+import symmetry as sym
+from conftest import load_golden
+from oracle import hydro_oracle as ho
+from oracle import integrator_oracle as io
+from silver2_isaacsim_amd import scenes
+from silver2_isaacsim_amd.engine import HydroEngine
+from silver2_isaacsim_amd.mooring import Mooring
+from silver2_isaacsim_amd.sea import SeaState
+from silver2_isaacsim_amd.simulate import ClosedLoopSim
+from test_applied_wrench_gpu import COEFFS, DEV, DRAG, DT, G, NAN, RHO, _buffers, _ke, _tiled
+from test_mooring import DEPTH, line_population
+from test_mooring_gpu import _buoys, _from
+from test_mooring_gpu import bed_pop, hold_pop, pop               # noqa: F401  (fixtures: the designed population and its lines)
+from test_seabed_gpu import BED, FAR, PROBE_BOUND, SEA
+from test_symmetry import contributing_corners, tilted_boxes
+
+pytestmark = pytest.mark.gpu
+SIZES = (200, 321)
+STEPS = (1, 7)
+SEMANTICS = ("numba", "warp")
+STEP0 = 11
+TWO_WAVES = SeaState((0.5, -0.2, 0.05)).add_wave(*SEA.waves[0]).add_wave(*SEA.waves[1])
+
+
+@pytest.fixture(scope="module")
+def engines(native_built):
+    """engines(key, params, coeff, rho, g, copy=0): the module's engine for that population and coefficient format, back at
+    its defaults (`copy`: a second engine over the same bodies, for the batched launch)."""
+    made = {}
+
+    def get(key, params, coeff, rho=RHO, g=G, copy=0):
+        k = (key, len(params), coeff, copy)
+        if k not in made:
+            made[k] = HydroEngine(len(params), DEV, rho, g)
+            made[k].set_params(params, coeff)
+        eng = made[k]
+        eng.set_tuning()
+        eng.set_semantics("numba")
+        eng.set_sea(None)
+        eng.set_seabed(None)
+        eng.set_watch(None)
+        return eng
+    yield get
+    for eng in made.values():
+        eng.close()
+
+
+def _soa(x):
+    return torch.from_numpy(scenes.to_soa(np.ascontiguousarray(x, np.float32))).to(DEV)
+
+
+def _rows(x):
+    return torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(DEV)
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+# ---- (a) the wrench entries ----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def wrench_pops():
+    """name -> (state, prev, params, rho, g, dt): every body of edge_cases (81) and ties (4 096), and config 4 drawn to 4 097
+    bodies (65 tiles: more than one block, the last wave with one live lane)."""
+    out = {}
+    for name in ("edge_cases", "ties"):
+        fx = load_golden(name)
+        out[name] = tuple(np.ascontiguousarray(fx[k], np.float32) for k in ("state", "prev", "params")) + (float(fx["rho"]), float(fx["g"]), float(fx["dt"]))
+    sc = scenes.scene_c4(n=4097, seed=4)
+    out["c4"] = (sc.state, sc.prev, sc.params, sc.rho, sc.g, sc.dt)
+    return out
+
+
+def _wrench_entries(eng, other, st, pv, dt):
+    """Every wrench entry on (st, pv): name -> (n, 6) wrench, (n, 8, 3) components, (n,) ratio or the energy pair.  `other`:
+    a second engine over the same bodies, which takes the second scene of the batched launch - given (st, pv) as well, so
+    that the launch holds the scene twice; the caller builds the launch of a scene and its image itself."""
+    n = len(st)
+    out = {}
+    out["ext"] = _np(eng.step_wrench(_soa(st), dt, prev=_soa(pv))).T
+    S, P = _tiled(st), _tiled(pv)
+    out["tiled"] = _from(eng.step_wrench_tiled(S, n, dt, prev=P), n)
+    ke = _ke()
+    out["tiled_ke"] = _from(eng.step_wrench_tiled(S, n, dt, prev=P, ke_out=ke), n)
+    out["ke"] = _np(ke)
+    pos, vel = _rows(st[:, 0:3]), _rows(st[:, 7:13])
+    for name, quat, xyzw in (("aos_wxyz", st[:, [6, 3, 4, 5]], False), ("aos_xyzw", st[:, 3:7], True)):
+        eng.set_prev_velocity(_soa(pv))
+        f, t = eng.step_wrench_aos(pos, _rows(quat), vel, dt, quat_xyzw=xyzw)
+        out[name] = np.concatenate([_np(f), _np(t)], axis=1)
+    with np.errstate(all="ignore"):
+        accel = ((st[:, 7:13].astype(np.float64) - pv.astype(np.float64)) / dt).astype(np.float32)
+    comps, ratio = eng.step_components(_soa(st), _soa(accel))
+    out["components"], out["ratio"] = _np(comps).T.reshape(n, 8, 3), _np(ratio)
+    aos = torch.full((8, n, 3), NAN, dtype=torch.float32, device=DEV)
+    r2 = torch.full((n,), NAN, dtype=torch.float32, device=DEV)
+    eng.step_components_aos(pos, _rows(st[:, 3:7]), _rows(st[:, 7:10]), _rows(st[:, 10:13]), _rows(accel[:, 0:3]), _rows(accel[:, 3:6]), aos, r2)
+    out["components_aos"], out["ratio_aos"] = _np(aos).transpose(1, 0, 2), _np(r2)
+    torch.cuda.synchronize()
+    return out, accel
+
+
+WRENCHES = ("ext", "tiled", "tiled_ke", "aos_wxyz", "aos_xyzw")
+
+
+@COEFFS
+@pytest.mark.parametrize("semantics", SEMANTICS)
+def test_wrench_entries_are_exactly_symmetric(coeff, semantics, wrench_pops, engines):
+    """hydro_step_wrench_ext, _tiled (with and without ke_out: the energy pair keeps its bits), _aos in both quaternion orders,
+    _tiled_batch with a scene and its image in ONE launch, hydro_step_components and _components_aos: 0 bodies differ."""
+    for name, (st, pv, pr, rho, g, dt) in wrench_pops.items():
+        n = len(st)
+        eng, other = engines(name, pr, coeff, rho, g), engines(name, pr, coeff, rho, g, copy=1)
+        eng.set_semantics(semantics)
+        other.set_semantics(semantics)
+        want, _ = _wrench_entries(eng, other, st, pv, dt)
+        wet = want["ratio"] > 0
+        assert name == "edge_cases" or (wet.mean() > 0.5 and np.isfinite(want["ext"]).all())
+        for m in sym.MAPS:
+            st_g, pv_g = sym.state(m, st), sym.prev(m, pv)
+            got, _ = _wrench_entries(eng, other, st_g, pv_g, dt)
+            for w in WRENCHES:
+                bad = sym.differing(got[w], sym.wrench(m, want[w]))
+                assert not bad.any(), (name, m, w, int(bad.sum()), np.nonzero(bad)[0][:8])
+            assert sym.equal(got["ke"], want["ke"]), (name, m, got["ke"], want["ke"])
+            for c, r in (("components", "ratio"), ("components_aos", "ratio_aos")):
+                bad = sym.differing(got[c], sym.components(m, want[c])) | sym.differing(got[r], want[r])
+                assert not bad.any(), (name, m, c, int(bad.sum()), np.nonzero(bad)[0][:8])
+            # the batched launch: the scene and its image side by side
+            both = HydroEngine.step_wrench_tiled_batch([eng, other], [_tiled(st), _tiled(st_g)], dt, prevs=[_tiled(pv), _tiled(pv_g)], ns=[n, n])
+            torch.cuda.synchronize()
+            a, b = _from(both[0], n), _from(both[1], n)
+            assert sym.equal(a, want["tiled"]) and not sym.differing(b, sym.wrench(m, a)).any(), (name, m, "batch")
+        print(f"[wrench entries {coeff} {semantics}] {name}: {n} bodies ({int(wet.sum())} wet) x 3 maps x 8 entries: 0 differ")
+
+
+# ---- (b) the integrator and the plain fused steps ---------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def int_pop():
+    st, pv, pr = populations.integrator_population(n=321, seed=31)
+    p16 = pr.copy()
+    p16[:, 3:10] = pr[:, 3:10].astype(np.float16).astype(np.float32)
+    return st, pv, {"f32": pr, "f16": p16}
+
+
+def _plain(eng, st, pv, w6, n, implicit):
+    """name -> outputs of hydro_integrate, hydro_integrate_tiled (explicit only: they take a wrench), hydro_step_fused_tiled
+    without and with ke_out, and hydro_step_fused_tiled_multi at 1 and 7 steps."""
+    out = {}
+    if not implicit:
+        out["integrate"] = (_np(eng.integrate(_soa(st), _soa(w6), DT)).T,)
+        out["integrate_tiled"] = (_from(eng.integrate_tiled(_tiled(st), _tiled(w6), n, DT), n),)
+    for with_ke in (False, True):
+        cur, old = _buffers(st, pv, n)
+        ke, wr = (_ke() if with_ke else None), eng.alloc_tiled(6, n)
+        new = eng.step_fused_tiled(cur, old, n, DT, wrench=wr, implicit_drag=implicit, ke_out=ke)
+        out["fused" + ("_ke" if with_ke else "")] = (_from(new, n), _from(wr, n)) + ((_np(ke),) if with_ke else ())
+    for steps in STEPS:
+        cur, old = _buffers(st, pv, n)
+        ke = _ke()
+        new = eng.step_fused_tiled_multi(cur, old, n, DT, steps, implicit_drag=implicit, ke_out=ke)
+        out[f"multi{steps}"] = (_from(new, n), _from(cur, n)[:, 7:13], _np(ke))
+    torch.cuda.synchronize()
+    return out
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("semantics", SEMANTICS)
+def test_integrator_and_fused_steps_are_exactly_symmetric(coeff, implicit, semantics, int_pop, engines):
+    """n = 321: state out, the wrench hydro_step_fused_tiled hands out, prev_out and the energy pair."""
+    st, pv, params = int_pop
+    n = len(st)
+    eng = engines("integrator", params[coeff], coeff)
+    eng.set_semantics(semantics)
+    w6 = _from(eng.step_wrench_tiled(_tiled(st), n, DT, prev=_tiled(pv)), n)
+    want = _plain(eng, st, pv, w6, n, implicit)
+    assert np.isfinite(want["multi1"][0]).all() and not sym.equal(want["multi1"][0], st)
+    for m in sym.MAPS:
+        got = _plain(eng, sym.state(m, st), sym.prev(m, pv), sym.wrench(m, w6), n, implicit)
+        for name, outs in want.items():
+            image = [sym.state(m, outs[0])]
+            if name.startswith("fused"):
+                image.append(sym.wrench(m, outs[1]))
+            elif name.startswith("multi"):
+                image.append(sym.prev(m, outs[1]))
+            image += list(outs[len(image):])                         # the energy pair: unchanged
+            assert len(image) == len(got[name])
+            for k, (a, b) in enumerate(zip(got[name], image)):
+                bad = sym.differing(a, b) if a.ndim == 2 else np.array([not sym.equal(a, b)])
+                assert not bad.any(), (m, name, k, int(bad.sum()), np.nonzero(bad)[0][:8], a if a.ndim == 1 else None, b if a.ndim == 1 else None)
+    # teeth on the device: the image with an angular velocity of the wrong hand (under the half turn: left unturned) is told apart
+    spinning = (st[:, 10:13] != 0).any(axis=1)
+    for m in sym.MAPS:
+        wrong, wrong_pv = sym.state(m, st), sym.prev(m, pv)
+        hand = sym.POLAR[m] if m != "half_turn" else sym.SAME3
+        wrong[:, 10:13], wrong_pv[:, 3:6] = sym._times(st[:, 10:13], hand), sym._times(pv[:, 3:6], hand)
+        cur, old = _buffers(wrong, wrong_pv, n)
+        new = _from(eng.step_fused_tiled_multi(cur, old, n, DT, 1, implicit_drag=implicit), n)
+        assert sym.differing(new, sym.state(m, want["multi1"][0]))[spinning].mean() >= 0.9, m
+    print(f"[integrator and fused steps {coeff} {semantics} {'implicit' if implicit else 'explicit'}] {n} bodies x 3 maps x {len(want)} entries: 0 differ")
+
+
+# ---- (c) the probes ---------------------------------------------------------------------------------------------------------------------
+@COEFFS
+def test_sea_sample_and_mooring_probe_are_exactly_symmetric(coeff, pop, engines):
+    st, _, params, _, _, rec = pop
+    for n in SIZES:
+        eng = engines("designed", params[coeff][:n], coeff)
+        s, m9 = st[:n], rec[:n]
+        for m in sym.MAPS:
+            s_g = sym.state(m, s)
+            for step in (0, 10 ** 6):
+                eng.set_sea(TWO_WAVES)
+                want = _from(eng.sea_sample(_tiled(s), n, step, DT), n)
+                eng.set_sea(sym.sea(m, TWO_WAVES))
+                got = _from(eng.sea_sample(_tiled(s_g), n, step, DT), n)
+                bad = sym.differing(got, sym.sea_sample(m, want))
+                assert not bad.any(), ("sea_sample", n, m, step, int(bad.sum()))
+                assert np.isfinite(want).all() and want[:, 0].any()
+            want = _from(eng.mooring_wrench(_tiled(s), _tiled(m9), n), n)
+            got = _from(eng.mooring_wrench(_tiled(s_g), _tiled(sym.mooring(m, m9)), n), n)
+            bad = sym.differing(got, sym.wrench(m, want))
+            assert not bad.any(), ("mooring_wrench", n, m, int(bad.sum()))
+            assert want.any(axis=1).mean() >= 0.25
+    print(f"[probes {coeff}] hydro_sea_sample (steps 0 and 10^6) and hydro_mooring_wrench, n = 200 and 321, 3 maps: 0 differ")
+
+
+@COEFFS
+def test_seabed_probe_single_corner_exact_the_others_within_twice_the_probe_bound(coeff, bed_pop, engines):
+    """The bed population with tilted_boxes of tests/test_symmetry.py (its shares are asserted there, on the CPU).  At most one
+    contributing corner on the body and on its image: exact.  The others: |image of the image's wrench - wrench| in units of
+    2^-24 of seabed_reference.wrench_scales, against 2 x PROBE_BOUND."""
+    st, pv, params, _, _ = bed_pop
+    st, _, _ = tilted_boxes(st, pv, params["f32"])
+    pr = params[coeff]
+    worst, exact, bounded = 0.0, 0, 0
+    for n in SIZES:
+        eng = engines("designed", pr[:n], coeff)
+        eng.set_seabed(BED)
+        s = st[:n]
+        want = _from(eng.seabed_wrench(_tiled(s), n), n)
+        scale = br.wrench_scales(BED, s, pr[:n], br.touching_fp32(BED, s, pr[:n]))
+        for m in sym.MAPS:
+            s_g = sym.state(m, s)
+            got = sym.wrench(m, _from(eng.seabed_wrench(_tiled(s_g), n), n))
+            count = np.maximum(contributing_corners(s, pr[:n]), contributing_corners(s_g, pr[:n]))
+            single = count <= 1
+            bad = sym.differing(got[single], want[single])
+            assert not bad.any(), (n, m, int(bad.sum()), np.nonzero(single)[0][bad][:8])
+            assert np.isfinite(got).all() and (want[count == 1] != 0).any(axis=1).mean() > 0.5        # (a corner that leaves fast enough bears nothing)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                err = np.where(got == want, 0.0, np.abs(got.astype(np.float64) - want) / (br.ULP * scale))[~single]
+            worst = max(worst, float(err.max()))
+            exact, bounded = exact + int(single.sum()), bounded + int((~single).sum())
+            assert (count == 1).mean() >= 0.25 and (~single).mean() >= 0.10
+    print(f"[seabed probe {coeff}] compared exactly {exact}, two or more corners {bounded}: largest difference {worst:.2f} units of 2^-24 of the scale "
+          f"(bound 2 x {PROBE_BOUND:g})")
+    assert worst <= 2 * PROBE_BOUND
+
+
+# ---- (d) the resident policies -------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def resident_pops(pop):
+    """name -> (state, prev, params, applied, control, lines): `designed` as the mooring tests draw it; `reseated`: tilted_boxes
+    and, for the bodies it moved, the lines drawn anew from the moved state (line_population builds every line from its
+    body's own state; the ties at bodies 0 .. 7 are not moved)."""
+    st, pv, params, applied, ctl, rec = pop
+    moved, _, _ = tilted_boxes(st, pv, params["f32"])
+    again = line_population(moved, params["f32"])
+    changed = (moved[:, 2] != st[:, 2])
+    lines = np.where(changed[:, None], again, rec)
+    # the controller's targets follow the body in z, so that the law's terms keep their sizes
+    c2 = ctl.copy()
+    c2[:, 2] = (ctl[:, 2].astype(np.float64) + (moved[:, 2].astype(np.float64) - st[:, 2])).astype(np.float32)
+    return {"designed": (st, pv, params, applied, ctl, rec), "reseated": (moved, pv, params, applied, c2, lines)}
+
+
+ENTRIES = ("rec", "app-world", "app-body", "ctl", "ctl+app", "sea", "bed", "moor", "ext", "all", "all-far")
+WITH_BED = ("bed", "moor", "ext", "all")
+
+
+def _resident(eng, entry, P, n, steps, implicit, m=None):
+    """One launch of `entry` on the population P (m: on its image under that map), every body watched and every step
+    recorded with its wrench; returns the outputs MAPPED BACK (the image of the image's outputs): dict of state, prev_out,
+    log (steps, n, 19), and where the entry has them extremes and ke."""
+    st, pv, params, applied, ctl, rec = (x if isinstance(x, dict) else x[:n] for x in P)
+    ident = m is None
+    if not ident:
+        st, pv, applied, ctl, rec = sym.state(m, st), sym.prev(m, pv), sym.applied(m, applied), sym.control(m, ctl), sym.mooring(m, rec)
+    sea = SEA if ident else sym.sea(m, SEA)
+    eng.set_watch(list(range(n)))
+    cur, old = _buffers(st, pv, n)
+    log = torch.full((steps, 19, n), NAN, dtype=torch.float32, device=DEV)
+    a, c17, m9 = _tiled(applied), _tiled(ctl), _tiled(rec)
+    kw = dict(implicit_drag=implicit)
+    rk = dict(log=log, every=1, phase=1, row0=0)
+    ke = record = None
+    eng.set_sea(None)
+    eng.set_seabed(None)
+    if entry == "rec":
+        eng.step_fused_tiled_multi_rec(cur, old, n, DT, steps, log, 1, 1, 0, **kw)
+    elif entry in ("app-world", "app-body"):
+        eng.step_fused_tiled_multi_applied(cur, old, n, DT, steps, a, entry[4:], **rk, **kw)
+    elif entry in ("ctl", "ctl+app"):
+        eng.step_fused_tiled_multi_controlled(cur, old, n, DT, steps, c17, a if entry == "ctl+app" else None, "body", **rk, **kw)
+    elif entry == "sea":
+        eng.set_sea(sea)
+        eng.step_fused_tiled_multi_sea(cur, old, n, DT, steps, STEP0, **rk, **kw)
+    elif entry == "bed":
+        eng.set_seabed(BED)
+        eng.step_fused_tiled_multi_bed(cur, old, n, DT, steps, STEP0, **rk, **kw)
+    elif entry == "moor":
+        eng.set_sea(sea)
+        eng.set_seabed(BED)
+        eng.step_fused_tiled_multi_moor(cur, old, n, DT, steps, STEP0, m9, **rk, **kw)
+    else:
+        eng.set_sea(sea)
+        eng.set_seabed(FAR if entry == "all-far" else BED)
+        record = torch.full((eng.tiles(n), 8, 64), NAN, dtype=torch.float32, device=DEV)
+        if entry == "ext":
+            eng.extremes_reset(record, n)
+            eng.step_fused_tiled_multi_ext(cur, old, n, DT, steps, STEP0, record, m9, **rk, **kw)
+        else:
+            eng.extremes_reset(record, n, cur)
+            ke = _ke()
+            eng.step_fused_tiled_multi_ext(cur, old, n, DT, steps, STEP0, record, m9, c17, a, "body", ke_out=ke, **rk, **kw)
+    torch.cuda.synchronize()
+    out = {"state": _from(old, n), "prev_out": _from(cur, n)[:, 7:13], "log": np.ascontiguousarray(_np(log).transpose(0, 2, 1))}
+    if record is not None:
+        out["extremes"] = _from(record, n)
+    if ke is not None:
+        out["ke"] = _np(ke)
+    if not ident:
+        out["state"], out["prev_out"], out["log"] = sym.state(m, out["state"]), sym.prev(m, out["prev_out"]), sym.log_row(m, out["log"])
+        if record is not None:
+            out["extremes"] = sym.extremes(m, out["extremes"])
+    return out, st
+
+
+def _sensitive_from(st0, log, pr):
+    """(n,) the first step (0-based row) whose INPUT state has two or more contributing corners; `steps` if none has.  The
+    input of row 0 is st0, of row j the state row j - 1 recorded."""
+    steps, n = log.shape[0], log.shape[1]
+    first = np.full(n, steps)
+    for j in range(steps - 1, -1, -1):
+        s = st0 if j == 0 else log[j - 1, :, 0:13]
+        with np.errstate(all="ignore"):
+            many = contributing_corners(np.nan_to_num(s, nan=0.0, posinf=0.0, neginf=0.0), pr) >= 2
+        first = np.where(many, j, first)
+    return first
+
+
+def _compare(entry, want, got, first, what):
+    """Exact where the reference calls the body order-insensitive; returns (bodies compared exactly through the last step,
+    bodies left out)."""
+    steps, n = want["log"].shape[0], want["log"].shape[1]
+    for j in range(steps):
+        live = first > j
+        bad = sym.differing(got["log"][j][live], want["log"][j][live])
+        assert not bad.any(), what + ("log row", j, int(bad.sum()), np.nonzero(live)[0][bad][:8])
+    whole = first >= steps
+    for k in ("state", "prev_out", "extremes"):
+        if k in want:
+            bad = sym.differing(got[k][whole], want[k][whole])
+            assert not bad.any(), what + (k, int(bad.sum()), np.nonzero(whole)[0][bad][:8])
+    if "ke" in want and whole.all():
+        assert sym.equal(got["ke"], want["ke"]), what + ("ke", got["ke"], want["ke"])
+    assert sym.equal(want["log"][steps - 1][:, 0:13], want["state"]), what                                                # the last row is the final state
+    return int(whole.sum()), int((~whole).sum())
+
+
+def _one_step_scales(entry, st, pv, pr, coeff, implicit, wrench):
+    """field_scales of the step the device made: its own logged wrench, and with implicit drag the drag coefficients of the
+    oracle on the state the wrench saw (relative to the sea, where there is one)."""
+    k = None
+    if implicit:
+        s_rel, pv_rel = st, pv
+        if entry in ("moor", "ext", "all"):
+            eta, u = sr.water(SEA, st[:, 0], st[:, 1], st[:, 2], STEP0, DT)
+            s_rel, pv_rel = sr.relative(st, pv, eta.astype(np.float32), u.astype(np.float32))
+        comps = ho.step_wrench(s_rel, pv_rel, io._coeffs(pr, coeff), RHO, G, DT)[2]
+        k = io.drag_jacobian(s_rel, pr, comps, RHO, coeff)
+    return k, wrench.astype(np.float64)
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("which", ["designed", "reseated"])
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_resident_policies_are_exactly_symmetric(entry, which, coeff, implicit, resident_pops, engines):
+    """_rec, _app (world and body frame), _ctl (without and with a body-frame applied wrench), _sea (waves + current), _bed,
+    _moor and _ext (over sea and bed), and the everything-on _ext launch (log, body-frame applied wrench, pose hold, sea, bed,
+    lines, extremes seeded from the state, ke_out; `all-far`: the same over a bed nobody reaches, where the energy pair can
+    be compared), each at 1 and 7 steps, n = 200 and 321, under the three maps."""
+    P = resident_pops[which]
+    pr = P[2][coeff]
+    Pc = (P[0], P[1], pr, P[3], P[4], P[5])
+    report = []
+    for n in SIZES:
+        eng = engines("designed", pr[:n], coeff)
+        for steps in STEPS:
+            want, st0 = _resident(eng, entry, Pc, n, steps, implicit)
+            assert not sym.equal(want["state"], st0)
+            bed = entry in WITH_BED
+            first0 = _sensitive_from(st0, want["log"], pr[:n]) if bed else np.full(n, steps)
+            fewest, most, one_step = n, 0, None
+            for m in sym.MAPS:
+                got, st_g = _resident(eng, entry, Pc, n, steps, implicit, m)
+                first = np.minimum(first0, _sensitive_from(sym.state(m, st_g), got["log"], pr[:n])) if bed else first0
+                exact, left = _compare(entry, want, got, first, (entry, which, n, steps, m))
+                fewest, most = min(fewest, exact), max(most, left)
+                out = first < steps
+                if bed and implicit:
+                    for j in range(steps):                          # left out, but finite
+                        gone = first <= j
+                        assert np.isfinite(got["log"][j][gone]).all() and np.isfinite(want["log"][j][gone]).all(), (entry, which, n, steps, m, j)
+                if bed and steps == 1 and out.any():
+                    k, w = _one_step_scales(entry, st0, Pc[1][:n], pr[:n], coeff, implicit, want["log"][0][:, 13:19])
+                    kk = None if k is None else (k[0][out], k[1][out])
+                    ref = want["state"][out].astype(np.float64)
+                    sc = io.field_scales(st0[out], w[out], pr[:n][out], G, DT, kk, ref)
+                    err = io.integrator_error_ulps(got["state"][out], ref, st0[out], w[out], pr[:n][out], G, DT, kk, scales=sc)
+                    worst = io.max_error_ulps(err)
+                    one_step = max(one_step or 0.0, worst)
+                    assert worst <= 2 * io.STEP_ULP_BOUND, (entry, which, n, m, worst)
+                if which == "reseated" and steps == 7 and implicit:
+                    assert left <= 0.25 * n, (entry, n, m, left)
+            report.append(f"n={n} x{steps}: {fewest} exact, {most} left out ({most / n:.0%})"
+                          + (f", their one step within {one_step:.2f} ulps of its image (bound 2 x {io.STEP_ULP_BOUND:g})" if one_step is not None else ""))
+    print(f"[resident {entry} {which} {coeff} {'implicit' if implicit else 'explicit'}, fewest / most over the 3 maps] " + "; ".join(report))
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("variant", ["non_temporal", "warp"])
+def test_everything_on_non_temporal_and_warp(variant, coeff, implicit, resident_pops, engines):
+    """The everything-on launch with non_temporal = 1, and under Warp semantics (the engine's settings; `_resident` leaves
+    them alone)."""
+    P = resident_pops["reseated"]
+    pr = P[2][coeff]
+    Pc = (P[0], P[1], pr, P[3], P[4], P[5])
+    shown = []
+    for n in SIZES:
+        eng = engines("designed", pr[:n], coeff)
+        if variant == "warp":
+            eng.set_semantics("warp")
+        else:
+            eng.set_tuning(0, 0, 1)
+        for entry in ("all", "all-far"):
+            for steps in STEPS:
+                want, st0 = _resident(eng, entry, Pc, n, steps, implicit)
+                bed = entry == "all"
+                first0 = _sensitive_from(st0, want["log"], pr[:n]) if bed else np.full(n, steps)
+                for m in sym.MAPS:
+                    got, st_g = _resident(eng, entry, Pc, n, steps, implicit, m)
+                    first = np.minimum(first0, _sensitive_from(sym.state(m, st_g), got["log"], pr[:n])) if bed else first0
+                    exact, left = _compare(entry, want, got, first, (variant, entry, n, steps, m))
+                    if steps == 7 and n == 321:
+                        shown.append(f"{entry} {m}: {exact} exact, {left} left out")
+    print(f"[everything on, {variant} {coeff} {'implicit' if implicit else 'explicit'}] n=321 steps=7 " + "; ".join(shown))
+
+
+# ---- (e) ClosedLoopSim ------------------------------------------------------------------------------------------------------------------
+def test_closed_loop_sim_builds_its_records_without_a_hand(native_built):
+    """64 moored buoys at 64 headings, a current with one wave component, an off-centre fairlead and a weak pose hold towards a
+    displaced, turned target - and the mirror_y image of all of it, both through ClosedLoopSim's own set_mooring / set_pose_hold
+    / set_sea: run_resident(20, chunk=7) with track_extremes leaves the image's final state and Extremes the images of the
+    scene's."""
+    sc, anchors, z_eq, mass = _buoys()
+    k, c = Mooring.for_body(mass, sc.dt)
+    sea = SeaState((0.5, -0.2, 0.0)).add_wave(0.3, 0.21, 0.13, 1.55, 0.7)
+    rng = np.random.default_rng(9)
+    fairlead = np.array([0.05, 0.02, -0.05])
+    target_p = sc.state[:, 0:3].astype(np.float64) + rng.uniform(-0.5, 0.5, (sc.n, 3))
+    axis = rng.normal(size=(sc.n, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    half = 0.5 * rng.uniform(0.1, 0.6, (sc.n, 1))
+    target_q = np.concatenate([np.sin(half) * axis, np.cos(half)], axis=1).astype(np.float32)
+    L0 = DEPTH - 0.2                                                # taut from the first step
+    m = "mirror_y"
+    polar = np.asarray(sym.POLAR[m], np.float64)
+    finals, records = {}, {}
+    for name in ("scene", "image"):
+        im = name == "image"
+        scene = scenes.Scene("buoys", sym.state(m, sc.state), sym.prev(m, sc.prev), sc.params, dt=sc.dt, rho=sc.rho, g=sc.g) if im else sc
+        sim = ClosedLoopSim(scene, implicit_drag=True)
+        sim.set_sea(sym.sea(m, sea) if im else sea)
+        sim.set_mooring(anchors * polar if im else anchors, fairlead * polar if im else fairlead, length=L0, stiffness=k, damping=c)
+        sim.set_pose_hold(position=(target_p * polar if im else target_p).astype(np.float32),
+                          orientation_xyzw=sym._times(target_q, sym.QUAT[m]) if im else target_q,
+                          kp_lin=2.0 * mass, kd_lin=0.5 * mass, kp_ang=1.0, kd_ang=0.2)
+        view = sim.track_extremes()
+        sim.run_resident(20, chunk=7)
+        finals[name], records[name] = sim.state(), view.bodies()
+        sim.close()
+    assert np.isfinite(finals["scene"]).all() and (records["scene"][:, 7] > 0).all()                     # every line pulled
+    assert (np.abs(finals["scene"][:, 0:3] - sc.state[:, 0:3]) > 1e-4).any(axis=1).all()
+    bad = sym.differing(sym.state(m, finals["image"]), finals["scene"]) | sym.differing(sym.extremes(m, records["image"]), records["scene"])
+    print(f"[ClosedLoopSim, 64 moored buoys and their mirror_y image, 20 steps in chunks of 7] {int(bad.sum())} bodies differ")
+    assert not bad.any(), np.nonzero(bad)[0]
