@@ -57,7 +57,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_mooring_wrench, hydro_step_fused_tiled_multi_moor,
  *        HYDRO_MOOR_FIELDS - one tension-only mooring line per body, evaluated inside every step of the multi-step kernel
  *        added to 0.7.1 (no existing entry changed): hydro_extremes_reset, hydro_step_fused_tiled_multi_ext,
- *        HYDRO_EXT_FIELDS - running per-body extremes (position box, speed, line tension) updated inside every step */
+ *        HYDRO_EXT_FIELDS - running per-body extremes (position box, speed, line tension) updated inside every step
+ *        added to 0.7.1 (no existing entry changed): hydro_tether_wrench, hydro_step_fused_tiled_multi_teth,
+ *        HYDRO_TETH_FIELDS - one tension-only line between two bodies of a tile, evaluated inside every step */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -74,6 +76,7 @@ extern "C" {
 #define HYDRO_CTL_FIELDS    17   /* the control record of hydro_step_fused_tiled_multi_ctl */
 #define HYDRO_MOOR_FIELDS    9   /* the mooring record of hydro_step_fused_tiled_multi_moor */
 #define HYDRO_EXT_FIELDS     8   /* the extremes record of hydro_step_fused_tiled_multi_ext */
+#define HYDRO_TETH_FIELDS    7   /* the tether record of hydro_step_fused_tiled_multi_teth */
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
@@ -781,6 +784,91 @@ int hydro_step_fused_tiled_multi_ext(hydro_t *h, int64_t n, const float *state, 
                                      const float *control, int64_t control_tile_stride,
                                      const float *mooring, int64_t mooring_tile_stride,
                                      float *extremes, int64_t extremes_tile_stride, int64_t step0, void *stream);
+
+/* Tether: ONE tension-only line between TWO BODIES in the closed-loop steps - an ROV on an umbilical under a buoy, a towed
+ * body behind a driven one, a float and its sinker: a spring and a damper along the line that act only while the line is
+ * stretched and never push.  It is the one term that couples bodies: the partner's fairlead of the very step is read from
+ * the partner's lane of the wavefront, inside the kernel.  Only hydro_step_fused_tiled_multi_teth and hydro_tether_wrench know
+ * tethers; every other entry ignores them.
+ *
+ * THE RECORD `tether`: HYDRO_TETH_FIELDS = 7 floats per body, tiled ([tiles][7][64] floats, tile stride
+ * tether_tile_stride >= 448, 16-byte aligned, whole tiles, addressed like `mooring`), in this order:
+ *     b(3)     this body's fairlead, in its own body frame (m)
+ *     L0       unstretched length (m), >= 0
+ *     k        stiffness (N/m), >= 0
+ *     c        damping along the line (N s/m), >= 0
+ *     partner  the other body, as a LANE INDEX WITHIN THE SAME TILE (0 .. 63), stored as a float: body 64 t + partner
+ * It is the caller's device buffer and is READ IN EVERY STEP of every launch; between launches a device-side winch may
+ * rewrite L0 (on both lanes of a pair).  A lane HAS A TETHER if k > 0 or c > 0 (a NaN is neither); a body without one has
+ * k = c = 0.  SCOPE: at most one tether per body; both bodies of a pair in one tile, 64 t .. 64 t + 63; the pairing an
+ * involution (partner of partner = self); both records of a pair carry the same L0, k, c (each its own b); the partner a
+ * body < n.  NO PARTNER INDEX EVER FORMS A MEMORY ADDRESS: the kernel uses (int)partner & 63 as a lane of its own wavefront.
+ * A malformed record - a partner that is not mutual, a partner among the lanes >= n of the last tile (it answers +0),
+ * constants that differ between the two, negative or non-finite values - is computed as given and cannot fault; the
+ * contents are not validated on the device (the Python host validates what it builds).
+ * RULE OF THUMB for a step dt: with the reduced mass mu = m_a m_b / (m_a + m_b), k dt^2 / mu <= 0.04 and c dt / mu <= 0.04
+ * (the mooring's rule, DESIGN.md section 19, for the pair's relative motion).
+ *
+ * THE TETHER'S WRENCH on a body with state s = [p | q | v | omega] (the TRUE state the step starts from, never the one
+ * relative to the water), in fp32, in exactly this order (fma(a, b, c): a * b + c rounded once; rsqrt: hardware seed + one
+ * Newton step, as for the mooring):
+ *     R      the fp32 matrix of q as given, non-unit included
+ *     r_i    = fma(R_i2, b_z, fma(R_i1, b_y, R_i0 * b_x))              the fairlead's arm, world frame
+ *     P_i    = p_i + r_i                                               the fairlead, world frame (one add)
+ *     U_x    = fma(omega_y, r_z, fma(-omega_z, r_y, v_x))              U = v + omega x r, the mooring's three forms;
+ *     U_y    = fma(omega_z, r_x, fma(-omega_x, r_z, v_y)),  U_z = fma(omega_x, r_y, fma(-omega_y, r_x, v_z))
+ *     P', U' = the partner's P and U of this step                      (six lane exchanges; no memory)
+ *     e_i    = P'_i - P_i                                              fairlead -> partner's fairlead
+ *     l2     = fma(e_z, e_z, fma(e_y, e_y, e_x * e_x)),  inv = rsqrt(l2),  l = l2 * inv
+ *     x      = l - L0                                                  the line is TAUT only if x > 0 (l2 = 0 gives NaN: not taut)
+ *     dU_i   = U'_i - U_i
+ *     rate   = fma(dU_z, e_z, fma(dU_y, e_y, dU_x * e_x)) * inv        > 0: the fairleads part
+ *     T      = max(0, fma(k, x, c * rate))                             tension; a line cannot push
+ *     F_i    = (T * inv) * e_i
+ *     M_x    = fma(r_y, F_z, -(r_z * F_y)),  M_y = fma(r_z, F_x, -(r_x * F_z)),  M_z = fma(r_x, F_y, -(r_y * F_x))
+ * W = [F | M]: force at, torque about the body origin, world frame.  IN A STEP it is added to the step's wrench with one
+ * fp32 add per component - behind the mooring line's wrench, in front of the integrator.  The sum is what the integrator
+ * takes (with implicit_drag it stands where f stands) and what the recorder logs.  A line PULLS if the lane has a tether and
+ * x > 0 and T > 0; otherwise the wrench is left untouched: +0 is NOT added.  Whole wavefronts without a tether skip the
+ * evaluation; that changes no bit.
+ * EQUAL AND OPPOSITE, EXACTLY (a property that is tested): negation is exact in fp32, so the partner forms -e and -dU and from
+ * them the same l2, inv, x, rate and T, and the force -F, bit for bit.  The pair's linear momentum changes by the rounding of
+ * the integrator's additions alone.  (The torques r x F and r' x -F are each body's own and need not cancel.)
+ * NOT MODELLED: chains, and more than one tether per body; pairs across tiles; the line's mass, sag and drag; the tether's
+ * tension in the extremes record - tension_max stays the mooring line's and is unchanged by a tether.
+ *
+ * hydro_tether_wrench: writes the tiled 6-field W ([tiles][6][64] floats, tile stride out_tile_stride >= 384) of bodies
+ * 0 .. n - 1 in `state` - exactly what a step that starts from `state` adds; +0 in all six fields for a body whose line adds
+ * nothing - and, unless `tension` is NULL, T in a tiled one-field record ([tiles][1][64] floats, tile stride >= 64; +0
+ * likewise).  A small kernel of its own; asynchronous on `stream`.  HYDRO_E_STATE without parameters; HYDRO_E_ARG for
+ * n > capacity, a null or misaligned buffer, a stride below 832 (state) / 448 (tether) / 384 (out) / 64 (tension), or an
+ * output overlapping an input or the other output.
+ *
+ * hydro_step_fused_tiled_multi_teth: the signature and the rules of hydro_step_fused_tiled_multi_ext, with `tether` and its
+ * stride in front of step0.
+ *   tether == NULL : the launch and its bits are those of hydro_step_fused_tiled_multi_ext with the same arguments.
+ *   tether != NULL : log, applied, control, the sea, the bed, `mooring` AND `extremes` are each optional, and each adds
+ *                    exactly what it adds in the entries without tethers; then W.  A record of zeros gives the bits of
+ *                    hydro_step_fused_tiled_multi_ext.
+ * The refusals are those of hydro_step_fused_tiled_multi_ext, in its order, then the tether's, behind the extremes': a stride
+ * below 448 or a misaligned buffer, a record that overlaps an output (state_out, prev_out, log, extremes): HYDRO_E_ARG, and
+ * nothing is launched or written.  Asynchronous, no allocation, no synchronisation, safe to capture (a tether does not
+ * depend on time).  Cost and registers: DESIGN.md section 22.  New functionality; the reference has no tethers. */
+int hydro_tether_wrench(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                        const float *tether, int64_t tether_tile_stride,
+                        float *out, int64_t out_tile_stride, float *tension, int64_t tension_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_teth(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                      const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float *state_out, int64_t out_tile_stride,
+                                      float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double *ke_out_dev,
+                                      float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t *rows_written_host,
+                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float *control, int64_t control_tile_stride,
+                                      const float *mooring, int64_t mooring_tile_stride,
+                                      float *extremes, int64_t extremes_tile_stride,
+                                      const float *tether, int64_t tether_tile_stride, int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -18,6 +18,7 @@ STATE_FIELDS, PREV_FIELDS, PARAM_FIELDS, WRENCH_FIELDS, COMP_FIELDS = 13, 6, 11,
 CTL_FIELDS = 17                         # the control record of hydro_step_fused_tiled_multi_ctl
 MOOR_FIELDS = 9                         # the mooring record of hydro_step_fused_tiled_multi_moor: a(3) | b(3) | L0 | k | c
 EXT_FIELDS = 8                          # the extremes record of hydro_step_fused_tiled_multi_ext: x, y, z min max | speed2_max | tension_max
+TETH_FIELDS = 7                         # the tether record of hydro_step_fused_tiled_multi_teth: b(3) | L0 | k | c | partner lane
 TILE = 64
 BATCH_MAX = 32
 WATCH_MAX = 65536
@@ -120,6 +121,12 @@ SIGNATURES = {
                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                                  c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_tether_wrench": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_teth": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                                  c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -1121,10 +1121,11 @@ __global__ void __launch_bounds__(kBlock) step_fused_tiled_kernel(const float* k
 // after the wrench acts on the true state (see SeaView; NoSea does nothing, and the kernels without a sea are unchanged).
 // `bed` is the seabed policy: add(s, d, mass, f6) behind app.add, before the integrator (see SeabedContact; NoBed does nothing).
 // `moor` is the mooring policy: add(s, f6) behind bed.add, before the integrator (see MooringLine; NoMooring does nothing).
-template <bool IMPLICIT, bool WARP, typename Applied, typename Sea, typename Bed, typename Moor>
+// `teth` is the tether policy: add(s, f6) behind moor.add, before the integrator (see TetherLine; NoTether does nothing).
+template <bool IMPLICIT, bool WARP, typename Applied, typename Sea, typename Bed, typename Moor, typename Teth>
 __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], const float (&d)[3], const float (&c)[7], float mass,
                                                         double rho, double g, double inv_dt, float dt, float (&f6)[HYDRO_WRENCH_FIELDS], const Applied& app,
-                                                        uint32_t k, const Sea& sea, const Bed& bed, const Moor& moor)
+                                                        uint32_t k, const Sea& sea, const Bed& bed, const Moor& moor, const Teth& teth)
 {
     sea.view(k, s, pv);
     const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
@@ -1133,6 +1134,7 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
     app.add(s, f6);
     bed.add(s, d, mass, f6);
     moor.add(s, f6);
+    teth.add(s, f6);
     float o[HYDRO_STATE_FIELDS];
     integrate_body<IMPLICIT>(s, f6, mass, d[0], d[1], d[2], g, dt, w.k_lin, w.k_ang, o);
 #pragma unroll
@@ -1160,11 +1162,13 @@ __device__ __forceinline__ void fused_step_in_registers(float (&s)[HYDRO_STATE_F
 // `ext` is the extremes policy: begin(tile, lane4) next to the record loads, after_step(s, T) behind rec.after_step with the
 // state the step produced and the tension moor.add formed in it, end(tile, lane4) in front of the final stores (see
 // ExtremesTrack; NoExtremes does nothing).
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed, typename Moor, typename Ext>
+// `teth` is the tether policy: begin(tile, lane4) next to the record loads, then add(s, f6) inside every step, behind moor.add
+// (see TetherLine; NoTether does nothing).
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP, typename Recorder, typename Applied, typename Sea, typename Bed, typename Moor, typename Ext, typename Teth>
 __device__ __forceinline__ void fused_multi_body(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
                                                  uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
                                                  uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed, Moor moor, Ext ext)
+                                                 double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out, Recorder rec, Applied app, Sea sea, Bed bed, Moor moor, Ext ext, Teth teth)
 {
     const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;      // (wave-uniform, see load_tile_records)
     const bool live = tile * 64u + lane < n;
@@ -1180,10 +1184,11 @@ __device__ __forceinline__ void fused_multi_body(const float* k_st, const float*
         sea.begin(lane4);
         moor.begin(tile, lane4);
         ext.begin(tile, lane4);
+        teth.begin(tile, lane4);
 #pragma unroll 1
         for (uint32_t k = 0; k < steps; ++k) {
             float f6[HYDRO_WRENCH_FIELDS];
-            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea, bed, moor);
+            fused_step_in_registers<IMPLICIT, WARP>(s, pv, d, c, mass, rho, g, inv_dt, dt, f6, app, k, sea, bed, moor, teth);
             rec.after_step(k, s, f6);
             ext.after_step(s, moor.tension());
         }
@@ -1225,6 +1230,10 @@ struct NoExtremes {
     __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
     __device__ __forceinline__ void after_step(const float (&)[HYDRO_STATE_FIELDS], float) const {}
     __device__ __forceinline__ void end(uint32_t, uint32_t) const {}
+};
+struct NoTether {
+    __device__ __forceinline__ void begin(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void add(const float (&)[HYDRO_STATE_FIELDS], float (&)[HYDRO_WRENCH_FIELDS]) const {}
 };
 
 // --------------------------------------------------------------------------
@@ -1277,7 +1286,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const fl
                                                                        double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
+                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
@@ -1291,7 +1300,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(cons
 {
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
+                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // --------------------------------------------------------------------------
@@ -1356,7 +1365,7 @@ __global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(cons
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
+                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // --------------------------------------------------------------------------
@@ -1487,7 +1496,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{});
+                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // --------------------------------------------------------------------------
@@ -1619,7 +1628,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    ke_partials, ke_stride, ke_rotational, ke_out,
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{}, NoMooring{}, NoExtremes{});
+                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
@@ -1755,7 +1764,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
                                                    OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, NoMooring{}, NoExtremes{});
+                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // hydro_seabed_wrench: the bed's W per body for the tiled state `st` (zeros for a body no corner of which is below the plane).
@@ -1892,7 +1901,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
                                                    OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
                                                    OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   MooringLine{{0u, 0u}, mooring, mooring_stride}, NoExtremes{});
+                                                   MooringLine{{0u, 0u}, mooring, mooring_stride}, NoExtremes{}, NoTether{});
 }
 
 // hydro_mooring_wrench: the line's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds nothing).
@@ -2016,7 +2025,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
                                                    OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
                                                    OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
-                                                   ExtremesTrack{{0u, 0u}, extremes, extremes_stride});
+                                                   ExtremesTrack{{0u, 0u}, extremes, extremes_stride}, NoTether{});
 }
 
 // hydro_extremes_reset: the empty record, or (st != nullptr) the record of the one sample `st`.
@@ -2034,6 +2043,157 @@ __global__ void __launch_bounds__(kBlock) extremes_reset_kernel(const float* st,
         v[6] = __builtin_fmaf(vz, vz, __builtin_fmaf(vy, vy, vx * vx));
     }
     store_record<HYDRO_EXT_FIELDS, false>(ext + (size_t)tile * ext_stride, lane4, v);
+}
+
+// --------------------------------------------------------------------------
+// TETHERS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_teth): ONE tension-only line between two bodies
+// of the same tile - a spring and a damper along the line that never push.  The first term of the model that couples two
+// bodies.  Per body a tiled 7-field record ([tiles][7][64], addressed like the mooring record):
+//   b(3) | L0 | k | c | partner
+// include/hydro.h states the model and the order of operations ("Tether"); tether_wrench below is its ONLY implementation
+// (the step kernel and hydro_tether_wrench's kernel both call it).  The line sees the TRUE state and adds its wrench behind
+// the mooring line's, in front of the integrator: one fp32 add per component.
+//   the exchange: a tile is one wavefront that steps in lockstep, so the partner's fairlead (position P, velocity U) of THIS
+//                 step is in the partner lane's registers: six ds_bpermute_b32 hand it over, with no LDS allocation and no
+//                 memory traffic.  `partner` is a lane index, never an address: (int)partner & 63, times four, is all the
+//                 instruction sees, and a lane that is masked off answers +0.  Every lane that reaches the exchange takes
+//                 part in it, tethered or not - the only branch in front of it is the wave-uniform skip.
+//   the record  : the extremes kernels stand at 165 VGPRs of 168 and their LDS fills the CU at three blocks, so the seven
+//                 values are neither carried through the loop nor parked: every step reads them anew from the caller's
+//                 buffer (seven coalesced loads of a launch-invariant 1 792 B per wave, L2 hits after the first step).  The
+//                 address is lane4 + the tile's record, a wave-uniform pointer in two SGPRs that an empty asm makes opaque
+//                 in every step (LaneSlots::parked's way), so that the compiler neither hoists the loads across the fp64
+//                 wrench nor forwards the values through registers.
+//   the skip    : a lane has a tether if k > 0 or c > 0.  If no lane of the wavefront has one (ballot == 0) the wave branches
+//                 round the evaluation: an untethered tile pays two loads, two compares and the branch
+//   no +0       : a lane whose line adds nothing (no tether, slack, or a tension that is not > 0) leaves f6 untouched
+//   antisymmetry: negation is exact, so the partner forms -e and -dU, hence the same l2, inv, x, rate and T, and -F, bit for bit
+// --------------------------------------------------------------------------
+__device__ __forceinline__ float from_lane(uint32_t lane_byte, float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)lane_byte, __builtin_bit_cast(int, v)));
+}
+// W (force at, torque about the body origin, world frame) of the tether whose record is t[j * 64], j = 0 .. 6, on a body in
+// state s.  Returns whether the line pulls; W and `tension` are meaningful (and complete) only then.  To be called in
+// wave-uniform control flow by every lane whose partner may ask for its fairlead.
+__device__ __forceinline__ bool tether_wrench(const float* t, const float (&s)[HYDRO_STATE_FIELDS], float (&W)[HYDRO_WRENCH_FIELDS], float& tension)
+{
+    const float k = t[4 * 64], c = t[5 * 64];
+    const bool has_tether = k > 0.0f || c > 0.0f;
+    if (__builtin_amdgcn_ballot_w64(has_tether) == 0) return false;       // (scalar branch: nobody in this wave is tethered)
+    const auto [r00, r01, r02, r10, r11, r12, r20, r21, r22] = rotation_of(s[3], s[4], s[5], s[6]);
+    const float bx = t[0 * 64], by = t[1 * 64], bz = t[2 * 64];
+    const float rx = __builtin_fmaf(r02, bz, __builtin_fmaf(r01, by, r00 * bx));
+    const float ry = __builtin_fmaf(r12, bz, __builtin_fmaf(r11, by, r10 * bx));
+    const float rz = __builtin_fmaf(r22, bz, __builtin_fmaf(r21, by, r20 * bx));
+    const float px = s[0] + rx, py = s[1] + ry, pz = s[2] + rz;
+    const float ux = __builtin_fmaf(s[11], rz, __builtin_fmaf(-s[12], ry, s[7]));
+    const float uy = __builtin_fmaf(s[12], rx, __builtin_fmaf(-s[10], rz, s[8]));
+    const float uz = __builtin_fmaf(s[10], ry, __builtin_fmaf(-s[11], rx, s[9]));
+    const uint32_t partner = ((uint32_t)(int)t[6 * 64] & 63u) << 2;       // (a lane index, in the byte form ds_bpermute takes)
+    const float ex = from_lane(partner, px) - px, ey = from_lane(partner, py) - py, ez = from_lane(partner, pz) - pz;
+    const float dux = from_lane(partner, ux) - ux, duy = from_lane(partner, uy) - uy, duz = from_lane(partner, uz) - uz;
+    const float l2 = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+    const float inv = rsqrt_nr(l2);
+    const float l = l2 * inv;
+    const float x = l - t[3 * 64];
+    const float rate = __builtin_fmaf(duz, ez, __builtin_fmaf(duy, ey, dux * ex)) * inv;
+    const float cr = c * rate;
+    const float T = __builtin_fmaxf(0.0f, __builtin_fmaf(k, x, cr));
+    const float ti = T * inv;
+    tension = T;
+    W[0] = ti * ex; W[1] = ti * ey; W[2] = ti * ez;
+    W[3] = __builtin_fmaf(ry, W[2], -(rz * W[1]));
+    W[4] = __builtin_fmaf(rz, W[0], -(rx * W[2]));
+    W[5] = __builtin_fmaf(rx, W[1], -(ry * W[0]));
+    return has_tether && x > 0.0f && T > 0.0f;                            // (l2 = 0: x is NaN, not taut)
+}
+
+struct TetherLine {
+    using GlobalFloats = const float __attribute__((address_space(1)))*;  // (the empty asm must not cost the loads their address space)
+    const float* rec; uint32_t stride;
+    GlobalFloats tile_rec; uint32_t lane4;                               // the tile's record: a wave-uniform pointer, in SGPRs
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        tile_rec = (GlobalFloats)(rec + (size_t)tile * stride);
+        lane4 = lane4_;
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        GlobalFloats r = tile_rec;
+        asm volatile("" : "+s"(r));
+        float W[HYDRO_WRENCH_FIELDS], T;
+        if (tether_wrench(at<float>((const float*)r, lane4), s, W, T)) {
+#pragma unroll
+            for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+        }
+    }
+};
+
+// The extremes of the tether kernel: optional (`rec` - a kernel argument: wave-uniform); an absent record loads, updates and
+// stores nothing.
+struct OptionalExtremesTrack : ExtremesTrack {
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        if (rec) ExtremesTrack::begin(tile, lane4_);
+    }
+    __device__ __forceinline__ void after_step(const float (&s)[HYDRO_STATE_FIELDS], float T) const
+    {
+        if (rec) ExtremesTrack::after_step(s, T);
+    }
+    __device__ __forceinline__ void end(uint32_t tile, uint32_t lane4_) const
+    {
+        if (rec) ExtremesTrack::end(tile, lane4_);
+    }
+};
+
+// The extremes kernel's arguments, then the tether record's.  `mooring` and `extremes` may be null.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_teth_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
+                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
+                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
+                                                                           const float* mooring, uint32_t mooring_stride,
+                                                                           float* extremes, uint32_t extremes_stride,
+                                                                           const float* tether, uint32_t tether_stride)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
+                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
+                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
+                                                   OptionalExtremesTrack{{{0u, 0u}, extremes, extremes_stride}},
+                                                   TetherLine{tether, tether_stride, nullptr, 0u});
+}
+
+// hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
+// nothing) and, if asked for, its tension T (+0 likewise).  The lanes >= n of the last tile leave first: the live ones
+// exchange among themselves, in uniform control flow.
+__global__ void __launch_bounds__(kBlock) tether_wrench_kernel(const float* st, uint32_t st_stride, const float* teth, uint32_t teth_stride,
+                                                               float* out, uint32_t out_stride, float* tension, uint32_t tension_stride, uint32_t n)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float s[HYDRO_STATE_FIELDS], W[HYDRO_WRENCH_FIELDS], T = 0.0f;
+#pragma unroll
+    for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) s[f] = *at<float>(r, lane4, f * 256u);
+    if (!tether_wrench(teth + (size_t)tile * teth_stride + lane, s, W, T)) {
+#pragma unroll
+        for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) W[f] = 0.0f;
+        T = 0.0f;
+    }
+    store_record<HYDRO_WRENCH_FIELDS, false>(out + (size_t)tile * out_stride, lane4, W);
+    if (tension) store_record<1, false>(tension + (size_t)tile * tension_stride, lane4, &T);    // (a kernel argument: wave-uniform)
 }
 
 // LaneSlots<SLOTS>::slots() is ONE __shared__ array per value of SLOTS: two policies of the same count that meet in one kernel
@@ -2907,6 +3067,7 @@ struct MultiStep {
     bool bed_entry = false;                              // the _bed entry: the _sea entry, and the steps meet the seabed if one is set
     const float* mooring = nullptr; int64_t mooring_tile_stride = 0;      // the _moor entry: the _bed entry, and a line per body if a record is given
     float* extremes = nullptr; int64_t extremes_tile_stride = 0;          // the _ext entry: the _moor entry, and the running extremes if a record is given
+    const float* tether = nullptr; int64_t tether_tile_stride = 0;        // the _teth entry: the _ext entry, and a line between two bodies of a tile if a record is given
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -2951,8 +3112,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
     return HYDRO_OK;
 }
 
-// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the extremes kernel takes
-// everything, the mooring kernel everything but the extremes, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the tether kernel takes
+// everything, the extremes kernel everything but the tethers, the mooring kernel everything but the extremes, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
 // kernel the recorder - and a launch is handed the options it goes without as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
@@ -2999,6 +3160,13 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
             || reads(m.mooring, m.mooring_tile_stride, HYDRO_MOOR_FIELDS))
             return fail(h, HYDRO_E_ARG, "extremes must not overlap an input (state, prev, applied, control, mooring)");
     }
+    if (m.tether) {
+        if ((rc = check_tiled(h, m.n, m.tether, m.tether_tile_stride, HYDRO_TETH_FIELDS, "null tether"))) return rc;
+        if ((rc = check_no_overlap(h, m, log_floats, "tether", m.tether, m.tether_tile_stride))) return rc;
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE;                 // the extremes record is an output too
+        if (m.extremes && ranges_overlap(m.tether, tiles * m.tether_tile_stride, m.extremes, tiled_extent(tiles, m.extremes_tile_stride, HYDRO_EXT_FIELDS)))
+            return fail(h, HYDRO_E_ARG, "tether must not overlap an output (extremes)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -3022,7 +3190,12 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (m.extremes) pushed(step_fused_multi_ext_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+        if (m.tether) pushed(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
+                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
+                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
+                        m.tether, (uint32_t)m.tether_tile_stride);
+        else if (m.extremes) pushed(step_fused_multi_ext_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
                         sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
                         h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
                         m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, (uint32_t)m.extremes_tile_stride);
@@ -3374,6 +3547,61 @@ int hydro_step_fused_tiled_multi_ext(hydro_t* h, int64_t n, const float* state, 
     m.bed_entry = true;
     m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
     m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_tether_wrench(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, const float* tether, int64_t tether_tile_stride,
+                        float* out, int64_t out_tile_stride, float* tension, int64_t tension_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    int rc;
+    if ((rc = check_common(h, n))) return rc;
+    if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
+    if ((rc = check_tiled(h, n, tether, tether_tile_stride, HYDRO_TETH_FIELDS, "null tether"))) return rc;
+    if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_WRENCH_FIELDS, "null out"))) return rc;
+    if (tension && (rc = check_tiled(h, n, tension, tension_tile_stride, 1, "null tension"))) return rc;
+    const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE, out_floats = tiled_extent(tiles, out_tile_stride, HYDRO_WRENCH_FIELDS);
+    const int64_t state_floats = tiled_extent(tiles, state_tile_stride, HYDRO_STATE_FIELDS), tether_floats = tiled_extent(tiles, tether_tile_stride, HYDRO_TETH_FIELDS);
+    if (ranges_overlap(state, state_floats, out, out_floats) || ranges_overlap(tether, tether_floats, out, out_floats))
+        return fail(h, HYDRO_E_ARG, "out must not overlap an input (state, tether)");
+    if (tension) {
+        const int64_t tension_floats = tiled_extent(tiles, tension_tile_stride, 1);
+        if (ranges_overlap(state, state_floats, tension, tension_floats) || ranges_overlap(tether, tether_floats, tension, tension_floats)
+            || ranges_overlap(out, out_floats, tension, tension_floats))
+            return fail(h, HYDRO_E_ARG, "tension must not overlap an input (state, tether) or out");
+    }
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (n == 0) return HYDRO_OK;
+    hipLaunchKernelGGL(tether_wrench_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
+                       tether, (uint32_t)tether_tile_stride, out, (uint32_t)out_tile_stride, tension, tension ? (uint32_t)tension_tile_stride : 0u, (uint32_t)n);
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+int hydro_step_fused_tiled_multi_teth(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                      const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float* state_out, int64_t out_tile_stride,
+                                      float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double* ke_out_dev,
+                                      float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t* rows_written_host,
+                                      const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float* control, int64_t control_tile_stride,
+                                      const float* mooring, int64_t mooring_tile_stride,
+                                      float* extremes, int64_t extremes_tile_stride,
+                                      const float* tether, int64_t tether_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    m.bed_entry = true;
+    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
+    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
+    m.tether = tether; m.tether_tile_stride = tether_tile_stride;
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -615,6 +615,46 @@ class HydroEngine:
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream, extra)
 
+    # ------------------------------------------------------------------ tethers
+    def tether_wrench(self, state: torch.Tensor, tether: torch.Tensor, n: int, out: torch.Tensor | None = None,
+                      tension: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The wrench of each body's tether on the tiled `state` (hydro_tether_wrench; the model: include/hydro.h,
+        "Tether"): `tether` is a tiled (tiles, 7, 64) buffer of [b(3) | L0 | k | c | partner lane] per body; the result a
+        tiled (tiles, 6, 64) buffer of [Fx Fy Fz | Tx Ty Tz], world frame, force at and torque about the body origin -
+        exactly what a step of `step_fused_tiled_multi_teth` that starts from `state` adds; zeros where the line adds
+        nothing.  `tension`, if given, is a tiled (tiles, 1, 64) buffer that receives T."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        t_ptr, t_stride = self._tiled(tether, nat.TETH_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
+        T_ptr, T_stride = self._tiled(tension, 1, n) if tension is not None else (None, 0)
+        self._check(self._lib.hydro_tether_wrench(self._h, n, s_ptr, s_stride, t_ptr, t_stride, o_ptr, o_stride, T_ptr, T_stride,
+                                                  self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_teth(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                    tether: torch.Tensor | None, extremes: torch.Tensor | None = None, mooring: torch.Tensor | None = None,
+                                    control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                    log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                    state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                    ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_ext with one tension-only line between two bodies of a tile (hydro_step_fused_tiled_multi_teth):
+        `tether` is the tiled (tiles, 7, 64) record of `tether_wrench`, read in every step.  A taut tether adds equal and
+        opposite spring and damper forces along itself at the two fairleads, formed from the true states the step starts
+        from, behind the mooring line's wrench and in front of the integrator.  extremes, mooring, control, applied, log,
+        the sea and the bed are each optional; tether=None is step_fused_tiled_multi_ext.  Returns the number of rows
+        written (0 without a log)."""
+        def extra():
+            tail = self._applied_control(applied, frame, control, n)
+            m_ptr, m_stride = self._tiled(mooring, nat.MOOR_FIELDS, n) if mooring is not None else (None, 0)
+            e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
+            t_ptr, t_stride = self._tiled(tether, nat.TETH_FIELDS, n) if tether is not None else (None, 0)
+            return (*tail, m_ptr, m_stride, e_ptr, e_stride, t_ptr, t_stride, int(step0))
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_teth,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

@@ -28,6 +28,7 @@ from . import scenes
 from .engine import HydroEngine
 from .extremes import Extremes
 from .mooring import Mooring
+from .tether import Tether
 
 
 class KineticEnergyMonitor:
@@ -338,6 +339,8 @@ class ClosedLoopSim:
     _mooring_buf = None         # the buffer itself (made once)
     extremes = None             # track_extremes(): the extremes.Extremes view over the bodies' running extremes while they are tracked
     _extremes_view = None       # the view and its buffer (made once)
+    tether = None               # set_tether(): the tiled (tiles, 7, 64) record of the bodies' tethers while tethers are set
+    _tether_buf = None          # the buffer itself (made once)
 
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
@@ -635,8 +638,46 @@ class ClosedLoopSim:
             self.extremes = None
             self._graph = None
 
+    def set_tether(self, pairs, fairlead_a=(0.0, 0.0, 0.0), fairlead_b=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0) -> torch.Tensor:
+        """Tie bodies to each other: from now on every physics step of run_eager, run (graph replays included) and
+        run_resident lets one tension-only line per pair pull the two fairleads towards each other with equal and opposite
+        forces (hydro_step_fused_tiled_multi_teth; the model: include/hydro.h, "Tether"), evaluated INSIDE the stepping
+        kernel from the states each step starts from - the partner's state is read from its lane of the wavefront, so both
+        bodies of a pair must lie in one block of 64 (bodies 64 t .. 64 t + 63).  It acts together with a sea, a seabed,
+        mooring lines, extremes, an applied wrench, a pose hold and a recorder where those are set.
+        pairs (m, 2): body indices (a, b), each body in at most one pair; fairlead_a, fairlead_b (., 3): body frame of a
+        and of b; length: unstretched, m; stiffness: N/m; damping: N s/m - each a scalar / one row, or one row per pair.
+        `tether.Tether` validates them, and its rule of thumb (k dt^2 / mu, c dt / mu <= 0.04 with the pair's reduced mass)
+        is enforced for the bodies' masses: `Tether.for_pair(m_a, m_b, sim.dt)` gives stable defaults.  The tethers stay
+        until the next call or `clear_tether()`.
+        Returns `sim.tether`, the tiled (tiles, 7, 64) device buffer the kernels read, fields [b | L0 | k | c | partner].
+        Its address never changes: a winch on the device may rewrite L0 in it - on both lanes of a pair - between chunks on
+        `sim.stream`, and a graph replay sees the contents of the moment."""
+        if not self.fused:
+            raise ValueError("tethers live in the fused step kernels (fused=True)")
+        lines = Tether(pairs, fairlead_a, fairlead_b, length=length, stiffness=stiffness, damping=damping, n=self.n)
+        lines.check_stable(np.asarray(self.scene.params, np.float64)[:, 10], self.dt)
+        with np.errstate(over="ignore"):
+            rec = lines.record.astype(np.float32)
+        if not np.isfinite(rec).all():
+            raise ValueError("tether: a value is out of fp32 range")
+        if self._tether_buf is None:
+            self._tether_buf = self.engine.alloc_tiled(nat.TETH_FIELDS, self.n)
+        with torch.cuda.stream(self.stream):
+            self._tether_buf.copy_(torch.from_numpy(scenes.to_tiled(rec)))
+        if self.tether is None:
+            self._graph = None                                              # captured steps are of another entry
+        self.tether = self._tether_buf
+        return self.tether
+
+    def clear_tether(self) -> None:
+        """Cut the tethers: every call the sim makes is again the one it made before set_tether."""
+        if self.tether is not None:
+            self.tether = None
+            self._graph = None
+
     # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
-    # the extremes if they are tracked, else with the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
+    # the tethers if tethers are set, else with the extremes if they are tracked, else with the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
     # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
     # graph captures: the single-step form of the entries, the bits of the single-step entry, include/hydro.h).  The plain
     # step has two forms: single_step=True is one hydro_step_fused_tiled (or the two-kernel path, fused=False), else one
@@ -649,7 +690,10 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.extremes is not None:
+        if self.tether is not None:
+            rows = e.step_fused_tiled_multi_teth(*args, k, self.steps_done, self.tether, self.extremes.buffer if self.extremes is not None else None,
+                                                 self.mooring, self.control, self.applied, self.applied_frame, **kw)
+        elif self.extremes is not None:
             rows = e.step_fused_tiled_multi_ext(*args, k, self.steps_done, self.extremes.buffer, self.mooring, self.control, self.applied,
                                                 self.applied_frame, **kw)
         elif self.mooring is not None:

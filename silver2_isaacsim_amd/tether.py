@@ -1,0 +1,159 @@
+"""Tethers for the closed loop: one tension-only line between two bodies of the same tile of 64.
+
+`Tether` builds and validates the (n, 7) record `ClosedLoopSim.set_tether` tiles onto the device and
+`HydroEngine.step_fused_tiled_multi_teth` / `tether_wrench` take.  The kernels evaluate the model of include/hydro.h
+("Tether") in fp32 inside every physics step, the partner's fairlead handed over between the lanes of a wavefront;
+`Tether.wrench` restates it on the host in fp64 NumPy - for checking a recorded trajectory, for sizing a line.
+
+For a body with position p, rotation R, velocity v, angular velocity omega and fairlead b (body frame), its partner with
+the same primed, and a line of unstretched length L0, stiffness k and damping c:
+
+    r    = R b,  P = p + r,  U = v + omega x r      the fairlead, world frame, and its velocity
+    e    = P' - P                                   fairlead -> partner's fairlead,  l = |e|
+    x    = l - L0                                   the line is taut only if x > 0
+    rate = (U' - U) . e / l                         > 0: the fairleads part
+    T    = max(0, k x + c rate)                     a line cannot push
+    F    = T e / l,    W = (F, r x F)               and -F on the partner
+
+A body has a tether if k > 0 or c > 0.  Both bodies of a pair lie in one tile (bodies 64 t .. 64 t + 63): the record names
+the partner as a lane of that tile.  This is an explicit spring between two masses: with the reduced mass
+mu = m_a m_b / (m_a + m_b), k dt^2 / mu and c dt / mu must stay at or below 0.04 (`STABLE`, the mooring's rule);
+`Tether.for_pair(m_a, m_b, dt)` gives k = 0.004 mu / dt^2 and c = 0.02 mu / dt, and `check_stable` refuses a record that
+breaks the rule.  Not modelled: chains and several tethers per body, pairs across tiles, the line's mass, sag and drag.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .mooring import DEFAULT_C, DEFAULT_K, STABLE
+from .seabed import rotation_matrices
+
+FIELDS = 7                      # b(3) | L0 | k | c | partner lane
+TILE = 64
+
+
+class Tether:
+    def __init__(self, pairs, fairlead_a=(0.0, 0.0, 0.0), fairlead_b=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0, n: int):
+        """`pairs` (m, 2) body indices (a, b); `fairlead_a`, `fairlead_b` (m, 3) body frame of a and of b; `length`,
+        `stiffness`, `damping` (m,) - each broadcast to the m pairs; `n`: the number of bodies of the scene.  ValueError
+        for a body tied to itself, a body in two pairs, an index outside 0 .. n - 1, a pair across two tiles of 64, a
+        non-finite value or a negative length, stiffness or damping."""
+        n = int(n)
+        pairs = np.asarray(pairs)
+        if pairs.size == 0:
+            pairs = np.zeros((0, 2), np.int64)
+        if pairs.ndim == 1 and pairs.shape == (2,):
+            pairs = pairs[None]
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+            raise ValueError("tether: pairs must be (m, 2) integer body indices")
+        pairs = pairs.astype(np.int64)
+        m = pairs.shape[0]
+        if m and (pairs.min() < 0 or pairs.max() >= n):
+            raise ValueError(f"tether: a body index is outside 0 .. {n - 1}")
+        for a, b in pairs:
+            if a == b:
+                raise ValueError(f"tether: body {a} is tied to itself")
+        seen, counts = np.unique(pairs, return_counts=True)
+        if (counts > 1).any():
+            raise ValueError(f"tether: body {int(seen[np.argmax(counts > 1)])} is in two pairs (at most one tether per body)")
+        for a, b in pairs:
+            if a // TILE != b // TILE:
+                raise ValueError(f"tether: bodies {a} and {b} lie in tiles {a // TILE} and {b // TILE}; a pair must lie inside one "
+                                 f"block of {TILE} bodies ({TILE} t .. {TILE} t + {TILE - 1}) - lay the pair out inside one block of {TILE}")
+        fa, fb = np.asarray(fairlead_a, np.float64), np.asarray(fairlead_b, np.float64)
+        for f in (fa, fb):
+            if f.ndim > 2 or f.shape[-1:] != (3,):
+                raise ValueError("tether: a fairlead must be (3,) or (m, 3)")
+        per_pair = np.empty((m, 9), np.float64)
+        try:
+            per_pair[:, 0:3] = fa
+            per_pair[:, 3:6] = fb
+            per_pair[:, 6] = np.asarray(length, np.float64)
+            per_pair[:, 7] = np.asarray(stiffness, np.float64)
+            per_pair[:, 8] = np.asarray(damping, np.float64)
+        except ValueError as e:
+            raise ValueError(f"tether: a field does not fit {m} pairs ({e})") from None
+        if not np.isfinite(per_pair).all():
+            raise ValueError("tether: non-finite value")
+        if (per_pair[:, 6:9] < 0.0).any():
+            raise ValueError("tether: length, stiffness and damping must be >= 0")
+        rec = np.zeros((n, FIELDS), np.float64)
+        rec[:, 6] = np.arange(n) % TILE                                     # a body without a tether names itself
+        a, b = pairs[:, 0], pairs[:, 1]
+        rec[a, 0:3], rec[b, 0:3] = per_pair[:, 0:3], per_pair[:, 3:6]
+        rec[a, 3:6] = rec[b, 3:6] = per_pair[:, 6:9]
+        rec[a, 6], rec[b, 6] = b % TILE, a % TILE
+        self.pairs = pairs
+        self.record = rec
+
+    @property
+    def n(self) -> int:
+        return self.record.shape[0]
+
+    @property
+    def partner(self) -> np.ndarray:
+        """(n,) the body each body's record names: its partner, itself without a tether."""
+        i = np.arange(self.n)
+        return (i // TILE) * TILE + (self.record[:, 6].astype(np.int64) & (TILE - 1))
+
+    @staticmethod
+    def for_pair(m_a, m_b, dt: float):
+        """The default (stiffness, damping) of a tether between bodies of mass `m_a` and `m_b` stepped with `dt`:
+        k = 0.004 mu / dt^2, c = 0.02 mu / dt with the reduced mass mu = m_a m_b / (m_a + m_b) - a tenth and a half of the
+        stability bound (include/hydro.h)."""
+        if not dt > 0.0:
+            raise ValueError("dt must be > 0")
+        m_a, m_b = np.asarray(m_a, np.float64), np.asarray(m_b, np.float64)
+        if not (np.isfinite(m_a).all() and (m_a > 0.0).all() and np.isfinite(m_b).all() and (m_b > 0.0).all()):
+            raise ValueError("mass must be finite and > 0")
+        mu = m_a * m_b / (m_a + m_b)
+        k, c = DEFAULT_K * mu / dt ** 2, DEFAULT_C * mu / dt
+        return (float(k), float(c)) if mu.ndim == 0 else (k, c)
+
+    def check_stable(self, mass, dt: float) -> None:
+        """ValueError if a tether breaks the rule of thumb k dt^2 / mu <= 0.04, c dt / mu <= 0.04 for bodies of `mass`
+        ((n,) or a scalar), mu the pair's reduced mass."""
+        if not dt > 0.0:
+            raise ValueError("dt must be > 0")
+        mass = np.broadcast_to(np.asarray(mass, np.float64), (self.n,))
+        if not len(self.pairs):
+            return
+        a, b = self.pairs[:, 0], self.pairs[:, 1]
+        mu = mass[a] * mass[b] / (mass[a] + mass[b])
+        tol = 1.0 + 1e-9
+        ks, cs = self.record[a, 4] * dt ** 2 / mu, self.record[a, 5] * dt / mu
+        if (ks > STABLE * tol).any() or (cs > STABLE * tol).any():
+            i = int(np.argmax(np.maximum(ks, cs)))
+            raise ValueError(f"tether: pair ({a[i]}, {b[i]}) has k dt^2 / mu = {ks[i]:.3g}, c dt / mu = {cs[i]:.3g}; both must be <= "
+                             f"{STABLE} (an explicit spring on the reduced mass: Tether.for_pair gives stable defaults)")
+
+    def geometry(self, state):
+        """(r, e, l, x, rate) of (n, 13) states: arm, fairlead -> partner's fairlead, its length, the stretch, the rate at
+        which the fairleads part."""
+        s = np.asarray(state, np.float64)
+        t, j = self.record, self.partner
+        r = np.einsum("nij,nj->ni", rotation_matrices(s[:, 3:7]), t[:, 0:3])
+        P = s[:, 0:3] + r
+        U = s[:, 7:10] + np.cross(s[:, 10:13], r)
+        e = P[j] - P
+        l = np.sqrt((e * e).sum(-1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rate = ((U[j] - U) * e).sum(-1) / l
+        return r, e, l, l - t[:, 3], rate
+
+    def tension(self, state) -> np.ndarray:
+        """(n,) tether tension T >= 0 (0 for a body without a tether or with a slack one); equal on both bodies of a pair."""
+        t = self.record
+        _, _, _, x, rate = self.geometry(state)
+        has = (t[:, 4] > 0.0) | (t[:, 5] > 0.0)
+        with np.errstate(invalid="ignore"):
+            T = np.maximum(0.0, t[:, 4] * x + t[:, 5] * rate)
+            return np.where(has & (x > 0.0) & (T > 0.0), T, 0.0)
+
+    def wrench(self, state) -> np.ndarray:
+        """(n, 6) tether wrench [F | torque about the body origin], world frame, of (n, 13) states [p | q xyzw | v | omega], fp64."""
+        r, e, l, _, _ = self.geometry(state)
+        T = self.tension(state)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            F = np.where((T > 0.0)[:, None], (T / l)[:, None] * e, 0.0)
+        return np.concatenate([F, np.cross(r, F)], -1)
