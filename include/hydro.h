@@ -487,9 +487,11 @@ int hydro_step_fused_tiled_multi_ctl(hydro_t *h, int64_t n, const float *state, 
  * the density and gravity of hydro_set_scene.  The hydrodynamic wrench is translation-invariant in x and y and sees the water
  * only through the depth of the body centre and the body's velocity, so moving water is the SAME wrench evaluated on a
  * relative state: depth below the local surface, velocity against the local water.  The integrator, the applied wrench, the
- * pose hold, the recorder and the kinetic energy keep acting on the true state.  Only hydro_step_fused_tiled_multi_sea and
- * hydro_sea_sample know the sea: the wrench-only, array-of-structs, batch, component and plugin entries, and the other
- * closed-loop entries, step through still water with its surface at z = 0 whatever is set here.
+ * pose hold, the recorder and the kinetic energy keep acting on the true state.  Only hydro_step_fused_tiled_multi_sea (and
+ * the entries built on it), hydro_sea_sample and the two open-loop entries hydro_step_wrench_tiled_sea and
+ * hydro_step_wrench_aos_sea ("Sea state, open loop" below; the plugin steps through the latter) know the sea: every other
+ * wrench-only, array-of-structs, batch and component entry, and the other closed-loop entries, step through still water with
+ * its surface at z = 0 whatever is set here.
  *
  * hydro_sea_t: `current` U (m/s, world frame) and `waves` = 0 .. HYDRO_SEA_WAVES_MAX components, each an amplitude a >= 0 (m),
  * a wave vector (kx, ky) (rad/m, world frame, kappa = |k| > 0 unless a == 0), an angular frequency omega (rad/s) and a phase
@@ -565,6 +567,35 @@ int hydro_step_fused_tiled_multi_sea(hydro_t *h, int64_t n, const float *state, 
                                      int64_t row0, int64_t *rows_written_host,
                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
                                      const float *control, int64_t control_tile_stride, int64_t step0, void *stream);
+
+/* Sea state, open loop: the sea for the caller who integrates - a simulator behind the plugin (PhysX integrates, the plugin
+ * supplies the wrench) or an integrator of one's own around hydro_step_wrench_tiled.  Two entries, each with the argument list
+ * of its parent and `double time` in front of `stream`:
+ *     hydro_step_wrench_tiled_sea = hydro_step_wrench_tiled    hydro_step_wrench_aos_sea = hydro_step_wrench_aos
+ * MODEL.  "WATER AT A BODY" above with ONE change: t = time, in seconds, an fp64 value taken as given, replaces
+ * t = (step0 + k) * dt.  Everything from x_j = fma(-omega_j, t, phi_j) onwards is the stated order, in the same code.  The
+ * wrench is that of the state with p_z - eta and v - u and of the previous velocity with pv[0:3] - u: fp32 subtractions with
+ * the same u, so the finite-difference acceleration stays the body's own.
+ * IDENTITY.  (double)1 * time == time exactly, so hydro_sea_sample(step_index = 1, dt = time) writes exactly the [eta, u] these
+ * entries use at time > 0; at time == 0 it is step_index = 0 (with any dt > 0).  A step is therefore, bit for bit, the parent
+ * entry on the relative state built from that sample.
+ * PREVIOUS VELOCITY.  The engine-owned previous velocity (the array-of-structs entry; the tiled entry with prev == NULL)
+ * receives the TRUE velocity, never the relative one.  With a caller-owned `prev` nothing is written but the wrench.
+ *   no sea set      : the launch and its bits are those of the parent entry with the same arguments (`time` is validated all
+ *                     the same).
+ *   a sea set       : kernels of their own beside the parents' (256-thread blocks whatever hydro_set_tuning's block_threads says).
+ * A sea with no current and no waves (or waves of amplitude 0) gives the parent's bits, sign of zero included.  HYDRO_E_ARG for
+ * a non-finite time, time < 0 or time > 2^52; after that the parent's refusals in the parent's order - all before anything is
+ * launched or written.  Asynchronous, no allocation, no synchronisation, safe to capture: a captured launch replays at the
+ * frozen `time` it was captured with - capture current-only seas.
+ * NOT COVERED - these step through still water whatever is set: hydro_step_wrench_tiled_ke, hydro_step_wrench_tiled_batch, the
+ * plain-SoA hydro_step_wrench[_ext], and the component / calculator entries hydro_step_components[_aos] (the calculator takes
+ * explicit accelerations and keeps the reference's signature).  Cost and registers: DESIGN.md section 23. */
+int hydro_step_wrench_tiled_sea(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                const float *prev, int64_t prev_tile_stride, double dt,
+                                float *wrench, int64_t wrench_tile_stride, double time, void *stream);
+int hydro_step_wrench_aos_sea(hydro_t *h, int64_t n, const float *positions, const float *orientations, int quat_xyzw,
+                              const float *velocities, double dt, float *forces, float *torques, double time, void *stream);
 
 /* Seabed: a floor under the water for the closed-loop steps - the horizontal plane z = z_b, scene-wide like the density, the
  * gravity and the sea.  A body touches it through the EIGHT CORNERS of the box the buoyancy already uses (x/y/zDimension),

@@ -129,13 +129,52 @@ class _AosStepper:
         self._key = key if same else None               # converted copies are good for this step only
         return p
 
-    def launch(self, dt: float) -> None:
-        self._step(dt)
+    def launch(self, dt: float, time: float | None = None) -> None:
+        """time None: `hydro_step_wrench_aos`, the call made without a sea; otherwise the `_sea` entry at `time` seconds."""
+        if time is None:
+            self._step(dt)
+        else:
+            self._step(dt, None, time)
 
-    def __call__(self, positions, orientations, velocities, dt: float) -> torch.Tensor:
+    def __call__(self, positions, orientations, velocities, dt: float, time: float | None = None) -> torch.Tensor:
         p = self.accept(positions, orientations, velocities)
-        self.launch(dt)
+        self.launch(dt, time)
         return p
+
+
+class _SeaClock:
+    """What a stepping unit - a `_Group`, or a behaviour with batched=False - keeps for the scene's sea (REGISTRY.set_sea):
+    `sea_time`, the fp64 sum, in order, of the delta_time of the unit's EARLIER physics-step callbacks (every callback past the
+    reference's 1e-6 guard counts, also one whose state fetch fails), and which version of the registry's sea its engine
+    holds.  The clock starts at 0 with the unit; a rebuild of the engine does not touch it.  Without a sea `sea_for` gives None
+    and the unit makes the calls it makes without this class."""
+
+    def __init__(self):
+        self.sea_time = 0.0
+        self._sea_seen = 0                  # the registry's sea_version this unit's engine was last given (0: never any)
+        self._sea_set = False
+
+    def start(self) -> None:
+        self.sea_time = 0.0
+
+    def tick(self, delta_time: float) -> float:
+        """Count this callback; returns the time of the state it fetches."""
+        now = self.sea_time
+        self.sea_time = now + float(delta_time)
+        return now
+
+    def new_engine(self) -> None:
+        self._sea_seen, self._sea_set = 0, False
+
+    def sea_for(self, engine, now: float) -> float | None:
+        """Bring `engine` up to the registry's sea if that changed (or the engine is new); `now` if a sea is set, else None."""
+        if self._sea_seen != REGISTRY.sea_version:
+            sea = REGISTRY.sea
+            if sea is not None or self._sea_set:
+                engine.sync()               # hydro_set_sea runs on the engine's own stream: earlier steps have to be done
+                engine.set_sea(sea)
+            self._sea_seen, self._sea_set = REGISTRY.sea_version, sea is not None
+        return now if self._sea_set else None
 
 
 class _Group:
@@ -160,6 +199,7 @@ class _Group:
         self.subscription = None            # the group's own physics-step subscription (scene mode)
         self.scene_members = 0              # members that rely on it
         self._engine_error_logged = False
+        self.clock = _SeaClock()            # starts with the group; rebuild() keeps it
 
     def add(self, b: "HydrodynamicsBehavior") -> None:
         if len(self.members) != len(self.member_set):       # somebody left since the last rebuild: compact first
@@ -233,6 +273,7 @@ class _Group:
         self.force = torch.empty((n, 3), dtype=torch.float32, device=self.engine.device)
         self.torque = torch.empty((n, 3), dtype=torch.float32, device=self.engine.device)
         self._stepper = _AosStepper(self.engine, self.force, self.torque)
+        self.clock.new_engine()
         self._rows = {m: i for i, m in enumerate(self.members)}
         if carried is not None:
             old_prev, old_rows = carried
@@ -245,7 +286,12 @@ class _Group:
                 self.engine.set_prev_velocity(prev)
         self.dirty = False
 
+    @property
+    def sea_time(self) -> float:
+        return self.clock.sea_time
+
     def step(self, dt: float) -> None:
+        now = self.clock.tick(dt)
         if self.dirty:
             self.rebuild()
         if self.view is None or not self.view.is_valid():
@@ -259,7 +305,8 @@ class _Group:
         except _STATE_FETCH_ERRORS:
             return
         try:
-            self._stepper.launch(dt)                    # engine errors are NOT a fetch failure: they surface
+            # engine errors are NOT a fetch failure: they surface
+            self._stepper.launch(dt, self.clock.sea_for(self.engine, now) if REGISTRY.sea_version else None)
         except HydroError as e:
             if not self._engine_error_logged:
                 self._engine_error_logged = True
@@ -283,6 +330,20 @@ class EngineRegistry:
 
     def __init__(self):
         self._groups: dict[tuple, _Group] = {}
+        # the scene's sea (sea.SeaState or None), scene-wide like rho and g; every stepping unit compares sea_version with
+        # the one its engine holds, once per step.  0: no sea has ever been set - the units make today's calls
+        self.sea = None
+        self.sea_version = 0
+        self._sea_source = None             # "python" (set_sea) or "config" (the JSON's "sea" block)
+
+    def set_sea(self, sea, source: str = "python") -> bool:
+        """The sea of every engine the plugin owns, now and later; None clears it.  A sea from the JSON configuration
+        (source="config") yields to one set from Python, and only the first block found counts.  Returns whether it was taken."""
+        if source == "config" and self._sea_source is not None:
+            return False
+        self.sea, self._sea_source = sea, source
+        self.sea_version += 1
+        return True
 
     def register(self, b: "HydrodynamicsBehavior") -> _Group:
         # the subscription mode is part of the key: a group is driven EITHER by its own subscription (scene mode) or by
@@ -319,6 +380,9 @@ class EngineRegistry:
         for grp in self._groups.values():
             grp.close()
         self._groups.clear()
+        if self.sea_version:
+            self.sea, self._sea_source = None, None
+            self.sea_version += 1
 
 
 REGISTRY = EngineRegistry()
@@ -351,6 +415,20 @@ class HydrodynamicsBehavior:
         self._group: _Group | None = None
         self._engine: HydroEngine | None = None
         self._callbacks = 0                 # physics-step callbacks received since the group last changed
+        self._clock = _SeaClock()           # batched=False: this behaviour is its own stepping unit (restarted by on_play)
+
+    @staticmethod
+    def set_sea(sea) -> None:
+        """The scene's moving water (sea.SeaState: a current and up to 8 regular waves; None clears it), scene-wide like the
+        water density and gravity: it applies to every engine the plugin owns - the groups', those of batched=False
+        behaviours, and engines built later - and may change between physics steps.  Every stepping unit evaluates it at its
+        own clock: the sum of the delta_time of its earlier physics-step callbacks since it started."""
+        REGISTRY.set_sea(sea)
+
+    @property
+    def sea_time(self) -> float:
+        """The clock of this behaviour's stepping unit: its group's, or its own with batched=False."""
+        return self._group.sea_time if self._group is not None else self._clock.sea_time
 
     # -- lifecycle -----------------------------------------------------------
     def on_init(self):
@@ -383,6 +461,9 @@ class HydrodynamicsBehavior:
                 return
             for name, value in cfg.resolve_overrides(self.prim.GetName(), data).items():
                 self._set_attr(name, value)
+            # an optional "sea" block (the reference reads `globals` and `parts` only): the first one found is the scene's sea
+            if isinstance(data, dict) and "sea" in data and REGISTRY._sea_source is None:
+                REGISTRY.set_sea(cfg.sea_from_config(data), source="config")
         except Exception as e:                                    # noqa: BLE001 - reference swallows and logs (:111-112)
             log.error("[Hydro] JSON Error: %s", e)
 
@@ -396,6 +477,7 @@ class HydrodynamicsBehavior:
             self._request_property_rebuild()                               # (:124-126)
 
     def on_play(self):
+        self._clock.start()
         self._setup()
         if self._batched and self._scene_mode:
             # one subscription per GROUP: host time per physics step does not grow with the number of prims
@@ -416,9 +498,10 @@ class HydrodynamicsBehavior:
             if self._group is not None and not (self._scene_mode and self._group.subscription is not None):
                 EngineRegistry.on_step(self._group, self, delta_time)
             return
+        now = self._clock.tick(delta_time)
         if self._rigid_prim_view is None or not self._rigid_prim_view.is_valid():
             return
-        self._apply_behavior(delta_time)
+        self._apply_behavior(delta_time, now)
 
     def _get_exposed_variable(self, attr_name):
         return self._host.get_exposed_variable(self.prim, cfg.full_attr_name(attr_name))
@@ -451,9 +534,10 @@ class HydrodynamicsBehavior:
         self._force = torch.empty((1, 3), dtype=torch.float32, device=self._engine.device)
         self._torque = torch.empty((1, 3), dtype=torch.float32, device=self._engine.device)
         self._stepper = _AosStepper(self._engine, self._force, self._torque)
+        self._clock.new_engine()
         log.info("HydrodynamicsBehavior (HIP) initialized for %s", self._prim_path)
 
-    def _apply_behavior(self, delta_time):
+    def _apply_behavior(self, delta_time, now: float = 0.0):
         try:
             positions, orientations = self._rigid_prim_view.get_world_poses(clone=False)
             full_velocities = self._rigid_prim_view.get_velocities(clone=False)
@@ -465,7 +549,7 @@ class HydrodynamicsBehavior:
         # quaternion reorder, finite-difference acceleration, model, lever arms, sum and clamp
         # (hydrodynamics_behavior.py:194-226) are one kernel; the previous velocity lives in the engine.  Engine errors
         # propagate, as an exception of the reference's calculator call (:205-209) would.
-        self._stepper.launch(delta_time)
+        self._stepper.launch(delta_time, self._clock.sea_for(self._engine, now) if REGISTRY.sea_version else None)
         self._rigid_prim_view.apply_forces_and_torques_at_pos(
             forces=self._force, torques=self._torque, positions=positions, is_global=True)
 

@@ -98,6 +98,36 @@ def load_config(path: str | None) -> dict | None:
         return json.load(f)
 
 
+def sea_from_config(data: Mapping[str, Any]):
+    """The optional top-level "sea" block of the configuration file as a `sea.SeaState`, or None without one:
+        {"current": [x, y, z], "waves": [{"height": m, "period": s, "heading_deg": deg, "phase": rad}, ...]}
+    Both keys are optional; every wave is built by `SeaState.regular` (deep-water dispersion relation) with the file's gravity
+    (`globals.gravity`, default 9.81).  The reference reads `globals` and `parts` only and ignores the block.  Raises
+    ValueError / TypeError / KeyError on a malformed block - the plugin logs that and keeps going, like other JSON errors."""
+    from .sea import SeaState
+    block = data.get("sea")
+    if block is None:
+        return None
+    if not isinstance(block, Mapping):
+        raise ValueError('"sea" must be an object')
+    unknown = set(block) - {"current", "waves"}
+    if unknown:
+        raise ValueError(f'"sea": unknown keys {sorted(unknown)}')
+    g = float(data.get("globals", {}).get("gravity", GLOBALS["gravity"]))
+    sea = SeaState(tuple(block.get("current", (0.0, 0.0, 0.0))))
+    waves = block.get("waves", [])
+    if not isinstance(waves, (list, tuple)):
+        raise ValueError('"sea.waves" must be a list')
+    for w in waves:
+        unknown = set(w) - {"height", "period", "heading_deg", "phase"}
+        if unknown:
+            raise ValueError(f'"sea.waves": unknown keys {sorted(unknown)}')
+        one = SeaState.regular(float(w["height"]), float(w["period"]), float(w.get("heading_deg", 0.0)),
+                               float(w.get("phase", 0.0)), g=g)
+        sea.add_wave(*one.waves[0])
+    return sea
+
+
 def match_part(prim_name: str, parts: Mapping[str, Any]) -> str | None:
     """First key of `parts` (dict order) contained in the lower-cased prim name;
     fall back to 'body' if the name contains it (hydrodynamics_behavior.py:91-101)."""

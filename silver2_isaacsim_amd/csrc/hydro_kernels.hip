@@ -1645,6 +1645,83 @@ __global__ void __launch_bounds__(kBlock) sea_sample_kernel(const float* st, uin
 }
 
 // --------------------------------------------------------------------------
+// The sea in the OPEN-LOOP steps (hydro_step_wrench_tiled_sea, hydro_step_wrench_aos_sea): the wrench-only kernels with the
+// view formed between their loads and body_wrench.  New kernels beside wrench_tiled_kernel and wrench_aos_direct_kernel, which
+// stay as they are (their instruction budget is the headline's); the host launches these only while a sea is set.
+//   time  : the caller's, in seconds, handed over as (step, sea_dt) with (double)step * sea_dt == time exactly - step = 1,
+//           sea_dt = time, or step = 0 at time 0 - so that sea_water stays the only implementation of the view.
+//   prev  : single-step kernels, nothing is parked: the TRUE velocity goes to the engine's record before the view is formed
+//           (its stores are issued early and no true value stays live across body_wrench); a caller-owned record is only read.
+// --------------------------------------------------------------------------
+__device__ __forceinline__ void sea_relative(SeaTablePtr tab, uint32_t waves, int64_t step, double sea_dt,
+                                             float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS])
+{
+    float eta, u[3];
+    sea_water(tab, waves, step, sea_dt, s[0], s[1], s[2], eta, u);
+    s[2] = s[2] - eta;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        s[7 + i] = s[7 + i] - u[i];
+        pv[i] = pv[i] - u[i];
+    }
+}
+
+// wrench_tiled_kernel<256, HALF, ENGINE_PREV, NT, no KE, WARP>'s arguments (the same 16 preloaded dwords), then the sea's.
+template <bool HALF, bool ENGINE_PREV, bool NT, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_TILED_OCC_ATTR wrench_tiled_sea_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_out, float* k_pv_out,
+                                                             uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
+                                                             uint32_t n, int warp, double rho, double g, double inv_dt,
+                                                             const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u;
+    const uint32_t first = tile * 64u;
+    const uint32_t left = n - __builtin_amdgcn_readfirstlane(n < first ? n : first);       // (scalar, see wrench_tiled_kernel)
+    if (lane >= left) return;
+    const uint32_t lane4 = lane * 4u;
+    float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass, f6[HYDRO_WRENCH_FIELDS];
+    load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
+    if constexpr (ENGINE_PREV) store_record<HYDRO_PREV_FIELDS, NT>(k_pv_out + (size_t)tile * pvo_stride, lane4, s + 7);
+    sea_relative(sea_table_ptr(sea_table), sea_waves, step, sea_dt, s, pv);
+    wrench_fields(body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP), f6);
+    store_record<HYDRO_WRENCH_FIELDS, NT>(k_out + (size_t)tile * out_stride, lane4, f6);
+}
+
+// wrench_aos_direct_kernel's arguments and frame - the same row accesses, temporal row loads - then the sea's.
+template <bool HALF, bool NT, bool WARP>
+__global__ void __launch_bounds__(kBlock) wrench_aos_sea_kernel(const float* k_pos, const float* k_quat, const float* k_vel, float* k_force, float* k_torque,
+                                                               float* k_pv, const float* k_prm, int quat_xyzw, uint32_t n,      // 16 dwords: preloaded
+                                                               int warp, double rho, double g, double inv_dt,
+                                                               const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const size_t first = (size_t)tile * 64u;
+    const float* t_pos = k_pos + first * 3; const float* t_quat = k_quat + first * 4; const float* t_vel = k_vel + first * 6;
+    float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
+    constexpr bool RNT = false;                              // (the simulator's rows: temporal, see wrench_aos_direct_kernel)
+    const f3_a4 p = ld_f3_a4<RNT>(t_pos, lane * 12u);
+    const f4_a16 q = ld_f4_a16<RNT>(t_quat, lane * 16u);
+    const f4_a8 v0 = ld_f4_a8<RNT>(t_vel, lane * 24u);
+    const f2_a8 v1 = ld_f2_a8<RNT>(t_vel, lane * 24u + 16u);
+    s[0] = p.x; s[1] = p.y; s[2] = p.z;
+    if (quat_xyzw) { s[3] = q.x; s[4] = q.y; s[5] = q.z; s[6] = q.w; }
+    else           { s[3] = q.y; s[4] = q.z; s[5] = q.w; s[6] = q.x; }
+    s[7] = v0.x; s[8] = v0.y; s[9] = v0.z; s[10] = v0.w; s[11] = v1.x; s[12] = v1.y;
+    float* t_pv = k_pv + (size_t)tile * (HYDRO_PREV_FIELDS * HYDRO_TILE);
+#pragma unroll
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = ldg<NT>(at<float>(t_pv, lane4, f * 256u));
+    load_param_record<HALF, NT>(k_prm, tile, lane4, d, c, mass);
+#pragma unroll
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg_aos<NT>(at<float>(t_pv, lane4, f * 256u), s[7 + f]);     // the TRUE velocity
+    sea_relative(sea_table_ptr(sea_table), sea_waves, step, sea_dt, s, pv);
+    const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
+    f3_a4 fo, to;
+    fo.x = w.fx; fo.y = w.fy; fo.z = w.fz; to.x = w.tx; to.y = w.ty; to.z = w.tz;
+    st_f3_a4<NT>(k_force + first * 3, lane * 12u, fo);
+    st_f3_a4<NT>(k_torque + first * 3, lane * 12u, to);
+}
+
+// --------------------------------------------------------------------------
 // The SEABED in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_bed): the horizontal plane z = z_b under the
 // water, scene-wide like rho, g and the sea (hydro_set_seabed).  A body touches it through the eight corners of the box the
 // buoyancy already uses: per corner below the plane a mass-normalised spring and damper along z (no adhesion) and a Coulomb
@@ -2837,13 +2914,34 @@ int hydro_step_wrench_ext(hydro_t* h, int64_t n, const float* const state[HYDRO_
 }  // extern "C"
 
 namespace {
+// The `time` of the open-loop _sea entries (hydro_step_wrench_tiled_sea, hydro_step_wrench_aos_sea): checked whether or not a
+// sea is set.  The kernels take it as sea_water's (step, dt) pair: (double)1 * time == time exactly, and step 0 at time 0.
+int check_sea_time(hydro_engine* h, double time)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!(time >= 0.0) || !(time <= 4503599627370496.0)) return fail(h, HYDRO_E_ARG, "time must be finite, >= 0 and <= 2^52 seconds");
+    return HYDRO_OK;
+}
+inline int64_t sea_step(double time) { return time > 0.0 ? 1 : 0; }
+// The launches of the two sea kernels, DEFINED AT THE END OF THIS FILE: a kernel template is emitted where it is first
+// instantiated, and these 24 instantiations are to come behind every kernel the library had before them - the existing kernels
+// then keep their places in the code object, not only their code.
+void launch_wrench_tiled_sea(hydro_engine* h, dim3 grid, dim3 blk, size_t lds, hipStream_t s, const float* state, const float* pv,
+                             float* wrench, float* pv_out, uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
+                             int64_t n, double dt, bool own_prev, double time);
+void launch_wrench_aos_sea(hydro_engine* h, hipStream_t s, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                           const float* velocities, double dt, float* forces, float* torques, double time);
+
 // hydro_step_wrench_tiled, optionally sampling the kinetic energy of the state it reads (ke_out != nullptr)
 int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
                            const float* prev, int64_t prev_tile_stride, double dt,
-                           float* wrench, int64_t wrench_tile_stride, int ke_rotational, double* ke_out, void* stream)
+                           float* wrench, int64_t wrench_tile_stride, int ke_rotational, double* ke_out, void* stream,
+                           const double* sea_time = nullptr)
 {
-    int rc = check_common(h, n);
+    // sea_time: the _sea entry - the time is checked first, and the step goes through the sea if one is set
+    int rc = sea_time ? check_sea_time(h, *sea_time) : HYDRO_OK;
     if (rc) return rc;
+    if ((rc = check_common(h, n))) return rc;
     if (!(dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
     if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
     if ((rc = check_tiled(h, n, wrench, wrench_tile_stride, HYDRO_WRENCH_FIELDS, "null wrench"))) return rc;
@@ -2858,7 +2956,8 @@ int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t st
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (own_prev && (rc = prev_acquire(h, hydro_engine::kPrevTiled, n, s))) return rc;
     if (ke_out && (rc = ke_prepare(h, s))) return rc;
-    const int block = (h->block && !ke_out) ? h->block : 256;               // (the energy partials are one per 256 bodies)
+    const bool sea = sea_time && h->sea_waves >= 0;
+    const int block = (h->block && !ke_out && !sea) ? h->block : 256;       // (the energy partials are one per 256 bodies; the sea kernel exists for 256 only)
     const dim3 grid(grid_for(n, block)), blk(block);
     // Occupancy shaping: the kernel uses no LDS, so a dynamic-LDS request is a pure residency cap
     // (160 KB per CU / blocks per CU).  Fewer resident waves = fewer DRAM streams in flight.
@@ -2871,7 +2970,9 @@ int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t st
     }
     // ke_out: the sampling variant - same body, same bits, plus one fp64 pair per block and the fixed-order final sum (same
     // launch).  It exists for 256-thread blocks only, which is what `block` is whenever it is asked for.
-    dispatch_flags([&](auto BIG, auto HALF, auto WP, auto NT, auto KE, auto WARP) {
+    if (sea) launch_wrench_tiled_sea(h, grid, blk, lds, s, state, pv, wrench, pv_out, (uint32_t)state_tile_stride, pv_stride,
+                                     (uint32_t)wrench_tile_stride, pvo_stride, n, dt, own_prev, *sea_time);
+    else dispatch_flags([&](auto BIG, auto HALF, auto WP, auto NT, auto KE, auto WARP) {
         if constexpr (BIG || !KE)
             hipLaunchKernelGGL((wrench_tiled_kernel<BIG ? 256 : 128, HALF, WP, NT, KE, WARP>), grid, blk, lds, s,
                                state, pv, h->params_tiled, wrench, pv_out, (uint32_t)state_tile_stride, pv_stride, (uint32_t)wrench_tile_stride, pvo_stride,
@@ -2898,6 +2999,13 @@ int hydro_step_wrench_tiled(hydro_t* h, int64_t n, const float* state, int64_t s
                             float* wrench, int64_t wrench_tile_stride, void* stream)
 {
     return step_wrench_tiled_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, wrench, wrench_tile_stride, 0, nullptr, stream);
+}
+
+int hydro_step_wrench_tiled_sea(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                const float* prev, int64_t prev_tile_stride, double dt,
+                                float* wrench, int64_t wrench_tile_stride, double time, void* stream)
+{
+    return step_wrench_tiled_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, wrench, wrench_tile_stride, 0, nullptr, stream, &time);
 }
 
 int hydro_step_wrench_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -3656,10 +3764,15 @@ int hydro_repack(hydro_t* h, int64_t n, int fields, float* const soa[], float* t
     return repack(h, soa, fields, tiled, tile_stride, n, to_tiled != 0, static_cast<hipStream_t>(stream));
 }
 
-int hydro_step_wrench_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
-                          const float* velocities, double dt, float* forces, float* torques, void* stream)
+}  // extern "C"
+
+namespace {
+// hydro_step_wrench_aos; sea_time: the _sea entry - the time is checked first, and the step goes through the sea if one is set
+int step_wrench_aos_impl(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                         const float* velocities, double dt, float* forces, float* torques, void* stream, const double* sea_time)
 {
     const float* orientations_wxyz = orientations;
+    if (sea_time) { const int bad = check_sea_time(h, *sea_time); if (bad) return bad; }
     if (h && n > ((int64_t)1 << 26)) return fail(h, HYDRO_E_ARG, "array-of-structs entry handles at most 2^26 bodies per call");
     int rc = check_common(h, n);
     if (rc) return rc;
@@ -3672,13 +3785,29 @@ int hydro_step_wrench_aos(hydro_t* h, int64_t n, const float* positions, const f
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if ((rc = prev_acquire(h, hydro_engine::kPrevTiled, n, s))) return rc;
-    dispatch_flags([&](auto HALF, auto NT, auto WARP) {
+    if (sea_time && h->sea_waves >= 0) launch_wrench_aos_sea(h, s, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, *sea_time);
+    else dispatch_flags([&](auto HALF, auto NT, auto WARP) {
         hipLaunchKernelGGL((wrench_aos_direct_kernel<HALF, NT, WARP>), dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
                            positions, orientations, velocities, forces, torques, h->prev_tiled, h->params_tiled, quat_xyzw ? 1 : 0, (uint32_t)n,
                            h->semantics, h->rho, h->g, 1.0 / dt);
     }, h->half_coeffs, streaming(h, n), is_warp(h));
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hydro_step_wrench_aos(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                          const float* velocities, double dt, float* forces, float* torques, void* stream)
+{
+    return step_wrench_aos_impl(h, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, stream, nullptr);
+}
+
+int hydro_step_wrench_aos_sea(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                              const float* velocities, double dt, float* forces, float* torques, double time, void* stream)
+{
+    return step_wrench_aos_impl(h, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, stream, &time);
 }
 
 int hydro_step_components(hydro_t* h, int64_t n, const float* const state[HYDRO_STATE_FIELDS],
@@ -3960,3 +4089,29 @@ int hydro_sync(hydro_t* h)
 void* hydro_stream(hydro_t* h) { return h ? static_cast<void*>(h->stream) : nullptr; }
 
 }  // extern "C"
+
+namespace {
+// (see their declarations: last in the file on purpose)
+void launch_wrench_tiled_sea(hydro_engine* h, dim3 grid, dim3 blk, size_t lds, hipStream_t s, const float* state, const float* pv,
+                             float* wrench, float* pv_out, uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
+                             int64_t n, double dt, bool own_prev, double time)
+{
+    dispatch_flags([&](auto HALF, auto WP, auto NT, auto WARP) {
+        hipLaunchKernelGGL((wrench_tiled_sea_kernel<HALF, WP, NT, WARP>), grid, blk, lds, s,
+                           state, pv, h->params_tiled, wrench, pv_out, st_stride, pv_stride, out_stride, pvo_stride,
+                           (uint32_t)n, h->semantics, h->rho, h->g, 1.0 / dt,
+                           (const void*)h->sea_table, (uint32_t)h->sea_waves, sea_step(time), time);
+    }, h->half_coeffs, own_prev, streaming(h, n), is_warp(h));
+}
+
+void launch_wrench_aos_sea(hydro_engine* h, hipStream_t s, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                           const float* velocities, double dt, float* forces, float* torques, double time)
+{
+    dispatch_flags([&](auto HALF, auto NT, auto WARP) {
+        hipLaunchKernelGGL((wrench_aos_sea_kernel<HALF, NT, WARP>), dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
+                           positions, orientations, velocities, forces, torques, h->prev_tiled, h->params_tiled, quat_xyzw ? 1 : 0, (uint32_t)n,
+                           h->semantics, h->rho, h->g, 1.0 / dt,
+                           (const void*)h->sea_table, (uint32_t)h->sea_waves, sea_step(time), time);
+    }, h->half_coeffs, streaming(h, n), is_warp(h));
+}
+}  // namespace

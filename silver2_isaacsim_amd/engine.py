@@ -227,15 +227,19 @@ class HydroEngine:
         if ke_out.dtype != torch.float64 or ke_out.device != self.device or ke_out.numel() < 2 or not ke_out.is_contiguous():
             raise ValueError(f"ke_out: expected a contiguous float64 tensor of 2 elements on {self.device}")
 
-    def _wrench_tiled_call(self, state, n, dt, out, prev, stream, ke_out, rotational):
-        """(name, args, out) of one `hydro_step_wrench_tiled[_ke]` launch: the buffers validated, `out` allocated when
-        None, the stream resolved now."""
+    def _wrench_tiled_call(self, state, n, dt, out, prev, stream, ke_out, rotational, time=None):
+        """(name, args, out) of one `hydro_step_wrench_tiled[_ke | _sea]` launch: the buffers validated, `out` allocated when
+        None, the stream resolved now.  `time` (seconds) selects the `_sea` entry, which takes it in front of the stream."""
         s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
         if out is None:
             out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
         o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
         p_ptr, p_stride = self._prev_velocity(prev, n)
         args = (self._h, n, s_ptr, s_stride, p_ptr, p_stride, float(dt), o_ptr, o_stride)
+        if time is not None:
+            if ke_out is not None:
+                raise ValueError("the sea entry does not sample the kinetic energy (ke_out must be None)")
+            return "hydro_step_wrench_tiled_sea", args + (float(time), self._stream(stream)), out
         if ke_out is None:
             return "hydro_step_wrench_tiled", args + (self._stream(stream),), out
         self._check_ke_out(ke_out)                      # the variant that samples the kinetic energy of `state` on the way
@@ -254,23 +258,42 @@ class HydroEngine:
         self._check(getattr(self._lib, name)(*args))
         return out
 
+    def step_wrench_tiled_sea(self, state: torch.Tensor, n: int, dt: float, time: float, out: torch.Tensor | None = None,
+                              prev: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """`step_wrench_tiled` through the sea set with `set_sea`, at `time` seconds (hydro_step_wrench_tiled_sea): the wrench
+        of the state relative to the local water - depth below the local surface, velocity against current and orbital
+        velocity.  The engine-owned previous velocity (prev=None) receives the TRUE velocity; a caller-owned `prev` is only
+        read.  Without a sea the call is step_wrench_tiled."""
+        name, args, out = self._wrench_tiled_call(state, n, dt, out, prev, stream, None, True, time)
+        self._check(getattr(self._lib, name)(*args))
+        return out
+
     def prepare_step_wrench_tiled(self, state: torch.Tensor, n: int, dt: float, out: torch.Tensor | None = None,
                                   prev: torch.Tensor | None = None, stream=None, ke_out: torch.Tensor | None = None,
                                   rotational: bool = True):
         """Build the launch of `step_wrench_tiled` ONCE (same validation, same arguments: `_wrench_tiled_call`) and
-        return a zero-argument callable that issues it again (same buffers, same stream - the one current now if
+        return a callable `step(time=None)` that issues it again (same buffers, same stream - the one current now if
         `stream` is None).  For step loops over small scenes, where the per-call Python work (shape checks, ctypes
         conversions: ~10 us) exceeds the kernel (~3 us at 4 096 bodies): the prepared call costs ~4 us of host time.
-        The callable returns `out`; errors raise HydroError as usual."""
+        `step()` is that launch, argument for argument; `step(time)` is `step_wrench_tiled_sea` at `time` seconds on the
+        same buffers (not with ke_out).  The callable returns `out`; errors raise HydroError as usual."""
         name, args, out = self._wrench_tiled_call(state, n, dt, out, prev, stream, ke_out, rotational)
         fn, args = getattr(self._lib, name), _prebuilt(name, args)
         keep = (state, prev, out, ke_out)               # the buffers must outlive the callable
         check = self._check
+        sea_fn, sea_args = None, None
+        if ke_out is None:                              # the same argument list with the time in front of the stream
+            sea_fn, sea_args = self._lib.hydro_step_wrench_tiled_sea, (args[:-1], args[-1])
 
-        def step():
+        def step(time=None):
             if self._h is None:                         # engine closed: the captured handle is gone
                 raise HydroError(nat.HYDRO_E_STATE, "engine is closed")
-            rc = fn(*args)
+            if time is None:
+                rc = fn(*args)
+            elif sea_fn is None:
+                raise ValueError("the sea entry does not sample the kinetic energy (prepared with ke_out)")
+            else:
+                rc = sea_fn(*sea_args[0], ctypes.c_double(time), sea_args[1])
             if rc:
                 check(rc)
             return keep[2]
@@ -462,7 +485,8 @@ class HydroEngine:
     def set_sea(self, sea) -> None:
         """The scene's moving water (hydro_set_sea; the model: include/hydro.h): `sea` has `current` (3 floats, m/s, world
         frame) and `waves`, up to `_native.SEA_WAVES_MAX` rows (amplitude, kx, ky, omega, phase) - a `sea.SeaState`.  None clears
-        it.  Only `step_fused_tiled_multi_sea` and `sea_sample` see the sea.  Synchronous: the copy runs on the engine's
+        it.  The `step_fused_tiled_multi_sea` family, `step_wrench_tiled_sea`, `step_wrench_aos_sea` and `sea_sample[_at]` see the
+        sea; every other entry steps through still water.  Synchronous: the copy runs on the engine's
         stream, so launches of this engine still in flight elsewhere are the caller's to wait for."""
         if sea is None:
             self._check(self._lib.hydro_set_sea(self._h, None))
@@ -491,6 +515,13 @@ class HydroEngine:
         self._check(self._lib.hydro_sea_sample(self._h, n, s_ptr, s_stride, int(step_index), float(dt), o_ptr, o_stride,
                                                self._stream(stream)))
         return out
+
+    def sea_sample_at(self, state: torch.Tensor, n: int, time: float, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The water each body of the tiled `state` meets at `time` seconds: exactly the [eta, u_x, u_y, u_z] that
+        `step_wrench_tiled_sea` / `step_wrench_aos_sea` use at that time.  `sea_sample` with (step_index, dt) = (1, time) -
+        (double)1 * time == time exactly - or (0, 1.0) at time 0 (include/hydro.h, "Sea state, open loop")."""
+        time = float(time)
+        return self.sea_sample(state, n, *((1, time) if time > 0.0 else (0, 1.0)), out=out, stream=stream)
 
     def step_fused_tiled_multi_sea(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
                                    control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
@@ -717,25 +748,35 @@ class HydroEngine:
         self._check(self._lib.hydro_step_wrench_aos(*head, float(dt), *tail, self._stream(stream)))
         return forces, torques
 
+    def step_wrench_aos_sea(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
+                            dt: float, time: float, forces: torch.Tensor | None = None, torques: torch.Tensor | None = None,
+                            quat_xyzw: bool = False, stream=None):
+        """`step_wrench_aos` through the sea set with `set_sea`, at `time` seconds (hydro_step_wrench_aos_sea).  The engine's
+        previous-velocity state receives the TRUE velocity.  Without a sea the call is step_wrench_aos."""
+        head, tail, forces, torques = self._wrench_aos_call(positions, orientations, velocities, forces, torques, quat_xyzw)
+        self._check(self._lib.hydro_step_wrench_aos_sea(*head, float(dt), *tail, float(time), self._stream(stream)))
+        return forces, torques
+
     def prepare_step_wrench_aos(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
                                 forces: torch.Tensor | None = None, torques: torch.Tensor | None = None,
                                 quat_xyzw: bool = False):
         """Build the launch of `step_wrench_aos` ONCE (`_wrench_aos_call`; given outputs are validated here as well) and
-        return `step(dt, stream=None) -> (forces, torques)`, which re-issues that launch on the same buffers (a
+        return `step(dt, stream=None, time=None) -> (forces, torques)`, which re-issues that launch on the same buffers (a
         simulator's tensor API hands out views of the same device buffers every physics step).  For the plugin path,
         where the per-call Python work of `step_wrench_aos` (tensor checks, pointer conversions) is several times the
-        kernel at 20 bodies.  `stream`: a torch stream / raw handle; None = the stream current at the time of the call."""
+        kernel at 20 bodies.  `time` None: `hydro_step_wrench_aos`, argument for argument; otherwise the `_sea` entry at
+        `time` seconds.  `stream`: a torch stream / raw handle; None = the stream current at the time of the call."""
         head, tail, forces, torques = self._wrench_aos_call(positions, orientations, velocities, forces, torques, quat_xyzw)
         self._rows((forces, torques), (3, 3), positions.shape[0], "output")
         head, tail = _prebuilt("hydro_step_wrench_aos", head), _prebuilt("hydro_step_wrench_aos", tail, len(head) + 1)
-        fn, check = self._lib.hydro_step_wrench_aos, self._check
+        fn, sea_fn, check = self._lib.hydro_step_wrench_aos, self._lib.hydro_step_wrench_aos_sea, self._check
         keep = (positions, orientations, velocities, forces, torques)          # the buffers must outlive the callable
         dev, cur = self.device, torch.cuda.current_stream
         # the current stream's raw handle without building a torch.cuda.Stream object (0.2 instead of 1 us per step)
         raw_current, dev_index = getattr(torch._C, "_cuda_getCurrentRawStream", None), self.device.index
         last = [None, None]                              # (dt, its c_double): a simulator steps with ONE dt
 
-        def step(dt: float, stream=None):
+        def step(dt: float, stream=None, time=None):          # (stream stays the second positional argument)
             if self._h is None:
                 raise HydroError(nat.HYDRO_E_STATE, "engine is closed")
             if stream is None:
@@ -744,7 +785,7 @@ class HydroEngine:
                 sp = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
             if dt != last[0]:
                 last[0], last[1] = dt, ctypes.c_double(dt)
-            rc = fn(*head, last[1], *tail, sp)
+            rc = fn(*head, last[1], *tail, sp) if time is None else sea_fn(*head, last[1], *tail, ctypes.c_double(time), sp)
             if rc:
                 check(rc)
             return keep[3], keep[4]

@@ -38,6 +38,17 @@ class FakeWorld:
         self.masses = torch.cat([self.masses, torch.tensor([mass], dtype=torch.float32, device=self.device)])
         return len(self.paths) - 1
 
+    def integrate(self, paths: Sequence[str], dt: float, gravity: float = 9.81) -> None:
+        """A semi-implicit Euler point mass in place of the simulator's solver, for the prims in `paths`: the velocity from
+        the force the plugin last applied and gravity, then the position from the new velocity.  Attitudes are held."""
+        g = torch.tensor([0.0, 0.0, -float(gravity)], device=self.device)
+        for path in paths:
+            i = self.index(path)
+            force, _ = self.applied[path]
+            v = self.velocities[i, 0:3] + dt * (force / self.masses[i] + g)
+            self.velocities[i, 0:3] = v
+            self.positions[i] = self.positions[i] + dt * v
+
     def index(self, path: str) -> int:
         if len(self._index) != len(self.paths):         # paths appended in bulk (build_c3_scene)
             self._index = {p: i for i, p in enumerate(self.paths)}
