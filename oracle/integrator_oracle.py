@@ -206,7 +206,7 @@ def closed_loop(state, prev, params, rho, g, dt, steps, implicit=False, coeff_dt
     the device hands it to its integrator), `integrate` (implicit: with drag_jacobian), the state rounded to fp32 as
     the device stores it; the previous velocity is the fp32 velocity of the step before.  Returns a list of per-step
     dicts: 'state' (the fp32 state after the step), 'input' (the state it started from), 'wrench', 'k', 'margin'
-    (scenes.branch_margins of the input state)."""
+    (scenes.branch_margins of the input state).  tests/closed_loop_reference.py is this loop with the resident options as arguments."""
     from silver2_isaacsim_amd import scenes
     p = _coeffs(params, coeff_dtype)
     st = np.asarray(state, dtype=np.float32)

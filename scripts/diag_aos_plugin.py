@@ -40,7 +40,7 @@ for n in (4096, 262144, 1048576, 4194304):
 
 # plugin path: the 20 prims of the main scene through HydrodynamicsBehavior + FakeHost
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-from test_plugin_gpu import build_scene
+from designed_populations import build_scene
 from silver2_isaacsim_amd import behavior as hb
 for batched in (True, False):
     hb.REGISTRY.clear()

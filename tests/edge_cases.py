@@ -9,6 +9,8 @@ cannot see a wrong centre whose lever arm happens to be parallel to the force (V
 """
 import numpy as np
 
+import rigid_reference
+
 STD = [1.2, 0.8, 300.0, 150.0, 1.0, 0.05, 0.02]
 
 
@@ -51,17 +53,10 @@ ORIENTATIONS = {
 }
 
 
-def _rot(q):
-    x, y, z, w = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
-
 def _add_tie_cases():
     for oname, (q, dims) in ORIENTATIONS.items():
         half = 0.5 * np.array(dims)
-        rot = _rot(q)
+        rot = rigid_reference.rot(np.array([q]))[0]
         e = half * rot[2]                                  # heights of the three half-extents
         extent = float(np.abs(e).sum())
         up = rot[:, 2]
@@ -151,3 +146,18 @@ def check(f, t, ratio=None, comps=None, comp_ratio=None):
             assert np.all(comps[i] == 0.0), name                      # Numba: zeros for everything, centres included (N6)
         if comp_ratio is not None:
             assert abs(comp_ratio[i] - c["ratio"][i]) < 1e-6, name
+
+
+def check_components(comps, ratio, ref):
+    """comps (n,8,3) fp32 / ratio (n) against the oracle's dict: forces and torques to 1e-6 of the body's largest term,
+    centres to half an fp32 ulp, exact zeros for dry bodies."""
+    from oracle import hydro_oracle as ho
+    force_scale = np.maximum(1.0, np.max([np.abs(ref[f]).max(axis=1) for f in ho.COMPONENT_FIELDS[:6]], axis=0))
+    for k, fld in enumerate(ho.COMPONENT_FIELDS[:6]):
+        assert np.all(np.abs(comps[:, k, :] - ref[fld]).max(axis=1) <= 1e-6 * force_scale), fld
+    for k, fld in ((6, "center_of_buoyancy"), (7, "center_of_pressure")):
+        tol = 0.5 * np.spacing(np.abs(ref[fld]).astype(np.float32)).astype(np.float64) * (1 + 1e-6) + 1e-12
+        assert np.all(np.abs(comps[:, k, :] - ref[fld]) <= tol), fld
+    dry = ref["ratio"] == 0.0
+    assert np.all(comps[dry] == 0.0)
+    assert np.abs(ratio - ref["ratio"]).max() < 5e-7

@@ -10,6 +10,7 @@ power of two at or above twice the largest, 2 x 0.77 = 1.53 -> TENSION_BOUND = 2
 import numpy as np
 
 import mooring_reference as mr
+from rigid_reference import point_velocity_scale, rot_magnitudes
 
 TENSION_BOUND = 2.0
 
@@ -25,18 +26,9 @@ def tension_scale(rec, state):
     """(n,) fp64: k (l^ + L0) + c u^ of mooring_reference.wrench_scales, for every body (meaningful for those with a line)."""
     m, st = np.asarray(rec, np.float64), np.asarray(state, np.float64)
     _, _, l, _, _, _ = mr.geometry(rec, state)
-    x, y, z, w = (np.abs(st[:, 3 + i]) for i in range(4))
-    Rh = np.empty((len(st), 3, 3))
-    Rh[:, 0, 0], Rh[:, 1, 1], Rh[:, 2, 2] = 1 + 2 * (y * y + z * z), 1 + 2 * (x * x + z * z), 1 + 2 * (x * x + y * y)
-    Rh[:, 0, 1] = Rh[:, 1, 0] = 2 * (x * y + w * z)
-    Rh[:, 0, 2] = Rh[:, 2, 0] = 2 * (x * z + w * y)
-    Rh[:, 1, 2] = Rh[:, 2, 1] = 2 * (y * z + w * x)
-    rh = np.einsum("nab,nb->na", Rh, np.abs(m[:, 3:6]))
+    rh = np.einsum("nab,nb->na", rot_magnitudes(st[:, 3:7]), np.abs(m[:, 3:6]))
     eh = np.abs(m[:, 0:3]) + np.abs(st[:, 0:3]) + rh
     lh = np.sqrt((eh * eh).sum(axis=1))
-    av, ao = np.abs(st[:, 7:10]), np.abs(st[:, 10:13])
-    uh = np.stack([av[:, 0] + ao[:, 1] * rh[:, 2] + ao[:, 2] * rh[:, 1],
-                   av[:, 1] + ao[:, 2] * rh[:, 0] + ao[:, 0] * rh[:, 2],
-                   av[:, 2] + ao[:, 0] * rh[:, 1] + ao[:, 1] * rh[:, 0]], axis=1)
+    uh = point_velocity_scale(st[:, 7:10], st[:, 10:13], rh)
     unh = (uh * eh).sum(axis=1) / np.where(l > 0, l, 1.0)
     return m[:, 7] * (lh + m[:, 6]) + m[:, 8] * unh

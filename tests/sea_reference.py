@@ -13,9 +13,6 @@ everything behind the wrench takes the true state.
 """
 import numpy as np
 
-from oracle import hydro_oracle as ho
-from oracle import integrator_oracle as io
-
 ULP = 2.0 ** -24
 
 
@@ -70,25 +67,3 @@ def relative(state, prev, eta, u):
     s[:, 7:10] = s[:, 7:10] - u
     pv[:, 0:3] = pv[:, 0:3] - u
     return s, pv
-
-
-def closed_loop_sea(state, prev, params, rho, g, dt, steps, sea, step0=0, implicit=False, coeff_dtype="f32"):
-    """integrator_oracle.closed_loop through a sea: per step the fp64 water at the fp32 state (rounded to fp32 as the device
-    holds it), hydro_oracle.step_wrench on the fp32 RELATIVE state, integrator_oracle.integrate on the TRUE state (implicit:
-    drag_jacobian from the relative state), the state rounded to fp32.  Returns per-step dicts: 'state' (after the step),
-    'input', 'eta' and 'u' (the water the step used), 'wrench', 'k'."""
-    p = io._coeffs(params, coeff_dtype)
-    st = np.asarray(state, dtype=np.float32)
-    pv = np.asarray(prev, dtype=np.float32)
-    out = []
-    for k in range(steps):
-        eta, u = water(sea, st[:, 0], st[:, 1], st[:, 2], step0 + k, dt)
-        eta, u = eta.astype(np.float32), u.astype(np.float32)
-        s_rel, pv_rel = relative(st, pv, eta, u)
-        f, t, comps = ho.step_wrench(s_rel, pv_rel, p, rho, g, dt)
-        wrench = np.concatenate([f, t], axis=1).astype(np.float32)
-        kk = io.drag_jacobian(s_rel, p, comps, rho) if implicit else None
-        new = io.integrate(st, wrench, p, g, dt, *(kk if kk is not None else (None, None)))
-        out.append({"input": st, "eta": eta, "u": u, "wrench": wrench, "k": kk, "state": new.astype(np.float32)})
-        pv, st = st[:, 7:13].copy(), out[-1]["state"]
-    return out

@@ -20,12 +20,10 @@ it: the comparison then measures the arithmetic, not the tie.
 """
 import numpy as np
 
-from oracle import hydro_oracle as ho
-from oracle import integrator_oracle as io
-
-import sea_reference as sr
+from rigid_reference import cross_scale, fma32, point_velocity_fp32, point_velocity_scale, rot, rot_fp32, rot_magnitudes, rsqrt_nr32
 
 ULP = 2.0 ** -24
+PROBE_BOUND = 4.0            # units of 2^-24 of wrench_scales: the bound of hydro_seabed_wrench (tests/test_seabed_gpu.py's docstring)
 SIGNS = [(-1.0 if not i & 1 else 1.0, -1.0 if not i & 2 else 1.0, -1.0 if not i & 4 else 1.0) for i in range(8)]
 
 
@@ -33,20 +31,10 @@ def _consts(bed):
     return tuple(float(getattr(bed, k)) for k in ("z", "stiffness", "damping", "friction", "slip_speed", "friction_rate"))
 
 
-def _rot(q):
-    """(n, 3, 3) matrices of the quaternions xyzw as given (non-unit included): 1 - 2(yy + zz), 2(xy - wz), ..."""
-    x, y, z, w = (q[:, i] for i in range(4))
-    R = np.empty((len(q), 3, 3), q.dtype)
-    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = 1 - (y * (y + y) + z * (z + z)), x * (y + y) - w * (z + z), x * (z + z) + w * (y + y)
-    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = x * (y + y) + w * (z + z), 1 - (x * (x + x) + z * (z + z)), y * (z + z) - w * (x + x)
-    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = x * (z + z) - w * (y + y), y * (z + z) + w * (x + x), 1 - (x * (x + x) + y * (y + y))
-    return R
-
-
 def corners(state, params):
     """(n, 8, 3) offsets of the corners from the body origin, world frame, fp64."""
     st, pr = np.asarray(state, np.float64), np.asarray(params, np.float64)
-    R = _rot(st[:, 3:7])
+    R = rot(st[:, 3:7])
     out = np.empty((len(st), 8, 3))
     for i, (sx, sy, sz) in enumerate(SIGNS):
         local = np.stack([sx * 0.5 * pr[:, 0], sy * 0.5 * pr[:, 1], sz * 0.5 * pr[:, 2]], axis=1)
@@ -64,9 +52,7 @@ def touching_fp32(bed, state, params):
     """(n, 8) bool: the kernel's own decision delta_i > 0, in the fp32 operations include/hydro.h lists (no fused operation
     among them: R from products and sums, A_z = 0.5 (R_20 dx) ..., r_z = (s_x A_z + s_y B_z) + s_z C_z, z_b - (p_z + r_z))."""
     st, pr = np.asarray(state, np.float32), np.asarray(params, np.float32)
-    x, y, z, w = (st[:, 3 + i] for i in range(4))
-    x2, y2 = x + x, y + y
-    r20, r21, r22 = x * (z + z) - w * y2, y * (z + z) + w * x2, np.float32(1) - (x * x2 + y * y2)
+    r20, r21, r22 = rot_fp32(st[:, 3:7])[2]
     az, bz, cz = np.float32(0.5) * (r20 * pr[:, 0]), np.float32(0.5) * (r21 * pr[:, 1]), np.float32(0.5) * (r22 * pr[:, 2])
     zb = np.float32(_consts(bed)[0])
     out = np.empty((len(st), 8), bool)
@@ -116,52 +102,24 @@ def wrench_scales(bed, state, params, touch=None):
     zb, kappa, beta, mu, vs, gamma = _consts(bed)
     m = pr[:, 10]
     _, _, u, F, on = _corner_terms(bed, state, params, touch)
-    x, y, z, w = (np.abs(st[:, 3 + i]) for i in range(4))
-    Rh = np.empty((len(st), 3, 3))
-    Rh[:, 0, 0], Rh[:, 1, 1], Rh[:, 2, 2] = 1 + 2 * (y * y + z * z), 1 + 2 * (x * x + z * z), 1 + 2 * (x * x + y * y)
-    Rh[:, 0, 1] = Rh[:, 1, 0] = 2 * (x * y + w * z)
-    Rh[:, 0, 2] = Rh[:, 2, 0] = 2 * (x * z + w * y)
-    Rh[:, 1, 2] = Rh[:, 2, 1] = 2 * (y * z + w * x)
-    rh = np.einsum("nab,nb->na", Rh, 0.5 * pr[:, 0:3])
+    rh = np.einsum("nab,nb->na", rot_magnitudes(st[:, 3:7]), 0.5 * pr[:, 0:3])
     dh = abs(zb) + np.abs(st[:, 2]) + rh[:, 2]
-    av, ao = np.abs(st[:, 7:10]), np.abs(st[:, 10:13])
-    uh = np.stack([av[:, 0] + ao[:, 1] * rh[:, 2] + ao[:, 2] * rh[:, 1],
-                   av[:, 1] + ao[:, 2] * rh[:, 0] + ao[:, 0] * rh[:, 2],
-                   av[:, 2] + ao[:, 0] * rh[:, 1] + ao[:, 1] * rh[:, 0]], axis=1)
+    uh = point_velocity_scale(st[:, 7:10], st[:, 10:13], rh)
     Nh = m * (kappa * dh + beta * uh[:, 2])
     root = np.sqrt(u[:, :, 0] ** 2 + u[:, :, 1] ** 2 + vs * vs)                          # (n, 8)
     capped = mu * F[:, :, 2] / root >= (m * gamma)[:, None]
     ch = np.where(capped, (m * gamma)[:, None], mu * Nh[:, None] / root)
     Fh = np.stack([ch * uh[:, None, 0], ch * uh[:, None, 1], np.broadcast_to(Nh[:, None], ch.shape)], axis=2) * on[:, :, None]
-    Th = np.stack([rh[:, None, 1] * Fh[:, :, 2] + rh[:, None, 2] * Fh[:, :, 1],
-                   rh[:, None, 2] * Fh[:, :, 0] + rh[:, None, 0] * Fh[:, :, 2],
-                   rh[:, None, 0] * Fh[:, :, 1] + rh[:, None, 1] * Fh[:, :, 0]], axis=2)
-    return np.concatenate([Fh.sum(axis=1), Th.sum(axis=1)], axis=1)
-
-
-def _fma32(a, b, c):
-    """fma of fp32 operands: the product is exact in fp64; the sum is rounded to fp64 and then to fp32 (a double rounding that
-    differs from the single one in about one case in 2^29)."""
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
-
-
-def _rsqrt_nr32(x):
-    """rsqrt_nr with a correctly rounded seed in place of the hardware's (1 ulp)."""
-    r = (1.0 / np.sqrt(x.astype(np.float64))).astype(np.float32)
-    return _fma32(_fma32(-x * r, r, np.ones_like(x)), np.float32(0.5) * r, r)
+    return np.concatenate([Fh.sum(axis=1), cross_scale(rh[:, None, :], Fh).sum(axis=1)], axis=1)
 
 
 def wrench_fp32_emulated(bed, state, params):
     """(n, 6) W by the operations of include/hydro.h in NumPy float32, corner by corner in the header's order: what the
-    kernel computes but for the seed of the reciprocal square root and the rare double rounding of _fma32."""
+    kernel computes but for the seed of the reciprocal square root and the rare double rounding of fma32."""
     f32 = np.float32
     st, pr = np.asarray(state, f32), np.asarray(params, f32)
     zb, ka, be, mu, vs, ga = (f32(v) for v in _consts(bed))
-    qx, qy, qz, qw = (st[:, 3 + i] for i in range(4))
-    x2, y2, z2 = qx + qx, qy + qy, qz + qz
-    xx, xy, xz, yy, yz, zz = qx * x2, qx * y2, qx * z2, qy * y2, qy * z2, qz * z2
-    wx, wy, wz = qw * x2, qw * y2, qw * z2
-    R = [[f32(1) - (yy + zz), xy - wz, xz + wy], [xy + wz, f32(1) - (xx + zz), yz - wx], [xz - wy, yz + wx, f32(1) - (xx + yy)]]
+    R = rot_fp32(st[:, 3:7])
     A, B, C = ([f32(0.5) * (R[k][j] * pr[:, j]) for k in range(3)] for j in range(3))
     m, n = pr[:, 10], len(st)
     W = [np.zeros(n, f32) for _ in range(6)]
@@ -169,39 +127,12 @@ def wrench_fp32_emulated(bed, state, params):
     for sx, sy, sz in SIGNS:
         r = [(f32(sx) * A[k] + f32(sy) * B[k]) + f32(sz) * C[k] for k in range(3)]
         delta = zb - (st[:, 2] + r[2])
-        ux = _fma32(st[:, 11], r[2], _fma32(-st[:, 12], r[1], st[:, 7]))
-        uy = _fma32(st[:, 12], r[0], _fma32(-st[:, 10], r[2], st[:, 8]))
-        uz = _fma32(st[:, 10], r[1], _fma32(-st[:, 11], r[0], st[:, 9]))
-        a = np.maximum(f32(0), _fma32(kav, delta, -(be * uz)))
+        ux, uy, uz = point_velocity_fp32(st, r)
+        a = np.maximum(f32(0), fma32(kav, delta, -(be * uz)))
         N = m * a
-        c = m * np.minimum((mu * a) * _rsqrt_nr32(_fma32(vsv, vsv, _fma32(uy, uy, ux * ux))), ga)
+        c = m * np.minimum((mu * a) * rsqrt_nr32(fma32(vsv, vsv, fma32(uy, uy, ux * ux))), ga)
         tx, ty = c * ux, c * uy
-        new = [W[0] - tx, W[1] - ty, W[2] + N, _fma32(r[1], N, _fma32(r[2], ty, W[3])),
-               _fma32(-r[2], tx, _fma32(-r[0], N, W[4])), _fma32(r[1], tx, _fma32(-r[0], ty, W[5]))]
+        new = [W[0] - tx, W[1] - ty, W[2] + N, fma32(r[1], N, fma32(r[2], ty, W[3])),
+               fma32(-r[2], tx, fma32(-r[0], N, W[4])), fma32(r[1], tx, fma32(-r[0], ty, W[5]))]
         W = [np.where(delta > 0, nw, w) for nw, w in zip(new, W)]
     return np.stack(W, axis=1)
-
-
-def closed_loop_bed(state, prev, params, rho, g, dt, steps, bed, sea=None, step0=0, implicit=True, coeff_dtype="f32", applied=None):
-    """sea_reference.closed_loop_sea over a bed: per step hydro_oracle.step_wrench (on the fp32 state relative to `sea`, if
-    there is one), + `applied` ((n, 6), world frame, may be None) + the fp64 bed wrench of the TRUE state, the sum rounded to
-    fp32, integrator_oracle.integrate on the true state, the state rounded to fp32.  Returns per-step dicts: 'state' (after the
-    step), 'input', 'wrench' (the sum), 'bed' (W), 'delta' ((n, 8) penetrations of the input state)."""
-    p = io._coeffs(params, coeff_dtype)
-    st = np.asarray(state, dtype=np.float32)
-    pv = np.asarray(prev, dtype=np.float32)
-    out = []
-    for k in range(steps):
-        s_rel, pv_rel = st, pv
-        if sea is not None:
-            eta, u = sr.water(sea, st[:, 0], st[:, 1], st[:, 2], step0 + k, dt)
-            s_rel, pv_rel = sr.relative(st, pv, eta.astype(np.float32), u.astype(np.float32))
-        f, t, comps = ho.step_wrench(s_rel, pv_rel, p, rho, g, dt)
-        W = wrench(bed, st, params)
-        total = np.concatenate([f, t], axis=1).astype(np.float64) + (0.0 if applied is None else np.asarray(applied, np.float64)) + W
-        total = total.astype(np.float32)
-        kk = io.drag_jacobian(s_rel, p, comps, rho) if implicit else None
-        new = io.integrate(st, total, p, g, dt, *(kk if kk is not None else (None, None)))
-        out.append({"input": st, "wrench": total, "bed": W, "delta": penetration(bed, st, params), "state": new.astype(np.float32)})
-        pv, st = st[:, 7:13].copy(), out[-1]["state"]
-    return out

@@ -6,7 +6,6 @@ a resident launch equals single stepping; the recorder logs the total wrench; gu
 Bound of the fp64 comparisons: integrator_oracle.STEP_ULP_BOUND (24), with the scales of field_scales on a surrogate wrench
 |F_hydro,i| + |f_applied|, |tau_hydro| + |tau_applied| - a thrust that cancels the water does not shrink the yardstick.
 Each of those tests prints its largest error per group."""
-import ctypes
 import importlib.util
 import os
 
@@ -17,25 +16,14 @@ import torch
 import populations
 from conftest import REPO
 from oracle import hydro_oracle as ho
-from oracle import integrator_oracle as io
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.engine import HydroEngine
 from silver2_isaacsim_amd.simulate import ClosedLoopSim, recorder_cadence
-from test_integrator_gpu import _guarded, _unguard, _untouched
+from resident_harness import (_bits, _buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, fp64_step_errors, FRAMES, G, _guarded, _hydro_wrench, _k, _ke,
+                              NAN, _push, raw, _report, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _same, _same_values, SIZES, step, STEPS, _tiled, _unguard,
+                              _untouched)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-B = io.STEP_ULP_BOUND
-SIZES = (1, 63, 64, 65, 257, 4097)
-STEPS = (1, 2, 7)
-FRAMES = ("world", "body")
-RHO, G, DT = populations.RHO, populations.G, populations.DT
-NAN = float("nan")
-COEFFS = pytest.mark.parametrize("coeff", ["f32", "f16"])
-DRAG = pytest.mark.parametrize("implicit", [False, True], ids=["explicit", "implicit"])
-# the chain tests (device against device, bit for bit) hold in either semantics: the Numba cases keep their ids
-COEFFS_SEMANTICS = pytest.mark.parametrize("coeff,semantics", [("f32", "numba"), ("f16", "numba"), ("f32", "warp"), ("f16", "warp")],
-                                           ids=["f32", "f16", "f32-warp", "f16-warp"])
 
 
 @pytest.fixture(scope="module")
@@ -59,78 +47,6 @@ def pop():
     return st, pv, params, applied, comps
 
 
-def _tiled(x):
-    return torch.from_numpy(scenes.to_tiled(x)).to(DEV)
-
-
-def _engine(n, params, coeff, semantics="numba"):
-    eng = HydroEngine(n, DEV, RHO, G)
-    eng.set_params(params[:n], coeff)
-    if semantics != "numba":
-        eng.set_semantics(semantics)
-    return eng
-
-
-def _buffers(st, pv, n):
-    """(cur, old): the state and the buffer whose velocity fields hold the previous velocity, as ClosedLoopSim keeps them."""
-    old = np.zeros((n, 13), np.float32)
-    old[:, 7:13] = pv[:n]
-    return _tiled(st[:n]), _tiled(old)
-
-
-def _ke():
-    return torch.full((2,), NAN, dtype=torch.float64, device=DEV)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_values(a, b):
-    """torch.equal that lets a NaN equal a NaN: the explicit form may carry a light, strongly damped body of the population
-    out of the fp32 range within seven steps, with or without an applied wrench."""
-    return bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
-
-
-def _step_applied(eng, cur, old, n, steps, applied, frame, implicit, ke=None, **kw):
-    """One launch through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one."""
-    eng.step_fused_tiled_multi_applied(cur, old, n, DT, steps, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
-
-
-def _hydro_wrench(eng, cur, old, n):
-    """The fp32 hydrodynamic wrench of (cur, previous velocity in old): what the fused kernels integrate (tests/test_closed_loop_gpu.py)."""
-    return eng.step_wrench_tiled(cur, n, DT, prev=old)
-
-
-def _fp64_errors(got, st, hydro, a, frame, pr, k):
-    """integrator_error_ulps of one applied step: reference io.integrate of hydro + (R a | a) in fp64, scales from the surrogate wrench."""
-    a64, h64 = a.astype(np.float64), hydro.astype(np.float64)
-    if frame == "body":
-        R = ho._rot_batch(st[:, 3:7].astype(np.float64))
-        a64 = np.concatenate([np.einsum("nab,nb->na", R, a64[:, 0:3]), np.einsum("nab,nb->na", R, a64[:, 3:6])], axis=1)
-    total = h64 + a64
-    ref = io.integrate(st, total, pr, G, DT, *(k or (None, None)))
-    surrogate = np.zeros_like(total)
-    surrogate[:, 0:3] = np.abs(h64[:, 0:3]) + np.linalg.norm(a64[:, 0:3], axis=1, keepdims=True)
-    surrogate[:, 3] = np.linalg.norm(h64[:, 3:6], axis=1) + np.linalg.norm(a64[:, 3:6], axis=1)
-    sc = io.field_scales(st, surrogate, pr, G, DT, k, ref)
-    err = io.integrator_error_ulps(got, ref, st, total, pr, G, DT, k, scales=sc)
-    return {g: float(np.nan_to_num(e, nan=np.inf).max(initial=0.0)) for g, e in err.items()}
-
-
-def _report(label, worst):
-    per_group = {g: max(w[g] for w in worst.values()) for g in io.GROUPS}
-    print(f"[{label}] max ulps " + "  ".join(f"{g} {v:.2f}" for g, v in per_group.items()) + f"  (bound {B:g})")
-    bad = {n: w for n, w in worst.items() if max(w.values()) > B}
-    assert not bad, (label, bad)
-
-
-def _k(comps, st, pr, coeff, n):
-    return io.drag_jacobian(st[:n], pr[:n], {c: comps[c][:n] for c in ("ratio", "area", "scale")}, RHO, coeff)
-
-
 # ---- 1. zero is nothing ------------------------------------------------------------------------------------------------------
 @COEFFS
 @DRAG
@@ -149,7 +65,7 @@ def test_zero_wrench_is_the_plain_step(coeff, implicit, pop, native_built):
             for applied, frame in ((zero, "world"), (zero, "body"), (None, "world"), (None, "body")):
                 c, o = _buffers(st, pv, n)
                 ke = _ke()
-                got, got_prev = _step_applied(eng, c, o, n, steps, applied, frame, implicit, ke)
+                got, got_prev = step(eng, "app", c, o, n, steps, applied=applied, frame=frame, implicit=implicit, ke=ke)
                 torch.cuda.synchronize()
                 assert _same_values(got, want) and _same_values(got_prev, want_prev) and _same_values(ke, ke0), (n, steps, frame, applied is None)
                 if applied is None:
@@ -170,7 +86,7 @@ def test_world_frame_is_the_two_kernel_path_bit_for_bit(coeff, semantics, pop, n
         cur, old = _buffers(st, pv, n)
         total = _hydro_wrench(eng, cur, old, n) + a                 # torch: one fp32 add per component
         want = eng.integrate_tiled(cur, total, n, DT)
-        got, _ = _step_applied(eng, cur, old, n, 1, a, "world", False)
+        got, _ = step(eng, "app", cur, old, n, 1, applied=a)
         torch.cuda.synchronize()
         assert torch.equal(_bits(got), _bits(want)), n
         assert (total != _hydro_wrench(eng, cur, old, n)).any()
@@ -189,10 +105,10 @@ def test_one_step_against_fp64(coeff, implicit, frame, pop, native_built):
         eng = _engine(n, pr, coeff)
         cur, old = _buffers(st, pv, n)
         hydro = scenes.from_tiled(_hydro_wrench(eng, cur, old, n).cpu().numpy(), n)
-        got, _ = _step_applied(eng, cur, old, n, 1, _tiled(applied[:n]), frame, implicit)
+        got, _ = step(eng, "app", cur, old, n, 1, applied=_tiled(applied[:n]), frame=frame, implicit=implicit)
         torch.cuda.synchronize()
         k = _k(comps(coeff), st, pr, coeff, n) if implicit else None
-        worst[n] = _fp64_errors(scenes.from_tiled(got.cpu().numpy(), n), st[:n], hydro, applied[:n], frame, pr[:n], k)
+        worst[n] = fp64_step_errors(scenes.from_tiled(got.cpu().numpy(), n), st[:n], hydro, pr[:n], k, applied=applied[:n], frame=frame)
         eng.close()
     _report(f"applied {frame} {'implicit' if implicit else 'explicit'} {coeff}", worst)
 
@@ -248,11 +164,11 @@ def test_resident_launch_equals_single_steps(coeff, implicit, frame, pop, native
         before = a.clone()
         cur, old = _buffers(st, pv, n)
         ke7 = _ke()
-        got, got_prev = _step_applied(eng, cur, old, n, 7, a, frame, implicit, ke7)
+        got, got_prev = step(eng, "app", cur, old, n, 7, applied=a, frame=frame, implicit=implicit, ke=ke7)
         c, o = _buffers(st, pv, n)
         ke1 = _ke()
         for k in range(7):
-            _step_applied(eng, c, o, n, 1, a, frame, implicit, ke1 if k == 6 else None)
+            step(eng, "app", c, o, n, 1, applied=a, frame=frame, implicit=implicit, ke=ke1 if k == 6 else None)
             c, o = o, c
         torch.cuda.synchronize()
         assert torch.equal(_bits(got), _bits(c)) and torch.equal(_bits(got_prev), _bits(o[:, 7:13])), (n, frame)
@@ -280,7 +196,7 @@ def test_recorded_rows_with_an_applied_wrench(coeff, implicit, pop, native_built
             states, wrenches = [], []
             for _ in range(steps):
                 wrenches.append(scenes.from_tiled((_hydro_wrench(eng, c, o, n) + a).cpu().numpy(), n)[watched])
-                _step_applied(eng, c, o, n, 1, a, frame, implicit)
+                step(eng, "app", c, o, n, 1, applied=a, frame=frame, implicit=implicit)
                 c, o = o, c
                 states.append(scenes.from_tiled(c.cpu().numpy(), n)[watched])
             log = torch.full((5, 19, len(watched) + 2), NAN, dtype=torch.float32, device=DEV)
@@ -296,27 +212,17 @@ def test_recorded_rows_with_an_applied_wrench(coeff, implicit, pop, native_built
             torch.cuda.synchronize()
             assert rows == 3
             host = log.cpu().numpy()
-            for r, step in enumerate((2, 4, 6)):
-                assert np.array_equal(host[r, :13, :len(watched)].T.view(np.uint32), states[step - 1].view(np.uint32)), (n, frame, step)
+            for r, after in enumerate((2, 4, 6)):
+                assert np.array_equal(host[r, :13, :len(watched)].T.view(np.uint32), states[after - 1].view(np.uint32)), (n, frame, after)
                 if frame == "world":
-                    gw, ww = host[r, 13:, :len(watched)].T, wrenches[step - 1]
-                    assert ((gw.view(np.uint32) == ww.view(np.uint32)) | (np.isnan(gw) & np.isnan(ww))).all(), (n, step)
+                    gw, ww = host[r, 13:, :len(watched)].T, wrenches[after - 1]
+                    assert ((gw.view(np.uint32) == ww.view(np.uint32)) | (np.isnan(gw) & np.isnan(ww))).all(), (n, after)
             assert np.isnan(host[3:]).all() and np.isnan(host[:, :, len(watched):]).all()
             assert torch.equal(_bits(cur), _bits(c))
         eng.close()
 
 
 # ---- 7. guards and refusals through the raw C ABI ----------------------------------------------------------------------------------
-S_IN, S_OUT, S_PV, S_PVO, S_A = 13 * 64 + 36, 13 * 64 + 100, 6 * 64 + 20, 6 * 64 + 12, 6 * 64 + 28
-
-
-def _raw(eng, n, state, prev, out, pvo, applied, implicit=0, stride=S_A, frame=0, log=None, steps=1):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_app(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        applied, stride, frame, eng._stream(None))
-    return rc, written.value
 
 
 @COEFFS
@@ -338,7 +244,7 @@ def test_strides_and_nan_guards(coeff, implicit, frame, pop, native_built):
         wbuf = _guarded(np.zeros((n, 6), np.float32), 6 * 64 + 8)
         eng._check(eng._lib.hydro_step_wrench_tiled(eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT,
                                                     wbuf.data_ptr(), 6 * 64 + 8, eng._stream(None)))
-        rc, written = _raw(eng, n, state, prev, out, pvo, a.data_ptr(), implicit, frame=FRAMES.index(frame))
+        rc, written = raw(eng, "app", n, state, prev, out, pvo, implicit=implicit, frame=FRAMES.index(frame), applied=a.data_ptr())
         eng._check(rc)
         torch.cuda.synchronize()
         assert written == 0
@@ -350,7 +256,7 @@ def test_strides_and_nan_guards(coeff, implicit, frame, pop, native_built):
         assert np.isfinite(got).all(), (n, "a sentinel was read")
         hydro, _ = _unguard(wbuf, n, 6, 6 * 64 + 8)
         k = _k(comps(coeff), st, pr, coeff, n) if implicit else None
-        worst[n] = _fp64_errors(got, st[:n], hydro, applied[:n], frame, pr[:n], k)
+        worst[n] = fp64_step_errors(got, st[:n], hydro, pr[:n], k, applied=applied[:n], frame=frame)
         eng.close()
     _report(f"C ABI applied {frame} {'implicit' if implicit else 'explicit'} {coeff}, strides {S_IN}/{S_OUT}/{S_A}", worst)
 
@@ -365,21 +271,21 @@ def test_refusals_launch_nothing(pop, native_built):
     pvo = torch.full((tiles * S_PVO,), NAN, device=DEV)
     log = torch.full((4, 13, 8), NAN, device=DEV)
     E_ARG, E_STATE = -1, -5
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr() + 4) == (E_ARG, -7)          # misaligned
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), stride=383) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), frame=2) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), frame=-1) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, out.data_ptr(), stride=S_OUT) == (E_ARG, -7)     # applied aliases state_out
-    assert _raw(eng, n, state, prev, out, pvo, pvo.data_ptr(), stride=S_PVO) == (E_ARG, -7)     # ... prev_out
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), log=log) == (E_STATE, -7)          # a log without a watch list
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), steps=0) == (E_ARG, -7)
+    assert raw(eng, "app", n, state, prev, out, pvo, applied=a.data_ptr() + 4) == (E_ARG, -7)          # misaligned
+    assert raw(eng, "app", n, state, prev, out, pvo, applied=a.data_ptr(), s_applied=383) == (E_ARG, -7)
+    assert raw(eng, "app", n, state, prev, out, pvo, frame=2, applied=a.data_ptr()) == (E_ARG, -7)
+    assert raw(eng, "app", n, state, prev, out, pvo, frame=-1, applied=a.data_ptr()) == (E_ARG, -7)
+    assert raw(eng, "app", n, state, prev, out, pvo, applied=out.data_ptr(), s_applied=S_OUT) == (E_ARG, -7)     # applied aliases state_out
+    assert raw(eng, "app", n, state, prev, out, pvo, applied=pvo.data_ptr(), s_applied=S_PVO) == (E_ARG, -7)     # ... prev_out
+    assert raw(eng, "app", n, state, prev, out, pvo, log=log, applied=a.data_ptr()) == (E_STATE, -7)          # a log without a watch list
+    assert raw(eng, "app", n, state, prev, out, pvo, steps=0, applied=a.data_ptr()) == (E_ARG, -7)
     eng.set_watch([0, 256])
-    assert _raw(eng, n, state, prev, out, pvo, log.data_ptr(), log=log) == (E_ARG, -7)          # applied aliases the log
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), log=log, steps=5) == (E_ARG, -7)   # rows 0 .. 4 of 4
+    assert raw(eng, "app", n, state, prev, out, pvo, log=log, applied=log.data_ptr()) == (E_ARG, -7)          # applied aliases the log
+    assert raw(eng, "app", n, state, prev, out, pvo, steps=5, log=log, applied=a.data_ptr()) == (E_ARG, -7)   # rows 0 .. 4 of 4
     torch.cuda.synchronize()
     assert torch.isnan(out).all() and torch.isnan(pvo).all() and torch.isnan(log).all()
     # and the legal launch next to them: with the log, rows are counted and written
-    assert _raw(eng, n, state, prev, out, pvo, a.data_ptr(), log=log, steps=3) == (0, 3)
+    assert raw(eng, "app", n, state, prev, out, pvo, steps=3, log=log, applied=a.data_ptr()) == (0, 3)
     torch.cuda.synchronize()
     state3, rest = _unguard(out, n, 13, S_OUT)
     assert not np.isnan(state3).all() and np.isnan(rest).all() and torch.isnan(log[3:]).all() and torch.isnan(log[:, :, 2:]).all()
@@ -390,17 +296,6 @@ def test_refusals_launch_nothing(pop, native_built):
 # ---- 8. ClosedLoopSim ------------------------------------------------------------------------------------------------------------
 def _c2():
     return scenes.scene_c2(n=257)
-
-
-def _push(sc, seed, scale=5.0):
-    """(n, 6): forces up to `scale` N per kg, torques up to that times 0.5 m."""
-    rng = np.random.default_rng(seed)
-    m = sc.params[:, 10:11].astype(np.float64)
-    return np.concatenate([rng.uniform(-1, 1, (sc.n, 3)) * scale * m, rng.uniform(-1, 1, (sc.n, 3)) * scale * 0.5 * m], axis=1).astype(np.float32)
-
-
-def _same(a, b):
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 @pytest.mark.parametrize("frame", FRAMES)

@@ -9,121 +9,25 @@ current stream.  Expected values are literals or arithmetic on the stand-ins' ad
 the output of the code under test.  ctypes values and plain Python values count as the same argument: the prepared
 forms pass the former, the direct ones may pass either.
 """
-import ctypes
 
 import pytest
 import torch
 
 from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd.engine import HydroEngine
+from engine_stand_ins import (DEV, DT, eng, F, FUSED_HEAD, H, HANDLE, KE, lib, make_engine, N, O, ORI, P13, P6, POS, PREVS, refused, S, SO, STREAM, T, TILES, TQ,
+                              VELS)  # noqa: F401  (fixtures are requested by name)
 
-DEV = torch.device("cuda:0")
-HANDLE = 0xABC000                 # engine k of a test gets HANDLE + 0x100 * k
-STREAM = 0x5700
-N, TILES = 1000, 16               # ceil(1000 / 64)
-DT = 0.01
 VEL = 7 * 64 * 4                  # byte offset of vx inside a state tile
 ST, WR = 13 * 64, 6 * 64          # tile strides, in floats
 
 
-class T:
-    """What the host reads of a tensor: data_ptr / shape / dtype / device / ndim / dim / numel / is_contiguous."""
-
-    def __init__(self, shape, ptr, dtype=torch.float32, device=DEV, contiguous=True):
-        self.shape, self._ptr, self.dtype, self.device, self._contiguous = tuple(shape), ptr, dtype, device, contiguous
-
-    ndim = property(lambda self: len(self.shape))
-
-    def dim(self):
-        return len(self.shape)
-
-    def numel(self):
-        k = 1
-        for s in self.shape:
-            k *= s
-        return k
-
-    def is_contiguous(self):
-        return self._contiguous
-
-    def data_ptr(self):
-        return self._ptr
-
-
-def plain(a):
-    """An argument as the C side would see it: ctypes scalars -> their value, arrays and structs -> tuples."""
-    if isinstance(a, ctypes.Array):
-        return tuple(plain(x) for x in a)
-    if isinstance(a, ctypes.Structure):
-        return tuple(plain(getattr(a, name)) for name, _ in a._fields_)
-    if hasattr(a, "_obj"):                                   # ctypes.byref(x)
-        return ("byref", plain(a._obj))
-    if isinstance(a, ctypes._SimpleCData):
-        return a.value
-    return a
-
-
-class FakeLib:
-    def __init__(self):
-        self.calls, self.created = [], 0
-
-    def __getattr__(self, name):
-        if not name.startswith("hydro_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            if name == "hydro_create":
-                args[2]._obj.value = HANDLE + 0x100 * self.created
-                self.created += 1
-            self.calls.append((name, tuple(plain(a) for a in args)))
-            return 0
-        return fn
-
-
-@pytest.fixture
-def lib(monkeypatch):
-    fake = FakeLib()
-    monkeypatch.setattr(nat, "_lib", fake)
-    return fake
-
-
-def make_engine(lib, n=N):
-    eng = HydroEngine(1000, "cuda:0")
-    eng.n = n                                                # what set_params would leave
-    lib.calls.clear()
-    return eng
-
-
-@pytest.fixture
-def eng(lib):
-    return make_engine(lib)
-
-
-# the stand-ins: one address each, far enough apart that no offset of one reaches another
-S = T((TILES, 13, 64), 0x10000000)
-P6 = T((TILES, 6, 64), 0x20000000)
-P13 = T((TILES, 13, 64), 0x30000000)
-O = T((TILES, 6, 64), 0x40000000)
-SO = T((TILES, 13, 64), 0x50000000)
-KE = T((2,), 0x60000000, dtype=torch.float64)
-POS, ORI, VELS = T((N, 3), 0x70000000), T((N, 4), 0x71000000), T((N, 6), 0x72000000)
-F, TQ = T((N, 3), 0x73000000), T((N, 3), 0x74000000)
 RATIO = T((N,), 0x75000000)
-
-PREVS = [(None, (None, 0)), (P6, (0x20000000, 384)), (P13, (0x30000000 + 1792, 832))]
-H = HANDLE
 
 
 def table(t):
     """Field pointers of a plain (F, n) float32 stand-in."""
     return tuple(t.data_ptr() + f * t.shape[1] * 4 for f in range(t.shape[0]))
-
-
-def refused(lib, msg, fn, *a, **kw):
-    with pytest.raises(ValueError) as ei:
-        fn(*a, **kw)
-    assert str(ei.value) == msg
-    assert lib.calls == []
 
 
 def test_construction_and_constants(lib):
@@ -234,7 +138,6 @@ def test_batch_refusals(lib, eng):
 
 
 # ------------------------------------------------------------------------------------------------------- fused
-FUSED_HEAD = (H, 1000, 0x10000000, 832, 0x30000000 + 1792, 832, 0.01)
 
 
 @pytest.mark.parametrize("state_out,so_ptr", [(SO, 0x50000000), (None, 0x30000000)])

@@ -18,6 +18,7 @@ import torch
 
 import extremes_reference as er
 import mooring_reference as mr
+from closed_loop_reference import closed_loop
 from conftest import REPO
 from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import extremes as ex
@@ -25,9 +26,8 @@ from silver2_isaacsim_amd import scenes, simulate
 from silver2_isaacsim_amd.extremes import Extremes
 from silver2_isaacsim_amd.mooring import Mooring
 from silver2_isaacsim_amd.sea import SeaState
-from test_engine_calls import FUSED_HEAD, H, KE, N, P13, S, SO, STREAM, TILES, T, eng, lib, refused  # noqa: F401  (fixtures)
-from test_mooring import BED, BODIES, DEPTH, LINES, TIES, FakeEngine, _Ctx, _without_lines, buoy, designed_population
-from test_mooring import _sim as _moor_sim
+from engine_stand_ins import BODIES, eng, ext_sim as _sim, FUSED_HEAD, H, KE, lib, N, P13, refused, S, SO, STREAM, T, TILES, _without_extremes  # noqa: F401  (fixtures are requested by name)
+from mooring_population import buoy, DEPTH, designed_population, TIES
 
 ENTRIES = ("hydro_extremes_reset", "hydro_step_fused_tiled_multi_ext")
 A = T((TILES, 6, 64), 0x88000000)
@@ -124,28 +124,6 @@ def test_step_fused_tiled_multi_ext(lib, eng):
 
 
 # ---- ClosedLoopSim's bookkeeping -------------------------------------------------------------------------------------------------
-class ExtEngine(FakeEngine):
-    """tests/test_mooring.py's recording engine with the two new calls."""
-
-    def extremes_reset(self, extremes, n, state=None, stream=None):
-        self.calls.append(("extremes_reset", extremes, n, state))
-        return extremes
-
-    def step_fused_tiled_multi_ext(self, cur, old, n, dt, steps, step0, extremes, mooring, control, applied, frame, implicit_drag=False, ke_out=None,
-                                   log=None, **rec):
-        return self._step("ext", cur, steps, step0=step0, extremes=extremes, mooring=mooring, control=control, applied=applied, frame=frame, log=log)
-
-
-def _sim(monkeypatch, recorder=False, applied=False, control=False, sea=False, bed=False, lines=False):
-    s = _moor_sim(monkeypatch, recorder, applied, control, sea, bed)
-    s.engine = ExtEngine()
-    if lines:
-        s.set_mooring(**LINES)
-    return s
-
-
-def _without_extremes(recorder, applied, control, sea, bed, lines, eager):
-    return "moor" if lines else _without_lines(recorder, applied, control, sea, bed, eager)
 
 
 @pytest.mark.parametrize("run", ["eager", "replay_sized_run", "resident"])
@@ -361,7 +339,7 @@ def test_the_buoy_in_a_current_its_peak_tension_and_its_reach():
     st, pv, pr, sc, dt, z_eq, mass = buoy()
     k, c = Mooring.for_body(mass, dt)
     lines = Mooring((0.0, 0.0, z_eq - DEPTH), length=DEPTH + 0.5, stiffness=k, damping=c)
-    run = mr.closed_loop_moor(st, pv, pr, sc.rho, sc.g, dt, 900, lines.record, sea=SeaState((0.5, 0.0, 0.0)), implicit=True)
+    run = closed_loop(st, pv, pr, sc.rho, sc.g, dt, 900, moor=lines.record, sea=SeaState((0.5, 0.0, 0.0)), implicit=True)
     states = np.stack([r["state"] for r in run])                 # (900, 1, 13): the state each step produced
     tensions = np.stack([r["tension"] for r in run])             # (900, 1): the T formed IN that step
     rec = Extremes.fold(states, tensions, ex.seed_of(st))

@@ -16,7 +16,6 @@ coefficients alike; the bound stays 2.  The test prints the device's figure.
 
 speed2_max is compared exactly: extremes.fma32 rounds once (tests/test_extremes.py holds it to rational arithmetic), so the
 host's chain is the kernel's, with or without math.fma."""
-import ctypes
 import os
 import re
 import subprocess
@@ -30,33 +29,18 @@ import extremes_reference as er
 import mooring_reference as mr
 from conftest import REPO
 from silver2_isaacsim_amd import extremes as ex
-from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.extremes import Extremes
 from silver2_isaacsim_amd.mooring import Mooring
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import COEFFS, DEV, DRAG, DT, NAN, S_A, S_IN, S_OUT, S_PV, S_PVO, _buffers, _engine, _ke, _tiled
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_mooring import DEPTH, TIES
-from test_mooring_gpu import OFF_TIES, S_M, SIZES, STEPS, _buoys, _from, _same_bits
-from test_mooring_gpu import bed_pop, hold_pop, pop              # noqa: F401  (fixtures: the designed population and its lines)
-from test_pose_hold_gpu import S_C
-from test_seabed_gpu import BED, SEA
+from designed_populations import BED, bed_pop, hold_pop, SEA, SIZES, STEPS  # noqa: F401  (fixtures are requested by name)
+from mooring_population import _buoys, DEPTH, moored_pop as pop, OFF_TIES, TIES  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (_buffers, COEFFS, DEV, DRAG, _engine, _from, _guarded, _ke, _log, NAN, raw, _rows, S_A, S_C, S_IN, S_M, S_OUT, S_PV, S_PVO,
+                              _same_bits, step, _tiled, _unguard, _untouched)
 
 pytestmark = pytest.mark.gpu
 S_E = 8 * 64 + 44                                                 # the extremes record's tile stride in the guard tests
 CURRENT = SeaState((0.5, -0.2, 0.05))                             # a sea a captured launch can replay: no waves
-
-
-def _ext(eng, cur, old, n, steps, step0, extremes, mooring=None, control=None, applied=None, implicit=False, ke=None, entry="ext", **kw):
-    """One launch through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one."""
-    if entry == "ext":
-        eng.step_fused_tiled_multi_ext(cur, old, n, DT, steps, step0, extremes, mooring, control, applied, "world", implicit_drag=implicit, ke_out=ke, **kw)
-    else:
-        assert extremes is None
-        eng.step_fused_tiled_multi_moor(cur, old, n, DT, steps, step0, mooring, control, applied, "world", implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
 
 
 def _record(eng, n, state=None):
@@ -64,17 +48,8 @@ def _record(eng, n, state=None):
     return eng.extremes_reset(torch.full((eng.tiles(n), 8, 64), NAN, dtype=torch.float32, device=DEV), n, state)
 
 
-def _rows(log):
-    """(rows, 19, n) device log -> (rows, n, 19) host."""
-    return np.ascontiguousarray(log.cpu().numpy().transpose(0, 2, 1))
-
-
 def _eq(a, b):
     return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def _log(rows, n):
-    return torch.full((rows, 19, n), NAN, dtype=torch.float32, device=DEV)
 
 
 # ---- 1, 2. positions and speed2: the fold of the recorded rows -------------------------------------------------------------------------
@@ -97,7 +72,7 @@ def test_positions_and_speed2_are_the_fold_of_the_recorded_rows(coeff, implicit,
                 torch.cuda.synchronize()
                 seed = _from(record, n)
                 assert _eq(seed, ex.seed_of(st[:n]) if seeded else Extremes.empty(n)), (n, seeded)
-                _ext(eng, cur, old, n, steps, 3, record, lines, c17, a, implicit, log=log)
+                step(eng, "ext", cur, old, n, steps, step0=3, extremes=record, mooring=lines, control=c17, applied=a, implicit=implicit, log=log)
                 torch.cuda.synchronize()
                 got, rows = _from(record, n), _rows(log)
                 want = Extremes.fold(rows[:, :, :13], np.zeros((steps, n), np.float32), seed)
@@ -119,7 +94,7 @@ def test_tension_after_one_step_against_the_reference(coeff, pop, native_built):
         for lines in (_tiled(m), None):
             cur, old = _buffers(st, pv, n)
             record = _record(eng, n)
-            _ext(eng, cur, old, n, 1, 0, record, lines)
+            step(eng, "ext", cur, old, n, 1, extremes=record, mooring=lines)
             torch.cuda.synchronize()
             got = _from(record, n)[:, ex.TENSION_MAX]
             if lines is None:                                    # no mooring record at all: exactly +0 for everybody
@@ -155,13 +130,13 @@ def test_tension_after_seven_steps_is_the_maximum_of_seven_single_steps(coeff, i
         lines = _tiled(rec[:n])
         cur, old = _buffers(st, pv, n)
         whole = _record(eng, n)
-        _ext(eng, cur, old, n, 7, 100, whole, lines, implicit=implicit)
+        step(eng, "ext", cur, old, n, 7, step0=100, extremes=whole, mooring=lines, implicit=implicit)
         cur, old = _buffers(st, pv, n)
         want = Extremes.empty(n)
         pulled = np.zeros(n, bool)
         for k in range(7):
             one = _record(eng, n)
-            _ext(eng, cur, old, n, 1, 100 + k, one, lines, implicit=implicit)
+            step(eng, "ext", cur, old, n, 1, step0=100 + k, extremes=one, mooring=lines, implicit=implicit)
             cur, old = old, cur
             torch.cuda.synchronize()
             r = _from(one, n)
@@ -191,7 +166,7 @@ def test_one_launch_equals_single_steps_and_chunks_and_a_second_launch_only_wide
             record = _record(eng, n, cur)
             done, history = 0, []
             for k in chunks:
-                _ext(eng, cur, old, n, k, 100 + done, record, lines, implicit=implicit)
+                step(eng, "ext", cur, old, n, k, step0=100 + done, extremes=record, mooring=lines, implicit=implicit)
                 cur, old = old, cur
                 done += k
                 torch.cuda.synchronize()
@@ -218,8 +193,8 @@ def test_a_graph_replayed_three_times_equals_three_eager_launches(pop, native_bu
     stream = torch.cuda.Stream(DEV)
 
     def pair(cur, old, record):
-        _ext(eng, cur, old, n, 3, 0, record, lines, implicit=True, stream=stream)
-        _ext(eng, old, cur, n, 3, 0, record, lines, implicit=True, stream=stream)
+        step(eng, "ext", cur, old, n, 3, extremes=record, mooring=lines, implicit=True, stream=stream)
+        step(eng, "ext", old, cur, n, 3, extremes=record, mooring=lines, implicit=True, stream=stream)
     cur, old = _buffers(st, pv, n)
     record = _record(eng, n, cur)
     torch.cuda.synchronize()
@@ -269,12 +244,13 @@ def test_no_record_is_the_mooring_entry_and_a_record_changes_no_other_bit(coeff,
                                     what = (n, steps, app is None, control is None, lines is None, with_log, sea is None, bed is None)
                                     cur, old = _buffers(st, pv, n)
                                     w_ke, w_log = _ke(), _log(steps, n) if with_log else None
-                                    want = _ext(eng, cur, old, n, steps, 3, None, lines, control, app, implicit, w_ke, entry="moor",
-                                                **(dict(log=w_log) if with_log else {}))
+                                    want = step(eng, "moor", cur, old, n, steps, step0=3, mooring=lines, control=control, applied=app, implicit=implicit, ke=w_ke,
+                                                **dict(log=w_log) if with_log else {})
                                     for record in (None, _record(eng, n)):
                                         c, o = _buffers(st, pv, n)
                                         ke, log = _ke(), _log(steps, n) if with_log else None
-                                        got = _ext(eng, c, o, n, steps, 3, record, lines, control, app, implicit, ke, **(dict(log=log) if with_log else {}))
+                                        got = step(eng, "ext", c, o, n, steps, step0=3, extremes=record, mooring=lines, control=control, applied=app, implicit=implicit,
+                                                   ke=ke, **dict(log=log) if with_log else {})
                                         torch.cuda.synchronize()
                                         assert _same_bits(got[0], want[0]) and _same_bits(got[1], want[1]) and _same_bits(ke, w_ke), what
                                         assert not with_log or _same_bits(log, w_log), what
@@ -298,7 +274,7 @@ def test_energy_and_non_temporal_instantiations(coeff, implicit, pop, native_bui
         def run(entry, ke=None):
             cur, old = _buffers(st, pv, n)
             record = _record(eng, n, cur) if entry == "ext" else None
-            state, prev = _ext(eng, cur, old, n, 7, 5, record, lines, c17, a, implicit, ke, entry=entry)
+            state, prev = step(eng, entry, cur, old, n, 7, step0=5, extremes=record, mooring=lines, control=c17, applied=a, implicit=implicit, ke=ke)
             torch.cuda.synchronize()
             return state, prev, (_from(record, n) if record is not None else None)
         eng.set_tuning(0, 0, 0)
@@ -319,14 +295,6 @@ def test_energy_and_non_temporal_instantiations(coeff, implicit, pop, native_bui
 
 
 # ---- 6. guards and refusals through the raw C ABI ---------------------------------------------------------------------------------------
-def _raw(eng, n, state, prev, out, pvo, extremes, stride=S_E, step0=0, steps=1, log=None, applied=None, control=None, mooring=None, implicit=0):
-    written = ctypes.c_int64(-7)
-    ptr = lambda b: b.data_ptr() if hasattr(b, "data_ptr") else b  # noqa: E731
-    rc = eng._lib.hydro_step_fused_tiled_multi_ext(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        ptr(applied), S_A, 0, ptr(control), S_C, ptr(mooring), S_M, ptr(extremes), stride, step0, eng._stream(None))
-    return rc, written.value
 
 
 @COEFFS
@@ -354,7 +322,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     assert _eq(got, ex.seed_of(st[:n])) and np.isnan(rest).all()
     out = torch.full((tiles * S_OUT,), NAN, device=DEV)
     pvo = torch.full((tiles * S_PVO,), NAN, device=DEV)
-    rc, _ = _raw(eng, n, state, prev, out, pvo, e8, step0=11, steps=3, applied=a, control=c17, mooring=m9, implicit=implicit)
+    rc, _ = raw(eng, "ext", n, state, prev, out, pvo, steps=3, step0=11, implicit=implicit, applied=a, control=c17, mooring=m9, extremes=e8, s_extremes=S_E)
     eng._check(rc)
     torch.cuda.synchronize()
     got, rest = _unguard(e8, n, 8, S_E)
@@ -364,7 +332,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     assert all(_untouched(b, was) for b, was in zip((state, prev, a, c17, m9), before))
     cur, old = _buffers(st, pv, n)
     packed = _record(eng, n, cur)
-    want_state, _ = _ext(eng, cur, old, n, 3, 11, packed, _tiled(rec[:n]), _tiled(ctl[:n]), _tiled(applied[:n]), implicit)
+    want_state, _ = step(eng, "ext", cur, old, n, 3, step0=11, extremes=packed, mooring=_tiled(rec[:n]), control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=implicit)
     torch.cuda.synchronize()
     assert _eq(got, _from(packed, n)) and _eq(_unguard(out, n, 13, S_OUT)[0], _from(want_state, n))
     eng.close()
@@ -391,25 +359,25 @@ def test_refusals_launch_nothing_and_leave_the_record(pop, native_built):
         eng.set_seabed(bed)
         eng.set_sea(sea)
         # the mooring entry's refusals, in its order, with a record
-        assert _raw(eng, n, state, prev, out, pvo, e, step0=-1, **every) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, e, steps=0, **every) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, e, applied=a.data_ptr() + 4) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, e, control=c17.data_ptr() + 4) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, e, mooring=m9.data_ptr() + 4) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, e, log=log, **every) == (E_STATE, -7)               # a log without a watch list
+        assert raw(eng, "ext", n, state, prev, out, pvo, step0=-1, extremes=e, s_extremes=S_E, **every) == (E_ARG, -7)
+        assert raw(eng, "ext", n, state, prev, out, pvo, steps=0, extremes=e, s_extremes=S_E, **every) == (E_ARG, -7)
+        assert raw(eng, "ext", n, state, prev, out, pvo, applied=a.data_ptr() + 4, extremes=e, s_extremes=S_E) == (E_ARG, -7)
+        assert raw(eng, "ext", n, state, prev, out, pvo, control=c17.data_ptr() + 4, extremes=e, s_extremes=S_E) == (E_ARG, -7)
+        assert raw(eng, "ext", n, state, prev, out, pvo, mooring=m9.data_ptr() + 4, extremes=e, s_extremes=S_E) == (E_ARG, -7)
+        assert raw(eng, "ext", n, state, prev, out, pvo, log=log, extremes=e, s_extremes=S_E, **every) == (E_STATE, -7)               # a log without a watch list
         # the mooring's come before the extremes'
-        assert _raw(eng, n, state, prev, out, pvo, e + 4, mooring=out) == (E_ARG, -7) and "mooring must not overlap" in last()
+        assert raw(eng, "ext", n, state, prev, out, pvo, mooring=out, extremes=e + 4, s_extremes=S_E) == (E_ARG, -7) and "mooring must not overlap" in last()
         # the extremes' own
-        assert _raw(eng, n, state, prev, out, pvo, e + 4, **every) == (E_ARG, -7) and "16-byte aligned" in last()
-        assert _raw(eng, n, state, prev, out, pvo, e, stride=508, **every) == (E_ARG, -7)              # below 8 * 64
-        assert _raw(eng, n, state, prev, out, pvo, e, stride=514, **every) == (E_ARG, -7)              # not a multiple of 4
+        assert raw(eng, "ext", n, state, prev, out, pvo, extremes=e + 4, s_extremes=S_E, **every) == (E_ARG, -7) and "16-byte aligned" in last()
+        assert raw(eng, "ext", n, state, prev, out, pvo, extremes=e, s_extremes=508, **every) == (E_ARG, -7)              # below 8 * 64
+        assert raw(eng, "ext", n, state, prev, out, pvo, extremes=e, s_extremes=514, **every) == (E_ARG, -7)              # not a multiple of 4
         for output in (out, pvo):
-            assert _raw(eng, n, state, prev, out, pvo, output, **every) == (E_ARG, -7) and "extremes must not overlap an output" in last()
+            assert raw(eng, "ext", n, state, prev, out, pvo, extremes=output, s_extremes=S_E, **every) == (E_ARG, -7) and "extremes must not overlap an output" in last()
         for inp in (state, prev, a, c17, m9):
-            assert _raw(eng, n, state, prev, out, pvo, inp, **every) == (E_ARG, -7) and "extremes must not overlap an input" in last(), last()
-        assert _raw(eng, n, state, prev, out, pvo, state.data_ptr() + 7 * 64 * 4) == (E_ARG, -7)       # inside the state: its velocity fields
+            assert raw(eng, "ext", n, state, prev, out, pvo, extremes=inp, s_extremes=S_E, **every) == (E_ARG, -7) and "extremes must not overlap an input" in last(), last()
+        assert raw(eng, "ext", n, state, prev, out, pvo, extremes=state.data_ptr() + 7 * 64 * 4, s_extremes=S_E) == (E_ARG, -7)       # inside the state: its velocity fields
         eng.set_watch([0, 320])
-        assert _raw(eng, n, state, prev, out, pvo, log, log=log, **every) == (E_ARG, -7) and "extremes must not overlap an output" in last()
+        assert raw(eng, "ext", n, state, prev, out, pvo, log=log, extremes=log, s_extremes=S_E, **every) == (E_ARG, -7) and "extremes must not overlap an output" in last()
     # the reset
     lib, s, sp = eng._lib, eng._stream(None), state.data_ptr()
     for args in ((n, None, 0, None, S_E), (n, None, 0, e + 4, S_E), (n, None, 0, e, 508), (n, None, 0, e, 514), (n + 1, None, 0, e, S_E),

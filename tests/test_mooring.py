@@ -2,7 +2,7 @@
 machine without a GPU can see them: the C boundary, the Python host's marshalling (with the stand-ins of
 tests/test_engine_calls.py), ClosedLoopSim's bookkeeping with a fake engine, the host restatement against the fp64 reference
 of tests/mooring_reference.py and cases worked by hand, and the physics - config 1's buoy on a line in still water and in a
-current - through mooring_reference.closed_loop_moor.
+current - through closed_loop_reference.closed_loop.
 
 THE FIGURES (config 1's buoy: a unit cube of 500 kg in water of 1025 kg/m^3, dt = 1/60, implicit drag, the anchor 20 m below
 the buoy's equilibrium position, the fairlead at the centre, k = 0.004 m / dt^2 = 7200 N/m, c = 0.02 m / dt = 600 N s/m):
@@ -17,27 +17,26 @@ import itertools
 import os
 import re
 import subprocess
-import types
 
 import numpy as np
 import pytest
-import torch
 
 import mooring_reference as mr
+from closed_loop_reference import closed_loop
 from conftest import REPO
 from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import scenes, simulate
 from silver2_isaacsim_amd.mooring import Mooring
 from silver2_isaacsim_amd.sea import SeaState
-from silver2_isaacsim_amd.seabed import Seabed
-from test_engine_calls import FUSED_HEAD, H, KE, N, P13, S, SO, STREAM, TILES, T, eng, lib, refused  # noqa: F401  (fixtures)
+from engine_stand_ins import BODIES, eng, FUSED_HEAD, H, KE, lib, LINES, moor_sim as _sim, N, P13, refused, S, SO, STREAM, T, TILES, _without_lines  # noqa: F401  (fixtures are requested by name)
+from mooring_population import ALL_TILE, buoy, CLAMPED, DEPTH, designed_population, NONE_TILE, population_report, TIE_ULPS, TIES
+from mooring_reference import PROBE_BOUND
 
 ENTRIES = ("hydro_mooring_wrench", "hydro_step_fused_tiled_multi_moor")
 A = T((TILES, 6, 64), 0x88000000)
 C = T((TILES, 17, 64), 0x90000000)
 W = T((TILES, 6, 64), 0x98000000)                                 # the probe's output
 M = T((TILES, 9, 64), 0xA0000000)                                 # the mooring record
-BED = Seabed(-25.0, 144.0, 2.4, 0.5, 0.01, 2.4)
 
 
 # ---- C boundary ----------------------------------------------------------------------------------------------------------------
@@ -166,86 +165,6 @@ def test_step_fused_tiled_multi_moor(lib, eng):
 
 
 # ---- ClosedLoopSim's bookkeeping -------------------------------------------------------------------------------------------------
-class FakeEngine:
-    """Records the calls ClosedLoopSim makes; nothing runs.  alloc_tiled gives a host tensor."""
-
-    def __init__(self):
-        self.calls = []
-
-    def alloc_tiled(self, fields, n):
-        return torch.zeros(((n + 63) // 64, fields, 64), dtype=torch.float32)
-
-    def set_seabed(self, bed):
-        self.calls.append(("set_seabed", bed))
-
-    def _step(self, name, cur, steps, **kw):
-        self.calls.append(dict(method=name, cur=cur, steps=steps, **kw))
-        return 0
-
-    def step_fused_tiled_multi_moor(self, cur, old, n, dt, steps, step0, mooring, control, applied, frame, implicit_drag=False, ke_out=None,
-                                    log=None, **rec):
-        return self._step("moor", cur, steps, step0=step0, mooring=mooring, control=control, applied=applied, frame=frame, log=log)
-
-    def step_fused_tiled_multi_bed(self, cur, old, n, dt, steps, step0, control, applied, frame, implicit_drag=False, ke_out=None, log=None, **rec):
-        return self._step("bed", cur, steps, step0=step0, control=control, applied=applied, frame=frame, log=log)
-
-    def step_fused_tiled_multi_sea(self, cur, old, n, dt, steps, step0, control, applied, frame, implicit_drag=False, ke_out=None, log=None, **rec):
-        return self._step("sea", cur, steps, step0=step0, control=control, applied=applied, frame=frame, log=log)
-
-    def step_fused_tiled_multi_controlled(self, cur, old, n, dt, steps, control, applied, frame, implicit_drag=False, ke_out=None, log=None, **rec):
-        return self._step("ctl", cur, steps, control=control, applied=applied, frame=frame, log=log)
-
-    def step_fused_tiled_multi_applied(self, cur, old, n, dt, steps, applied, frame, implicit_drag=False, ke_out=None, log=None, **rec):
-        return self._step("app", cur, steps, applied=applied, frame=frame, log=log)
-
-    def step_fused_tiled_multi_rec(self, cur, old, n, dt, steps, implicit_drag=False, ke_out=None, log=None, **rec):
-        return self._step("rec", cur, steps, log=log)
-
-    def step_fused_tiled_multi(self, cur, old, n, dt, steps, **kw):
-        self._step("plain", cur, steps)
-
-    def step_fused_tiled(self, cur, old, n, dt, **kw):
-        self._step("single", cur, None)
-
-
-class _Ctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-BODIES = 70                                                        # two tiles
-
-
-def _sim(monkeypatch, recorder=False, applied=False, control=False, sea=False, bed=False):
-    monkeypatch.setattr(simulate.torch.cuda, "stream", lambda s: _Ctx())
-    s = object.__new__(simulate.ClosedLoopSim)
-    s.fused, s.implicit_drag, s.n, s.dt, s.engine = True, True, BODIES, 1.0 / 60.0, FakeEngine()
-    params = np.zeros((BODIES, 11), np.float32)
-    params[:, 10] = 500.0
-    s.scene = types.SimpleNamespace(params=params)
-    s.cur, s.old, s.stream = "buffer A", "buffer B", None
-    s.steps_done, s.monitor, s._monitor_warm, s.ke_dev = 0, None, True, None
-    s.recorder = simulate.TrajectoryRecorder([5, 2], every=2, rows=64, sim=s) if recorder else None
-    s.applied, s.applied_frame = ("the applied buffer" if applied else None), "world"
-    s.control = "the control buffer" if control else None
-    s.sea = SeaState((0.3, 0.0, 0.0)) if sea else None
-    if bed:
-        s.seabed = BED
-    s._graph, s._graph_steps, s._graph_bufs = None, 0, None
-    s.synchronize = lambda timeout_s=None: None
-    return s
-
-
-LINES = dict(anchor=[[1.0, 2.0, -20.0], [3.0, 4.0, -21.0]], fairlead=(0.0, 0.1, -0.5), length=[19.0, 20.0], stiffness=7200.0, damping=600.0,
-             bodies=[66, 3])
-
-
-# what the sim calls without lines, by the rule of tests/test_sim_dispatch.py and tests/test_seabed.py
-def _without_lines(recorder, applied, control, sea, bed, eager):
-    return "bed" if bed else "sea" if sea else "ctl" if control else "app" if applied else "rec" if recorder else "single" if eager else "plain"
 
 
 @pytest.mark.parametrize("run", ["eager", "replay_sized_run", "resident"])
@@ -365,9 +284,6 @@ def test_host_restatement_equals_the_reference():
     assert ((got[pulling, 0:3] * e[pulling]).sum(axis=1) > 0).all()
 
 
-PROBE_BOUND = 2.0             # units of 2^-24 of wrench_scales: tests/test_mooring_gpu.py's bound (its docstring)
-
-
 def test_the_header_s_fp32_order_stands_within_the_probe_bound_of_fp64():
     """The operations include/hydro.h lists, carried out in NumPy float32 (mooring_reference.wrench_fp32_emulated), against the
     fp64 reference with the same lines taut, in units of 2^-24 of mooring_reference.wrench_scales: what the stated order costs
@@ -384,89 +300,6 @@ def test_the_header_s_fp32_order_stands_within_the_probe_bound_of_fp64():
 
 
 # ---- the designed population of tests/test_mooring_gpu.py ---------------------------------------------------------------------------
-NONE_TILE, ALL_TILE = 2, 1                                         # (the bed's population: nobody touches in tile 1, everybody in tile 2)
-TIES = np.arange(8)                                                # l within 2 fp32 ulps of L0: 0 .. 3 with c = 0, 4 .. 7 with c > 0
-TIE_ULPS = (-2, -1, 1, 2, -2, -1, 1, 2)                            # L0 - l, in ulps of l: negative = taut
-CLAMPED = 64 + np.arange(8)                                        # taut, the fairlead closing in so fast that T clamps to 0
-
-
-def line_population(st, pr, seed=2027):
-    """A line per body of the 321-body population of tests/test_seabed_gpu.py, built from each body's own state: the anchor is
-    the fairlead's world position + a drawn direction x L (L = 2 .. 30 m), L0 = L (1 -+ margin), margin 1e-3 .. 0.1; k and c per
-    unit mass up to 14.4 / s^2 and 1.2 / s (the defaults at 60 Hz).  Returns the (321, 9) float32 record:
-      bodies 0 .. 7          : l within 2 fp32 ulps of L0 (TIE_ULPS), the fairlead running away from the anchor; 0 .. 3 with c = 0
-      the rest of tile 0     : slack, but four in every sixteen taut
-      tile 1 (64 .. 127)     : all taut; 64 .. 71 with a fairlead that closes in fast enough for T to clamp to 0, the others pulling
-                               (no body of this tile touches the bed of tests/test_seabed_gpu.py: lines alone)
-      tile 2 (128 .. 191)    : no lines (the wave skips the evaluation; every body of this tile touches the bed: the bed alone)
-      192 .. 199             : slack
-      200 .. 319             : in turn taut and pulling, slack, no line
-      320                    : the one live lane of the last wave, taut and pulling."""
-    n = len(st)
-    assert n == 321
-    rng = np.random.default_rng(seed)
-    st64 = np.asarray(st, np.float64)
-    i = np.arange(n)
-    tile = i // 64
-    TAUT, SLACK, NONE = 0, 1, 2
-    kind = np.where(tile == NONE_TILE, NONE, np.where(tile == ALL_TILE, TAUT, np.where(tile == 0, np.where(i % 4 == 1, TAUT, SLACK),
-                                                                                      np.where(i < 200, SLACK, (i - 200) % 3))))
-    kind[320] = TAUT
-    kind[TIES] = TAUT
-    rec = np.zeros((n, 9))
-    rec[:, 3:6] = rng.uniform(-0.5, 0.5, (n, 3)) * pr[:, 0:3]                      # fairleads within the box
-    rec0 = rec.copy()
-    r, _, _, _, u, _ = mr.geometry(rec0, st64)                                     # (the arm and the fairlead's velocity do not depend on the anchor)
-    d = rng.normal(size=(n, 3))
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    speed = np.linalg.norm(u, axis=1)
-    away = np.where(speed[:, None] > 0, -u / np.maximum(speed, 1e-30)[:, None], d)
-    d[TIES] = away[TIES]                                                          # e along -u: the fairlead runs away (un < 0), so a taut tie pulls
-    d[CLAMPED] = -away[CLAMPED]                                                   # e along +u: it closes in at its full speed
-    assert (speed[TIES] > 1e-4).all() and (speed[CLAMPED] > 1e-3).all()
-    L = rng.uniform(2.0, 30.0, n)
-    margin = 10.0 ** rng.uniform(-3.0, -1.0, n)
-    margin[CLAMPED] = 1e-3
-    rec[:, 0:3] = st64[:, 0:3] + r + d * L[:, None]
-    rec[:, 6] = np.where(kind == SLACK, L * (1.0 + margin), L * (1.0 - margin))
-    m = pr[:, 10].astype(np.float64)
-    rec[:, 7] = np.where(kind == NONE, 0.0, m * rng.uniform(0.5, 14.4, n))
-    rec[:, 8] = np.where(kind == NONE, 0.0, m * rng.uniform(0.0, 1.2, n) * (i % 5 != 0))          # one line in five without a damper
-    rec = rec.astype(np.float32).astype(np.float64)
-    # taut and meant to pull: keep the damper below half the spring's force
-    _, _, _, x, _, un = mr.geometry(rec, st64)
-    pull = (kind == TAUT) & ~np.isin(i, CLAMPED) & ~np.isin(i, TIES)
-    too_much = pull & (rec[:, 8] * un > 0.5 * rec[:, 7] * x)
-    rec[too_much, 8] = 0.5 * rec[too_much, 7] * x[too_much] / un[too_much]
-    rec[CLAMPED, 8] = 4.0 * rec[CLAMPED, 7] * x[CLAMPED] / un[CLAMPED]             # c un = 4 k x
-    rec[TIES[:4], 8] = 0.0
-    rec[TIES[4:], 8] = np.maximum(rec[TIES[4:], 8], 0.3 * m[TIES[4:]])
-    rec = rec.astype(np.float32)
-    # the ties: L0 is the kernel's own l moved by whole fp32 steps
-    free = rec.copy()
-    free[:, 6] = 0.0
-    l32 = mr._fp32_terms(free, st)[3]                                             # x with L0 = 0: l itself
-    for b, k in zip(TIES, TIE_ULPS):
-        v = l32[b]
-        for _ in range(abs(k)):
-            v = np.nextafter(v, np.float32(np.inf if k > 0 else -np.inf))
-        rec[b, 6] = v
-    return rec
-
-
-def designed_population():
-    """(state, prev, params f32, record) of the 321 bodies, built without a device."""
-    import populations
-    from test_seabed_gpu import bed_population
-    st, pv, pr = populations.integrator_population(n=4097, seed=31)
-    st, pv, pr = bed_population(st, pv, pr)
-    return st, pv, pr, line_population(st, pr)
-
-
-def population_report(rec, st):
-    """What the population is made of, by the fp64 reference: (taut and pulling, slack, no line, taut and clamped)."""
-    has, on, T = mr.has_line(rec), mr.taut(rec, st), mr.tension(rec, st)
-    return on & (T > 0), has & ~on, ~has, on & ~(T > 0)
 
 
 def test_the_designed_population_and_the_probe_bound_on_the_host():
@@ -482,7 +315,7 @@ def test_the_designed_population_and_the_probe_bound_on_the_host():
     assert pulling[320] and clamped[CLAMPED].all() and clamped.sum() >= 8
     # over the bed of tests/test_seabed_gpu.py every combination of "touches" and "pulls" occurs, at either size
     import seabed_reference as br
-    from test_seabed_gpu import BED as STEP_BED
+    from designed_populations import BED as STEP_BED
     touches = br.touching_fp32(STEP_BED, st, pr).any(axis=1)
     for n in (200, 321):
         classes = [(touches & pulling)[:n].sum(), (touches & ~pulling)[:n].sum(), (pulling & ~touches)[:n].sum(), (~pulling & ~touches)[:n].sum()]
@@ -546,18 +379,6 @@ def test_lines_by_hand():
 
 
 # ---- the physics: config 1's buoy on a line --------------------------------------------------------------------------------------------
-DEPTH = 20.0                                                       # the anchor, below the buoy's equilibrium position (m)
-
-
-def buoy():
-    """Config 1's buoy at rest at its draught: (state, prev, params, scene, dt, z_eq, mass)."""
-    sc = scenes.scene_c1()
-    pr = sc.params[:1].astype(np.float32)
-    mass = float(pr[0, 10])
-    z_eq = 0.5 * float(pr[0, 2]) - mass / (sc.rho * float(pr[0, 0] * pr[0, 1]))
-    st = np.zeros((1, 13), np.float32)
-    st[0, 2], st[0, 6] = z_eq, 1.0
-    return st, np.zeros((1, 6), np.float32), pr, sc, float(np.float32(1.0 / 60.0)), z_eq, mass
 
 
 def test_still_water_a_short_line_pulls_the_buoy_down_to_the_analytic_depth():
@@ -565,7 +386,7 @@ def test_still_water_a_short_line_pulls_the_buoy_down_to_the_analytic_depth():
     k, c = Mooring.for_body(mass, dt)
     lines = Mooring((0.0, 0.0, z_eq - DEPTH), length=DEPTH - 1.0, stiffness=k, damping=c)          # 1 m short
     lines.check_stable(mass, dt)
-    run = mr.closed_loop_moor(st, pv, pr, sc.rho, sc.g, dt, 1800, lines.record, implicit=True)
+    run = closed_loop(st, pv, pr, sc.rho, sc.g, dt, 1800, moor=lines.record, implicit=True)
     s = run[-1]["state"][0].astype(np.float64)
     # rho g A (0.5 - z) - m g = k ((z - z_anchor) - L0), A = 1 m^2: linear in z
     z_want = (sc.rho * sc.g * 0.5 - mass * sc.g - k * (DEPTH - z_eq - (DEPTH - 1.0))) / (sc.rho * sc.g + k)
@@ -584,8 +405,8 @@ def in_a_current():
     k, c = Mooring.for_body(mass, dt)
     lines = Mooring((0.0, 0.0, z_eq - DEPTH), length=DEPTH + 0.5, stiffness=k, damping=c)
     sea = SeaState((0.5, 0.0, 0.0))
-    moored = mr.closed_loop_moor(st, pv, pr, sc.rho, sc.g, dt, 3600, lines.record, sea=sea, implicit=True)
-    adrift = mr.closed_loop_moor(st, pv, pr, sc.rho, sc.g, dt, 3600, None, sea=sea, implicit=True)
+    moored = closed_loop(st, pv, pr, sc.rho, sc.g, dt, 3600, moor=lines.record, sea=sea, implicit=True)
+    adrift = closed_loop(st, pv, pr, sc.rho, sc.g, dt, 3600, sea=sea, implicit=True)
     return lines, moored, adrift
 
 

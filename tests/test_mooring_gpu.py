@@ -6,7 +6,7 @@ bound; a launch of 7 steps equals 7 of 1 and (2, 5), recorded rows included; ref
 runners and a graph replay; the buoy of tests/test_mooring.py settles and keeps station on the device; the example.
 
 Sizes: n = 200 (one block: three full tiles and 8 lanes) and n = 321 (two blocks, the last wave with one live lane).  The
-population is test_mooring.line_population over the bodies of tests/test_seabed_gpu.py.
+population is mooring_population.line_population over the bodies of tests/test_seabed_gpu.py.
 
 THE PROBE BOUND.  Errors of hydro_mooring_wrench against mooring_reference.wrench (fp64), in units of 2^-24 of
 mooring_reference.wrench_scales, over the designed population, the eight bodies at the tie aside.  The rule: the next power
@@ -24,7 +24,6 @@ formed on the host in fp32 from three device results.
 
 Bound of the fp64 step comparison: integrator_oracle.STEP_ULP_BOUND (24), scales as in tests/test_seabed_gpu.py with the
 line's own term magnitudes (mooring_reference.wrench_scales) added to the surrogate wrench."""
-import ctypes
 import os
 import re
 import subprocess
@@ -44,26 +43,15 @@ from silver2_isaacsim_amd.mooring import Mooring
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.seabed import Seabed
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import B, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, G, NAN, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers, _engine, _k, _ke, _same, _tiled
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_mooring import ALL_TILE, CLAMPED, DEPTH, NONE_TILE, PROBE_BOUND, TIES, buoy, line_population, population_report
-from test_pose_hold_gpu import S_C
-from test_seabed_gpu import BED, SEA, _fp64_errors
-from test_seabed_gpu import pop as bed_pop                        # noqa: F401  (fixture: the designed population moved onto the bed)
-from test_seabed_gpu import hold_pop                              # noqa: F401  (fixture bed_pop is built from)
+from designed_populations import BED, bed_pop, hold_pop, SEA, SIZES, STEPS  # noqa: F401  (fixtures are requested by name)
+from mooring_population import ALL_TILE, _buoys, CLAMPED, DEPTH, moored_pop as pop, NONE_TILE, OFF_TIES, population_report, TIES  # noqa: F401  (fixtures are requested by name)
+from mooring_reference import PROBE_BOUND
+from resident_harness import (B, _buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, fp64_step_errors, _from, G, _guarded, _k, _ke, NAN, raw, RHO, S_A,
+                              S_C, S_IN, S_M, S_OUT, S_PV, S_PVO, _same, _same_bits, step, _tiled, _unguard, _untouched, _watched)
 
 pytestmark = pytest.mark.gpu
-SIZES = (200, 321)
-STEPS = (1, 7)
-S_M = 9 * 64 + 52                                                 # the mooring record's tile stride in the guard tests
+WATCH = (0, 5, 63, 64, 80, 130)                                   # the watched bodies, with the last one
 S_W = 6 * 64 + 28                                                 # the probe's
-OFF_TIES = ~np.isin(np.arange(321), TIES)
-
-
-@pytest.fixture(scope="module")
-def pop(bed_pop):
-    st, pv, params, applied, ctl = bed_pop
-    return st, pv, params, applied, ctl, line_population(st, params["f32"])
 
 
 def test_population_is_what_it_was_designed_to_be(pop):
@@ -78,29 +66,6 @@ def test_population_is_what_it_was_designed_to_be(pop):
     assert not rec[TIES[:4], 8].any() and (rec[TIES[4:], 8] > 0).all()
 
 
-def _step(eng, cur, old, n, steps, step0=0, mooring=None, control=None, applied=None, implicit=False, ke=None, frame="world", entry="moor", **kw):
-    """One launch through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one."""
-    if entry == "moor":
-        eng.step_fused_tiled_multi_moor(cur, old, n, DT, steps, step0, mooring, control, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    else:
-        assert mooring is None
-        eng.step_fused_tiled_multi_bed(cur, old, n, DT, steps, step0, control, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
-
-
-def _watched(n):
-    return sorted({b for b in (0, 5, 63, 64, 80, 130, n - 1) if b < n})
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _from(t, n):
-    return scenes.from_tiled(t.contiguous().cpu().numpy(), n)
-
-
 # ---- 1. no record, and a record without lines --------------------------------------------------------------------------------------
 @COEFFS
 @DRAG
@@ -113,7 +78,7 @@ def test_no_record_and_no_lines_are_the_bed_entry(coeff, implicit, pop, native_b
     unmoored[:, 7:9] = 0.0
     for n in SIZES:
         eng = _engine(n, params[coeff], coeff)
-        watched = _watched(n)
+        watched = _watched(n, WATCH)
         eng.set_watch(watched)
         a, c17, none = _tiled(applied[:n]), _tiled(ctl[:n]), _tiled(unmoored[:n])
         combos = [(steps, app, control, with_log) for steps in STEPS for app in (None, a) for control in (None, c17) for with_log in (False, True)]
@@ -127,12 +92,12 @@ def test_no_record_and_no_lines_are_the_bed_entry(coeff, implicit, pop, native_b
                 for steps, app, control, with_log in combos:
                     cur, old = _buffers(st, pv, n)
                     w_ke, kw = _ke(), logs(with_log)
-                    w_state, w_prev = _step(eng, cur, old, n, steps, 3, None, control, app, implicit, w_ke, entry="bed", **kw)
+                    w_state, w_prev = step(eng, "bed", cur, old, n, steps, step0=3, control=control, applied=app, implicit=implicit, ke=w_ke, **kw)
                     w_log = kw.get("log")
                     for lines in (None, none):
                         c, o = _buffers(st, pv, n)
                         ke, kw = _ke(), logs(with_log)
-                        got, got_prev = _step(eng, c, o, n, steps, 3, lines, control, app, implicit, ke, **kw)
+                        got, got_prev = step(eng, "moor", c, o, n, steps, step0=3, mooring=lines, control=control, applied=app, implicit=implicit, ke=ke, **kw)
                         torch.cuda.synchronize()
                         what = (n, steps, app is None, control is None, with_log, sea is None, bed is None, lines is None)
                         assert _same_bits(got, w_state) and _same_bits(got_prev, w_prev) and _same_bits(ke, w_ke), what
@@ -199,7 +164,7 @@ def test_mooring_step_is_the_bed_step_with_the_probe_wrench_applied(coeff, seman
             eng.set_seabed(bed)
             log = torch.full((1, 19, n), NAN, dtype=torch.float32, device=DEV)
             cur, old = _buffers(st, pv, n)
-            state, prev = _step(eng, cur, old, n, 1, 7, mooring, None, applied, implicit, entry=entry, log=log)
+            state, prev = step(eng, entry, cur, old, n, 1, step0=7, mooring=mooring, applied=applied, implicit=implicit, log=log)
             torch.cuda.synchronize()
             return state.clone(), prev.clone(), log
 
@@ -250,7 +215,7 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
         keep[TIES[4:]] = False
         hydro = _from(eng.step_wrench_tiled(_tiled(s_rel), n, DT, prev=_tiled(pv_rel)), n)
         cur, old = _buffers(st, pv, n)
-        got, _ = _step(eng, cur, old, n, 1, 7, _tiled(rec[:n]), _tiled(ctl[:n]), _tiled(applied[:n]), True)
+        got, _ = step(eng, "moor", cur, old, n, 1, step0=7, mooring=_tiled(rec[:n]), control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=True)
         torch.cuda.synchronize()
         got = _from(got, n)
         comps = ho.step_wrench(s_rel, pv_rel, pr[:n], RHO, G, DT)[2]
@@ -261,7 +226,7 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
         extra = br.wrench(BED, st[:n], pr[:n], touch) + mr.wrench(rec[:n], st[:n], on)
         extra_scale = br.wrench_scales(BED, st[:n], pr[:n], touch) + mr.wrench_scales(rec[:n], st[:n], on)
         assert (mr.tension(rec[:n], st[:n], on)[keep] > 0).mean() > 0.25
-        worst[n] = _fp64_errors(got[keep], st[:n][keep], hydro[keep], applied[:n][keep], ctl[:n][keep], pr[:n][keep], k, extra[keep], extra_scale[keep])
+        worst[n] = fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=applied[:n][keep], ctl=ctl[:n][keep], bed_wrench=extra[keep], bed_scale=extra_scale[keep])
         eng.close()
     from oracle import integrator_oracle as io
     per_group = {g: max(w[g] for w in worst.values()) for g in io.GROUPS}
@@ -281,7 +246,7 @@ def test_one_launch_equals_single_steps_and_chunks(coeff, implicit, pop, native_
         eng = _engine(n, params[coeff], coeff)
         eng.set_sea(SEA)
         eng.set_seabed(BED)
-        watched = _watched(n)
+        watched = _watched(n, WATCH)
         eng.set_watch(watched)
         assert (mr.tension(rec[:n], st[:n])[watched] > 0).sum() >= 2
         lines = _tiled(rec[:n])
@@ -291,7 +256,7 @@ def test_one_launch_equals_single_steps_and_chunks(coeff, implicit, pop, native_
             log = torch.full((7, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)
             done = 0
             for k in chunks:
-                _step(eng, cur, old, n, k, 100 + done, lines, implicit=implicit, log=log, every=1, phase=1, row0=done)
+                step(eng, "moor", cur, old, n, k, step0=100 + done, mooring=lines, implicit=implicit, log=log, every=1, phase=1, row0=done)
                 cur, old = old, cur
                 done += k
             torch.cuda.synchronize()
@@ -319,7 +284,7 @@ def test_energy_and_non_temporal_instantiations_with_lines_pulling(coeff, semant
 
         def run(ke=None, **kw):
             cur, old = _buffers(st, pv, n)
-            state, prev = _step(eng, cur, old, n, 7, 5, lines, c17, a, implicit, ke, **kw)
+            state, prev = step(eng, "moor", cur, old, n, 7, step0=5, mooring=lines, control=c17, applied=a, implicit=implicit, ke=ke, **kw)
             torch.cuda.synchronize()
             return state, prev
         eng.set_tuning(0, 0, 0)
@@ -346,13 +311,6 @@ def test_energy_and_non_temporal_instantiations_with_lines_pulling(coeff, semant
 
 
 # ---- 6. refusals and guards through the raw C ABI ------------------------------------------------------------------------------------
-def _raw(eng, n, state, prev, out, pvo, step0=0, steps=1, log=None, applied=None, control=None, mooring=None, stride=S_M, implicit=0):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_moor(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        applied, S_A, 0, control, S_C, mooring, stride, step0, eng._stream(None))
-    return rc, written.value
 
 
 def test_refusals_launch_nothing(pop, native_built):
@@ -373,26 +331,26 @@ def test_refusals_launch_nothing(pop, native_built):
         eng.set_seabed(bed)
         eng.set_sea(sea)
         for lines in (m, None):                                  # the bed entry's refusals, with lines and without
-            assert _raw(eng, n, state, prev, out, pvo, step0=-1, mooring=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, step0=2 ** 52 - 1, steps=1, mooring=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, steps=0, mooring=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, applied=a.data_ptr() + 4, mooring=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, control=c17.data_ptr() + 4, mooring=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, control=out.data_ptr(), mooring=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, log=log, mooring=lines) == (E_STATE, -7)        # a log without a watch list
+            assert raw(eng, "moor", n, state, prev, out, pvo, step0=-1, mooring=lines) == (E_ARG, -7)
+            assert raw(eng, "moor", n, state, prev, out, pvo, step0=2 ** 52 - 1, mooring=lines) == (E_ARG, -7)
+            assert raw(eng, "moor", n, state, prev, out, pvo, steps=0, mooring=lines) == (E_ARG, -7)
+            assert raw(eng, "moor", n, state, prev, out, pvo, applied=a.data_ptr() + 4, mooring=lines) == (E_ARG, -7)
+            assert raw(eng, "moor", n, state, prev, out, pvo, control=c17.data_ptr() + 4, mooring=lines) == (E_ARG, -7)
+            assert raw(eng, "moor", n, state, prev, out, pvo, control=out.data_ptr(), mooring=lines) == (E_ARG, -7)
+            assert raw(eng, "moor", n, state, prev, out, pvo, log=log, mooring=lines) == (E_STATE, -7)        # a log without a watch list
         # the mooring's own
-        assert _raw(eng, n, state, prev, out, pvo, mooring=m + 4) == (E_ARG, -7)                       # misaligned
-        assert _raw(eng, n, state, prev, out, pvo, mooring=m, stride=572) == (E_ARG, -7)               # below 9 * 64
-        assert _raw(eng, n, state, prev, out, pvo, mooring=m, stride=578) == (E_ARG, -7)               # not a multiple of 4
-        assert _raw(eng, n, state, prev, out, pvo, mooring=out.data_ptr()) == (E_ARG, -7)              # aliases state_out
-        assert _raw(eng, n, state, prev, out, pvo, mooring=pvo.data_ptr()) == (E_ARG, -7)              # aliases prev_out
+        assert raw(eng, "moor", n, state, prev, out, pvo, mooring=m + 4) == (E_ARG, -7)                       # misaligned
+        assert raw(eng, "moor", n, state, prev, out, pvo, mooring=m, s_mooring=572) == (E_ARG, -7)               # below 9 * 64
+        assert raw(eng, "moor", n, state, prev, out, pvo, mooring=m, s_mooring=578) == (E_ARG, -7)               # not a multiple of 4
+        assert raw(eng, "moor", n, state, prev, out, pvo, mooring=out.data_ptr()) == (E_ARG, -7)              # aliases state_out
+        assert raw(eng, "moor", n, state, prev, out, pvo, mooring=pvo.data_ptr()) == (E_ARG, -7)              # aliases prev_out
         assert "mooring must not overlap" in eng._lib.hydro_last_error(eng._h).decode()
         # control is refused before the mooring
-        assert _raw(eng, n, state, prev, out, pvo, control=c17.data_ptr() + 4, mooring=m + 4) == (E_ARG, -7)
+        assert raw(eng, "moor", n, state, prev, out, pvo, control=c17.data_ptr() + 4, mooring=m + 4) == (E_ARG, -7)
         assert "mooring" not in eng._lib.hydro_last_error(eng._h).decode()
         eng.set_watch([0, 320])
-        assert _raw(eng, n, state, prev, out, pvo, log=log, steps=5, mooring=m) == (E_ARG, -7)          # rows 0 .. 4 of 4
-        assert _raw(eng, n, state, prev, out, pvo, log=log, steps=1, mooring=log.data_ptr()) == (E_ARG, -7)     # aliases the log
+        assert raw(eng, "moor", n, state, prev, out, pvo, steps=5, log=log, mooring=m) == (E_ARG, -7)          # rows 0 .. 4 of 4
+        assert raw(eng, "moor", n, state, prev, out, pvo, log=log, mooring=log.data_ptr()) == (E_ARG, -7)     # aliases the log
     # the probe
     lib, s = eng._lib, eng._stream(None)
     sp, wp = state.data_ptr(), w.data_ptr()
@@ -429,8 +387,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     log = torch.full((4, 13, 8), NAN, device=DEV)
     w = torch.full((tiles * S_W,), NAN, device=DEV)
     eng._check(eng._lib.hydro_mooring_wrench(eng._h, n, state.data_ptr(), S_IN, m9.data_ptr(), S_M, w.data_ptr(), S_W, eng._stream(None)))
-    rc, written = _raw(eng, n, state, prev, out, pvo, step0=11, steps=3, log=log, applied=a.data_ptr(), control=c17.data_ptr(),
-                       mooring=m9.data_ptr(), implicit=implicit)
+    rc, written = raw(eng, "moor", n, state, prev, out, pvo, steps=3, step0=11, implicit=implicit, log=log, applied=a.data_ptr(), control=c17.data_ptr(), mooring=m9.data_ptr())
     eng._check(rc)
     torch.cuda.synchronize()
     assert written == 3
@@ -443,7 +400,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     assert all(_untouched(b, was) for b, was in zip((state, prev, a, c17, m9), before))
     assert np.isfinite(line).all(), "a sentinel was read"
     cur, old = _buffers(st, pv, n)
-    want, want_prev = _step(eng, cur, old, n, 3, 11, _tiled(rec[:n]), _tiled(ctl[:n]), _tiled(applied[:n]), implicit)
+    want, want_prev = step(eng, "moor", cur, old, n, 3, step0=11, mooring=_tiled(rec[:n]), control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=implicit)
     torch.cuda.synchronize()
     assert np.array_equal(got.view(np.uint32), _from(want, n).view(np.uint32))
     assert np.array_equal(pv_out.view(np.uint32), _from(want_prev, n).view(np.uint32))
@@ -517,16 +474,6 @@ def test_graph_replays_with_lines_bed_and_current_and_clear_mooring(native_built
 
 
 # ---- 8. the buoy of tests/test_mooring.py on the device ---------------------------------------------------------------------------------
-def _buoys():
-    """64 copies of config 1's buoy at rest at their draught, 50 m apart, copy i turned by i / 64 of a revolution about z."""
-    st, pv, pr, sc, dt, z_eq, mass = buoy()
-    i = np.arange(64)
-    st, pv, pr = np.tile(st, (64, 1)), np.tile(pv, (64, 1)), np.tile(pr, (64, 1))
-    st[:, 0], st[:, 1] = 50.0 * (i % 8), 50.0 * (i // 8)
-    yaw = 2.0 * np.pi * i / 64.0
-    st[:, 5], st[:, 6] = np.sin(0.5 * yaw), np.cos(0.5 * yaw)
-    anchors = np.stack([st[:, 0], st[:, 1], np.full(64, z_eq - DEPTH)], axis=1).astype(np.float64)
-    return scenes.Scene("buoys", st, pv, pr, dt=dt, rho=sc.rho, g=sc.g), anchors, z_eq, mass
 
 
 def test_still_water_the_buoys_settle_at_the_analytic_depth_on_the_device(native_built):

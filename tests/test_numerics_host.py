@@ -9,6 +9,7 @@ import pytest
 
 from conftest import REPO, SCENE_FIXTURES, load_golden
 from oracle import hydro_oracle as ho
+from edge_cases import check_components
 
 GATE = 1e-5
 
@@ -164,15 +165,3 @@ def test_quantised_fuzz_host(emul):
     check_components(comps, cr, ref)
 
 
-def check_components(comps, ratio, ref):
-    """comps (n,8,3) fp32 / ratio (n) against the oracle's dict: forces and torques to 1e-6 of the body's largest term,
-    centres to half an fp32 ulp, exact zeros for dry bodies."""
-    force_scale = np.maximum(1.0, np.max([np.abs(ref[f]).max(axis=1) for f in ho.COMPONENT_FIELDS[:6]], axis=0))
-    for k, fld in enumerate(ho.COMPONENT_FIELDS[:6]):
-        assert np.all(np.abs(comps[:, k, :] - ref[fld]).max(axis=1) <= 1e-6 * force_scale), fld
-    for k, fld in ((6, "center_of_buoyancy"), (7, "center_of_pressure")):
-        tol = 0.5 * np.spacing(np.abs(ref[fld]).astype(np.float32)).astype(np.float64) * (1 + 1e-6) + 1e-12
-        assert np.all(np.abs(comps[:, k, :] - ref[fld]) <= tol), fld
-    dry = ref["ratio"] == 0.0
-    assert np.all(comps[dry] == 0.0)
-    assert np.abs(ratio - ref["ratio"]).max() < 5e-7

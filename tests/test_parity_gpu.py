@@ -913,7 +913,7 @@ def test_surface_ties_through_every_entry(native_built):
     hydro_step_wrench_ext, _tiled and _aos, and the calculator surface through hydro_step_components and _aos (forces to
     1e-6 of the body's largest term, centres to half an fp32 ulp, cob = position exactly when the top keypoint is on the
     surface: numba_hydrodynamics.py:87-88)."""
-    from test_numerics_host import check_components
+    from edge_cases import check_components
     fx = load_golden("ties")
     rho, g, dt = float(fx["rho"]), float(fx["g"]), float(fx["dt"])
     f, t = _every_wrench_entry(fx["state"], fx["prev"], fx["params"], rho, g, dt)
@@ -944,7 +944,7 @@ def test_quantised_fuzz_on_device(native_built):
     DEVICE, whose reciprocals and roots are the seeded forms: wrench within the gate, ratio, and the calculator surface
     (centres to half an fp32 ulp) - every exact tie of the model decided as the reference decides it."""
     import populations
-    from test_numerics_host import check_components
+    from edge_cases import check_components
     st, pv, pr, kind = populations.surface_ties(n=200000, seed=777)
     f, t = run_ext(st, pv, pr, populations.RHO, populations.G, populations.DT)
     rf, rt, aux = ho.step_wrench(st, pv, pr, populations.RHO, populations.G, populations.DT)

@@ -14,11 +14,7 @@ from silver2_isaacsim_amd.wrapper import HipHydrodynamicsWrapper
 
 pytestmark = pytest.mark.gpu
 from silver2_isaacsim_amd.testing import MAIN_SCENE, build_main_scene      # noqa: E402
-
-
-def build_scene(batched, config_path=None, seed=0):
-    """The 20 prims of silver2_isaac_sim.usd that carry the behavior."""
-    return build_main_scene(batched, config_path, seed)
+from designed_populations import build_scene
 
 
 def oracle_wrench(world, prims, host, prev6, dt, semantics="numba"):

@@ -13,7 +13,7 @@ import torch
 import pose_hold_reference as phr
 from conftest import REPO
 from silver2_isaacsim_amd import _native as nat
-from test_engine_calls import DEV, FUSED_HEAD, KE, N, P13, S, SO, STREAM, TILES, T, eng, lib, refused  # noqa: F401  (fixtures)
+from engine_stand_ins import DEV, eng, FUSED_HEAD, KE, lib, N, P13, refused, S, SO, STREAM, T, TILES  # noqa: F401  (fixtures are requested by name)
 
 ENTRY = "hydro_step_fused_tiled_multi_ctl"
 A = T((TILES, 6, 64), 0x88000000)                                # the applied wrench's stand-in

@@ -9,7 +9,6 @@ scales are those of field_scales on a surrogate wrench that extends the applied 
 before they cancel: per axis |F_hydro,i| + |f_applied| + |(|kp e_p| + |kd v|)|, and |tau_hydro| + |tau_applied| +
 kp_ang 2 |q*| |q| + kd_ang |omega|.  Each of those tests prints its largest error per group.
 Measured on an MI355X: see DESIGN.md section 16."""
-import ctypes
 import importlib.util
 import os
 
@@ -17,61 +16,17 @@ import numpy as np
 import pytest
 import torch
 
-import populations
 import pose_hold_reference as phr
 from conftest import REPO
-from oracle import hydro_oracle as ho
 from oracle import integrator_oracle as io
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.simulate import ClosedLoopSim, recorder_cadence
-from test_applied_wrench_gpu import (B, COEFFS, DEV, DRAG, DT, G, NAN, RHO, SIZES, STEPS, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers,
-                                     _engine, _hydro_wrench, _k, _ke, _push, _report, _same, _same_values, _tiled)
-from test_integrator_gpu import _guarded, _unguard, _untouched
+from designed_populations import hold_pop as pop  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (B, _bits, _buffers, COEFFS, DEV, DRAG, DT, _engine, fp64_step_errors, G, _guarded, _hydro_wrench, _k, _ke, NAN, _push, raw,
+                              _report, RHO, S_A, S_C, S_IN, S_OUT, S_PV, S_PVO, _same, _same_values, SIZES, step, step_wrench_terms, STEPS, _tiled, _unguard,
+                              _untouched)
 
 pytestmark = pytest.mark.gpu
-S_C = 17 * 64 + 44                                               # the control record's tile stride in the guard tests
-
-
-@pytest.fixture(scope="module")
-def pop():
-    """The designed population of the applied-wrench tests with its applied wrench, and a control record per body:
-    targets up to 2 m and up to 2.4 rad away (half of the target quaternions written with the opposite sign, so that both
-    sides of the law's sign flip occur; every |q_e.w| >= 0.1), gains per unit mass / inertia of 5 .. 50 s^-2 and 1 .. 10 s^-1
-    (one axis in eight without a linear gain), and limits: body 6k saturates f_max, body 6k + 3 saturates t_max (at 0.1 .. 0.9
-    of the unclamped norm), the others are unlimited or stay below twice their unclamped norm."""
-    st, pv, pr = populations.integrator_population(n=max(SIZES), seed=31)
-    n = len(st)
-    params = {"f32": pr, "f16": pr.copy()}
-    params["f16"][:, 3:10] = pr[:, 3:10].astype(np.float16).astype(np.float32)
-    rng = np.random.default_rng(77)
-    top = 50.0 * pr[:, 10:11].astype(np.float64)
-    applied = np.concatenate([rng.uniform(-1, 1, (n, 3)) * top,
-                              rng.uniform(-1, 1, (n, 3)) * top * pr[:, 0:3].max(axis=1, keepdims=True)], axis=1).astype(np.float32)
-    rng = np.random.default_rng(78)
-    mass = pr[:, 10:11].astype(np.float64)
-    inertia = io.box_inertia(pr.astype(np.float64)).mean(axis=1)
-    axis = rng.normal(size=(n, 3))
-    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
-    half = 0.5 * rng.uniform(0.0, 2.4, (n, 1))
-    dq = np.concatenate([np.sin(half) * axis, np.cos(half)], axis=1)
-    q = st[:, 3:7].astype(np.float64)
-    target_q = np.concatenate([dq[:, 3:4] * q[:, 0:3] + q[:, 3:4] * dq[:, 0:3] + np.cross(dq[:, 0:3], q[:, 0:3]),
-                               dq[:, 3:4] * q[:, 3:4] - np.sum(dq[:, 0:3] * q[:, 0:3], axis=1, keepdims=True)], axis=1)
-    target_q *= np.where(np.arange(n) % 2 == 0, 1.0, -1.0)[:, None]
-    kp_lin = mass * rng.uniform(5.0, 50.0, (n, 3)) * (rng.uniform(0, 1, (n, 3)) > 0.125)
-    ctl = phr.record(n, st[:, 0:3].astype(np.float64) + rng.uniform(-2.0, 2.0, (n, 3)), target_q, kp_lin, mass * rng.uniform(1.0, 10.0, (n, 3)),
-                     inertia * rng.uniform(5.0, 50.0, n), inertia * rng.uniform(1.0, 10.0, n))
-    force, torque = phr.unclamped(st, ctl)
-    which, frac = np.arange(n) % 6, rng.uniform(0.1, 0.9, n)
-    ctl[:, phr.F_MAX] = np.where(which == 0, frac * np.linalg.norm(force, axis=1), np.where(which == 1, 2.0 * np.linalg.norm(force, axis=1), np.inf))
-    ctl[:, phr.T_MAX] = np.where(which == 3, frac * np.linalg.norm(torque, axis=1), np.where(which == 4, 2.0 * np.linalg.norm(torque, axis=1), np.inf))
-    cache = {}
-
-    def comps(coeff):
-        if coeff not in cache:
-            cache[coeff] = ho.step_wrench(st, pv, params[coeff], RHO, G, DT)[2]
-        return cache[coeff]
-    return st, pv, params, applied, ctl, comps
 
 
 def test_population_covers_the_law(pop):
@@ -84,31 +39,6 @@ def test_population_covers_the_law(pop):
     sat_f, sat_t = phr.saturated(st, ctl)
     assert 0.25 <= (sat_f | sat_t).mean() <= 0.45 and sat_f.mean() > 0.1 and sat_t.mean() > 0.1
     assert np.isfinite(phr.wrench(st, ctl)).all()
-
-
-def _step(eng, cur, old, n, steps, control, applied, implicit, ke=None, frame="world", **kw):
-    """One launch through the engine; returns (state, prev_out) like the applied tests' helper."""
-    eng.step_fused_tiled_multi_controlled(cur, old, n, DT, steps, control, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
-
-
-def _surrogate(st, hydro, a, ctl):
-    """(fp64 total wrench, surrogate wrench for the scales): hydro + applied (world frame) + law."""
-    h64, a64, law = hydro.astype(np.float64), a.astype(np.float64), phr.wrench(st, ctl)
-    lin, ang = phr.term_magnitudes(st, ctl)
-    total = h64 + a64 + law
-    surrogate = np.zeros_like(total)
-    surrogate[:, 0:3] = np.abs(h64[:, 0:3]) + np.linalg.norm(a64[:, 0:3], axis=1, keepdims=True) + np.linalg.norm(lin, axis=1, keepdims=True)
-    surrogate[:, 3] = np.linalg.norm(h64[:, 3:6], axis=1) + np.linalg.norm(a64[:, 3:6], axis=1) + ang
-    return total, surrogate
-
-
-def _fp64_errors(got, st, hydro, a, ctl, pr, k):
-    total, surrogate = _surrogate(st, hydro, a, ctl)
-    ref = io.integrate(st, total, pr, G, DT, *(k or (None, None)))
-    sc = io.field_scales(st, surrogate, pr, G, DT, k, ref)
-    err = io.integrator_error_ulps(got, ref, st, total, pr, G, DT, k, scales=sc)
-    return {g: float(np.nan_to_num(e, nan=np.inf).max(initial=0.0)) for g, e in err.items()}
 
 
 # ---- 1. dispatch ---------------------------------------------------------------------------------------------------------------
@@ -137,7 +67,7 @@ def test_no_control_is_the_applied_entry_and_zero_gains_change_nothing(coeff, im
                     for control in (None, z):
                         c, o = _buffers(st, pv, n)
                         ke, kw = _ke(), logs()
-                        got, got_prev = _step(eng, c, o, n, steps, control, app, implicit, ke, **kw)
+                        got, got_prev = step(eng, "ctl", c, o, n, steps, control=control, applied=app, implicit=implicit, ke=ke, **kw)
                         torch.cuda.synchronize()
                         what = (n, steps, app is None, with_log, control is None)
                         assert _same_values(got, want) and _same_values(got_prev, want_prev) and _same_values(ke, ke0), what
@@ -151,7 +81,7 @@ def test_no_control_is_the_applied_entry_and_zero_gains_change_nothing(coeff, im
         cur, old = _buffers(st, pv, n)
         want = eng.step_fused_tiled_multi(cur, old, n, DT, 2, implicit_drag=implicit)
         c, o = _buffers(st, pv, n)
-        got, _ = _step(eng, c, o, n, 2, z, None, implicit)
+        got, _ = step(eng, "ctl", c, o, n, 2, control=z, implicit=implicit)
         torch.cuda.synchronize()
         assert _same_values(got, want), n
         eng.close()
@@ -170,10 +100,10 @@ def test_one_step_against_fp64(coeff, implicit, with_applied, pop, native_built)
         eng = _engine(n, pr, coeff)
         cur, old = _buffers(st, pv, n)
         hydro = scenes.from_tiled(_hydro_wrench(eng, cur, old, n).cpu().numpy(), n)
-        got, _ = _step(eng, cur, old, n, 1, _tiled(ctl[:n]), _tiled(applied[:n]) if with_applied else None, implicit)
+        got, _ = step(eng, "ctl", cur, old, n, 1, control=_tiled(ctl[:n]), applied=_tiled(applied[:n]) if with_applied else None, implicit=implicit)
         torch.cuda.synchronize()
         k = _k(comps(coeff), st, pr, coeff, n) if implicit else None
-        worst[n] = _fp64_errors(scenes.from_tiled(got.cpu().numpy(), n), st[:n], hydro, a_host[:n], ctl[:n], pr[:n], k)
+        worst[n] = fp64_step_errors(scenes.from_tiled(got.cpu().numpy(), n), st[:n], hydro, pr[:n], k, applied=a_host[:n], ctl=ctl[:n])
         eng.close()
     _report(f"pose hold{' + applied' if with_applied else ''} {'implicit' if implicit else 'explicit'} {coeff}", worst)
 
@@ -189,11 +119,11 @@ def test_resident_launch_equals_single_steps_and_is_no_zero_order_hold(coeff, im
         before = c17.clone()
         cur, old = _buffers(st, pv, n)
         ke7 = _ke()
-        got, got_prev = _step(eng, cur, old, n, 7, c17, a, implicit, ke7, frame="body")
+        got, got_prev = step(eng, "ctl", cur, old, n, 7, control=c17, applied=a, frame="body", implicit=implicit, ke=ke7)
         c, o = _buffers(st, pv, n)
         ke1 = _ke()
         for k in range(7):
-            _step(eng, c, o, n, 1, c17, a, implicit, ke1 if k == 6 else None, frame="body")
+            step(eng, "ctl", c, o, n, 1, control=c17, applied=a, frame="body", implicit=implicit, ke=ke1 if k == 6 else None)
             c, o = o, c
         torch.cuda.synchronize()
         assert torch.equal(_bits(got), _bits(c)) and torch.equal(_bits(got_prev), _bits(o[:, 7:13])), n
@@ -203,7 +133,7 @@ def test_resident_launch_equals_single_steps_and_is_no_zero_order_hold(coeff, im
         cz, oz = _buffers(st, pv, n)
         eng.step_fused_tiled_multi_applied(cz, oz, n, DT, 7, held, "world", implicit_drag=implicit)
         cf, of = _buffers(st, pv, n)
-        fed, _ = _step(eng, cf, of, n, 7, c17, None, implicit)
+        fed, _ = step(eng, "ctl", cf, of, n, 7, control=c17, implicit=implicit)
         torch.cuda.synchronize()
         fed, zoh = scenes.from_tiled(fed.cpu().numpy(), n), scenes.from_tiled(oz.cpu().numpy(), n)
         both = np.isfinite(fed).all(axis=1) & np.isfinite(zoh).all(axis=1)   # (seven explicit steps carry some light bodies out of range, body 0 among them)
@@ -277,11 +207,11 @@ def test_recorded_rows_with_a_pose_hold(coeff, implicit, pop, native_built):
         for _ in range(steps):
             before = scenes.from_tiled(c.cpu().numpy(), n)
             hydro = scenes.from_tiled(_hydro_wrench(eng, c, o, n).cpu().numpy(), n)
-            total, surrogate = _surrogate(before[watched], hydro[watched], applied[:n][watched], ctl[:n][watched])
+            total, surrogate = step_wrench_terms(before[watched], hydro[watched], applied=applied[:n][watched], ctl=ctl[:n][watched])
             surrogate[:, 3:6] = surrogate[:, 3:4]
             totals.append(total)
             scales.append(surrogate)
-            _step(eng, c, o, n, 1, c17, a, implicit)
+            step(eng, "ctl", c, o, n, 1, control=c17, applied=a, implicit=implicit)
             c, o = o, c
             states.append(scenes.from_tiled(c.cpu().numpy(), n)[watched])
         log = torch.full((5, 19, len(watched) + 2), NAN, dtype=torch.float32, device=DEV)
@@ -297,11 +227,11 @@ def test_recorded_rows_with_a_pose_hold(coeff, implicit, pop, native_built):
         torch.cuda.synchronize()
         assert rows == 3
         host = log.cpu().numpy()
-        for r, step in enumerate((2, 4, 6)):
-            assert np.array_equal(host[r, :13, :len(watched)].T.view(np.uint32), states[step - 1].view(np.uint32)), (n, step)
-            gw, ww, sc = host[r, 13:, :len(watched)].T.astype(np.float64), totals[step - 1], scales[step - 1]
+        for r, after in enumerate((2, 4, 6)):
+            assert np.array_equal(host[r, :13, :len(watched)].T.view(np.uint32), states[after - 1].view(np.uint32)), (n, after)
+            gw, ww, sc = host[r, 13:, :len(watched)].T.astype(np.float64), totals[after - 1], scales[after - 1]
             fine = np.isfinite(ww) & np.isfinite(sc)             # (the explicit form may have carried a light body out of range)
-            assert (np.isfinite(gw) == np.isfinite(ww))[fine].all(), (n, step)
+            assert (np.isfinite(gw) == np.isfinite(ww))[fine].all(), (n, after)
             err = np.abs(gw - ww)[fine & np.isfinite(gw)] / (io.ULP * sc[fine & np.isfinite(gw)])
             worst = max(worst, float(err.max(initial=0.0)))
         assert np.isnan(host[3:]).all() and np.isnan(host[:, :, len(watched):]).all()
@@ -312,13 +242,6 @@ def test_recorded_rows_with_a_pose_hold(coeff, implicit, pop, native_built):
 
 
 # ---- 6. guards and refusals through the raw C ABI ----------------------------------------------------------------------------------
-def _raw(eng, n, state, prev, out, pvo, applied, control, implicit=0, a_stride=S_A, c_stride=S_C, log=None, steps=1):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_ctl(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        applied, a_stride, 0, control, c_stride, eng._stream(None))
-    return rc, written.value
 
 
 @COEFFS
@@ -339,7 +262,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
         wbuf = _guarded(np.zeros((n, 6), np.float32), 6 * 64 + 8)
         eng._check(eng._lib.hydro_step_wrench_tiled(eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT,
                                                     wbuf.data_ptr(), 6 * 64 + 8, eng._stream(None)))
-        rc, written = _raw(eng, n, state, prev, out, pvo, a.data_ptr(), c17.data_ptr(), implicit)
+        rc, written = raw(eng, "ctl", n, state, prev, out, pvo, implicit=implicit, applied=a.data_ptr(), control=c17.data_ptr())
         eng._check(rc)
         torch.cuda.synchronize()
         assert written == 0
@@ -351,7 +274,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
         assert np.isfinite(got).all(), (n, "a sentinel was read")
         hydro, _ = _unguard(wbuf, n, 6, 6 * 64 + 8)
         k = _k(comps(coeff), st, pr, coeff, n) if implicit else None
-        worst[n] = _fp64_errors(got, st[:n], hydro, applied[:n], ctl[:n], pr[:n], k)
+        worst[n] = fp64_step_errors(got, st[:n], hydro, pr[:n], k, applied=applied[:n], ctl=ctl[:n])
         eng.close()
     _report(f"C ABI pose hold {'implicit' if implicit else 'explicit'} {coeff}, strides {S_IN}/{S_OUT}/{S_A}/{S_C}", worst)
 
@@ -368,24 +291,24 @@ def test_refusals_launch_nothing(pop, native_built):
     E_ARG, E_STATE = -1, -5
     ap, cp = a.data_ptr(), c17.data_ptr()
     for app in (None, ap):
-        assert _raw(eng, n, state, prev, out, pvo, app, cp + 4) == (E_ARG, -7)                # misaligned
-        assert _raw(eng, n, state, prev, out, pvo, app, cp, c_stride=1087) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, app, cp, c_stride=1090) == (E_ARG, -7)     # not a multiple of 4
-        assert _raw(eng, n, state, prev, out, pvo, app, cp, c_stride=1 << 24) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, app, out.data_ptr()) == (E_ARG, -7)        # control aliases state_out
-        assert _raw(eng, n, state, prev, out, pvo, app, pvo.data_ptr()) == (E_ARG, -7)        # ... prev_out
-        assert _raw(eng, n, state, prev, out, pvo, app, cp, steps=0) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, ap + 4, cp) == (E_ARG, -7)                     # what the applied entry refuses
-    assert _raw(eng, n, state, prev, out, pvo, ap, cp, a_stride=383) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, None, cp, log=log) == (E_STATE, -7)            # a log without a watch list
+        assert raw(eng, "ctl", n, state, prev, out, pvo, applied=app, control=cp + 4) == (E_ARG, -7)                # misaligned
+        assert raw(eng, "ctl", n, state, prev, out, pvo, applied=app, control=cp, s_control=1087) == (E_ARG, -7)
+        assert raw(eng, "ctl", n, state, prev, out, pvo, applied=app, control=cp, s_control=1090) == (E_ARG, -7)     # not a multiple of 4
+        assert raw(eng, "ctl", n, state, prev, out, pvo, applied=app, control=cp, s_control=1 << 24) == (E_ARG, -7)
+        assert raw(eng, "ctl", n, state, prev, out, pvo, applied=app, control=out.data_ptr()) == (E_ARG, -7)        # control aliases state_out
+        assert raw(eng, "ctl", n, state, prev, out, pvo, applied=app, control=pvo.data_ptr()) == (E_ARG, -7)        # ... prev_out
+        assert raw(eng, "ctl", n, state, prev, out, pvo, steps=0, applied=app, control=cp) == (E_ARG, -7)
+    assert raw(eng, "ctl", n, state, prev, out, pvo, applied=ap + 4, control=cp) == (E_ARG, -7)                     # what the applied entry refuses
+    assert raw(eng, "ctl", n, state, prev, out, pvo, applied=ap, s_applied=383, control=cp) == (E_ARG, -7)
+    assert raw(eng, "ctl", n, state, prev, out, pvo, log=log, control=cp) == (E_STATE, -7)            # a log without a watch list
     eng.set_watch([0, 256])
-    assert _raw(eng, n, state, prev, out, pvo, None, log.data_ptr() + 4 * 13 * 8 * 4 - 64, log=log) == (E_ARG, -7)    # control reaches into the log
-    assert _raw(eng, n, state, prev, out, pvo, None, cp, log=log, steps=5) == (E_ARG, -7)     # rows 0 .. 4 of 4
+    assert raw(eng, "ctl", n, state, prev, out, pvo, log=log, control=log.data_ptr() + 4 * 13 * 8 * 4 - 64) == (E_ARG, -7)    # control reaches into the log
+    assert raw(eng, "ctl", n, state, prev, out, pvo, steps=5, log=log, control=cp) == (E_ARG, -7)     # rows 0 .. 4 of 4
     torch.cuda.synchronize()
     assert torch.isnan(out).all() and torch.isnan(pvo).all() and torch.isnan(log).all()
     # and the legal launches next to them: a record just behind the log; with the log, rows are counted and written
     log[4 * 13 * 8:] = c17
-    assert _raw(eng, n, state, prev, out, pvo, None, log.data_ptr() + 4 * 13 * 8 * 4, log=log, steps=3) == (0, 3)
+    assert raw(eng, "ctl", n, state, prev, out, pvo, steps=3, log=log, control=log.data_ptr() + 4 * 13 * 8 * 4) == (0, 3)
     torch.cuda.synchronize()
     state3, _ = _unguard(out[:tiles * S_OUT], n, 13, S_OUT)
     rows = log[:4 * 13 * 8].view(4, 13, 8)

@@ -2,7 +2,7 @@
 as a machine without a GPU can see it: the dispersion relation of SeaState.regular, the host restatement against the fp64
 reference of tests/sea_reference.py, the C boundary, the Python host's marshalling (with the stand-ins of
 tests/test_engine_calls.py), ClosedLoopSim's bookkeeping with a fake engine, and the two physical checks the device tests lean
-on, run through sea_reference.closed_loop_sea."""
+on, run through closed_loop_reference.closed_loop."""
 import ctypes
 import math
 import os
@@ -13,11 +13,13 @@ import numpy as np
 import pytest
 
 import sea_reference as sr
+from closed_loop_reference import closed_loop
 from conftest import REPO
 from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import scenes, simulate
 from silver2_isaacsim_amd.sea import SeaState
-from test_engine_calls import FUSED_HEAD, H, KE, N, P13, S, SO, STREAM, TILES, T, eng, lib, refused  # noqa: F401  (fixtures)
+from designed_populations import drift_scene, _test_sea, wave_scene
+from engine_stand_ins import eng, FUSED_HEAD, H, KE, lib, N, P13, refused, S, SO, STREAM, T, TILES  # noqa: F401  (fixtures are requested by name)
 
 ENTRIES = ("hydro_set_sea", "hydro_sea_sample", "hydro_step_fused_tiled_multi_sea")
 A = T((TILES, 6, 64), 0x88000000)
@@ -51,14 +53,6 @@ def test_sea_state_refuses_what_the_library_refuses():
     with pytest.raises(ValueError, match="at most 8"):
         sea.add_wave(0.1, 0.5, 0.0, 2.0)
     assert len(sea.waves) == 8 and SeaState().add_wave(0.0, 0.0, 0.0, 0.0).waves == [(0.0, 0.0, 0.0, 0.0, 0.0)]
-
-
-def _test_sea():
-    sea = SeaState((0.5, -0.2, 0.05))
-    for lam, head, a, ph in ((100.0, 20.0, 0.2, 0.3), (25.0, -70.0, 0.1, 1.1), (8.0, 160.0, 0.05, -2.0)):
-        kappa = 2.0 * math.pi / lam
-        sea.add_wave(a, kappa * math.cos(math.radians(head)), kappa * math.sin(math.radians(head)), math.sqrt(9.81 * kappa), ph)
-    return sea
 
 
 def test_host_restatement_equals_the_reference():
@@ -261,24 +255,12 @@ def test_set_sea_needs_the_fused_step(sim):
 
 
 # ---- the physics the device tests lean on ------------------------------------------------------------------------------------------
-def drift_scene():
-    """A neutrally buoyant 0.5 m cube at z = -10 m, README coefficients, at rest; the current it is released into."""
-    st = np.zeros((1, 13), np.float32)
-    st[0, 2], st[0, 6] = -10.0, 1.0
-    pr = np.concatenate([[0.5, 0.5, 0.5], scenes._DEFAULT_COEFFS, [scenes.RHO * 0.125]])[None, :].astype(np.float32)
-    return st, np.zeros((1, 6), np.float32), pr, SeaState((0.5, 0.2, 0.0))
-
-
-def wave_scene():
-    """Config 1's buoy (unit cube, 500 kg) and the wave it rides: a = 0.2 m, T = 8 s, along +x; its equilibrium z."""
-    sc = scenes.scene_c1()
-    return sc, SeaState.regular(0.4, 8.0, 0.0), 0.5 - 500.0 / scenes.RHO
 
 
 @pytest.mark.parametrize("implicit", [False, True], ids=["explicit", "implicit"])
 def test_a_body_released_into_a_current_drifts_with_it(implicit):
     st, pv, pr, sea = drift_scene()
-    run = sr.closed_loop_sea(st, pv, pr, scenes.RHO, scenes.G, float(np.float32(1.0 / 60.0)), 1200, sea, implicit=implicit)
+    run = closed_loop(st, pv, pr, scenes.RHO, scenes.G, float(np.float32(1.0 / 60.0)), 1200, sea=sea, implicit=implicit)
     v, U = run[-1]["state"][0, 7:10].astype(np.float64), np.asarray(sea.current)
     drift = np.linalg.norm(v - U) / np.linalg.norm(U)
     print(f"[drift, {'implicit' if implicit else 'explicit'}] |v - U| / |U| after 1 200 steps: {drift:.3e}")
@@ -288,7 +270,7 @@ def test_a_body_released_into_a_current_drifts_with_it(implicit):
 
 def test_a_buoy_rides_the_wave():
     sc, sea, z_eq = wave_scene()
-    run = sr.closed_loop_sea(sc.state, sc.prev, sc.params, sc.rho, sc.g, sc.dt, 1920, sea)
+    run = closed_loop(sc.state, sc.prev, sc.params, sc.rho, sc.g, sc.dt, 1920, sea=sea, implicit=False)
     dev = np.array([abs(float(r["state"][0, 2]) - z_eq - float(sea.elevation(r["state"][0, 0], r["state"][0, 1], (k + 1) * sc.dt)))
                     for k, r in enumerate(run)])
     print(f"[wave] largest |z - z_eq - eta| after step 480: {dev[480:].max():.4f} m (over the whole run {dev.max():.4f} m)")

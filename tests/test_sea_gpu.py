@@ -29,30 +29,15 @@ from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import (B, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, G, NAN, RHO, SIZES, STEPS, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers,
-                                     _engine, _k, _ke, _report, _same, _tiled)
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_pose_hold_gpu import S_C, _fp64_errors
-from test_pose_hold_gpu import pop as hold_pop                    # noqa: F401  (fixture: the designed population with its control record)
-from test_sea import _test_sea, drift_scene, wave_scene
+from designed_populations import drift_scene, hold_pop, SEA, sea_pop as pop, wave_scene  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (B, _buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, fp64_step_errors, G, _guarded, _k, _ke, NAN, raw, _relative,
+                              _report, RHO, S_A, S_C, S_IN, S_OUT, S_PV, S_PVO, _same, _same_bits, SIZES, step, STEPS, _tiled, _unguard, _untouched, VIEW_STEPS,
+                              _watched)
 
 pytestmark = pytest.mark.gpu
+WATCH = (0, 63, 64)                                               # the watched bodies, with the last one
 VIEW_BOUND = 4.0
-VIEW_STEPS = (0, 1, 7, 10 ** 6)
 S_W = 4 * 64 + 52                                                 # the sample's tile stride in the guard tests
-
-
-SEA = _test_sea()              # U = (0.5, -0.2, 0.05); components of 100, 25 and 8 m wavelength at different headings, a = 0.2 .. 0.05 m
-
-
-@pytest.fixture(scope="module")
-def pop(hold_pop):
-    """The designed population of the applied-wrench and pose-hold tests, every body moved up or down by the surface
-    elevation above it at t = 0, so that the partial ones straddle the DISPLACED surface."""
-    st, pv, params, applied, ctl, _ = hold_pop
-    st = st.copy()
-    st[:, 2] = (st[:, 2].astype(np.float64) + SEA.elevation(st[:, 0], st[:, 1], 0.0)).astype(np.float32)
-    return st, pv, params, applied, ctl
 
 
 def test_population_meets_the_displaced_surface(pop):
@@ -63,20 +48,6 @@ def test_population_meets_the_displaced_surface(pop):
     straddle, submerged = np.abs(z_rel) < ext, z_rel < -ext
     assert straddle.mean() >= 1 / 3 and submerged.mean() >= 1 / 3, (straddle.mean(), submerged.mean())
     assert np.abs(eta).max() > 0.2 and (np.abs(eta) > 0.05).mean() > 0.5          # and the surface IS displaced there
-
-
-def _step(eng, cur, old, n, steps, step0, control=None, applied=None, implicit=False, ke=None, frame="world", **kw):
-    """One launch through the engine; returns (state, prev_out) like the applied tests' helper."""
-    eng.step_fused_tiled_multi_sea(cur, old, n, DT, steps, step0, control, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
-
-
-def _watched(n):
-    return sorted({b for b in (0, 63, 64, n - 1) if b < n})
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 # ---- 1. dispatch and the sea that does not move --------------------------------------------------------------------------------
@@ -90,7 +61,7 @@ def test_no_sea_and_a_still_sea_are_the_pose_hold_entry(coeff, implicit, pop, na
     flat = SeaState().add_wave(0.0, 0.3, -0.2, 1.7, 0.4)
     for n in SIZES:
         eng = _engine(n, params[coeff], coeff)
-        watched = _watched(n)
+        watched = _watched(n, WATCH)
         eng.set_watch(watched)
         a, c17 = _tiled(applied[:n]), _tiled(ctl[:n])
         combos = [(steps, app, control, with_log) for steps in STEPS for app in (None, a) for control in (None, c17) for with_log in (False, True)]
@@ -108,7 +79,7 @@ def test_no_sea_and_a_still_sea_are_the_pose_hold_entry(coeff, implicit, pop, na
             for (steps, app, control, with_log), (w_state, w_prev, w_ke, w_log) in zip(combos, want):
                 c, o = _buffers(st, pv, n)
                 ke, kw = _ke(), logs(with_log)
-                got, got_prev = _step(eng, c, o, n, steps, 3, control, app, implicit, ke, **kw)
+                got, got_prev = step(eng, "sea", c, o, n, steps, step0=3, control=control, applied=app, implicit=implicit, ke=ke, **kw)
                 torch.cuda.synchronize()
                 what = (n, steps, app is None, control is None, with_log, None if sea is None else len(sea.waves))
                 assert _same_bits(got, w_state) and _same_bits(got_prev, w_prev) and _same_bits(ke, w_ke), what
@@ -139,10 +110,6 @@ def test_sample_against_the_fp64_restatement(pop, native_built):
 
 
 # ---- 3. the step is the existing arithmetic on the relative state ----------------------------------------------------------------------
-def _relative(eng, st, pv, n, step):
-    """(s_rel, pv_rel) built on the host in fp32 from hydro_sea_sample's output."""
-    w = scenes.from_tiled(eng.sea_sample(_tiled(st[:n]), n, step, DT).cpu().numpy(), n)
-    return sr.relative(st[:n], pv[:n], w[:, 0], w[:, 1:4])
 
 
 @COEFFS_SEMANTICS
@@ -151,7 +118,7 @@ def test_explicit_step_is_wrench_of_the_relative_state_then_integrator_of_the_tr
     for n in SIZES:
         eng = _engine(n, params[coeff], coeff, semantics)
         eng.set_sea(SEA)
-        watched = _watched(n)
+        watched = _watched(n, WATCH)
         eng.set_watch(watched)
         for step0 in (0, 7):
             s_rel, pv_rel = _relative(eng, st, pv, n, step0)
@@ -160,7 +127,7 @@ def test_explicit_step_is_wrench_of_the_relative_state_then_integrator_of_the_tr
             cur, old = _buffers(st, pv, n)
             want = eng.integrate_tiled(cur, wrench, n, DT)
             log = torch.full((1, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)
-            got, got_prev = _step(eng, cur, old, n, 1, step0, log=log)
+            got, got_prev = step(eng, "sea", cur, old, n, 1, step0=step0, log=log)
             torch.cuda.synchronize()
             assert _same_bits(got, want), (n, step0)
             assert np.array_equal(got_prev.cpu().numpy().view(np.uint32), scenes.to_tiled(st[:n, 7:13]).view(np.uint32))    # the TRUE velocity
@@ -189,7 +156,7 @@ def test_one_step_with_applied_wrench_and_pose_hold_against_fp64(coeff, implicit
         assert keep.mean() > 0.9 or n == 1, (n, keep.mean())
         hydro = scenes.from_tiled(eng.step_wrench_tiled(_tiled(s_rel), n, DT, prev=_tiled(pv_rel)).cpu().numpy(), n)
         cur, old = _buffers(st, pv, n)
-        got, _ = _step(eng, cur, old, n, 1, 7, _tiled(ctl[:n]), _tiled(applied[:n]), implicit)
+        got, _ = step(eng, "sea", cur, old, n, 1, step0=7, control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=implicit)
         torch.cuda.synchronize()
         got = scenes.from_tiled(got.cpu().numpy(), n)
         k = None
@@ -198,10 +165,10 @@ def test_one_step_with_applied_wrench_and_pose_hold_against_fp64(coeff, implicit
             k = _k(comps, s_rel, pr, coeff, n)
             k = (k[0][keep], k[1][keep])
         if keep.any():
-            worst[n] = _fp64_errors(got[keep], st[:n][keep], hydro[keep], applied[:n][keep], ctl[:n][keep], pr[:n][keep], k)
+            worst[n] = fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=applied[:n][keep], ctl=ctl[:n][keep])
             # the reference with the law of the relative state instead: hydro + applied + law(s_rel), written as another applied wrench
             swapped = applied[:n].astype(np.float64) + phr.wrench(s_rel, ctl[:n]) - phr.wrench(st[:n], ctl[:n])
-            wrong[n] = max(_fp64_errors(got[keep], st[:n][keep], hydro[keep], swapped[keep], ctl[:n][keep], pr[:n][keep], k).values())
+            wrong[n] = max(fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=swapped[keep], ctl=ctl[:n][keep]).values())
         eng.close()
     _report(f"sea + applied + pose hold {'implicit' if implicit else 'explicit'} {coeff}", worst)
     assert wrong[max(SIZES)] > 10 * B, wrong
@@ -216,7 +183,7 @@ def test_one_launch_equals_single_steps_and_chunks_and_differs_from_a_frozen_pha
     for n in SIZES:
         eng = _engine(n, params[coeff], coeff)
         eng.set_sea(SEA)
-        watched = _watched(n)
+        watched = _watched(n, WATCH)
         eng.set_watch(watched)
 
         def run(chunks, frozen=False):
@@ -224,7 +191,7 @@ def test_one_launch_equals_single_steps_and_chunks_and_differs_from_a_frozen_pha
             log = torch.full((7, 13, len(watched)), NAN, dtype=torch.float32, device=DEV)
             done = 0
             for k in chunks:
-                _step(eng, cur, old, n, k, start if frozen else start + done, implicit=implicit, log=log, every=1, phase=1, row0=done)
+                step(eng, "sea", cur, old, n, k, step0=start if frozen else start + done, implicit=implicit, log=log, every=1, phase=1, row0=done)
                 cur, old = old, cur
                 done += k
             torch.cuda.synchronize()
@@ -288,15 +255,6 @@ def _c_sea(current=(0.5, -0.2, 0.05), waves=((0.2, 0.06, 0.02, 0.8, 0.3),), coun
     return c
 
 
-def _raw(eng, n, state, prev, out, pvo, step0=0, steps=1, log=None, applied=None, control=None, implicit=0):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_sea(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        applied, S_A, 0, control, S_C, step0, eng._stream(None))
-    return rc, written.value
-
-
 def test_set_sea_refusals_keep_the_previous_sea(pop, native_built):
     st, _, params, _, _ = pop
     n = 65
@@ -348,25 +306,25 @@ def test_step_refusals_launch_nothing(pop, native_built):
     pvo = torch.full((tiles * S_PVO,), NAN, device=DEV)
     log = torch.full((4, 13, 8), NAN, device=DEV)
     E_ARG, E_STATE = -1, -5
-    assert _raw(eng, n, state, prev, out, pvo, step0=-1) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, step0=2 ** 52 - 1, steps=1) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, step0=2 ** 52 - 3, steps=3) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, steps=0) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, applied=a.data_ptr() + 4) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, control=c17.data_ptr() + 4) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, control=out.data_ptr()) == (E_ARG, -7)            # control aliases state_out
-    assert _raw(eng, n, state, prev, out, pvo, log=log) == (E_STATE, -7)                         # a log without a watch list
+    assert raw(eng, "sea", n, state, prev, out, pvo, step0=-1) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, step0=2 ** 52 - 1) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, steps=3, step0=2 ** 52 - 3) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, steps=0) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, applied=a.data_ptr() + 4) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, control=c17.data_ptr() + 4) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, control=out.data_ptr()) == (E_ARG, -7)            # control aliases state_out
+    assert raw(eng, "sea", n, state, prev, out, pvo, log=log) == (E_STATE, -7)                         # a log without a watch list
     eng.set_watch([0, 256])
-    assert _raw(eng, n, state, prev, out, pvo, log=log, steps=5) == (E_ARG, -7)                  # rows 0 .. 4 of 4
+    assert raw(eng, "sea", n, state, prev, out, pvo, steps=5, log=log) == (E_ARG, -7)                  # rows 0 .. 4 of 4
     eng.set_sea(None)                                            # and without a sea the refusals are the pose-hold entry's
-    assert _raw(eng, n, state, prev, out, pvo, step0=-1) == (E_ARG, -7)
-    assert _raw(eng, n, state, prev, out, pvo, log=log, steps=5) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, step0=-1) == (E_ARG, -7)
+    assert raw(eng, "sea", n, state, prev, out, pvo, steps=5, log=log) == (E_ARG, -7)
     torch.cuda.synchronize()
     assert torch.isnan(out).all() and torch.isnan(pvo).all() and torch.isnan(log).all()
     # the legal launches next to them: the last step index that exists, and a recording one
     eng.set_sea(SEA)
-    assert _raw(eng, n, state, prev, out, pvo, step0=2 ** 52 - 4, steps=3) == (0, 0)
-    assert _raw(eng, n, state, prev, out, pvo, log=log, steps=3, applied=a.data_ptr(), control=c17.data_ptr()) == (0, 3)
+    assert raw(eng, "sea", n, state, prev, out, pvo, steps=3, step0=2 ** 52 - 4) == (0, 0)
+    assert raw(eng, "sea", n, state, prev, out, pvo, steps=3, log=log, applied=a.data_ptr(), control=c17.data_ptr()) == (0, 3)
     torch.cuda.synchronize()
     state3, rest = _unguard(out, n, 13, S_OUT)
     assert not np.isnan(state3).all() and np.isnan(rest).all() and torch.isnan(log[3:]).all() and torch.isnan(log[:, :, 2:]).all()
@@ -392,7 +350,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     log = torch.full((4, 13, 8), NAN, device=DEV)
     w = torch.full((tiles * S_W,), NAN, device=DEV)
     eng._check(eng._lib.hydro_sea_sample(eng._h, n, state.data_ptr(), S_IN, 11, DT, w.data_ptr(), S_W, eng._stream(None)))
-    rc, written = _raw(eng, n, state, prev, out, pvo, step0=11, steps=3, log=log, applied=a.data_ptr(), control=c17.data_ptr(), implicit=implicit)
+    rc, written = raw(eng, "sea", n, state, prev, out, pvo, steps=3, step0=11, implicit=implicit, log=log, applied=a.data_ptr(), control=c17.data_ptr())
     eng._check(rc)
     torch.cuda.synchronize()
     assert written == 3
@@ -405,7 +363,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     assert all(_untouched(b, was) for b, was in zip((state, prev, a, c17), before))
     assert np.isfinite(water).all(), "a sentinel was read"
     cur, old = _buffers(st, pv, n)
-    want, want_prev = _step(eng, cur, old, n, 3, 11, _tiled(ctl[:n]), _tiled(applied[:n]), implicit)
+    want, want_prev = step(eng, "sea", cur, old, n, 3, step0=11, control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=implicit)
     torch.cuda.synchronize()
     assert np.array_equal(got.view(np.uint32), scenes.from_tiled(want.cpu().numpy(), n).view(np.uint32))
     assert np.array_equal(pv_out.view(np.uint32), scenes.from_tiled(want_prev.contiguous().cpu().numpy(), n).view(np.uint32))

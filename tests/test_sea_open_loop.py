@@ -17,7 +17,7 @@ from silver2_isaacsim_amd import behavior as hb
 from silver2_isaacsim_amd import config as cfg
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.testing import build_main_scene
-from test_engine_calls import DT, F, H, KE, N, O, ORI, P6, POS, PREVS, S, STREAM, TILES, TQ, VELS, T, eng, lib, refused  # noqa: F401  (fixtures)
+from engine_stand_ins import DT, eng, F, H, KE, lib, N, O, ORI, P6, POS, PREVS, refused, S, STREAM, T, TILES, TQ, VELS  # noqa: F401  (fixtures are requested by name)
 
 ENTRIES = ("hydro_step_wrench_tiled_sea", "hydro_step_wrench_aos_sea")
 PARENTS = {"hydro_step_wrench_tiled_sea": "hydro_step_wrench_tiled", "hydro_step_wrench_aos_sea": "hydro_step_wrench_aos"}

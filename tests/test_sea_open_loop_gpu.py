@@ -24,10 +24,9 @@ from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.engine import HydroEngine
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.testing import build_main_scene
-from test_applied_wrench_gpu import COEFFS_SEMANTICS, DEV, DT, G, NAN, RHO, SIZES, S_IN, S_PV, _bits, _buffers, _engine, _tiled
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_pose_hold_gpu import pop as hold_pop                    # noqa: F401  (fixture behind test_sea_gpu.pop)
-from test_sea_gpu import SEA, VIEW_STEPS, _relative, _same_bits, pop  # noqa: F401  (fixture)
+from designed_populations import hold_pop, SEA, sea_pop as pop  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (_buffers, COEFFS_SEMANTICS, DEV, DT, _engine, G, _guarded, NAN, RHO, S_IN, S_PV, _same_bits, SIZES, _tiled, _unguard, _untouched,
+                              VIEW_STEPS)
 
 pytestmark = pytest.mark.gpu
 assert SIZES == (1, 63, 64, 65, 257, 4097)

@@ -2,7 +2,7 @@
 far as a machine without a GPU can see it: the C boundary, the Python host's marshalling (with the stand-ins of
 tests/test_engine_calls.py), ClosedLoopSim's bookkeeping with a fake engine, the host restatement against the fp64 reference
 of tests/seabed_reference.py and cases worked by hand, and the physics - boxes that sink, land and come to rest, and a resting
-box that is pushed - through seabed_reference.closed_loop_bed.  (hydro_set_seabed's own refusals need an engine, hence a
+box that is pushed - through closed_loop_reference.closed_loop.  (hydro_set_seabed's own refusals need an engine, hence a
 device: tests/test_seabed_gpu.py; the refusals of the Seabed dataclass, which are the same list, are here.)
 
 THE PUSHED BOX.  The friction of the model is capped at the damping m gamma per corner, so below the Coulomb limit a resting
@@ -20,12 +20,14 @@ import numpy as np
 import pytest
 
 import seabed_reference as br
+from closed_loop_reference import closed_loop
 from conftest import REPO
 from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import scenes, simulate
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.seabed import Seabed
-from test_engine_calls import FUSED_HEAD, H, KE, N, P13, S, SO, STREAM, TILES, T, eng, lib, refused  # noqa: F401  (fixtures)
+from designed_populations import BOXES, PENETRATION, rest_report, REST_V, REST_W, REST_Z, settling_boxes, Z_B
+from engine_stand_ins import eng, FUSED_HEAD, H, KE, lib, N, P13, refused, S, SO, STREAM, T, TILES  # noqa: F401  (fixtures are requested by name)
 
 ENTRIES = ("hydro_set_seabed", "hydro_seabed_wrench", "hydro_step_fused_tiled_multi_bed")
 A = T((TILES, 6, 64), 0x88000000)
@@ -375,47 +377,6 @@ def test_four_corners_by_hand():
 
 
 # ---- the physics: boxes that sink, land and rest --------------------------------------------------------------------------------------
-Z_B = -5.0
-BOXES = (((0.5, 0.5, 0.5), 2.0), ((1.0, 1.0, 1.0), 1.05), ((0.8, 0.3, 0.2), 1.3), ((0.3, 0.2, 0.1), 7.8))     # dimensions (m), rho_body / rho
-REST_V, REST_W, REST_Z, PENETRATION = 1e-4, 1e-4, 1e-4, 0.15
-
-
-def _quat(axis, angle):
-    q = np.zeros(4)
-    q[axis], q[3] = np.sin(angle / 2), np.cos(angle / 2)
-    return q
-
-
-def _qmul(a, b):
-    ax, ay, az, aw = a
-    bx, by, bz, bw = b
-    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
-                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz])
-
-
-ATTITUDES = {"flat": _quat(0, 0.0), "tilted": _qmul(_quat(1, 0.35), _quat(0, 0.5)), "edge": _quat(0, np.pi / 4)}
-
-
-def settling_boxes():
-    """The twelve boxes (four boxes x flat / tilted by 0.5 rad about x then 0.35 rad about y / on an edge), README coefficients,
-    released with their centre 1 m above the bed and v_x = 0.3 m/s: (state, prev, params, rho_body / rho per box)."""
-    st, pr, ratios = [], [], []
-    for dims, ratio in BOXES:
-        for q in ATTITUDES.values():
-            s = np.zeros(13)
-            s[2], s[3:7], s[7] = Z_B + 1.0, q, 0.3
-            st.append(s)
-            pr.append(np.concatenate([dims, scenes._DEFAULT_COEFFS, [ratio * scenes.RHO * np.prod(dims)]]))
-            ratios.append(ratio)
-    return np.array(st, np.float32), np.zeros((len(st), 6), np.float32), np.array(pr, np.float32), np.array(ratios)
-
-
-def rest_report(bed, state, params, ratios, g=scenes.G):
-    """Per box: corners in contact, |v|, |omega|, and how far the lowest corner is from z_b - g (1 - rho / rho_body) / (4 kappa)."""
-    delta = br.penetration(bed, state, params)
-    st = np.asarray(state, np.float64)
-    return ((delta > 0).sum(axis=1), np.linalg.norm(st[:, 7:10], axis=1), np.linalg.norm(st[:, 10:13], axis=1),
-            np.abs(delta.max(axis=1) - g * (1.0 - 1.0 / ratios) / (4.0 * bed.stiffness)))
 
 
 @pytest.mark.parametrize("rate", [60, 120])
@@ -423,7 +384,7 @@ def test_boxes_sink_land_and_come_to_rest(rate):
     st, pv, pr, ratios = settling_boxes()
     dt = float(np.float32(1.0 / rate))
     bed = Seabed.for_step(Z_B, dt)
-    run = br.closed_loop_bed(st, pv, pr, scenes.RHO, scenes.G, dt, 12 * rate, bed, implicit=True)
+    run = closed_loop(st, pv, pr, scenes.RHO, scenes.G, dt, 12 * rate, bed=bed, implicit=True)
     deepest = np.max([r["delta"].max(axis=1) for r in run], axis=0)
     contacts, v, w, off = rest_report(bed, run[-1]["state"], pr, ratios)
     print(f"[rest, dt = 1/{rate}] corners {contacts.tolist()}  |v| <= {v.max():.2e} m/s  |omega| <= {w.max():.2e} rad/s  "
@@ -457,7 +418,7 @@ def test_a_resting_box_creeps_under_half_the_friction_limit_and_runs_away_over_t
     for factor in (0.5, 2.0):
         push = np.zeros((1, 6))
         push[0, 0] = factor * bed.friction * n_total
-        run = br.closed_loop_bed(st, np.zeros((1, 6), np.float32), pr, scenes.RHO, scenes.G, dt, 5 * rate, bed, implicit=True, applied=push)
+        run = closed_loop(st, np.zeros((1, 6), np.float32), pr, scenes.RHO, scenes.G, dt, 5 * rate, bed=bed, implicit=True, applied=push)
         moved[factor] = float(run[-1]["state"][0, 0])
         assert abs(float(run[-1]["state"][0, 2]) - float(st[0, 2])) < 1e-3          # it stays on the bed
     creep_speed = 0.5 * bed.friction * n_total / (4.0 * float(pr[0, 10]) * bed.friction_rate)

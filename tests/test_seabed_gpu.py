@@ -36,82 +36,14 @@ from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.seabed import Seabed
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import B, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, G, NAN, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers, _engine, _k, _ke, _same, _tiled
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_pose_hold_gpu import S_C, _surrogate
-from test_pose_hold_gpu import pop as hold_pop                    # noqa: F401  (fixture: the designed population with its control record)
-from test_sea import _test_sea
-from test_seabed import Z_B, REST_V, REST_W, REST_Z, rest_report, settling_boxes
+from designed_populations import (ALL_TILE, BED, bed_pop as pop, FAR, hold_pop, _lowest_fp32, NEAR, NONE_TILE, rest_report, REST_V, REST_W, REST_Z, SEA,
+                                  settling_boxes, SIZES, STEPS, Z_B, Z_BED)  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (B, _buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, fp64_step_errors, _from, G, _guarded, _k, _ke, NAN, raw, RHO, S_A,
+                              S_C, S_IN, S_OUT, S_PV, S_PVO, _same, _same_bits, step, _tiled, _unguard, _untouched, _watched)
+from seabed_reference import PROBE_BOUND
 
 pytestmark = pytest.mark.gpu
-SIZES = (200, 321)
-STEPS = (1, 7)
-PROBE_BOUND = 4.0
-Z_BED = -3.0
-BED = Seabed.for_step(Z_BED, DT)
-FAR = Seabed.for_step(-1e6, DT)
-SEA = _test_sea()              # U = (0.5, -0.2, 0.05); components of 100, 25 and 8 m wavelength, a = 0.2 .. 0.05 m
 S_W = 6 * 64 + 28                                                 # the probe's tile stride in the guard tests
-NEAR = np.arange(8)                                               # the bodies whose lowest corner stands within an ulp of the plane
-NONE_TILE, ALL_TILE = 1, 2
-
-
-def _lowest_fp32(st, pr):
-    """p_z - ((|A_z| + |B_z|) + |C_z|) as the kernel forms it, in NumPy float32 (no fused operation in it)."""
-    x, y, z, w = (st[:, 3 + i] for i in range(4))
-    r20, r21, r22 = x * (z + z) - w * (y + y), y * (z + z) + w * (x + x), np.float32(1) - (x * (x + x) + y * (y + y))
-    half = np.float32(0.5)
-    reach = (np.abs(half * (r20 * pr[:, 0])) + np.abs(half * (r21 * pr[:, 1]))) + np.abs(half * (r22 * pr[:, 2]))
-    return st[:, 2] - reach, reach
-
-
-def bed_population(st, pv, pr):
-    """The first 321 bodies of the designed population (every attitude, 5 % of the quaternions non-unit, |v| up to 5 m/s,
-    |omega| up to 10 rad/s, slabs up to 1:10) moved in z only, so that against the plane z = Z_BED
-      bodies 0 .. 7          : the lowest corner stands at Z_BED + (-1, 0, 1, -1, 0, 1, -1, 0) fp32 ulps of Z_BED, in the kernel's
-                               own arithmetic - the decision delta > 0 at its tie
-      the rest of tile 0     : alternately 1 .. 3 and 4 .. 8 corners below the plane
-      tile 1 (64 .. 127)     : nobody reaches the plane (the wave skips the contact)
-      tile 2 (128 .. 191)    : everybody touches, alternately 1 .. 3 and 4 .. 8 corners
-      192 .. 319             : in turn none, 1 .. 3, 4 .. 8
-      320                    : the one live lane of the last wave, 4 .. 8 corners."""
-    n = 321
-    st, pv, pr = st[:n].copy(), pv[:n].copy(), pr[:n].copy()
-    rng = np.random.default_rng(2026)
-    st[:, 2] = 0.0
-    h = np.sort(br.corners(st, pr)[:, :, 2], axis=1)             # corner heights above the centre, ascending
-    i = np.arange(n)
-    tile = i // 64
-    kind = np.where(tile == NONE_TILE, 0, np.where((tile == 0) | (tile == ALL_TILE), 1 + i % 2, i % 3))      # 0 none, 1 few, 2 many
-    kind[320] = 2
-    f = rng.uniform(0.15, 0.85, n)
-    plane_above_centre = np.where(kind == 0, h[:, 0] - rng.uniform(0.05, 0.4, n),
-                                  np.where(kind == 1, h[:, 0] + f * (h[:, 3] - h[:, 0]), h[:, 3] + f * (h[:, 7] - h[:, 3])))
-    st[:, 2] = (Z_BED - plane_above_centre).astype(np.float32)
-    # the eight at the tie: move p_z by single fp32 steps until the kernel's lowest corner is the wanted neighbour of Z_BED
-    zb = np.float32(Z_BED)
-    for b, k in zip(NEAR, (-1, 0, 1, -1, 0, 1, -1, 0)):
-        want = zb
-        for _ in range(abs(k)):
-            want = np.nextafter(want, np.float32(np.inf if k > 0 else -np.inf))
-        one = st[b:b + 1]
-        one[0, 2] = want + _lowest_fp32(one, pr[b:b + 1])[1][0]
-        for _ in range(64):
-            low = _lowest_fp32(one, pr[b:b + 1])[0][0]
-            if low == want:
-                break
-            one[0, 2] = np.nextafter(one[0, 2], np.float32(np.inf if low < want else -np.inf))
-        assert _lowest_fp32(one, pr[b:b + 1])[0][0] == want, b
-    return st, pv, pr
-
-
-@pytest.fixture(scope="module")
-def pop(hold_pop):
-    st, pv, params, applied, ctl, _ = hold_pop
-    st, pv, pr = bed_population(st, pv, params["f32"])
-    n = len(st)
-    p16 = params["f16"][:n].copy()
-    return st, pv, {"f32": pr, "f16": p16}, applied[:n].copy(), ctl[:n].copy()
 
 
 def test_population_meets_the_bed(pop):
@@ -132,26 +64,6 @@ def test_population_meets_the_bed(pop):
     q = np.linalg.norm(st[:, 3:7].astype(np.float64), axis=1)
     assert (np.abs(q - 1) > 5e-4).sum() >= 8 and (np.abs(st[:, 7:13]) > 0).any(axis=1).mean() > 0.9
     assert not (br.corner_count(FAR, st, pr) > 0).any()
-
-
-def _step(eng, cur, old, n, steps, step0=0, control=None, applied=None, implicit=False, ke=None, frame="world", entry="bed", **kw):
-    """One launch through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one."""
-    fn = eng.step_fused_tiled_multi_bed if entry == "bed" else eng.step_fused_tiled_multi_sea
-    fn(cur, old, n, DT, steps, step0, control, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
-
-
-def _watched(n):
-    return sorted({b for b in (0, 5, 63, 64, 130, n - 1) if b < n})
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _from(t, n):
-    return scenes.from_tiled(t.contiguous().cpu().numpy(), n)
 
 
 # ---- 1. no bed, and a bed nobody reaches -----------------------------------------------------------------------------------------
@@ -177,14 +89,14 @@ def test_no_bed_and_a_far_bed_are_the_sea_entry(coeff, implicit, pop, native_bui
             for steps, app, control, with_log in combos:
                 cur, old = _buffers(st, pv, n)
                 ke, kw = _ke(), logs(with_log)
-                state, prev = _step(eng, cur, old, n, steps, 3, control, app, implicit, ke, entry="sea", **kw)
+                state, prev = step(eng, "sea", cur, old, n, steps, step0=3, control=control, applied=app, implicit=implicit, ke=ke, **kw)
                 want.append((state, prev, ke, kw.get("log")))
             for bed in (None, FAR):
                 eng.set_seabed(bed)
                 for (steps, app, control, with_log), (w_state, w_prev, w_ke, w_log) in zip(combos, want):
                     c, o = _buffers(st, pv, n)
                     ke, kw = _ke(), logs(with_log)
-                    got, got_prev = _step(eng, c, o, n, steps, 3, control, app, implicit, ke, **kw)
+                    got, got_prev = step(eng, "bed", c, o, n, steps, step0=3, control=control, applied=app, implicit=implicit, ke=ke, **kw)
                     torch.cuda.synchronize()
                     what = (n, steps, app is None, control is None, with_log, sea is None, bed is None)
                     assert _same_bits(got, w_state) and _same_bits(got_prev, w_prev) and _same_bits(ke, w_ke), what
@@ -235,9 +147,9 @@ def test_bed_step_is_the_sea_step_with_the_probe_wrench_applied(coeff, semantics
         assert (_from(probe, n)[:, 2] > 0).mean() > 0.5
         logs = [torch.full((1, 19, len(watched)), NAN, dtype=torch.float32, device=DEV) for _ in range(2)]
         cur, old = _buffers(st, pv, n)
-        want, want_prev = _step(eng, cur, old, n, 1, 7, None, probe, implicit, entry="sea", log=logs[0])
+        want, want_prev = step(eng, "sea", cur, old, n, 1, step0=7, applied=probe, implicit=implicit, log=logs[0])
         cur, old = _buffers(st, pv, n)
-        got, got_prev = _step(eng, cur, old, n, 1, 7, None, None, implicit, log=logs[1])
+        got, got_prev = step(eng, "bed", cur, old, n, 1, step0=7, implicit=implicit, log=logs[1])
         torch.cuda.synchronize()
         assert _same_bits(got, want) and _same_bits(got_prev, want_prev), n
         assert _same_bits(logs[1], logs[0]), n                   # the recorded state and the recorded wrench
@@ -247,16 +159,6 @@ def test_bed_step_is_the_sea_step_with_the_probe_wrench_applied(coeff, semantics
 
 
 # ---- 4. everything together against fp64 ---------------------------------------------------------------------------------------------
-def _fp64_errors(got, st, hydro, a, ctl, pr, k, bed_wrench, bed_scale):
-    """test_pose_hold_gpu._fp64_errors with the bed: its fp64 wrench in the sum, its term magnitudes in the surrogate."""
-    total, surrogate = _surrogate(st, hydro, a, ctl)
-    total = total + bed_wrench
-    surrogate[:, 0:3] += bed_scale[:, 0:3]
-    surrogate[:, 3] += np.linalg.norm(bed_scale[:, 3:6], axis=1)
-    ref = io.integrate(st, total, pr, G, DT, *(k or (None, None)))
-    sc = io.field_scales(st, surrogate, pr, G, DT, k, ref)
-    err = io.integrator_error_ulps(got, ref, st, total, pr, G, DT, k, scales=sc)
-    return {g: float(np.nan_to_num(e, nan=np.inf).max(initial=0.0)) for g, e in err.items()}
 
 
 @COEFFS
@@ -279,7 +181,7 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
         assert keep.mean() > 0.8, (n, keep.mean())
         hydro = _from(eng.step_wrench_tiled(_tiled(s_rel), n, DT, prev=_tiled(pv_rel)), n)
         cur, old = _buffers(st, pv, n)
-        got, _ = _step(eng, cur, old, n, 1, 7, _tiled(ctl[:n]), _tiled(applied[:n]), True)
+        got, _ = step(eng, "bed", cur, old, n, 1, step0=7, control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=True)
         torch.cuda.synchronize()
         got = _from(got, n)
         comps = ho.step_wrench(s_rel, pv_rel, pr[:n], RHO, G, DT)[2]
@@ -287,9 +189,9 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
         k = (k[0][keep], k[1][keep])
         touch = br.touching_fp32(BED, st[:n], pr[:n])
         bed_w, bed_s = br.wrench(BED, st[:n], pr[:n], touch), br.wrench_scales(BED, st[:n], pr[:n], touch)
-        worst[n] = _fp64_errors(got[keep], st[:n][keep], hydro[keep], applied[:n][keep], ctl[:n][keep], pr[:n][keep], k, bed_w[keep], bed_s[keep])
+        worst[n] = fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=applied[:n][keep], ctl=ctl[:n][keep], bed_wrench=bed_w[keep], bed_scale=bed_s[keep])
         rel_w = br.wrench(BED, s_rel, pr[:n])
-        wrong[n] = max(_fp64_errors(got[keep], st[:n][keep], hydro[keep], applied[:n][keep], ctl[:n][keep], pr[:n][keep], k, rel_w[keep], bed_s[keep]).values())
+        wrong[n] = max(fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=applied[:n][keep], ctl=ctl[:n][keep], bed_wrench=rel_w[keep], bed_scale=bed_s[keep]).values())
         eng.close()
     per_group = {g: max(w[g] for w in worst.values()) for g in io.GROUPS}
     print(f"[sea + applied + pose hold + bed, implicit, {coeff}] max ulps " + "  ".join(f"{g} {v:.2f}" for g, v in per_group.items())
@@ -315,7 +217,7 @@ def test_one_launch_equals_single_steps_and_chunks(coeff, implicit, pop, native_
             log = torch.full((7, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)
             done = 0
             for k in chunks:
-                _step(eng, cur, old, n, k, 100 + done, implicit=implicit, log=log, every=1, phase=1, row0=done)
+                step(eng, "bed", cur, old, n, k, step0=100 + done, implicit=implicit, log=log, every=1, phase=1, row0=done)
                 cur, old = old, cur
                 done += k
             torch.cuda.synchronize()
@@ -350,15 +252,6 @@ def test_boxes_come_to_rest_on_the_device(rate, native_built):
 # ---- 7. refusals and guards through the raw C ABI ------------------------------------------------------------------------------------
 def _c_bed(z=-3.0, stiffness=144.0, damping=2.4, friction=0.5, slip_speed=0.01, friction_rate=2.4):
     return nat.Seabed(z, stiffness, damping, friction, slip_speed, friction_rate)
-
-
-def _raw(eng, n, state, prev, out, pvo, step0=0, steps=1, log=None, applied=None, control=None, implicit=0):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_bed(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        applied, S_A, 0, control, S_C, step0, eng._stream(None))
-    return rc, written.value
 
 
 def test_set_seabed_refusals_keep_the_previous_bed(pop, native_built):
@@ -414,15 +307,15 @@ def test_step_refusals_launch_nothing(pop, native_built):
         eng.set_watch(None)
         eng.set_seabed(bed)
         eng.set_sea(sea)
-        assert _raw(eng, n, state, prev, out, pvo, step0=-1) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, step0=2 ** 52 - 1, steps=1) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, steps=0) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, applied=a.data_ptr() + 4) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, control=c17.data_ptr() + 4) == (E_ARG, -7)
-        assert _raw(eng, n, state, prev, out, pvo, control=out.data_ptr()) == (E_ARG, -7)        # control aliases state_out
-        assert _raw(eng, n, state, prev, out, pvo, log=log) == (E_STATE, -7)                     # a log without a watch list
+        assert raw(eng, "bed", n, state, prev, out, pvo, step0=-1) == (E_ARG, -7)
+        assert raw(eng, "bed", n, state, prev, out, pvo, step0=2 ** 52 - 1) == (E_ARG, -7)
+        assert raw(eng, "bed", n, state, prev, out, pvo, steps=0) == (E_ARG, -7)
+        assert raw(eng, "bed", n, state, prev, out, pvo, applied=a.data_ptr() + 4) == (E_ARG, -7)
+        assert raw(eng, "bed", n, state, prev, out, pvo, control=c17.data_ptr() + 4) == (E_ARG, -7)
+        assert raw(eng, "bed", n, state, prev, out, pvo, control=out.data_ptr()) == (E_ARG, -7)        # control aliases state_out
+        assert raw(eng, "bed", n, state, prev, out, pvo, log=log) == (E_STATE, -7)                     # a log without a watch list
         eng.set_watch([0, 320])
-        assert _raw(eng, n, state, prev, out, pvo, log=log, steps=5) == (E_ARG, -7)              # rows 0 .. 4 of 4
+        assert raw(eng, "bed", n, state, prev, out, pvo, steps=5, log=log) == (E_ARG, -7)              # rows 0 .. 4 of 4
     torch.cuda.synchronize()
     assert torch.isnan(out).all() and torch.isnan(pvo).all() and torch.isnan(log).all()
     eng.close()
@@ -447,7 +340,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     log = torch.full((4, 13, 8), NAN, device=DEV)
     w = torch.full((tiles * S_W,), NAN, device=DEV)
     eng._check(eng._lib.hydro_seabed_wrench(eng._h, n, state.data_ptr(), S_IN, w.data_ptr(), S_W, eng._stream(None)))
-    rc, written = _raw(eng, n, state, prev, out, pvo, step0=11, steps=3, log=log, applied=a.data_ptr(), control=c17.data_ptr(), implicit=implicit)
+    rc, written = raw(eng, "bed", n, state, prev, out, pvo, steps=3, step0=11, implicit=implicit, log=log, applied=a.data_ptr(), control=c17.data_ptr())
     eng._check(rc)
     torch.cuda.synchronize()
     assert written == 3
@@ -460,7 +353,7 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     assert all(_untouched(b, was) for b, was in zip((state, prev, a, c17), before))
     assert np.isfinite(contact).all(), "a sentinel was read"
     cur, old = _buffers(st, pv, n)
-    want, want_prev = _step(eng, cur, old, n, 3, 11, _tiled(ctl[:n]), _tiled(applied[:n]), implicit)
+    want, want_prev = step(eng, "bed", cur, old, n, 3, step0=11, control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=implicit)
     torch.cuda.synchronize()
     assert np.array_equal(got.view(np.uint32), _from(want, n).view(np.uint32))
     assert np.array_equal(pv_out.view(np.uint32), _from(want_prev, n).view(np.uint32))

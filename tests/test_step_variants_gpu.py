@@ -28,7 +28,6 @@ tests/test_seabed_gpu.py; kinetic energy rel = 1e-12 against scenes.kinetic_ener
 NO DEVICE FIGURE YET: this file has not run on an MI355X.  With the fp64 oracle rounded to fp32 standing in for the device, the
 references of sections 2 and 4 agree within 1 ulp and the wrong ones (Numba wrench, R^T a) miss by more than 5e6; the tests
 print the device's figures."""
-import ctypes
 from types import SimpleNamespace
 
 import numpy as np
@@ -41,12 +40,9 @@ from oracle import hydro_oracle as ho
 from oracle import integrator_oracle as io
 from silver2_isaacsim_amd import scenes
 from silver2_isaacsim_amd.sea import SeaState
-from test_applied_wrench_gpu import B, COEFFS, DEV, DRAG, DT, G, NAN, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _buffers, _engine, _k, _ke, _tiled
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_pose_hold_gpu import S_C, _surrogate
-from test_pose_hold_gpu import pop as hold_pop                    # noqa: F401  (fixture: the designed population with its control record)
-from test_seabed_gpu import BED, FAR, SEA, SIZES, STEPS, _from, _same_bits, _watched, bed_population
-from test_seabed_gpu import _fp64_errors as _errors_with_bed
+from designed_populations import BED, bed_population, FAR, hold_pop, SEA, SIZES, STEPS  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (B, _buffers, COEFFS, DEV, DRAG, DT, _engine, fp64_step_errors, _from, G, _guarded, _k, _ke, _log, NAN, raw, RHO, S_A, S_C, S_IN,
+                              S_OUT, S_PV, S_PVO, _same_bits, step_wrench_terms, _tiled, _unguard, _untouched, _watched)
 
 pytestmark = pytest.mark.gpu
 FAMILIES = ("single", "multi", "rec", "app", "ctl", "sea", "bed")
@@ -93,10 +89,6 @@ def engines(pops, native_built):
         eng.close()
 
 
-def _log(steps, watched):
-    return torch.full((steps, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)
-
-
 def _launch(eng, family, cur, old, n, steps, implicit, ke=None, rotational=True, applied=None, control=None, frame="body", log=None,
             wrench=None, step0=STEP0):
     """`steps` steps of one family from (cur, old); returns (the buffer that holds the final state, the other one).  The
@@ -128,7 +120,7 @@ def _loaded(eng, family, base, n, steps, implicit, ke_mode, watched, a, c17):
     log.  sea and bed: the same through the sea / over the bed the engine holds."""
     cur, old = base[0].clone(), base[1].clone()
     ke = _ke() if ke_mode else None
-    log = _log(steps, watched) if family not in ("single", "multi") else None
+    log = _log(steps, len(watched)) if family not in ("single", "multi") else None
     wrench = torch.full((eng.tiles(n), 6, 64), NAN, dtype=torch.float32, device=DEV) if family == "single" else None
     state, other = _launch(eng, family, cur, old, n, steps, implicit, ke, ke_mode != "linear", a if family not in ("single", "multi", "rec") else None,
                            c17 if family in ("ctl", "sea", "bed") else None, "body", log, wrench)
@@ -191,15 +183,6 @@ def test_set_tuning_refuses_a_non_temporal_of_two(pops, engines):
         assert eng._lib.hydro_set_tuning(eng._h, 0, 0, ok, -1) == 0
 
 
-def _raw_bed(eng, n, state, prev, out, pvo, log, applied, control, implicit, steps, step0):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_bed(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr(), 8, 4, 19, 1, 1, 0, ctypes.byref(written),
-        applied.data_ptr(), S_A, 1, control.data_ptr(), S_C, step0, eng._stream(None))
-    return rc, written.value
-
-
 @COEFFS
 @DRAG
 def test_non_temporal_bed_launch_keeps_to_its_records(coeff, implicit, pops, engines):
@@ -222,7 +205,7 @@ def test_non_temporal_bed_launch_keeps_to_its_records(coeff, implicit, pops, eng
     pvo = torch.full((tiles * S_PVO,), NAN, device=DEV)
     log = torch.full((4, 19, 8), NAN, device=DEV)
     eng.set_tuning(0, 0, 1)
-    rc, written = _raw_bed(eng, n, state, prev, out, pvo, log, a, c17, implicit, steps, 11)
+    rc, written = raw(eng, "bed", n, state, prev, out, pvo, steps=steps, step0=11, implicit=implicit, log=log, fields=19, frame=1, applied=a, control=c17)
     eng._check(rc)
     torch.cuda.synchronize()
     assert written == steps
@@ -338,17 +321,15 @@ def test_warp_semantics_one_step_against_fp64(case, coeff, implicit, pops, engin
     f, t, comps = ho.step_wrench(s_rel, pv_rel, pr, RHO, G, DT, "warp")
     # can the comparison tell the semantics apart?  On the CPU oracle, in units of 2^-24 of the surrogate wrench the bound is measured with
     f_nb, t_nb, _ = ho.step_wrench(s_rel, pv_rel, pr, RHO, G, DT, "numba")
-    _, surrogate = _surrogate(st, np.concatenate([f, t], axis=1), a, ctl)
-    surrogate[:, 0:3] += bed_s[:, 0:3]
-    surrogate[:, 3] += np.linalg.norm(bed_s[:, 3:6], axis=1)
+    _, surrogate = step_wrench_terms(st, np.concatenate([f, t], axis=1), applied=a, ctl=ctl, bed_wrench=bed_w, bed_scale=bed_s)
     apart = np.maximum((np.abs(f - f_nb) / (io.ULP * surrogate[:, 0:3])).max(axis=1), np.linalg.norm(t - t_nb, axis=1) / (io.ULP * surrogate[:, 3]))
     assert (apart[keep] > 100.0).mean() >= 0.25, (apart[keep] > 100.0).mean()
     k = None
     if implicit:
         k = _k(comps, s_rel, pr, coeff, n)
         k = (k[0][keep], k[1][keep])
-    worst = _errors_with_bed(got[keep], st[keep], warp[keep], a[keep], ctl[keep], pr[keep], k, bed_w[keep], bed_s[keep])
-    wrong = max(_errors_with_bed(got[keep], st[keep], numba[keep], a[keep], ctl[keep], pr[keep], k, bed_w[keep], bed_s[keep]).values())
+    worst = fp64_step_errors(got[keep], st[keep], warp[keep], pr[keep], k, applied=a[keep], ctl=ctl[keep], bed_wrench=bed_w[keep], bed_scale=bed_s[keep])
+    wrong = max(fp64_step_errors(got[keep], st[keep], numba[keep], pr[keep], k, applied=a[keep], ctl=ctl[keep], bed_wrench=bed_w[keep], bed_scale=bed_s[keep]).values())
     print(f"[warp {case} {'implicit' if implicit else 'explicit'} {coeff}] max ulps " + "  ".join(f"{g} {v:.2f}" for g, v in worst.items())
           + f"  (bound {B:g}); with the Numba wrench: {wrong:.0f}; oracle wrenches apart on {(apart[keep] > 100.0).mean():.0%} of {int(keep.sum())} bodies")
     assert max(worst.values()) <= B, worst
@@ -402,7 +383,7 @@ def test_kinetic_energy_is_that_of_the_returned_true_state(family, semantics, co
 # ---- 4. a body-frame applied wrench in the sea and bed entries ---------------------------------------------------------------------
 def _all_outputs(eng, family, st, pv, n, steps, implicit, a, c17, watched):
     cur, old = _buffers(st, pv, n)
-    ke, log = _ke(), _log(steps, watched)
+    ke, log = _ke(), _log(steps, len(watched))
     state, other = _launch(eng, family, cur, old, n, steps, implicit, ke, True, a, c17, "body", log, step0=3)
     return state, other, ke, log, None
 
@@ -471,7 +452,7 @@ def test_body_frame_applied_wrench_in_waves_against_fp64(coeff, implicit, with_c
         none = np.zeros((int(keep.sum()), 6))
         for turn, into in ((_to_world, worst), (_to_world_transposed, wrong)):
             a = turn(st[:n], pops.applied[:n])
-            into[n] = _errors_with_bed(got[keep], st[:n][keep], hydro[keep], a[keep], ctl[:n][keep], pr[:n][keep], k, none, none)
+            into[n] = fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=a[keep], ctl=ctl[:n][keep], bed_wrench=none, bed_scale=none)
     per_group = {g: max(w[g] for w in worst.values()) for g in io.GROUPS}
     missed = {n: max(w.values()) for n, w in wrong.items()}
     print(f"[sea + body-frame applied{' + pose hold' if with_control else ''} {'implicit' if implicit else 'explicit'} {coeff}] max ulps "

@@ -28,13 +28,14 @@ import pose_hold_reference as phr
 import sea_reference as sr
 import seabed_reference as br
 import symmetry as sym
+from closed_loop_reference import closed_loop
 from conftest import REPO, accel_of, load_golden
 from oracle import c_oracle
 from oracle import hydro_oracle as ho
 from oracle import integrator_oracle as io
 from silver2_isaacsim_amd.extremes import Extremes
-from test_mooring_gpu import bed_pop, hold_pop, pop               # noqa: F401  (fixtures, NumPy only: the designed populations of the feature tests)
-from test_seabed_gpu import BED, SEA
+from designed_populations import BED, bed_pop, contributing_corners, hold_pop, SEA, tilted_boxes  # noqa: F401  (fixtures are requested by name)
+from mooring_population import moored_pop as pop  # noqa: F401  (fixtures are requested by name)
 
 RHO, G, DT = populations.RHO, populations.G, populations.DT
 TOL = 1e-12                                                       # tests/test_oracle_golden.py: same fp64 formula, other summation order
@@ -284,7 +285,7 @@ def test_extremes_fold_is_exactly_symmetric(g, pop):
     """Extremes.fold over a short fp64 trajectory of the moored population and over its image: the record of the image is the
     image of the record, min and max of a flipped axis swapped."""
     st, pv, params, _, _, rec = pop
-    steps = mr.closed_loop_moor(st, pv, params["f32"], RHO, G, DT, 3, rec, bed=BED)
+    steps = closed_loop(st, pv, params["f32"], RHO, G, DT, 3, moor=rec, bed=BED, implicit=True)
     states = np.stack([s["state"] for s in steps])
     tension = np.stack([s["tension"] for s in steps]).astype(np.float32)
     with np.errstate(over="ignore", invalid="ignore"):
@@ -342,27 +343,6 @@ def test_teeth_a_polar_applied_torque_breaks_the_equality(g, designed, hold_pop)
 
 
 # ---- (d) the populations of tests/test_symmetry_gpu.py -----------------------------------------------------------------------------------
-def contributing_corners(st, pr):
-    """(n,) the most corners seabed_reference counts on a body: decided in fp64 and as the kernel decides, whichever is more."""
-    return np.maximum(br.corner_count(BED, st, pr), br.corner_count(BED, st, pr, br.touching_fp32(BED, st, pr)))
-
-
-def tilted_boxes(st, pv, pr, seed=2028):
-    """The bed population with four bodies in five lowered or raised, in z only, so that exactly ONE corner is below the plane
-    (between its lowest and its second-lowest corner) - but for bodies 0 .. 7 (the ties) and tile 1, which nobody touches in:
-    the bed population itself draws 1 .. 3 corners together and leaves the single-corner bodies, on which the device is exact,
-    to chance.  A population of this module; the feature tests' population is not touched."""
-    st = st.copy()
-    rng = np.random.default_rng(seed)
-    flat = st.copy()
-    flat[:, 2] = 0.0
-    h = np.sort(br.corners(flat, pr)[:, :, 2], axis=1)
-    i = np.arange(len(st))
-    one = (i % 5 != 1) & (i >= 8) & (i // 64 != 1) & (h[:, 1] - h[:, 0] > 1e-3)
-    f = rng.uniform(0.2, 0.8, len(st))
-    z = float(BED.z) - (h[:, 0] + f * (h[:, 1] - h[:, 0]))
-    st[one, 2] = z[one].astype(np.float32)
-    return st, pv.copy(), pr.copy()
 
 
 @pytest.mark.parametrize("n", [200, 321])

@@ -66,12 +66,10 @@ from silver2_isaacsim_amd.engine import HydroEngine
 from silver2_isaacsim_amd.mooring import Mooring
 from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
-from test_applied_wrench_gpu import COEFFS, DEV, DRAG, DT, G, NAN, RHO, _buffers, _ke, _tiled
-from test_mooring import DEPTH, line_population
-from test_mooring_gpu import _buoys, _from
-from test_mooring_gpu import bed_pop, hold_pop, pop               # noqa: F401  (fixtures: the designed population and its lines)
-from test_seabed_gpu import BED, FAR, PROBE_BOUND, SEA
-from test_symmetry import contributing_corners, tilted_boxes
+from designed_populations import BED, bed_pop, contributing_corners, FAR, hold_pop, SEA, tilted_boxes  # noqa: F401  (fixtures are requested by name)
+from mooring_population import _buoys, DEPTH, line_population, moored_pop as pop  # noqa: F401  (fixtures are requested by name)
+from resident_harness import _buffers, COEFFS, DEV, DRAG, DT, _from, G, _ke, NAN, RHO, _tiled
+from seabed_reference import PROBE_BOUND
 
 pytestmark = pytest.mark.gpu
 SIZES = (200, 321)

@@ -7,7 +7,7 @@ instantiations; refusals and guard bands; ClosedLoopSim's three runners and a gr
 tests/test_tether.py on the device; the example.
 
 Sizes: n = 200 (one block: three full tiles and 8 lanes), n = 321 (two blocks, the last wave with one live lane, which has no
-tether) and n = 322 (the last wave's two live lanes are a pair).  The population is test_tether.tether_population over the
+tether) and n = 322 (the last wave's two live lanes are a pair).  The population is tether_population.tether_population over the
 bodies of tests/test_seabed_gpu.py and one more; the mooring lines are those of tests/test_mooring.py.
 
 THE PROBE BOUND.  Errors of hydro_tether_wrench against tether_reference.wrench (fp64), in units of 2^-24 of
@@ -25,7 +25,6 @@ W_teth and (h + W_moor) + W_teth, the same two additions in the same order.
 
 Bound of the fp64 step comparison: integrator_oracle.STEP_ULP_BOUND (24), scales as in tests/test_mooring_gpu.py with the
 tether's own term magnitudes (tether_reference.wrench_scales) added to the surrogate wrench."""
-import ctypes
 import os
 import re
 import subprocess
@@ -46,19 +45,15 @@ from silver2_isaacsim_amd.sea import SeaState
 from silver2_isaacsim_amd.seabed import Seabed
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
 from silver2_isaacsim_amd.tether import Tether
-from test_applied_wrench_gpu import B, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, G, NAN, RHO, S_A, S_IN, S_OUT, S_PV, S_PVO, _bits, _buffers, _engine, _k, _ke, _same, _tiled
-from test_integrator_gpu import _guarded, _unguard, _untouched
-from test_mooring import line_population
-from test_pose_hold_gpu import S_C
-from test_pose_hold_gpu import pop as hold_pop                    # noqa: F401  (fixture bed_pop is built from)
-from test_seabed_gpu import BED, SEA, _fp64_errors
-from test_seabed_gpu import pop as bed_pop                        # noqa: F401  (fixture: the designed population moved onto the bed)
-from test_tether import (LINE, PROBE_BOUND, SIZES, assert_antisymmetric, bodies_of, check_population, designed_population, hanging_pair,
-                         record_for, tether_population)
+from designed_populations import BED, bed_pop, hold_pop, SEA  # noqa: F401  (fixtures are requested by name)
+from mooring_population import line_population
+from resident_harness import (B, _buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, fp64_step_errors, _from, G, _guarded, _k, _ke, NAN, raw, RHO, S_A,
+                              S_C, S_IN, S_M, S_OUT, S_PV, S_PVO, _same, _same_bits, step, _tiled, _unguard, _untouched)
+from tether_population import (assert_antisymmetric, bodies_of, check_population, designed_population, hanging_pair, LINE, record_for, SIZES, tether_population)
+from tether_reference import PROBE_BOUND
 
 pytestmark = pytest.mark.gpu
 STEPS = (1, 7)
-S_M = 9 * 64 + 52                                                 # the mooring record's tile stride in the guard tests
 S_E = 8 * 64 + 36                                                 # the extremes record's
 S_T = 7 * 64 + 44                                                 # the tether record's
 S_W = 6 * 64 + 28                                                 # the probe's wrench
@@ -68,7 +63,7 @@ S_T1 = 64 + 12                                                    # the probe's 
 @pytest.fixture(scope="module")
 def pop(bed_pop, hold_pop):
     """The 321 bodies of tests/test_seabed_gpu.py and body 321 of the population they were drawn from, with the tethers of
-    test_tether.tether_population and the mooring lines of test_mooring.line_population (body 321 has none)."""
+    tether_population.tether_population and the mooring lines of mooring_population.line_population (body 321 has none)."""
     st, pv, params, applied, ctl = bed_pop
     more = hold_pop
     cat = lambda a, b: np.concatenate([a, b[321:322]])  # noqa: E731
@@ -84,27 +79,6 @@ def test_population_is_what_it_was_designed_to_be(pop):
     check_population(pop["st"], pop["rec"], pop["groups"])
     st, _, _, rec, _ = designed_population()                      # and it is the one tests/test_tether.py derives the bound on
     assert np.array_equal(st, pop["st"]) and np.array_equal(rec, pop["rec"])
-
-
-def _step(eng, cur, old, n, steps, step0=0, tether=None, extremes=None, mooring=None, control=None, applied=None, implicit=False, ke=None,
-          frame="world", entry="teth", **kw):
-    """One launch through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one."""
-    if entry == "teth":
-        eng.step_fused_tiled_multi_teth(cur, old, n, DT, steps, step0, tether, extremes, mooring, control, applied, frame, implicit_drag=implicit,
-                                        ke_out=ke, **kw)
-    else:
-        assert tether is None
-        eng.step_fused_tiled_multi_ext(cur, old, n, DT, steps, step0, extremes, mooring, control, applied, frame, implicit_drag=implicit, ke_out=ke, **kw)
-    return old, cur[:, 7:13]
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _from(t, n):
-    return scenes.from_tiled(t.contiguous().cpu().numpy(), n)
 
 
 def _probe(eng, st, rec, n):
@@ -190,8 +164,8 @@ def test_no_record_and_a_record_of_zeros_are_the_extremes_entry(coeff, implicit,
                     ke = _ke()
                     kw = dict(log=torch.full((8, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)) if "log" in chosen else {}
                     ext = eng.extremes_reset(eng.alloc_tiled(8, n), n) if "extremes" in chosen else None
-                    state, prev = _step(eng, cur, old, n, steps, 3, tether, ext, m9 if "mooring" in chosen else None,
-                                        c17 if "control" in chosen else None, a if "applied" in chosen else None, implicit, ke, entry=entry, **kw)
+                    state, prev = step(eng, entry, cur, old, n, steps, step0=3, tether=tether, extremes=ext, mooring=m9 if "mooring" in chosen else None,
+                                       control=c17 if "control" in chosen else None, applied=a if "applied" in chosen else None, implicit=implicit, ke=ke, **kw)
                     torch.cuda.synchronize()
                     return [state, prev, ke] + ([kw["log"]] if kw else []) + ([ext] if ext is not None else [])
                 want = run(None, "ext")
@@ -223,7 +197,7 @@ def test_tether_step_is_the_extremes_step_with_the_probe_wrench_applied(coeff, s
             eng.set_seabed(bed)
             log = torch.full((1, 19, n), NAN, dtype=torch.float32, device=DEV)
             cur, old = _buffers(st, pv, n)
-            state, prev = _step(eng, cur, old, n, 1, 7, tether, None, mooring, None, applied, implicit, entry=entry, log=log)
+            state, prev = step(eng, entry, cur, old, n, 1, step0=7, tether=tether, mooring=mooring, applied=applied, implicit=implicit, log=log)
             torch.cuda.synchronize()
             return state.clone(), prev.clone(), log
 
@@ -264,7 +238,7 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
     the fp64 bed, mooring and tether wrenches of the TRUE state), drag_jacobian of the relative state.  Bodies within 1e-4 of a
     branch of the hydrodynamic model in the relative state are left out, as in tests/test_sea_gpu.py, and the ties with a
     damper of either kind of line."""
-    from test_mooring import TIES as MOOR_TIES
+    from mooring_population import TIES as MOOR_TIES
     st, pv, applied, ctl = pop["st"], pop["pv"], pop["applied"], pop["ctl"]
     pr = pop["params"][coeff]
     worst = {}
@@ -281,7 +255,7 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
         keep[bodies_of(pop["groups"], "ties_c")] = False
         hydro = _from(eng.step_wrench_tiled(_tiled(s_rel), n, DT, prev=_tiled(pv_rel)), n)
         cur, old = _buffers(st, pv, n)
-        got, _ = _step(eng, cur, old, n, 1, 7, _tiled(rec), None, _tiled(moor), _tiled(ctl[:n]), _tiled(applied[:n]), True)
+        got, _ = step(eng, "teth", cur, old, n, 1, step0=7, tether=_tiled(rec), mooring=_tiled(moor), control=_tiled(ctl[:n]), applied=_tiled(applied[:n]), implicit=True)
         torch.cuda.synchronize()
         got = _from(got, n)
         comps = ho.step_wrench(s_rel, pv_rel, pr[:n], RHO, G, DT)[2]
@@ -292,7 +266,7 @@ def test_one_step_with_everything_against_fp64(coeff, pop, native_built):
         extra = br.wrench(BED, st[:n], pr[:n], touch) + mr.wrench(moor, st[:n], on_m) + tr.wrench(rec, st[:n], on_t)
         extra_scale = br.wrench_scales(BED, st[:n], pr[:n], touch) + mr.wrench_scales(moor, st[:n], on_m) + tr.wrench_scales(rec, st[:n], on_t)
         assert (tr.tension(rec, st[:n], on_t)[keep] > 0).mean() > 0.2
-        worst[n] = _fp64_errors(got[keep], st[:n][keep], hydro[keep], applied[:n][keep], ctl[:n][keep], pr[:n][keep], k, extra[keep], extra_scale[keep])
+        worst[n] = fp64_step_errors(got[keep], st[:n][keep], hydro[keep], pr[:n][keep], k, applied=applied[:n][keep], ctl=ctl[:n][keep], bed_wrench=extra[keep], bed_scale=extra_scale[keep])
         eng.close()
     from oracle import integrator_oracle as io
     per_group = {g: max(w[g] for w in worst.values()) for g in io.GROUPS}
@@ -330,7 +304,7 @@ def test_one_launch_equals_single_steps_and_chunks(coeff, implicit, pop, native_
             log = torch.full((7, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)
             done = 0
             for k in chunks:
-                _step(eng, cur, old, n, k, 100 + done, lines, None, m9, implicit=implicit, log=log, every=1, phase=1, row0=done)
+                step(eng, "teth", cur, old, n, k, step0=100 + done, tether=lines, mooring=m9, implicit=implicit, log=log, every=1, phase=1, row0=done)
                 cur, old = old, cur
                 done += k
             torch.cuda.synchronize()
@@ -359,7 +333,7 @@ def test_energy_and_non_temporal_instantiations_with_tethers_pulling(coeff, sema
         def run(ke=None, **kw):
             cur, old = _buffers(st, pv, n)
             ext = eng.extremes_reset(eng.alloc_tiled(8, n), n)
-            state, prev = _step(eng, cur, old, n, 7, 5, lines, ext, m9, c17, a, implicit, ke, **kw)
+            state, prev = step(eng, "teth", cur, old, n, 7, step0=5, tether=lines, extremes=ext, mooring=m9, control=c17, applied=a, implicit=implicit, ke=ke, **kw)
             torch.cuda.synchronize()
             return state, prev, ext
         eng.set_tuning(0, 0, 0)
@@ -386,14 +360,6 @@ def test_energy_and_non_temporal_instantiations_with_tethers_pulling(coeff, sema
 
 
 # ---- 6. refusals and guards through the raw C ABI ------------------------------------------------------------------------------------
-def _raw(eng, n, state, prev, out, pvo, step0=0, steps=1, log=None, applied=None, control=None, mooring=None, extremes=None, tether=None,
-         stride=S_T, implicit=0):
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_teth(
-        eng._h, n, state.data_ptr(), S_IN, prev.data_ptr(), S_PV, DT, steps, out.data_ptr(), S_OUT, pvo.data_ptr(), S_PVO,
-        int(implicit), 1, None, log.data_ptr() if log is not None else None, 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        applied, S_A, 0, control, S_C, mooring, S_M, extremes, S_E, tether, stride, step0, eng._stream(None))
-    return rc, written.value
 
 
 def test_refusals_launch_nothing(pop, native_built):
@@ -418,34 +384,34 @@ def test_refusals_launch_nothing(pop, native_built):
         eng.set_seabed(bed)
         eng.set_sea(sea)
         for lines in (t, None):                                  # the extremes entry's refusals, with tethers and without
-            assert _raw(eng, n, state, prev, out, pvo, step0=-1, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, step0=2 ** 52 - 1, steps=1, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, steps=0, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, applied=a.data_ptr() + 4, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, control=c17.data_ptr() + 4, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, control=out.data_ptr(), tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, mooring=m + 4, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, mooring=m, extremes=e + 4, tether=lines) == (E_ARG, -7)
-            assert _raw(eng, n, state, prev, out, pvo, extremes=state.data_ptr(), tether=lines) == (E_ARG, -7)     # extremes over an input
-            assert _raw(eng, n, state, prev, out, pvo, log=log, tether=lines) == (E_STATE, -7)       # a log without a watch list
+            assert raw(eng, "teth", n, state, prev, out, pvo, step0=-1, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, step0=2 ** 52 - 1, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, steps=0, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, applied=a.data_ptr() + 4, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, control=c17.data_ptr() + 4, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, control=out.data_ptr(), s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, mooring=m + 4, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, mooring=m, extremes=e + 4, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)
+            assert raw(eng, "teth", n, state, prev, out, pvo, extremes=state.data_ptr(), s_extremes=S_E, tether=lines, s_tether=S_T) == (E_ARG, -7)     # extremes over an input
+            assert raw(eng, "teth", n, state, prev, out, pvo, log=log, s_extremes=S_E, tether=lines, s_tether=S_T) == (E_STATE, -7)       # a log without a watch list
         # the tether's own
-        assert _raw(eng, n, state, prev, out, pvo, tether=t + 4) == (E_ARG, -7)                      # misaligned
-        assert _raw(eng, n, state, prev, out, pvo, tether=t, stride=444) == (E_ARG, -7)              # below 7 * 64
-        assert _raw(eng, n, state, prev, out, pvo, tether=t, stride=450) == (E_ARG, -7)              # not a multiple of 4
-        assert _raw(eng, n, state, prev, out, pvo, tether=out.data_ptr()) == (E_ARG, -7)             # aliases state_out
+        assert raw(eng, "teth", n, state, prev, out, pvo, s_extremes=S_E, tether=t + 4, s_tether=S_T) == (E_ARG, -7)                      # misaligned
+        assert raw(eng, "teth", n, state, prev, out, pvo, s_extremes=S_E, tether=t, s_tether=444) == (E_ARG, -7)              # below 7 * 64
+        assert raw(eng, "teth", n, state, prev, out, pvo, s_extremes=S_E, tether=t, s_tether=450) == (E_ARG, -7)              # not a multiple of 4
+        assert raw(eng, "teth", n, state, prev, out, pvo, s_extremes=S_E, tether=out.data_ptr(), s_tether=S_T) == (E_ARG, -7)             # aliases state_out
         assert "tether must not overlap" in last()
-        assert _raw(eng, n, state, prev, out, pvo, tether=pvo.data_ptr()) == (E_ARG, -7)             # aliases prev_out
+        assert raw(eng, "teth", n, state, prev, out, pvo, s_extremes=S_E, tether=pvo.data_ptr(), s_tether=S_T) == (E_ARG, -7)             # aliases prev_out
         assert "tether must not overlap" in last()
-        assert _raw(eng, n, state, prev, out, pvo, extremes=e, tether=e) == (E_ARG, -7)              # aliases the extremes record
+        assert raw(eng, "teth", n, state, prev, out, pvo, extremes=e, s_extremes=S_E, tether=e, s_tether=S_T) == (E_ARG, -7)              # aliases the extremes record
         assert "tether must not overlap" in last()
         # the mooring and the extremes are refused before the tether
-        assert _raw(eng, n, state, prev, out, pvo, mooring=m + 4, tether=t + 4) == (E_ARG, -7)
+        assert raw(eng, "teth", n, state, prev, out, pvo, mooring=m + 4, s_extremes=S_E, tether=t + 4, s_tether=S_T) == (E_ARG, -7)
         assert "tether" not in last()
-        assert _raw(eng, n, state, prev, out, pvo, extremes=e + 4, tether=t + 4) == (E_ARG, -7)
+        assert raw(eng, "teth", n, state, prev, out, pvo, extremes=e + 4, s_extremes=S_E, tether=t + 4, s_tether=S_T) == (E_ARG, -7)
         assert "tether" not in last()
         eng.set_watch([0, 320])
-        assert _raw(eng, n, state, prev, out, pvo, log=log, steps=5, tether=t) == (E_ARG, -7)        # rows 0 .. 4 of 4
-        assert _raw(eng, n, state, prev, out, pvo, log=log, steps=1, tether=log.data_ptr()) == (E_ARG, -7)      # aliases the log
+        assert raw(eng, "teth", n, state, prev, out, pvo, steps=5, log=log, s_extremes=S_E, tether=t, s_tether=S_T) == (E_ARG, -7)        # rows 0 .. 4 of 4
+        assert raw(eng, "teth", n, state, prev, out, pvo, log=log, s_extremes=S_E, tether=log.data_ptr(), s_tether=S_T) == (E_ARG, -7)      # aliases the log
     # the probe
     lib, s = eng._lib, eng._stream(None)
     sp, wp, tp = state.data_ptr(), w.data_ptr(), w1.data_ptr()
@@ -491,8 +457,8 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     w = torch.full((tiles * S_W,), NAN, device=DEV)
     w1 = torch.full((tiles * S_T1,), NAN, device=DEV)
     eng._check(eng._lib.hydro_tether_wrench(eng._h, n, state.data_ptr(), S_IN, t7.data_ptr(), S_T, w.data_ptr(), S_W, w1.data_ptr(), S_T1, eng._stream(None)))
-    rc, written = _raw(eng, n, state, prev, out, pvo, step0=11, steps=3, log=log, applied=a.data_ptr(), control=c17.data_ptr(),
-                       mooring=m9.data_ptr(), extremes=e8.data_ptr(), tether=t7.data_ptr(), implicit=implicit)
+    rc, written = raw(eng, "teth", n, state, prev, out, pvo, steps=3, step0=11, implicit=implicit, log=log, applied=a.data_ptr(), control=c17.data_ptr(),
+                      mooring=m9.data_ptr(), extremes=e8.data_ptr(), s_extremes=S_E, tether=t7.data_ptr(), s_tether=S_T)
     eng._check(rc)
     torch.cuda.synchronize()
     assert written == 3
@@ -508,7 +474,8 @@ def test_strides_and_nan_guards(coeff, implicit, pop, native_built):
     assert np.isfinite(line).all() and np.isfinite(tension).all(), "a sentinel was read"
     cur, old = _buffers(st, pv, n)
     want_ext = eng.extremes_reset(eng.alloc_tiled(8, n), n)
-    want, want_prev = _step(eng, cur, old, n, 3, 11, _tiled(rec), want_ext, _tiled(pop["moor"][:n]), _tiled(pop["ctl"][:n]), _tiled(pop["applied"][:n]), implicit)
+    want, want_prev = step(eng, "teth", cur, old, n, 3, step0=11, tether=_tiled(rec), extremes=want_ext, mooring=_tiled(pop["moor"][:n]),
+                           control=_tiled(pop["ctl"][:n]), applied=_tiled(pop["applied"][:n]), implicit=implicit)
     torch.cuda.synchronize()
     assert np.array_equal(got.view(np.uint32), _from(want, n).view(np.uint32))
     assert np.array_equal(pv_out.view(np.uint32), _from(want_prev, n).view(np.uint32))
