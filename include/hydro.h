@@ -59,7 +59,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_extremes_reset, hydro_step_fused_tiled_multi_ext,
  *        HYDRO_EXT_FIELDS - running per-body extremes (position box, speed, line tension) updated inside every step
  *        added to 0.7.1 (no existing entry changed): hydro_tether_wrench, hydro_step_fused_tiled_multi_teth,
- *        HYDRO_TETH_FIELDS - one tension-only line between two bodies of a tile, evaluated inside every step */
+ *        HYDRO_TETH_FIELDS - one tension-only line between two bodies of a tile, evaluated inside every step
+ *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_net, HYDRO_TETH_LAYERS_MAX - up to four
+ *        layers of tether records, so that bodies form chains and cables */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -77,6 +79,7 @@ extern "C" {
 #define HYDRO_MOOR_FIELDS    9   /* the mooring record of hydro_step_fused_tiled_multi_moor */
 #define HYDRO_EXT_FIELDS     8   /* the extremes record of hydro_step_fused_tiled_multi_ext */
 #define HYDRO_TETH_FIELDS    7   /* the tether record of hydro_step_fused_tiled_multi_teth */
+#define HYDRO_TETH_LAYERS_MAX 4  /* tether records, one behind the other, in the net of hydro_step_fused_tiled_multi_net */
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
@@ -866,7 +869,9 @@ int hydro_step_fused_tiled_multi_ext(hydro_t *h, int64_t n, const float *state, 
  * them the same l2, inv, x, rate and T, and the force -F, bit for bit.  The pair's linear momentum changes by the rounding of
  * the integrator's additions alone.  (The torques r x F and r' x -F are each body's own and need not cancel.)
  * NOT MODELLED: chains, and more than one tether per body; pairs across tiles; the line's mass, sag and drag; the tether's
- * tension in the extremes record - tension_max stays the mooring line's and is unchanged by a tether.
+ * tension in the extremes record - tension_max stays the mooring line's and is unchanged by a tether.  (The first and the
+ * third are the TETHER NET's, below: up to four of these records in layers, and a cable of small bodies has what one
+ * massless line has not.)
  *
  * hydro_tether_wrench: writes the tiled 6-field W ([tiles][6][64] floats, tile stride out_tile_stride >= 384) of bodies
  * 0 .. n - 1 in `state` - exactly what a step that starts from `state` adds; +0 in all six fields for a body whose line adds
@@ -900,6 +905,53 @@ int hydro_step_fused_tiled_multi_teth(hydro_t *h, int64_t n, const float *state,
                                       const float *mooring, int64_t mooring_tile_stride,
                                       float *extremes, int64_t extremes_tile_stride,
                                       const float *tether, int64_t tether_tile_stride, int64_t step0, void *stream);
+
+/* Tether net: SEVERAL tethers per body in the closed-loop steps - chains and cables of bodies: a lumped-mass umbilical or
+ * riser (a string of small bodies joined by short lines, each carrying its share of mass, buoyancy and drag), a buoy with
+ * a clump weight and a sinker below it, a towed array, a bridle.  No new physics: every line is the tether above, and the
+ * bodies of a cable get their mass, sag and drag from the hydrodynamics every body has.
+ *
+ * THE RECORD: a net is L LAYERS of the tether record, 1 <= L <= HYDRO_TETH_LAYERS_MAX = 4, tiled as ONE record of 7 L
+ * fields: [tiles][7 L][64] floats, layer l's field f in row 7 l + f, tile stride tether_tile_stride >= 448 L, 16-byte
+ * aligned, whole tiles.  EACH LAYER IS A COMPLETE, VALID TETHER RECORD in the sense above (within a layer: at most one line
+ * per body, the pairing an involution inside a tile, both ends the same L0, k, c): `tether + 448 l` with the net's tile
+ * stride is an argument for hydro_tether_wrench, which is the net's probe, layer by layer.  A body may have a line in every
+ * layer: a chain 0-1-2-3-4 is two layers, (0,1) (2,3) in layer 0 and (1,2) (3,4) in layer 1.  Two lines between the same
+ * two bodies (a bridle) are two layers.  A layer of zeros is a layer without lines.
+ * IN A STEP every line is evaluated exactly as hydro_step_fused_tiled_multi_teth evaluates its one, from the TRUE state the
+ * step starts from (no line sees what another line did in this step), and the wrenches are added to the step's wrench IN
+ * ASCENDING LAYER ORDER, one fp32 add per component each, behind the mooring line's wrench and in front of the
+ * integrator: f = fl(fl(fl(f + W_0) + W_1) + ...) over the layers in which the body's line pulls.  A layer in which it does
+ * not pull leaves f untouched: +0 is not added.  Equal and opposite forces hold bit for bit per line.
+ * SCOPE: every line lies inside one tile of 64 bodies, 64 t .. 64 t + 63 - so a cable with its end bodies has at most 64
+ * bodies; at most 4 lines per body; the tether tensions still do not enter the extremes record (tension_max stays the
+ * mooring line's); no bending stiffness.
+ * RULE OF THUMB for a step dt, per body i with mass m_i (Gershgorin on M^-1 K: a body between two springs is not a pair on
+ * its reduced mass): 2 (sum of k over the body's lines) dt^2 / m_i <= 0.04 and 2 (sum of c) dt / m_i <= 0.04.
+ *
+ * hydro_step_fused_tiled_multi_net: the signature and the rules of hydro_step_fused_tiled_multi_teth, with `tether_layers`
+ * between tether_tile_stride and step0.
+ *   tether == NULL      : the launch and its bits are those of hydro_step_fused_tiled_multi_ext; tether_layers is ignored.
+ *   tether_layers == 1  : the bits of hydro_step_fused_tiled_multi_teth with the same record.
+ *   trailing layers of zeros change no bit.
+ * The refusals are those of hydro_step_fused_tiled_multi_teth, in its order, then: tether_layers outside
+ * 1 .. HYDRO_TETH_LAYERS_MAX; a stride below 448 tether_layers or a misaligned buffer; a net that overlaps an output
+ * (state_out, prev_out, log, extremes) anywhere in its 7 tether_layers fields: HYDRO_E_ARG, and nothing is launched or
+ * written.  Asynchronous, no allocation, no synchronisation, safe to capture.  The layers are a loop inside the kernel:
+ * cost and registers in DESIGN.md section 24.  New functionality; the reference has no tethers. */
+int hydro_step_fused_tiled_multi_net(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride,
+                                     const float *mooring, int64_t mooring_tile_stride,
+                                     float *extremes, int64_t extremes_tile_stride,
+                                     const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                     int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -19,6 +19,7 @@ CTL_FIELDS = 17                         # the control record of hydro_step_fused
 MOOR_FIELDS = 9                         # the mooring record of hydro_step_fused_tiled_multi_moor: a(3) | b(3) | L0 | k | c
 EXT_FIELDS = 8                          # the extremes record of hydro_step_fused_tiled_multi_ext: x, y, z min max | speed2_max | tension_max
 TETH_FIELDS = 7                         # the tether record of hydro_step_fused_tiled_multi_teth: b(3) | L0 | k | c | partner lane
+TETH_LAYERS_MAX = 4                     # layers of tether records in the net of hydro_step_fused_tiled_multi_net
 TILE = 64
 BATCH_MAX = 32
 WATCH_MAX = 65536
@@ -131,6 +132,11 @@ SIGNATURES = {
                                                   c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
                                                   c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                                   c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_net": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                                 c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -2252,6 +2252,81 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    TetherLine{tether, tether_stride, nullptr, 0u});
 }
 
+// --------------------------------------------------------------------------
+// TETHER NETS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_net): `layers` tether records, one behind
+// the other ([tiles][7 * layers][64], layer l in rows 7 l .. 7 l + 6), each a complete record of the kind above - so a body
+// has up to `layers` lines, and a chain 0-1-2-3-4 is two layers: (0,1) (2,3) | (1,2) (3,4).  include/hydro.h states the
+// contract ("Tether net").  Every line is tether_wrench's, from the TRUE state the step starts from, and the wrenches are
+// added to f6 in ascending layer order, one fp32 add per component, where the line pulls - one layer gives TetherLine's bits.
+//   the loop    : a REAL loop over the layers, never unrolled.  The _teth kernels stand at 163-167 VGPRs of 168: rolled,
+//                 the peak pressure is that of one evaluation (plus the trip counter, in SGPRs); unrolled, the compiler
+//                 would carry rotation_of(q) and the fairlead arithmetic it shares from layer to layer.  The trip count is
+//                 a kernel argument: wave-uniform, so the exchange of every taken layer stays in wave-uniform control
+//                 flow and every live lane takes part in its six ds_bpermute_b32.
+//   the record  : each trip moves the tile's wave-uniform pointer on by 448 floats and makes it opaque again (TetherLine's
+//                 empty asm), so no layer's loads are hoisted or shared.  The quaternion is made opaque per trip in the same
+//                 way (four VGPR copies), or the compiler forms rotation_of(q) once in front of the loop.
+//   the skip    : per layer, tether_wrench's own ballot: a tile with no line in a layer pays two loads, two compares and the
+//                 branch for that layer
+// --------------------------------------------------------------------------
+struct TetherNet {
+    using GlobalFloats = const float __attribute__((address_space(1)))*;
+    const float* rec; uint32_t stride, layers;
+    GlobalFloats tile_rec; uint32_t lane4;                               // layer 0 of the tile's record: a wave-uniform pointer, in SGPRs
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        tile_rec = (GlobalFloats)(rec + (size_t)tile * stride);
+        lane4 = lane4_;
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        GlobalFloats r = tile_rec;
+#pragma clang loop unroll(disable)
+        for (uint32_t l = 0; l < layers; ++l, r += HYDRO_TETH_FIELDS * HYDRO_TILE) {
+            asm volatile("" : "+s"(r));
+            // (the orientation as well: rotation_of(q) is the same in every trip, and hoisted in front of the loop it would live
+            // across it - nine registers, and paid by a tile without a line)
+            float t[HYDRO_STATE_FIELDS];
+#pragma unroll
+            for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) t[f] = s[f];
+            asm volatile("" : "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]));
+            float W[HYDRO_WRENCH_FIELDS], T;
+            if (tether_wrench(at<float>((const float*)r, lane4), t, W, T)) {
+#pragma unroll
+                for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+            }
+        }
+    }
+};
+
+// The tether kernel's arguments, then the number of layers.  `mooring` and `extremes` may be null.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_net_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
+                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
+                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
+                                                                           const float* mooring, uint32_t mooring_stride,
+                                                                           float* extremes, uint32_t extremes_stride,
+                                                                           const float* tether, uint32_t tether_stride, uint32_t layers)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
+                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
+                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
+                                                   OptionalExtremesTrack{{{0u, 0u}, extremes, extremes_stride}},
+                                                   TetherNet{tether, tether_stride, layers, nullptr, 0u});
+}
+
 // hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
 // nothing) and, if asked for, its tension T (+0 likewise).  The lanes >= n of the last tile leave first: the live ones
 // exchange among themselves, in uniform control flow.
@@ -3176,6 +3251,7 @@ struct MultiStep {
     const float* mooring = nullptr; int64_t mooring_tile_stride = 0;      // the _moor entry: the _bed entry, and a line per body if a record is given
     float* extremes = nullptr; int64_t extremes_tile_stride = 0;          // the _ext entry: the _moor entry, and the running extremes if a record is given
     const float* tether = nullptr; int64_t tether_tile_stride = 0;        // the _teth entry: the _ext entry, and a line between two bodies of a tile if a record is given
+    int64_t tether_layers = 0;                           // the _net entry: the _teth entry with `tether` a net of that many layers (0: a single record, the _teth entry's)
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3269,7 +3345,9 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
             return fail(h, HYDRO_E_ARG, "extremes must not overlap an input (state, prev, applied, control, mooring)");
     }
     if (m.tether) {
-        if ((rc = check_tiled(h, m.n, m.tether, m.tether_tile_stride, HYDRO_TETH_FIELDS, "null tether"))) return rc;
+        if (m.tether_layers != 0 && (m.tether_layers < 1 || m.tether_layers > HYDRO_TETH_LAYERS_MAX))            // (0: not the _net entry)
+            return fail(h, HYDRO_E_ARG, "tether_layers must be in 1 .. HYDRO_TETH_LAYERS_MAX");
+        if ((rc = check_tiled(h, m.n, m.tether, m.tether_tile_stride, HYDRO_TETH_FIELDS * (m.tether_layers ? (int)m.tether_layers : 1), "null tether"))) return rc;
         if ((rc = check_no_overlap(h, m, log_floats, "tether", m.tether, m.tether_tile_stride))) return rc;
         const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE;                 // the extremes record is an output too
         if (m.extremes && ranges_overlap(m.tether, tiles * m.tether_tile_stride, m.extremes, tiled_extent(tiles, m.extremes_tile_stride, HYDRO_EXT_FIELDS)))
@@ -3298,7 +3376,12 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (m.tether) pushed(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+        if (m.tether && m.tether_layers) pushed(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
+                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
+                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
+                        m.tether, (uint32_t)m.tether_tile_stride, (uint32_t)m.tether_layers);
+        else if (m.tether) pushed(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
                         sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
                         h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
                         m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
@@ -3710,6 +3793,35 @@ int hydro_step_fused_tiled_multi_teth(hydro_t* h, int64_t n, const float* state,
     m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
     m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
     m.tether = tether; m.tether_tile_stride = tether_tile_stride;
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_net(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride,
+                                     const float* mooring, int64_t mooring_tile_stride,
+                                     float* extremes, int64_t extremes_tile_stride,
+                                     const float* tether, int64_t tether_tile_stride, int64_t tether_layers, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    m.bed_entry = true;
+    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
+    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
+    m.tether = tether; m.tether_tile_stride = tether_tile_stride;
+    // (a net of no layers is none of the launch's forms: it is refused as out of range, never taken for the _teth entry's record)
+    m.tether_layers = tether_layers == 0 ? -1 : tether_layers;
     return step_fused_tiled_multi_launch(h, m);
 }
 

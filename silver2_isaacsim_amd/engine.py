@@ -686,6 +686,55 @@ class HydroEngine:
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream, extra)
 
+    # ------------------------------------------------------------------ tether nets
+    def _net(self, tether, layers, n):
+        """(address, tile stride) of a net of `layers` tether records, a tiled (tiles, 7 * layers, 64) buffer."""
+        layers = int(layers)
+        if not 1 <= layers <= nat.TETH_LAYERS_MAX:
+            raise ValueError(f"layers must be in 1 .. {nat.TETH_LAYERS_MAX}")
+        return self._tiled(tether, nat.TETH_FIELDS * layers, n)
+
+    def tether_net_wrench(self, state: torch.Tensor, net: torch.Tensor, n: int, layers: int, stream=None):
+        """The wrench and the tension of each body's line in EACH LAYER of the net on the tiled `state`: `net` is a tiled
+        (tiles, 7 * layers, 64) buffer, layer l in rows 7 l .. 7 l + 6 (include/hydro.h, "Tether net").  One call of
+        hydro_tether_wrench per layer, on the layer's sub-record (the net's address + 448 l floats, the net's tile stride).
+        Returns (wrenches, tensions): lists of `layers` tiled (tiles, 6, 64) and (tiles, 1, 64) buffers - what a step of
+        `step_fused_tiled_multi_net` that starts from `state` adds, layer by layer; zeros where a line adds nothing."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        t_ptr, t_stride = self._net(net, layers, n)
+        wrenches, tensions = [], []
+        for l in range(int(layers)):
+            out, tension = self.alloc_tiled(nat.WRENCH_FIELDS, n), self.alloc_tiled(1, n)
+            o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
+            T_ptr, T_stride = self._tiled(tension, 1, n)
+            self._check(self._lib.hydro_tether_wrench(self._h, n, s_ptr, s_stride, t_ptr + 4 * nat.TETH_FIELDS * nat.TILE * l, t_stride,
+                                                      o_ptr, o_stride, T_ptr, T_stride, self._stream(stream)))
+            wrenches.append(out)
+            tensions.append(tension)
+        return wrenches, tensions
+
+    def step_fused_tiled_multi_net(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                   tether: torch.Tensor | None, layers: int = 1, extremes: torch.Tensor | None = None,
+                                   mooring: torch.Tensor | None = None,
+                                   control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                   log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_teth with up to four lines per body (hydro_step_fused_tiled_multi_net): `tether` is a net,
+        the tiled (tiles, 7 * layers, 64) buffer of `tether_net_wrench`, read in every step.  Every layer is a tether record
+        of its own; the lines are all evaluated from the true states the step starts from and their wrenches added in
+        ascending layer order.  layers=1 gives the bits of step_fused_tiled_multi_teth, tether=None those of
+        step_fused_tiled_multi_ext (and `layers` is not looked at).  Returns the number of rows written (0 without a log)."""
+        def extra():
+            tail = self._applied_control(applied, frame, control, n)
+            m_ptr, m_stride = self._tiled(mooring, nat.MOOR_FIELDS, n) if mooring is not None else (None, 0)
+            e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
+            t_ptr, t_stride = self._net(tether, layers, n) if tether is not None else (None, 0)
+            return (*tail, m_ptr, m_stride, e_ptr, e_stride, t_ptr, t_stride, int(layers), int(step0))
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_net,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

@@ -28,7 +28,7 @@ from . import scenes
 from .engine import HydroEngine
 from .extremes import Extremes
 from .mooring import Mooring
-from .tether import Tether
+from .tether import Tether, TetherNet
 
 
 class KineticEnergyMonitor:
@@ -341,6 +341,9 @@ class ClosedLoopSim:
     _extremes_view = None       # the view and its buffer (made once)
     tether = None               # set_tether(): the tiled (tiles, 7, 64) record of the bodies' tethers while tethers are set
     _tether_buf = None          # the buffer itself (made once)
+    tether_net = None           # set_tether_net(): the tiled (tiles, 7 * layers, 64) net of the bodies' tethers while a net is set
+    tether_layers = 0           # the layers of that net (0 without one)
+    _tether_net_bufs = None     # the buffers themselves, by number of layers (each made once)
 
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
@@ -655,6 +658,8 @@ class ClosedLoopSim:
         `sim.stream`, and a graph replay sees the contents of the moment."""
         if not self.fused:
             raise ValueError("tethers live in the fused step kernels (fused=True)")
+        if self.tether_net is not None:
+            raise ValueError("a tether net is set: a net and a set_tether record exclude each other - clear_tether_net() first")
         lines = Tether(pairs, fairlead_a, fairlead_b, length=length, stiffness=stiffness, damping=damping, n=self.n)
         lines.check_stable(np.asarray(self.scene.params, np.float64)[:, 10], self.dt)
         with np.errstate(over="ignore"):
@@ -676,7 +681,51 @@ class ClosedLoopSim:
             self.tether = None
             self._graph = None
 
+    def set_tether_net(self, links, fairlead_a=(0.0, 0.0, 0.0), fairlead_b=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0,
+                       layer=None) -> torch.Tensor:
+        """Tie bodies into chains and cables: `set_tether` with up to four lines per body (hydro_step_fused_tiled_multi_net; the
+        model: include/hydro.h, "Tether net").  Every link is set_tether's tension-only line, evaluated INSIDE the stepping
+        kernel of run_eager, run (graph replays included) and run_resident from the states each step starts from; a string of
+        small bodies joined by short links is a lumped-mass cable with the mass, sag and drag one massless line has not.
+        links (m, 2): body indices (a, b), both inside one block of 64 bodies; fairlead_a, fairlead_b, length, stiffness,
+        damping: as for set_tether, per link; layer (m,): each link's layer, or None for the lowest free one in the order
+        given (`tether.TetherNet` validates and layers them; `TetherNet.chain` alternates two layers).  The per-body rule of
+        thumb, 2 sum(k) dt^2 / m and 2 sum(c) dt / m <= 0.04, is enforced for the bodies' masses:
+        `TetherNet.for_chain(masses, sim.dt)` gives stable defaults.  A net and a set_tether record exclude each other.
+        The net stays until the next call or `clear_tether_net()`.
+        Returns `sim.tether_net`, the tiled (tiles, 7 * sim.tether_layers, 64) device buffer the kernels read, layer l in rows
+        7 l .. 7 l + 6, fields [b | L0 | k | c | partner] each.  For a given number of layers its address never changes: a
+        winch on the device may rewrite L0 in it - on both lanes of a link - between chunks on `sim.stream`."""
+        if not self.fused:
+            raise ValueError("tethers live in the fused step kernels (fused=True)")
+        if self.tether is not None:
+            raise ValueError("tethers are set: a net and a set_tether record exclude each other - clear_tether() first")
+        net = TetherNet(links, fairlead_a, fairlead_b, length=length, stiffness=stiffness, damping=damping, n=self.n, layer=layer)
+        net.check_stable(np.asarray(self.scene.params, np.float64)[:, 10], self.dt)
+        with np.errstate(over="ignore"):
+            rec = net.record.astype(np.float32)
+        if not np.isfinite(rec).all():
+            raise ValueError("tether: a value is out of fp32 range")
+        if self._tether_net_bufs is None:
+            self._tether_net_bufs = {}
+        buf = self._tether_net_bufs.get(net.layers)
+        if buf is None:
+            buf = self._tether_net_bufs[net.layers] = self.engine.alloc_tiled(nat.TETH_FIELDS * net.layers, self.n)
+        with torch.cuda.stream(self.stream):
+            buf.copy_(torch.from_numpy(scenes.to_tiled(rec)))
+        if self.tether_net is not buf:
+            self._graph = None                                              # captured steps are of another entry, or of another buffer
+        self.tether_net, self.tether_layers = buf, net.layers
+        return self.tether_net
+
+    def clear_tether_net(self) -> None:
+        """Cut the net: every call the sim makes is again the one it made before set_tether_net."""
+        if self.tether_net is not None:
+            self.tether_net, self.tether_layers = None, 0
+            self._graph = None
+
     # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # the tether net if one is set, else with
     # the tethers if tethers are set, else with the extremes if they are tracked, else with the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
     # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
     # graph captures: the single-step form of the entries, the bits of the single-step entry, include/hydro.h).  The plain
@@ -690,7 +739,11 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.tether is not None:
+        if self.tether_net is not None:
+            rows = e.step_fused_tiled_multi_net(*args, k, self.steps_done, self.tether_net, self.tether_layers,
+                                                self.extremes.buffer if self.extremes is not None else None,
+                                                self.mooring, self.control, self.applied, self.applied_frame, **kw)
+        elif self.tether is not None:
             rows = e.step_fused_tiled_multi_teth(*args, k, self.steps_done, self.tether, self.extremes.buffer if self.extremes is not None else None,
                                                  self.mooring, self.control, self.applied, self.applied_frame, **kw)
         elif self.extremes is not None:

@@ -19,7 +19,14 @@ A body has a tether if k > 0 or c > 0.  Both bodies of a pair lie in one tile (b
 the partner as a lane of that tile.  This is an explicit spring between two masses: with the reduced mass
 mu = m_a m_b / (m_a + m_b), k dt^2 / mu and c dt / mu must stay at or below 0.04 (`STABLE`, the mooring's rule);
 `Tether.for_pair(m_a, m_b, dt)` gives k = 0.004 mu / dt^2 and c = 0.02 mu / dt, and `check_stable` refuses a record that
-breaks the rule.  Not modelled: chains and several tethers per body, pairs across tiles, the line's mass, sag and drag.
+breaks the rule.  Not modelled by ONE record: chains and several tethers per body - `TetherNet` below layers up to four
+records, so that a string of small bodies makes a cable with mass, sag and drag.  Not modelled at all: pairs across tiles.
+
+`TetherNet` (include/hydro.h, "Tether net") is L <= 4 layers of that record: within a layer every body has at most one line,
+across the layers up to L.  The kernels of `step_fused_tiled_multi_net` evaluate the layers one after the other from the
+same state and add the wrenches in ascending layer order.  A body between two springs is not a pair on its reduced mass:
+the net's rule is per body, 2 (sum of k) dt^2 / m <= 0.04 and 2 (sum of c) dt / m <= 0.04 (`TetherNet.check_stable`,
+`TetherNet.for_chain`).
 """
 from __future__ import annotations
 
@@ -30,6 +37,7 @@ from .seabed import rotation_matrices
 
 FIELDS = 7                      # b(3) | L0 | k | c | partner lane
 TILE = 64
+LAYERS_MAX = 4                  # HYDRO_TETH_LAYERS_MAX: lines per body, layers per net
 
 
 class Tether:
@@ -157,3 +165,135 @@ class Tether:
         with np.errstate(divide="ignore", invalid="ignore"):
             F = np.where((T > 0.0)[:, None], (T / l)[:, None] * e, 0.0)
         return np.concatenate([F, np.cross(r, F)], -1)
+
+
+class TetherNet:
+    """Up to LAYERS_MAX tethers per body, as layers of `Tether` records: chains, cables of small bodies, bridles."""
+
+    def __init__(self, links, fairlead_a=(0.0, 0.0, 0.0), fairlead_b=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0, n: int,
+                 layer=None):
+        """`links` (m, 2) body indices (a, b), `fairlead_a`, `fairlead_b`, `length`, `stiffness`, `damping` as for `Tether`,
+        per link.  `layer` (m,), if given, is each link's layer 0 .. 3 as it stands (two links of a layer at one body are
+        refused, with Tether's message); otherwise each link, in the caller's order, gets the lowest layer that is free at
+        both of its bodies.  Two links between the same two bodies are allowed (a bridle): they take two layers.
+        ValueError for whatever `Tether` refuses in a layer - a body tied to itself, an index outside 0 .. n - 1, a link
+        across two tiles of 64, a non-finite or negative value - and for a link that finds no free layer below 4."""
+        n = int(n)
+        links = np.asarray(links)
+        if links.size == 0:
+            links = np.zeros((0, 2), np.int64)
+        if links.ndim == 1 and links.shape == (2,):
+            links = links[None]
+        if links.ndim != 2 or links.shape[1] != 2 or not np.issubdtype(links.dtype, np.integer):
+            raise ValueError("tether: links must be (m, 2) integer body indices")
+        links = links.astype(np.int64)
+        m = links.shape[0]
+        if m and (links.min() < 0 or links.max() >= n):
+            raise ValueError(f"tether: a body index is outside 0 .. {n - 1}")
+        fa, fb = np.asarray(fairlead_a, np.float64), np.asarray(fairlead_b, np.float64)
+        for f in (fa, fb):
+            if f.ndim > 2 or f.shape[-1:] != (3,):
+                raise ValueError("tether: a fairlead must be (3,) or (m, 3)")
+        per_link = np.empty((m, 9), np.float64)
+        try:
+            per_link[:, 0:3] = fa
+            per_link[:, 3:6] = fb
+            per_link[:, 6] = np.asarray(length, np.float64)
+            per_link[:, 7] = np.asarray(stiffness, np.float64)
+            per_link[:, 8] = np.asarray(damping, np.float64)
+        except ValueError as e:
+            raise ValueError(f"tether: a field does not fit {m} links ({e})") from None
+        if layer is not None:
+            layer = np.asarray(layer)
+            if layer.shape != (m,) or not np.issubdtype(layer.dtype, np.integer):
+                raise ValueError(f"tether: layer must be ({m},) integers, one per link")
+            layer = layer.astype(np.int64)
+            if m and (layer.min() < 0 or layer.max() >= LAYERS_MAX):
+                raise ValueError(f"tether: a layer is outside 0 .. {LAYERS_MAX - 1}")
+        else:
+            layer = np.zeros(m, np.int64)
+            taken: dict[int, set] = {}
+            for i, (a, b) in enumerate(links):
+                a, b = int(a), int(b)
+                used = taken.setdefault(a, set()) | taken.setdefault(b, set())
+                free = [l for l in range(LAYERS_MAX) if l not in used]
+                if not free:
+                    full = a if len(taken[a]) >= len(taken[b]) else b
+                    raise ValueError(f"tether: link {i} ({a}, {b}) finds no free layer: body {full} already has "
+                                     f"{len(taken[full])} lines (at most {LAYERS_MAX} lines per body, and a link needs one layer free at both ends)")
+                layer[i] = free[0]
+                taken[a].add(free[0])
+                taken[b].add(free[0])
+        self.layers = int(layer.max()) + 1 if m else 1
+        self.links, self.layer = links, layer
+        self.nets = []
+        for l in range(self.layers):
+            w = layer == l
+            self.nets.append(Tether(links[w], per_link[w, 0:3], per_link[w, 3:6], length=per_link[w, 6], stiffness=per_link[w, 7],
+                                    damping=per_link[w, 8], n=n))
+        self.record = np.concatenate([t.record for t in self.nets], axis=1)
+
+    @property
+    def n(self) -> int:
+        return self.record.shape[0]
+
+    @classmethod
+    def chain(cls, bodies, fairlead_up=(0.0, 0.0, 0.0), fairlead_down=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0, n: int):
+        """The chain bodies[0] - bodies[1] - ... : consecutive bodies linked, link i from `fairlead_down` of bodies[i] to
+        `fairlead_up` of bodies[i + 1], in layers 0, 1, 0, 1, ... - two layers whatever the order, never three."""
+        bodies = np.asarray(bodies)
+        if bodies.ndim != 1 or bodies.size < 2 or not np.issubdtype(bodies.dtype, np.integer):
+            raise ValueError("tether: a chain is a list of at least two body indices")
+        links = np.stack([bodies[:-1], bodies[1:]], axis=1)
+        return cls(links, fairlead_down, fairlead_up, length=length, stiffness=stiffness, damping=damping, n=n,
+                   layer=np.arange(len(links)) % 2)
+
+    @staticmethod
+    def for_chain(masses, dt: float):
+        """Uniform default (stiffness, damping) for the chain of bodies with `masses` (in the chain's order) stepped with
+        `dt`: the minimum over the bodies of DEFAULT_K m_i / (2 degree_i dt^2) and of DEFAULT_C m_i / (2 degree_i dt) -
+        a tenth and a half of the per-body bound of `check_stable`; degree_i is 1 at the two ends and 2 between them.
+        For a lone pair this is STRICTER than `Tether.for_pair`: there the relative motion of the pair is one oscillator
+        on the reduced mass mu, and k dt^2 / mu is the exact figure; here each body's row of M^-1 K is bounded on its own
+        (Gershgorin: the row sum is 2 k / m_i), which for two equal masses asks k <= 0.02 m / dt^2 where the pair's rule
+        allows 0.04 mu / dt^2 = 0.02 m / dt^2 - the same - and for unequal ones less, m_min / 2 against mu > m_min / 2.
+        The per-body bound needs no eigenvalues and holds for every net."""
+        if not dt > 0.0:
+            raise ValueError("dt must be > 0")
+        masses = np.asarray(masses, np.float64)
+        if masses.ndim != 1 or masses.size < 2:
+            raise ValueError("a chain has at least two bodies")
+        if not (np.isfinite(masses).all() and (masses > 0.0).all()):
+            raise ValueError("mass must be finite and > 0")
+        degree = np.full(masses.shape, 2.0)
+        degree[0] = degree[-1] = 1.0
+        per_body = masses / (2.0 * degree)
+        return float(DEFAULT_K * per_body.min() / dt ** 2), float(DEFAULT_C * per_body.min() / dt)
+
+    def check_stable(self, mass, dt: float) -> None:
+        """ValueError if a body breaks the net's rule of thumb, 2 (sum of k over its lines) dt^2 / m <= 0.04 and
+        2 (sum of c) dt / m <= 0.04, for bodies of `mass` ((n,) or a scalar) - Gershgorin's bound on M^-1 K, body by body."""
+        if not dt > 0.0:
+            raise ValueError("dt must be > 0")
+        mass = np.broadcast_to(np.asarray(mass, np.float64), (self.n,))
+        k_sum = sum(t.record[:, 4] for t in self.nets)
+        c_sum = sum(t.record[:, 5] for t in self.nets)
+        ks, cs = 2.0 * k_sum * dt ** 2 / mass, 2.0 * c_sum * dt / mass
+        tol = 1.0 + 1e-9
+        if (ks > STABLE * tol).any() or (cs > STABLE * tol).any():
+            i = int(np.argmax(np.maximum(ks, cs)))
+            lines = int(sum(((t.record[i, 4] > 0.0) | (t.record[i, 5] > 0.0)) for t in self.nets))
+            raise ValueError(f"tether: body {i} ({lines} lines) has 2 sum(k) dt^2 / m = {ks[i]:.3g}, 2 sum(c) dt / m = {cs[i]:.3g}; both "
+                             f"must be <= {STABLE} (explicit springs, bounded body by body: TetherNet.for_chain gives stable defaults)")
+
+    def wrench(self, state) -> np.ndarray:
+        """(n, 6) the net's wrench, the fp64 sum over the layers of `Tether.wrench`."""
+        return sum(t.wrench(state) for t in self.nets)
+
+    def tensions(self, state) -> np.ndarray:
+        """(m,) the tension of each link, in the caller's order."""
+        out = np.zeros(len(self.links), np.float64)
+        for l, t in enumerate(self.nets):
+            w = self.layer == l
+            out[w] = t.tension(state)[self.links[w, 0]]
+        return out
