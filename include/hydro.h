@@ -61,7 +61,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_tether_wrench, hydro_step_fused_tiled_multi_teth,
  *        HYDRO_TETH_FIELDS - one tension-only line between two bodies of a tile, evaluated inside every step
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_net, HYDRO_TETH_LAYERS_MAX - up to four
- *        layers of tether records, so that bodies form chains and cables */
+ *        layers of tether records, so that bodies form chains and cables
+ *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_peak - the running maximum of every
+ *        tether's tension, per body and layer, updated inside every step */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -952,6 +954,51 @@ int hydro_step_fused_tiled_multi_net(hydro_t *h, int64_t n, const float *state, 
                                      float *extremes, int64_t extremes_tile_stride,
                                      const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
                                      int64_t step0, void *stream);
+
+/* Link tensions: the PEAK TENSION of every tether, tracked inside the closed-loop steps.  The load that sizes a cable is
+ * the largest tension each of its links ever carried.  Inside a resident launch the states between the first and the last
+ * step exist in registers only, and so do the tensions: hydro_tether_wrench sees them at the ends of launches alone.  The
+ * record below is kept by the stepping kernel itself, in every step.
+ *
+ * THE RECORD: a running maximum per body and per layer of the net, tiled [tiles][L][64] floats, L = tether_layers; row l
+ * belongs to layer l of the net.  Tile stride tether_peaks_tile_stride >= 64 L floats, a multiple of 4; 16-byte aligned;
+ * whole tiles - the rules of every tiled record.  The caller's device buffer.
+ * THE SAMPLE of body i, layer l, in a step is what the step's evaluation of that line formed: T where the line pulls, +0
+ * where it adds nothing (no line, a slack line, or a T that is not > 0) - exactly the value hydro_tether_wrench writes to
+ * its `tension` output for layer l and the state the step starts from.
+ * THE UPDATE is the extremes record's: M <- (T > M) ? T : M, a compare-and-select.  A NaN sample never enters, a NaN in the
+ * record stays, an equal value leaves the record's bits.  (A sample of +0 changes nothing and is not written.)  Both bodies
+ * of a link get the same T bit for bit (antisymmetry), so both hold the same maximum.
+ * The record ACCUMULATES over launches, chunks and graph replays.  The empty record is all +0: a plain zero fill resets it,
+ * and there is no reset entry.  A slot holds +0, a positive value or a NaN - what the entry itself leaves in a record that
+ * started empty; a slot seeded with the sign bit set (-0, a negative value) is outside the contract and is kept as it is.
+ * The padding lanes of the last tile, and the floats between 64 L and the tile stride, are never written.
+ * NOTHING FEEDS BACK: state_out, prev_out, the kinetic energy, the log and the extremes record are bit for bit those of
+ * hydro_step_fused_tiled_multi_net with the same arguments; tension_max of the extremes record stays the mooring line's.
+ *
+ * hydro_step_fused_tiled_multi_peak: the signature and the rules of hydro_step_fused_tiled_multi_net, with `tether_peaks`,
+ * `tether_peaks_tile_stride` between tether_layers and step0.
+ *   tether_peaks == NULL : the launch and its bits are those of hydro_step_fused_tiled_multi_net; the stride is ignored.
+ * The refusals are those of hydro_step_fused_tiled_multi_net, in its order, then: a record with tether == NULL; a stride
+ * below 64 tether_layers or a misaligned record; a record that overlaps state_out, prev_out, the log, state, prev, applied,
+ * control, mooring, the net or the extremes record: HYDRO_E_ARG, and nothing is launched or written.  Asynchronous, no
+ * allocation, no synchronisation, safe to capture.  The update is one vector memory instruction per pulling line and step
+ * (DESIGN.md section 25).  SCOPE: the maximum only - not its time of occurrence, no minima, no cycle counts.  New
+ * functionality; the reference has no tethers. */
+int hydro_step_fused_tiled_multi_peak(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                      const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float *state_out, int64_t out_tile_stride,
+                                      float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double *ke_out_dev,
+                                      float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t *rows_written_host,
+                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float *control, int64_t control_tile_stride,
+                                      const float *mooring, int64_t mooring_tile_stride,
+                                      float *extremes, int64_t extremes_tile_stride,
+                                      const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                      float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                      int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -137,6 +137,11 @@ SIGNATURES = {
                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                                  c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_peak": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
+                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
+                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                                  c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -2327,6 +2327,92 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
                                                    TetherNet{tether, tether_stride, layers, nullptr, 0u});
 }
 
+// --------------------------------------------------------------------------
+// LINK TENSIONS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_peak): the running maximum of every line's
+// tension, per body and layer ([tiles][layers][64] fp32, row l the layer's), updated in every step of a launch.  The states
+// between the ends of a launch exist in registers only, so the tensions do too: the design load of a cable - the largest
+// tension each link ever carried - can be taken nowhere else.  include/hydro.h states the contract ("Link tensions").
+// PeakTetherNet is TetherNet, trip for trip, plus ONE instruction behind the wrench of a line that pulls:
+//   the update  : extreme_max(record, T) as a NO-RETURN integer maximum on the bits of T (global_atomic_umax, a vector memory
+//                 instruction), from the lanes whose line pulls.  Such a lane has T > 0, and the non-negative floats order as
+//                 their bits do as unsigned integers: the larger bits are the larger value, an equal value leaves the slot's
+//                 bits, and a NaN already in the slot (bits above +inf's, either sign) stays - extreme_max's rule, bit for bit,
+//                 for a record that holds what the entry itself leaves there: +0, a positive value or a NaN.  A NaN sample has no
+//                 T > 0 and never gets here.
+//   why not load, compare, store: the _net kernels stand at 163-167 VGPRs of 168 and their LDS fills the CU at three blocks, so
+//                 the accumulators can be neither carried nor parked.  Read-modify-write in the caller's buffer would put a
+//                 load's round trip to L2 into every taken layer of every step and cost a register for the value; the
+//                 maximum is done by the L2 itself, nothing comes back and the wave does not wait.  Each slot belongs to one
+//                 lane of one wave: there is no contention, the atomic is used for where it executes, not for mutual exclusion.
+//   the slot    : the tile's row of the record, a wave-uniform pointer in two SGPRs that moves on by 64 floats per trip and is
+//                 made opaque per trip like the net's, plus lane4: the compiler forms the 64-bit address with one
+//                 v_lshl_add_u64 inside the branch (an atomic takes no scalar base here), in registers that are free there.
+//                 Left transparent, the address is formed in front of the step loop and lives across it: 12 bytes of scratch
+//                 in the eight instantiations that stand at 167
+//   control flow: the update sits behind tether_wrench, inside the branch of the lanes whose line pulls: the exchange of every
+//                 taken layer is in wave-uniform control flow as in TetherNet, and a tile without a line in a layer branches
+//                 round everything on tether_wrench's ballot and touches no memory
+// Nothing read here feeds back: state, prev_out, energy, log and extremes are TetherNet's bits.
+// --------------------------------------------------------------------------
+struct PeakTetherNet : TetherNet {
+    using GlobalWords = uint32_t __attribute__((address_space(1)))*;
+    float* peaks; uint32_t peaks_stride;
+    GlobalWords tile_peaks;                                              // row 0 of the tile's record: a wave-uniform pointer, in SGPRs
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        TetherNet::begin(tile, lane4_);
+        tile_peaks = (GlobalWords)(peaks + (size_t)tile * peaks_stride);
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        GlobalFloats r = tile_rec;
+        GlobalWords p = tile_peaks;
+#pragma clang loop unroll(disable)
+        for (uint32_t l = 0; l < layers; ++l, r += HYDRO_TETH_FIELDS * HYDRO_TILE, p += HYDRO_TILE) {
+            asm volatile("" : "+s"(r), "+s"(p));                         // (p as well: left alone, the lane's 64-bit slot address is formed in front of the step loop and lives across it)
+            float t[HYDRO_STATE_FIELDS];
+#pragma unroll
+            for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) t[f] = s[f];
+            asm volatile("" : "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]));
+            float W[HYDRO_WRENCH_FIELDS], T;
+            if (tether_wrench(at<float>((const float*)r, lane4), t, W, T)) {
+#pragma unroll
+                for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+                (void)__hip_atomic_fetch_max(at<uint32_t>((uint32_t*)p, lane4), __builtin_bit_cast(uint32_t, T), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+};
+
+// The net kernel's arguments, then the record of the link tensions.  `mooring` and `extremes` may be null.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_peak_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
+                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
+                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
+                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
+                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
+                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
+                                                                           const float* applied, uint32_t applied_stride, int body_frame,
+                                                                           const float* control, uint32_t control_stride,
+                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
+                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
+                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
+                                                                           const float* mooring, uint32_t mooring_stride,
+                                                                           float* extremes, uint32_t extremes_stride,
+                                                                           const float* tether, uint32_t tether_stride, uint32_t layers,
+                                                                           float* peaks, uint32_t peaks_stride)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
+                                                   ke_partials, ke_stride, ke_rotational, ke_out,
+                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
+                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
+                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
+                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
+                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
+                                                   OptionalExtremesTrack{{{0u, 0u}, extremes, extremes_stride}},
+                                                   PeakTetherNet{{tether, tether_stride, layers, nullptr, 0u}, peaks, peaks_stride, nullptr});
+}
+
 // hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
 // nothing) and, if asked for, its tension T (+0 likewise).  The lanes >= n of the last tile leave first: the live ones
 // exchange among themselves, in uniform control flow.
@@ -3252,6 +3338,7 @@ struct MultiStep {
     float* extremes = nullptr; int64_t extremes_tile_stride = 0;          // the _ext entry: the _moor entry, and the running extremes if a record is given
     const float* tether = nullptr; int64_t tether_tile_stride = 0;        // the _teth entry: the _ext entry, and a line between two bodies of a tile if a record is given
     int64_t tether_layers = 0;                           // the _net entry: the _teth entry with `tether` a net of that many layers (0: a single record, the _teth entry's)
+    float* tether_peaks = nullptr; int64_t tether_peaks_tile_stride = 0;  // the _peak entry: the _net entry, and the running maximum of every line's tension if a record is given
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3296,8 +3383,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
     return HYDRO_OK;
 }
 
-// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the tether kernel takes
-// everything, the extremes kernel everything but the tethers, the mooring kernel everything but the extremes, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the link-tension kernel
+// takes everything, the net kernel everything but the record of the link tensions, the tether kernel everything but the net's layers, the extremes kernel everything but the tethers, the mooring kernel everything but the extremes, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
 // kernel the recorder - and a launch is handed the options it goes without as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
@@ -3353,6 +3440,22 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         if (m.extremes && ranges_overlap(m.tether, tiles * m.tether_tile_stride, m.extremes, tiled_extent(tiles, m.extremes_tile_stride, HYDRO_EXT_FIELDS)))
             return fail(h, HYDRO_E_ARG, "tether must not overlap an output (extremes)");
     }
+    if (m.tether_peaks) {
+        if (!m.tether) return fail(h, HYDRO_E_ARG, "tether_peaks without a tether net");
+        const int layers = (int)m.tether_layers;                                   // (the _peak entry is a _net entry: 1 .. 4 by now)
+        if ((rc = check_tiled(h, m.n, m.tether_peaks, m.tether_peaks_tile_stride, layers, "null tether_peaks"))) return rc;
+        // it is written in every step: it must stay out of everything else the launch reads or writes
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiled_extent(tiles, m.tether_peaks_tile_stride, layers);
+        const auto meets = [&](const float* p, int64_t stride, int fields) {
+            return p && ranges_overlap(m.tether_peaks, floats, p, tiled_extent(tiles, stride, fields));
+        };
+        if (meets(m.state_out, m.out_tile_stride, HYDRO_STATE_FIELDS) || meets(m.prev_out, m.prev_out_tile_stride, HYDRO_PREV_FIELDS)
+            || meets(m.state, m.state_tile_stride, HYDRO_STATE_FIELDS) || meets(m.prev, m.prev_tile_stride, HYDRO_PREV_FIELDS)
+            || meets(m.applied, m.applied_tile_stride, HYDRO_WRENCH_FIELDS) || meets(m.control, m.control_tile_stride, HYDRO_CTL_FIELDS)
+            || meets(m.mooring, m.mooring_tile_stride, HYDRO_MOOR_FIELDS) || meets(m.tether, m.tether_tile_stride, HYDRO_TETH_FIELDS * layers)
+            || meets(m.extremes, m.extremes_tile_stride, HYDRO_EXT_FIELDS) || (m.log && ranges_overlap(m.tether_peaks, floats, m.log, log_floats)))
+            return fail(h, HYDRO_E_ARG, "tether_peaks must not overlap an output, an input record, the net, the extremes or the log");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -3376,7 +3479,12 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (m.tether && m.tether_layers) pushed(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+        if (m.tether_peaks) pushed(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
+                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
+                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
+                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
+                        m.tether, (uint32_t)m.tether_tile_stride, (uint32_t)m.tether_layers, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
+        else if (m.tether && m.tether_layers) pushed(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
                         sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
                         h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
                         m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
@@ -3822,6 +3930,36 @@ int hydro_step_fused_tiled_multi_net(hydro_t* h, int64_t n, const float* state, 
     m.tether = tether; m.tether_tile_stride = tether_tile_stride;
     // (a net of no layers is none of the launch's forms: it is refused as out of range, never taken for the _teth entry's record)
     m.tether_layers = tether_layers == 0 ? -1 : tether_layers;
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_peak(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                      const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float* state_out, int64_t out_tile_stride,
+                                      float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double* ke_out_dev,
+                                      float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t* rows_written_host,
+                                      const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float* control, int64_t control_tile_stride,
+                                      const float* mooring, int64_t mooring_tile_stride,
+                                      float* extremes, int64_t extremes_tile_stride,
+                                      const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                      float* tether_peaks, int64_t tether_peaks_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
+    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.sea_entry = true; m.step0 = step0;
+    m.bed_entry = true;
+    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
+    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
+    m.tether = tether; m.tether_tile_stride = tether_tile_stride;
+    m.tether_layers = tether_layers == 0 ? -1 : tether_layers;           // (as in the _net entry: no layers is out of range)
+    m.tether_peaks = tether_peaks; m.tether_peaks_tile_stride = tether_peaks_tile_stride;
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -735,6 +735,30 @@ class HydroEngine:
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream, extra)
 
+    # ------------------------------------------------------------------ link tensions
+    def step_fused_tiled_multi_peak(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                    tether: torch.Tensor | None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                    extremes: torch.Tensor | None = None, mooring: torch.Tensor | None = None,
+                                    control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                    log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                    state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                    ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_net that also keeps the PEAK TENSION of every line (hydro_step_fused_tiled_multi_peak; the
+        record: include/hydro.h, "Link tensions"): `peaks` is a tiled (tiles, layers, 64) buffer, row l the running maximum of
+        each body's line in layer l of the net - updated in every step where the line pulls, never reset by a launch (zero it
+        to start over), so it accumulates over launches.  Nothing feeds back: states, energy, log and extremes are the bits
+        of step_fused_tiled_multi_net.  peaks=None IS that call.  Returns the number of rows written (0 without a log)."""
+        def extra():
+            tail = self._applied_control(applied, frame, control, n)
+            m_ptr, m_stride = self._tiled(mooring, nat.MOOR_FIELDS, n) if mooring is not None else (None, 0)
+            e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
+            t_ptr, t_stride = self._net(tether, layers, n) if tether is not None else (None, 0)
+            p_ptr, p_stride = self._tiled(peaks, int(layers), n) if peaks is not None else (None, 0)
+            return (*tail, m_ptr, m_stride, e_ptr, e_stride, t_ptr, t_stride, int(layers), p_ptr, p_stride, int(step0))
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_peak,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

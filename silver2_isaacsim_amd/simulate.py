@@ -28,7 +28,7 @@ from . import scenes
 from .engine import HydroEngine
 from .extremes import Extremes
 from .mooring import Mooring
-from .tether import Tether, TetherNet
+from .tether import LinkTensions, Tether, TetherNet
 
 
 class KineticEnergyMonitor:
@@ -344,6 +344,9 @@ class ClosedLoopSim:
     tether_net = None           # set_tether_net(): the tiled (tiles, 7 * layers, 64) net of the bodies' tethers while a net is set
     tether_layers = 0           # the layers of that net (0 without one)
     _tether_net_bufs = None     # the buffers themselves, by number of layers (each made once)
+    _tether_links = None        # (links, layer) of the tethers or the net that is set, in the caller's order
+    link_tensions = None        # track_link_tensions(): the tether.LinkTensions view over the lines' peak tensions while they are tracked
+    _link_tension_views = None  # the views and their buffers, by number of layers (each made once)
 
     def __init__(self, scene: "scenes.Scene", device: int | str = 0, coeff_dtype: str | None = None,
                  fused: bool = True, implicit_drag: bool = False, ke_every: int = 0, graph_resident_sampling: bool | None = None,
@@ -673,11 +676,14 @@ class ClosedLoopSim:
         if self.tether is None:
             self._graph = None                                              # captured steps are of another entry
         self.tether = self._tether_buf
+        self._tether_links = (lines.pairs, np.zeros(len(lines.pairs), np.int64))
+        self._relink_tensions()
         return self.tether
 
     def clear_tether(self) -> None:
         """Cut the tethers: every call the sim makes is again the one it made before set_tether."""
         if self.tether is not None:
+            self._tracked_layers_stay(0)
             self.tether = None
             self._graph = None
 
@@ -706,6 +712,7 @@ class ClosedLoopSim:
             rec = net.record.astype(np.float32)
         if not np.isfinite(rec).all():
             raise ValueError("tether: a value is out of fp32 range")
+        self._tracked_layers_stay(net.layers)
         if self._tether_net_bufs is None:
             self._tether_net_bufs = {}
         buf = self._tether_net_bufs.get(net.layers)
@@ -716,15 +723,70 @@ class ClosedLoopSim:
         if self.tether_net is not buf:
             self._graph = None                                              # captured steps are of another entry, or of another buffer
         self.tether_net, self.tether_layers = buf, net.layers
+        self._tether_links = (net.links, net.layer)
+        self._relink_tensions()
         return self.tether_net
 
     def clear_tether_net(self) -> None:
         """Cut the net: every call the sim makes is again the one it made before set_tether_net."""
         if self.tether_net is not None:
+            self._tracked_layers_stay(0)
             self.tether_net, self.tether_layers = None, 0
             self._graph = None
 
+    def track_link_tensions(self) -> LinkTensions:
+        """Keep the PEAK TENSION of every tether link: from now on every physics step of run_eager, run (graph replays
+        included) and run_resident updates, INSIDE the stepping kernel, the largest tension each line of the net has carried
+        (hydro_step_fused_tiled_multi_peak; the record: include/hydro.h, "Link tensions") - one float per body and layer,
+        touched only by a line that pulls.  The design load of a cable is read off one resident run, without a trajectory.
+        Nothing feeds back: states, energy, log and extremes are bit for bit those of a run that tracks nothing, and
+        `tension_max` of the extremes stays the mooring line's.  ValueError unless a net (`set_tether_net`) or tethers
+        (`set_tether`) are set.
+        With a net the kernels take the net's buffer and its layers.  With a `set_tether` record they take that record as a
+        net of ONE layer: the tether kernel has no loop over layers to hook the update into, so while the tensions are tracked
+        the steps go through the net kernels, which compute the same bits and were measured at 1.08 - 1.19 times the tether
+        kernel's time per step at one layer; `clear_link_tensions()` gives the tether kernel back.
+        Calling it again resets the record.  While tensions are tracked the number of layers is fixed: a `set_tether_net` of
+        another layer count, `clear_tether_net()` and `clear_tether()` raise and name `clear_link_tensions()`; a net of the
+        same layer count replaces the links `peak()` reads and leaves the record as it is.
+        Returns `sim.link_tensions`, a `tether.LinkTensions` view; the address of its buffer never changes for a given number
+        of layers, and `view.reset()` starts over without leaving the entry."""
+        if not self.fused:
+            raise ValueError("link tensions are tracked in the fused step kernels (fused=True)")
+        if self.tether_net is None and self.tether is None:
+            raise ValueError("no tethers to track: call set_tether_net() or set_tether() first")
+        layers = self.tether_layers if self.tether_net is not None else 1
+        if self._link_tension_views is None:
+            self._link_tension_views = {}
+        view = self._link_tension_views.get(layers)
+        if view is None:
+            view = self._link_tension_views[layers] = LinkTensions(self, self.engine.alloc_tiled(layers, self.n), *self._tether_links)
+        view.links, view.layer = self._tether_links
+        view.reset()
+        if self.link_tensions is not view:
+            self._graph = None                                              # captured steps are of another entry, or of another record
+        self.link_tensions = view
+        return view
+
+    def clear_link_tensions(self) -> None:
+        """Stop tracking: every call the sim makes is again the one it made before track_link_tensions.  The record keeps its
+        contents (the view returned by track_link_tensions still reads them)."""
+        if self.link_tensions is not None:
+            self.link_tensions = None
+            self._graph = None
+
+    def _tracked_layers_stay(self, layers: int) -> None:
+        # the record of the link tensions has one row per layer: a change of the layer count under it is refused, before anything is changed
+        if self.link_tensions is not None and self.link_tensions.layers != layers:
+            raise ValueError(f"link tensions are tracked over {self.link_tensions.layers} layer(s): clear_link_tensions() first "
+                             f"(then track_link_tensions() again for the new tethers)")
+
+    def _relink_tensions(self) -> None:
+        if self.link_tensions is not None:
+            self.link_tensions.links, self.link_tensions.layer = self._tether_links
+
     # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # the link tensions if they are tracked (over the net, or over the tethers as a net of one layer), else with
     # the tether net if one is set, else with
     # the tethers if tethers are set, else with the extremes if they are tracked, else with the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
     # takes the options behind it in that list, and a recorder rides in whichever is picked (k = 1 from run_eager and inside
@@ -739,7 +801,12 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.tether_net is not None:
+        if self.link_tensions is not None:
+            net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
+            rows = e.step_fused_tiled_multi_peak(*args, k, self.steps_done, net, layers, self.link_tensions.buffer,
+                                                 self.extremes.buffer if self.extremes is not None else None,
+                                                 self.mooring, self.control, self.applied, self.applied_frame, **kw)
+        elif self.tether_net is not None:
             rows = e.step_fused_tiled_multi_net(*args, k, self.steps_done, self.tether_net, self.tether_layers,
                                                 self.extremes.buffer if self.extremes is not None else None,
                                                 self.mooring, self.control, self.applied, self.applied_frame, **kw)

@@ -27,6 +27,10 @@ across the layers up to L.  The kernels of `step_fused_tiled_multi_net` evaluate
 same state and add the wrenches in ascending layer order.  A body between two springs is not a pair on its reduced mass:
 the net's rule is per body, 2 (sum of k) dt^2 / m <= 0.04 and 2 (sum of c) dt / m <= 0.04 (`TetherNet.check_stable`,
 `TetherNet.for_chain`).
+
+`LinkTensions` (include/hydro.h, "Link tensions") is the view `ClosedLoopSim.track_link_tensions()` returns over the peak
+tension of every line: the kernels of `step_fused_tiled_multi_peak` keep, per body and layer, the largest T a line formed in
+any step - the load that sizes a cable, read off one resident run without a trajectory.
 """
 from __future__ import annotations
 
@@ -297,3 +301,59 @@ class TetherNet:
             w = self.layer == l
             out[w] = t.tension(state)[self.links[w, 0]]
         return out
+
+
+class LinkTensions:
+    """View over the tiled (tiles, L, 64) device record of the peak tension of every line of a `ClosedLoopSim`
+    (`sim.track_link_tensions()`; include/hydro.h, "Link tensions"): row l holds, per body, the largest tension its line in
+    layer l of the net has carried in any physics step since the record was last empty.  The kernels of
+    `HydroEngine.step_fused_tiled_multi_peak` update it inside every step - in a resident launch the tensions between the
+    first and the last step exist nowhere else.  A step's sample is the T its evaluation of the line formed where the line
+    pulls (what `tether_net_wrench` returns as the tension for the state the step starts from) and +0 where it adds
+    nothing; the update is the extremes record's compare-and-select: a NaN sample never enters, a NaN in the record stays,
+    an equal value leaves the record's bits.  Both bodies of a link hold the same bits.  Empty is all +0.
+    `buffer` is the tensor the kernels write - its address never changes; every reader waits for the step stream first.
+    Not provided: when the peak occurred, minima, cycle counts."""
+
+    def __init__(self, sim, buffer, links, layer):
+        self._sim = sim
+        self.buffer = buffer
+        self.n = sim.n
+        self.layers = int(buffer.shape[1])
+        self.links = np.asarray(links, np.int64).reshape(-1, 2)
+        self.layer = np.asarray(layer, np.int64).reshape(-1)
+
+    @staticmethod
+    def fold(tensions, seed=None) -> np.ndarray:
+        """The host restatement: the (n, L) fp32 record after the samples `tensions` (rows, L, n) - one (L, n) set of
+        per-layer tensions per step, +0 where a line adds nothing - have entered, row by row, a record that starts as
+        `seed` (n, L; all +0 if None): M = T if T > M else M, bit for bit."""
+        tensions = np.asarray(tensions, np.float32)
+        if tensions.ndim != 3:
+            raise ValueError("fold: tensions must be (rows, L, n)")
+        _, layers, n = tensions.shape
+        rec = np.zeros((n, layers), np.float32) if seed is None else np.array(seed, np.float32, copy=True)
+        if rec.shape != (n, layers):
+            raise ValueError(f"fold: seed must be ({n}, {layers})")
+        with np.errstate(invalid="ignore"):
+            for T in tensions:
+                rec = np.where(T.T > rec, T.T, rec)
+        return rec
+
+    def record(self) -> np.ndarray:
+        """(n, L) host copy of the record: the peak tension of body i's line in layer l, N (+0: it never pulled)."""
+        from . import scenes
+        self._sim.synchronize()
+        return scenes.from_tiled(self.buffer.cpu().numpy(), self.n)
+
+    def peak(self, record=None) -> np.ndarray:
+        """(m,) the peak tension of each link, in the caller's order of `set_tether_net` / `set_tether`: read at the link's
+        first body, links[:, 0], in the link's layer (`TetherNet.tensions`' convention; the other end holds the same bits)."""
+        rec = self.record() if record is None else np.asarray(record)
+        return rec[self.links[:, 0], self.layer]
+
+    def reset(self) -> None:
+        """Start over from the empty record (all +0), on the sim's stream."""
+        import torch
+        with torch.cuda.stream(self._sim.stream):
+            self.buffer.zero_()
