@@ -58,6 +58,21 @@ STATUS_NAMES = {v: k for k, v in list(globals().items()) if k == "HYDRO_OK" or k
 
 # every symbol include/hydro.h declares: (restype, argtypes)
 _FP = POINTER(c_void_p)      # table of field pointers (const float *const [N])
+# The argument groups of the hydro_step_fused_tiled_multi* entries, each stated once, in the header's order within a group:
+# an entry is the base group, the groups of the options it takes, `step0` from the _sea entry on, and the stream.
+_MULTI = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,       # h, n, state, prev (+ strides), dt, steps
+          c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p]                   # state_out, prev_out (+ strides), implicit_drag, rotational, ke_out_dev
+_REC = [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64)]       # log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host
+_APP = [c_void_p, c_int64, c_int]                                                         # applied, applied_tile_stride, applied_frame
+_CTL = _MOOR = _EXT = _TETH = _PEAK = [c_void_p, c_int64]                                 # a per-body record and its tile stride
+_LAYERS = _STEP0 = [c_int64]                                                              # tether_layers; step0
+_STREAM = [c_void_p]
+
+
+def _multi(*groups):
+    return c_int, sum(groups, _MULTI) + _STREAM
+
+
 SIGNATURES = {
     "hydro_version": (c_int, []),
     "hydro_status_string": (c_char_p, [c_int]),
@@ -84,64 +99,30 @@ SIGNATURES = {
                                        c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "hydro_step_fused_tiled_ke": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                           c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "hydro_step_fused_tiled_multi": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                             c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "hydro_step_fused_tiled_multi": _multi(),
     "hydro_set_watch": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
     "hydro_watch_count": (c_int64, [c_void_p]),
-    "hydro_step_fused_tiled_multi_rec": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64), c_void_p]),
-    "hydro_step_fused_tiled_multi_app": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                 c_void_p, c_int64, c_int, c_void_p]),
-    "hydro_step_fused_tiled_multi_ctl": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_rec": _multi(_REC),
+    "hydro_step_fused_tiled_multi_app": _multi(_REC, _APP),
+    "hydro_step_fused_tiled_multi_ctl": _multi(_REC, _APP, _CTL),
     "hydro_set_sea": (c_int, [c_void_p, POINTER(Sea)]),
     "hydro_sea_sample": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_sea": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_sea": _multi(_REC, _APP, _CTL, _STEP0),
     "hydro_step_wrench_tiled_sea": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                             c_void_p, c_int64, c_double, c_void_p]),
     "hydro_step_wrench_aos_sea": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_double,
                                           c_void_p, c_void_p, c_double, c_void_p]),
     "hydro_set_seabed": (c_int, [c_void_p, POINTER(Seabed)]),
     "hydro_seabed_wrench": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_bed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_bed": _multi(_REC, _APP, _CTL, _STEP0),
     "hydro_mooring_wrench": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_moor": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_moor": _multi(_REC, _APP, _CTL, _MOOR, _STEP0),
     "hydro_extremes_reset": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_ext": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
-                                                 c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_ext": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _STEP0),
     "hydro_tether_wrench": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_teth": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
-                                                  c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_net": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                 c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
-                                                 c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "hydro_step_fused_tiled_multi_peak": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_int,
-                                                  c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                                  c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int64),
-                                                  c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64,
-                                                  c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_teth": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _STEP0),
+    "hydro_step_fused_tiled_multi_net": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _LAYERS, _STEP0),
+    "hydro_step_fused_tiled_multi_peak": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

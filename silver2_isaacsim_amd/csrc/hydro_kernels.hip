@@ -1237,6 +1237,56 @@ struct NoTether {
 };
 
 // --------------------------------------------------------------------------
+// THE ARGUMENT GROUPS of the step_fused_multi_*_tiled_kernel family, each spelled ONCE: HYDRO_<GROUP>_PARAMS is the group as
+// kernel parameters, HYDRO_<GROUP>_ARGS the same names as arguments.  A kernel's signature is a run of groups (every family
+// takes its predecessor's and one more) and its body one fused_multi_body call; a group's policy is built from its ARGS by an
+// inline factory that stands behind the policy's struct (log_recorder / optional_recorder, pose_hold / optional_pose_hold, ...)
+// and takes the group's PARAMS as its own parameters.
+// Macros and not by-value structs: a struct per group, laid out so that every kernarg offset stays where it is, still
+// changed every instantiation it was tried on (other SGPR allocation, regrouped s_load_dwordx2/x4 from the kernarg
+// segment, other mangled names), and these kernels stand at 163-167 of 168 VGPRs with the first 16 kernarg dwords preloaded
+// (BASE's: tests/test_recorder.py).  The preprocessor leaves the flattened signatures, hence the code, as they were:
+// scripts/asm_symbols.py shows every kernel of the file identical (section 26 of DESIGN.md).
+// --------------------------------------------------------------------------
+#define HYDRO_BASE_PARAMS const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,                   \
+                          uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,                       \
+                          uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,                             \
+                          double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out
+#define HYDRO_BASE_ARGS k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt, \
+                        ke_partials, ke_stride, ke_rotational, ke_out
+#define HYDRO_REC_PARAMS const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,                        \
+                         uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0
+#define HYDRO_REC_ARGS w_mask, w_first, log, log_stride, fields, every, phase, row0
+#define HYDRO_APP_PARAMS const float* applied, uint32_t applied_stride, int body_frame
+#define HYDRO_APP_ARGS applied, applied_stride, body_frame
+#define HYDRO_CTL_PARAMS const float* control, uint32_t control_stride
+#define HYDRO_CTL_ARGS control, control_stride
+#define HYDRO_SEA_PARAMS const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt
+#define HYDRO_SEA_ARGS sea_table, sea_waves, step0, sea_dt
+#define HYDRO_BED_PARAMS float bed_z, float bed_stiffness, float bed_damping, float bed_friction, float bed_slip_speed, float bed_friction_rate
+#define HYDRO_BED_ARGS bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate
+#define HYDRO_OPT_BED_PARAMS HYDRO_BED_PARAMS, int bed_present                   // (the families behind _bed: the bed is optional)
+#define HYDRO_OPT_BED_ARGS HYDRO_BED_ARGS, bed_present
+#define HYDRO_MOOR_PARAMS const float* mooring, uint32_t mooring_stride
+#define HYDRO_MOOR_ARGS mooring, mooring_stride
+#define HYDRO_EXT_PARAMS float* extremes, uint32_t extremes_stride
+#define HYDRO_EXT_ARGS extremes, extremes_stride
+#define HYDRO_TETH_PARAMS const float* tether, uint32_t tether_stride
+#define HYDRO_TETH_ARGS tether, tether_stride
+#define HYDRO_NET_PARAMS HYDRO_TETH_PARAMS, uint32_t layers                      // (the families behind _teth: the record is a net)
+#define HYDRO_NET_ARGS HYDRO_TETH_ARGS, layers
+#define HYDRO_PEAK_PARAMS float* peaks, uint32_t peaks_stride
+#define HYDRO_PEAK_ARGS peaks, peaks_stride
+// The three tether families share everything in front of the tether: the groups up to the extremes, every one optional.
+#define HYDRO_UP_TO_EXT_PARAMS HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS, HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS,      \
+                               HYDRO_MOOR_PARAMS, HYDRO_EXT_PARAMS
+#define HYDRO_UP_TO_EXT_OPTIONAL HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),             \
+                                 optional_sea_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), optional_mooring_line(HYDRO_MOOR_ARGS), \
+                                 optional_extremes_track(HYDRO_EXT_ARGS)
+// What the policies that park in LDS ask for (see PoseHold): 3 waves per SIMD, named once like HYDRO_TILED_OCC_ATTR.
+#define HYDRO_MULTI_OCC_ATTR __attribute__((amdgpu_waves_per_eu(3)))
+
+// --------------------------------------------------------------------------
 // The TRAJECTORY RECORDER in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_rec): the states between the
 // first and the last step of a launch exist in registers only, so the bodies on the engine's watch list are written to a
 // device log from inside the loop.  Everything the recorder decides on is wave-uniform:
@@ -1279,28 +1329,22 @@ struct LogRecorder {
     }
 };
 
-template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                       uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                       uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                       double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out)
+__device__ __forceinline__ LogRecorder log_recorder(HYDRO_REC_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
+    return LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u};
+}
+
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) step_fused_multi_tiled_kernel(HYDRO_BASE_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, NoRecorder{}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0)
+__global__ void __launch_bounds__(kBlock) step_fused_multi_rec_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   LogRecorder{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}, NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, log_recorder(HYDRO_REC_ARGS), NoApplied{}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // --------------------------------------------------------------------------
@@ -1351,21 +1395,14 @@ struct OptionalLogRecorder : LogRecorder {
         else { watched = false; column = 0u; due = 0u; row = row0; }
     }
 };
+__device__ __forceinline__ OptionalLogRecorder optional_recorder(HYDRO_REC_PARAMS) { return OptionalLogRecorder{log_recorder(HYDRO_REC_ARGS)}; }
 
 // Same first 16 argument dwords (kernarg preload), the recorder's arguments behind them, then the applied wrench's.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame)
+__global__ void __launch_bounds__(kBlock) step_fused_multi_app_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   AppliedWrench{applied, applied_stride, body_frame, {}}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), AppliedWrench{HYDRO_APP_ARGS, {}},
+                                                   NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // --------------------------------------------------------------------------
@@ -1482,21 +1519,17 @@ struct PoseHold : LaneSlots<kCtlSlots> {
     }
 };
 
+__device__ __forceinline__ PoseHold pose_hold(HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS)
+{
+    return PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame};
+}
+
 // The applied kernel's arguments, then the control record's.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_ctl_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_ctl_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   PoseHold{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}, NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   NoSea{}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // --------------------------------------------------------------------------
@@ -1611,24 +1644,16 @@ struct OptionalPoseHold : PoseHold {
         if (applied) add_parked_applied(parked(), s, f6);
     }
 };
+__device__ __forceinline__ OptionalPoseHold optional_pose_hold(HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS) { return OptionalPoseHold{pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS)}; }
+__device__ __forceinline__ SeaView sea_view(HYDRO_SEA_PARAMS) { return SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}; }
 
 // The pose-hold kernel's arguments, then the sea's.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_sea_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_sea_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                 HYDRO_SEA_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   SeaView{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}, NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   sea_view(HYDRO_SEA_ARGS), NoBed{}, NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // hydro_sea_sample: [eta, u_x, u_y, u_z] per body, the values a step that starts from `st` at step index `step` uses.
@@ -1821,27 +1846,16 @@ struct OptionalSeaView : SeaView {
         if (tab) SeaView::restore(s, pv);
     }
 };
+__device__ __forceinline__ OptionalSeaView optional_sea_view(HYDRO_SEA_PARAMS) { return OptionalSeaView{sea_view(HYDRO_SEA_ARGS)}; }
+__device__ __forceinline__ SeabedContact seabed_contact(HYDRO_BED_PARAMS) { return SeabedContact{{HYDRO_BED_ARGS}}; }
 
 // The sea kernel's arguments, then the bed's six constants.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_bed_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
-                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
-                                                                           float bed_slip_speed, float bed_friction_rate)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_bed_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                 HYDRO_SEA_PARAMS, HYDRO_BED_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   SeabedContact{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, NoMooring{}, NoExtremes{}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   optional_sea_view(HYDRO_SEA_ARGS), seabed_contact(HYDRO_BED_ARGS), NoMooring{}, NoExtremes{}, NoTether{});
 }
 
 // hydro_seabed_wrench: the bed's W per body for the tiled state `st` (zeros for a body no corner of which is below the plane).
@@ -1956,29 +1970,17 @@ struct OptionalSeabedContact : SeabedContact {
         if (present) SeabedContact::add(s, d, mass, f6);
     }
 };
+__device__ __forceinline__ OptionalSeabedContact optional_seabed_contact(HYDRO_OPT_BED_PARAMS) { return OptionalSeabedContact{seabed_contact(HYDRO_BED_ARGS), bed_present}; }
+__device__ __forceinline__ MooringLine mooring_line(HYDRO_MOOR_PARAMS) { return MooringLine{{0u, 0u}, mooring, mooring_stride}; }
 
 // The bed kernel's arguments, then the bed's presence, then the mooring record's.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_moor_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
-                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
-                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
-                                                                           const float* mooring, uint32_t mooring_stride)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_moor_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                  HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_MOOR_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   MooringLine{{0u, 0u}, mooring, mooring_stride}, NoExtremes{}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   optional_sea_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), mooring_line(HYDRO_MOOR_ARGS),
+                                                   NoExtremes{}, NoTether{});
 }
 
 // hydro_mooring_wrench: the line's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds nothing).
@@ -2079,30 +2081,16 @@ struct ExtremesTrack : LaneSlots<kExtSlots> {
     }
 };
 
+__device__ __forceinline__ OptionalMooringLine optional_mooring_line(HYDRO_MOOR_PARAMS) { return OptionalMooringLine{{mooring_line(HYDRO_MOOR_ARGS), 0.0f}}; }
+__device__ __forceinline__ ExtremesTrack extremes_track(HYDRO_EXT_PARAMS) { return ExtremesTrack{{0u, 0u}, extremes, extremes_stride}; }
+
 // The mooring kernel's arguments, then the extremes record's.  `mooring` may be null.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_ext_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
-                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
-                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
-                                                                           const float* mooring, uint32_t mooring_stride,
-                                                                           float* extremes, uint32_t extremes_stride)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_ext_tiled_kernel(HYDRO_UP_TO_EXT_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
-                                                   ExtremesTrack{{0u, 0u}, extremes, extremes_stride}, NoTether{});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   optional_sea_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), optional_mooring_line(HYDRO_MOOR_ARGS),
+                                                   extremes_track(HYDRO_EXT_ARGS), NoTether{});
 }
 
 // hydro_extremes_reset: the empty record, or (st != nullptr) the record of the one sample `st`.
@@ -2223,33 +2211,13 @@ struct OptionalExtremesTrack : ExtremesTrack {
         if (rec) ExtremesTrack::end(tile, lane4_);
     }
 };
+__device__ __forceinline__ OptionalExtremesTrack optional_extremes_track(HYDRO_EXT_PARAMS) { return OptionalExtremesTrack{extremes_track(HYDRO_EXT_ARGS)}; }
 
 // The extremes kernel's arguments, then the tether record's.  `mooring` and `extremes` may be null.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_teth_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
-                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
-                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
-                                                                           const float* mooring, uint32_t mooring_stride,
-                                                                           float* extremes, uint32_t extremes_stride,
-                                                                           const float* tether, uint32_t tether_stride)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_teth_tiled_kernel(HYDRO_UP_TO_EXT_PARAMS, HYDRO_TETH_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
-                                                   OptionalExtremesTrack{{{0u, 0u}, extremes, extremes_stride}},
-                                                   TetherLine{tether, tether_stride, nullptr, 0u});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_UP_TO_EXT_OPTIONAL, TetherLine{HYDRO_TETH_ARGS, nullptr, 0u});
 }
 
 // --------------------------------------------------------------------------
@@ -2301,30 +2269,9 @@ struct TetherNet {
 
 // The tether kernel's arguments, then the number of layers.  `mooring` and `extremes` may be null.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_net_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
-                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
-                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
-                                                                           const float* mooring, uint32_t mooring_stride,
-                                                                           float* extremes, uint32_t extremes_stride,
-                                                                           const float* tether, uint32_t tether_stride, uint32_t layers)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_net_tiled_kernel(HYDRO_UP_TO_EXT_PARAMS, HYDRO_NET_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
-                                                   OptionalExtremesTrack{{{0u, 0u}, extremes, extremes_stride}},
-                                                   TetherNet{tether, tether_stride, layers, nullptr, 0u});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_UP_TO_EXT_OPTIONAL, TetherNet{HYDRO_NET_ARGS, nullptr, 0u});
 }
 
 // --------------------------------------------------------------------------
@@ -2386,31 +2333,9 @@ struct PeakTetherNet : TetherNet {
 
 // The net kernel's arguments, then the record of the link tensions.  `mooring` and `extremes` may be null.
 template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) step_fused_multi_peak_tiled_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_so, float* k_pvo,
-                                                                           uint32_t st_stride, uint32_t pv_stride, uint32_t so_stride, uint32_t pvo_stride,
-                                                                           uint32_t n, uint32_t steps, float dt, double rho, double g, double inv_dt,
-                                                                           double* ke_partials, uint32_t ke_stride, int ke_rotational, double* ke_out,
-                                                                           const uint64_t* w_mask, const uint32_t* w_first, float* log, uint32_t log_stride,
-                                                                           uint32_t fields, uint32_t every, uint32_t phase, uint32_t row0,
-                                                                           const float* applied, uint32_t applied_stride, int body_frame,
-                                                                           const float* control, uint32_t control_stride,
-                                                                           const void* sea_table, uint32_t sea_waves, int64_t step0, double sea_dt,
-                                                                           float bed_z, float bed_stiffness, float bed_damping, float bed_friction,
-                                                                           float bed_slip_speed, float bed_friction_rate, int bed_present,
-                                                                           const float* mooring, uint32_t mooring_stride,
-                                                                           float* extremes, uint32_t extremes_stride,
-                                                                           const float* tether, uint32_t tether_stride, uint32_t layers,
-                                                                           float* peaks, uint32_t peaks_stride)
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_peak_tiled_kernel(HYDRO_UP_TO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS)
 {
-    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(k_st, k_pv, k_prm, k_so, k_pvo, st_stride, pv_stride, so_stride, pvo_stride, n, steps, dt, rho, g, inv_dt,
-                                                   ke_partials, ke_stride, ke_rotational, ke_out,
-                                                   OptionalLogRecorder{{w_mask, w_first, log, log_stride, fields, every, phase, row0, false, 0u, 0u, 0u}},
-                                                   OptionalPoseHold{{{0u, 0u}, control, control_stride, applied, applied_stride, body_frame}},
-                                                   OptionalSeaView{{{0u, 0u}, sea_table_ptr(sea_table), sea_waves, step0, sea_dt}},
-                                                   OptionalSeabedContact{{{bed_z, bed_stiffness, bed_damping, bed_friction, bed_slip_speed, bed_friction_rate}}, bed_present},
-                                                   OptionalMooringLine{{{{0u, 0u}, mooring, mooring_stride}, 0.0f}},
-                                                   OptionalExtremesTrack{{{0u, 0u}, extremes, extremes_stride}},
-                                                   PeakTetherNet{{tether, tether_stride, layers, nullptr, 0u}, peaks, peaks_stride, nullptr});
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_UP_TO_EXT_OPTIONAL, PeakTetherNet{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr});
 }
 
 // hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
@@ -3319,9 +3244,11 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// hydro_step_fused_tiled_multi, its recording twin, the applied-wrench, the pose-hold and the sea entry, described ONCE: each
-// entry fills a MultiStep with what it was given and step_fused_tiled_multi_launch validates and launches it.  An option is
-// absent by its pointer: log == nullptr no recorder, applied == nullptr no applied wrench, control == nullptr no pose hold.
+// A launch of any of the eleven hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
+// copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
+// (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
+// engine's, and an entry that knows of them says so (sea_entry, bed_entry).
 struct MultiStep {
     int64_t n; const float* state; int64_t state_tile_stride; const float* prev; int64_t prev_tile_stride; double dt; int steps;
     float* state_out; int64_t out_tile_stride; float* prev_out; int64_t prev_out_tile_stride;
@@ -3339,6 +3266,22 @@ struct MultiStep {
     const float* tether = nullptr; int64_t tether_tile_stride = 0;        // the _teth entry: the _ext entry, and a line between two bodies of a tile if a record is given
     int64_t tether_layers = 0;                           // the _net entry: the _teth entry with `tether` a net of that many layers (0: a single record, the _teth entry's)
     float* tether_peaks = nullptr; int64_t tether_peaks_tile_stride = 0;  // the _peak entry: the _net entry, and the running maximum of every line's tension if a record is given
+
+    void with_recorder(float* log_, int64_t log_stride_, int64_t rows_capacity_, int fields_, int every_, int phase_, int64_t row0_, int64_t* rows_written_host_)
+    {
+        log = log_; log_stride = log_stride_; rows_capacity = rows_capacity_; fields = fields_; every = every_; phase = phase_;
+        row0 = row0_; rows_written_host = rows_written_host_;
+    }
+    void with_applied(const float* p, int64_t stride, int frame) { applied = p; applied_tile_stride = stride; applied_frame = frame; }
+    void with_control(const float* p, int64_t stride) { control = p; control_tile_stride = stride; }
+    void with_sea(int64_t step0_) { sea_entry = true; step0 = step0_; }
+    void with_seabed() { bed_entry = true; }
+    void with_mooring(const float* p, int64_t stride) { mooring = p; mooring_tile_stride = stride; }
+    void with_extremes(float* p, int64_t stride) { extremes = p; extremes_tile_stride = stride; }
+    void with_tether(const float* p, int64_t stride) { tether = p; tether_tile_stride = stride; }
+    // (a net of no layers is none of the launch's forms: it is refused as out of range, never taken for the _teth entry's record)
+    void with_layers(int64_t layers) { tether_layers = layers == 0 ? -1 : layers; }
+    void with_peaks(float* p, int64_t stride) { tether_peaks = p; tether_peaks_tile_stride = stride; }
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3383,9 +3326,11 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
     return HYDRO_OK;
 }
 
-// The refusals in the order the entries have always reported them, then ONE choice of kernel family: the link-tension kernel
-// takes everything, the net kernel everything but the record of the link tensions, the tether kernel everything but the net's layers, the extremes kernel everything but the tethers, the mooring kernel everything but the extremes, the bed kernel everything but the lines, the sea kernel everything but the bed, the pose-hold kernel everything but sea and bed, the applied kernel recorder and applied wrench, the recording
-// kernel the recorder - and a launch is handed the options it goes without as absent ones.
+// The refusals in the order the entries have always reported them, then ONE choice of kernel family.  The families form a
+// ladder, each taking its predecessor's argument groups and one more:
+//   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak
+// and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
+// the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
 {
     if (!h) return HYDRO_E_ARG;
@@ -3470,7 +3415,10 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
     const uint32_t applied_stride = m.applied ? (uint32_t)m.applied_tile_stride : 0u, control_stride = m.control ? (uint32_t)m.control_tile_stride : 0u;
     const int frame = m.applied ? m.applied_frame : HYDRO_FRAME_WORLD;
     dispatch_flags([&](auto HALF, auto NT, auto IMPL, auto KE, auto WARP) {
-        // the arguments every kernel takes, then the recorder's, then the applied wrench's, then the family's own
+        // One link per argument group, in the kernels' order (HYDRO_*_PARAMS): a link hands its group on to the link below it and
+        // whatever the links above it gave behind that, so a group's expressions stand here once.  Where an argument depends on
+        // its option being there (`sea ? table : null`, `m.mooring ? stride : 0`), the family that is chosen BECAUSE the option is
+        // there finds the condition true and gets the option's own values: the conditional form is exact for every family.
         const auto plain = [&](auto kernel, auto... tail) {
             hipLaunchKernelGGL(kernel, grid, blk, 0, s, m.state, m.prev, h->params_tiled, m.state_out, m.prev_out,
                                (uint32_t)m.state_tile_stride, (uint32_t)m.prev_tile_stride, (uint32_t)m.out_tile_stride, (uint32_t)m.prev_out_tile_stride,
@@ -3479,35 +3427,26 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         };
         const auto recording = [&](auto kernel, auto... tail) { plain(kernel, r.mask, r.first, r.log, r.stride, r.fields, r.every, r.phase, r.row0, tail...); };
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
-        if (m.tether_peaks) pushed(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
-                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
-                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
-                        m.tether, (uint32_t)m.tether_tile_stride, (uint32_t)m.tether_layers, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
-        else if (m.tether && m.tether_layers) pushed(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
-                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
-                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
-                        m.tether, (uint32_t)m.tether_tile_stride, (uint32_t)m.tether_layers);
-        else if (m.tether) pushed(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
-                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
-                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
-                        m.tether, (uint32_t)m.tether_tile_stride);
-        else if (m.extremes) pushed(step_fused_multi_ext_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
-                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
-                        m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.extremes, (uint32_t)m.extremes_tile_stride);
-        else if (m.mooring) pushed(step_fused_multi_moor_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
-                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, bed ? 1 : 0,
-                        m.mooring, (uint32_t)m.mooring_tile_stride);
-        else if (bed) pushed(step_fused_multi_bed_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt,
-                        h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate);
-        else if (sea) pushed(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride,
-                        (const void*)h->sea_table, (uint32_t)h->sea_waves, m.step0, m.dt);
-        else if (m.control) pushed(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.control, control_stride);
+        const auto held = [&](auto kernel, auto... tail) { pushed(kernel, m.control, control_stride, tail...); };
+        const auto in_sea = [&](auto kernel, auto... tail) {
+            held(kernel, sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
+        };
+        const auto on_bed = [&](auto kernel, auto... tail) {
+            in_sea(kernel, h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, tail...);
+        };
+        const auto on_optional_bed = [&](auto kernel, auto... tail) { on_bed(kernel, bed ? 1 : 0, tail...); };
+        const auto moored = [&](auto kernel, auto... tail) { on_optional_bed(kernel, m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, tail...); };
+        const auto tracked = [&](auto kernel, auto... tail) { moored(kernel, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u, tail...); };
+        const auto tethered = [&](auto kernel, auto... tail) { tracked(kernel, m.tether, (uint32_t)m.tether_tile_stride, tail...); };
+        const auto netted = [&](auto kernel, auto... tail) { tethered(kernel, (uint32_t)m.tether_layers, tail...); };
+        if (m.tether_peaks) netted(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
+        else if (m.tether && m.tether_layers) netted(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (m.tether) tethered(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (m.extremes) tracked(step_fused_multi_ext_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (m.mooring) moored(step_fused_multi_moor_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (bed) on_bed(step_fused_multi_bed_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (sea) in_sea(step_fused_multi_sea_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (m.control) held(step_fused_multi_ctl_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.applied) pushed(step_fused_multi_app_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (rec) recording(step_fused_multi_rec_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else plain(step_fused_multi_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
@@ -3581,8 +3520,7 @@ int hydro_step_fused_tiled_multi_rec(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
     m.log_required = true;
     return step_fused_tiled_multi_launch(h, m);
 }
@@ -3598,9 +3536,8 @@ int hydro_step_fused_tiled_multi_app(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3616,10 +3553,9 @@ int hydro_step_fused_tiled_multi_ctl(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3695,11 +3631,10 @@ int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3752,12 +3687,11 @@ int hydro_step_fused_tiled_multi_bed(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
-    m.bed_entry = true;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3795,13 +3729,12 @@ int hydro_step_fused_tiled_multi_moor(hydro_t* h, int64_t n, const float* state,
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
-    m.bed_entry = true;
-    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3838,14 +3771,13 @@ int hydro_step_fused_tiled_multi_ext(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
-    m.bed_entry = true;
-    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
-    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_extremes(extremes, extremes_tile_stride);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3892,15 +3824,14 @@ int hydro_step_fused_tiled_multi_teth(hydro_t* h, int64_t n, const float* state,
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
-    m.bed_entry = true;
-    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
-    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
-    m.tether = tether; m.tether_tile_stride = tether_tile_stride;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3919,17 +3850,15 @@ int hydro_step_fused_tiled_multi_net(hydro_t* h, int64_t n, const float* state, 
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
-    m.bed_entry = true;
-    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
-    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
-    m.tether = tether; m.tether_tile_stride = tether_tile_stride;
-    // (a net of no layers is none of the launch's forms: it is refused as out of range, never taken for the _teth entry's record)
-    m.tether_layers = tether_layers == 0 ? -1 : tether_layers;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
     return step_fused_tiled_multi_launch(h, m);
 }
 
@@ -3949,17 +3878,16 @@ int hydro_step_fused_tiled_multi_peak(hydro_t* h, int64_t n, const float* state,
 {
     MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
                    implicit_drag, rotational, ke_out_dev, stream};
-    m.log = log; m.log_stride = log_stride; m.rows_capacity = rows_capacity; m.fields = fields; m.every = every; m.phase = phase;
-    m.row0 = row0; m.rows_written_host = rows_written_host;
-    m.applied = applied; m.applied_tile_stride = applied_tile_stride; m.applied_frame = applied_frame;
-    m.control = control; m.control_tile_stride = control_tile_stride;
-    m.sea_entry = true; m.step0 = step0;
-    m.bed_entry = true;
-    m.mooring = mooring; m.mooring_tile_stride = mooring_tile_stride;
-    m.extremes = extremes; m.extremes_tile_stride = extremes_tile_stride;
-    m.tether = tether; m.tether_tile_stride = tether_tile_stride;
-    m.tether_layers = tether_layers == 0 ? -1 : tether_layers;           // (as in the _net entry: no layers is out of range)
-    m.tether_peaks = tether_peaks; m.tether_peaks_tile_stride = tether_peaks_tile_stride;
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -161,15 +161,18 @@ ENTRIES = {
     "moor": ("step_fused_tiled_multi_moor", ("step0", "mooring", "control", "applied")),
     "ext": ("step_fused_tiled_multi_ext", ("step0", "extremes", "mooring", "control", "applied")),
     "teth": ("step_fused_tiled_multi_teth", ("step0", "tether", "extremes", "mooring", "control", "applied")),
+    "net": ("step_fused_tiled_multi_net", ("step0", "tether", "layers", "extremes", "mooring", "control", "applied")),
+    "peak": ("step_fused_tiled_multi_peak", ("step0", "tether", "layers", "peaks", "extremes", "mooring", "control", "applied")),
 }
 
 
 def step(eng, entry, cur, old, n, steps, *, step0=0, applied=None, frame="world", control=None, mooring=None, extremes=None, tether=None,
-         implicit=False, ke=None, **kw):
+         layers=None, peaks=None, implicit=False, ke=None, **kw):
     """One launch of `entry` through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one.  An option the entry does not take must be None (step0: 0)."""
+    velocity fields of the other one.  An option the entry does not take must be None (step0: 0); `layers` is the net's, for
+    the entries that take one."""
     method, takes = ENTRIES[entry]
-    given = dict(step0=step0, applied=applied, control=control, mooring=mooring, extremes=extremes, tether=tether)
+    given = dict(step0=step0, applied=applied, control=control, mooring=mooring, extremes=extremes, tether=tether, layers=layers, peaks=peaks)
     for name, value in given.items():
         assert name in takes or value is None or (name == "step0" and value == 0), (entry, name)
     getattr(eng, method)(cur, old, n, DT, steps, *(given[name] for name in takes), frame, implicit_drag=implicit, ke_out=ke, **kw)
