@@ -841,7 +841,8 @@ int hydro_step_fused_tiled_multi_ext(hydro_t *h, int64_t n, const float *state, 
  * body < n.  NO PARTNER INDEX EVER FORMS A MEMORY ADDRESS: the kernel uses (int)partner & 63 as a lane of its own wavefront.
  * A malformed record - a partner that is not mutual, a partner among the lanes >= n of the last tile (it answers +0),
  * constants that differ between the two, negative or non-finite values - is computed as given and cannot fault; the
- * contents are not validated on the device (the Python host validates what it builds).
+ * contents are not validated on the device (the Python host validates what it builds).  A partner that is not finite or
+ * lies outside the range of int names an unspecified lane of the tile and still never an address.
  * RULE OF THUMB for a step dt: with the reduced mass mu = m_a m_b / (m_a + m_b), k dt^2 / mu <= 0.04 and c dt / mu <= 0.04
  * (the mooring's rule, DESIGN.md section 19, for the pair's relative motion).
  *

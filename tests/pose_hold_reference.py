@@ -32,10 +32,13 @@ def error_quaternion(state, control):
 
 
 def _clamp(x, top):
-    norm = np.linalg.norm(x, axis=1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        k = np.where(norm > top, top / norm, 1.0)
-    return x * k[:, None], norm > top
+    """The header's comparison, literally: if (n2 > top * top) x = x * (top / sqrt(n2)).  A NaN `top` compares false and does not
+    clamp; top = 0 gives a zero; a negative `top` acts where n2 > top^2 and turns the vector round (the record is the caller's)."""
+    n2 = (x * x).sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        acts = n2 > top * top
+        k = np.where(acts, top / np.sqrt(n2), 1.0)
+        return np.where(acts[:, None], x * k[:, None], x), acts
 
 
 def unclamped(state, control):

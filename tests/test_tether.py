@@ -74,6 +74,7 @@ def test_header_and_binding_carry_the_entries():
     for phrase in ("b(3)     this body's fairlead", "partner  the other body, as a LANE INDEX WITHIN THE SAME TILE", "tether_tile_stride >= 448",
                    "READ IN EVERY STEP", "at most one tether per body", "both bodies of a pair in one tile", "an\n * involution",
                    "carry the same L0, k, c", "NO PARTNER INDEX EVER FORMS A MEMORY ADDRESS", "(int)partner & 63", "computed as given and cannot fault",
+                   "names an unspecified lane of the tile and still never an address",
                    "never the one\n * relative to the water", "P_i    = p_i + r_i", "e_i    = P'_i - P_i", "T      = max(0, fma(k, x, c * rate))",
                    "+0 is NOT added", "EQUAL AND OPPOSITE, EXACTLY (a property that is tested)", "negation is exact in fp32",
                    "chains, and more than one tether per body", "pairs across tiles", "the line's mass, sag and drag",

@@ -82,9 +82,10 @@ def wrench(rec, state, taut=None):
     """(n, 6) W in fp64."""
     r, e, l, _, _, _ = geometry(rec, state)
     T = tension(rec, state, taut)
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         F = np.where((T > 0)[:, None], (T / l)[:, None] * e, 0.0)
-    return np.concatenate([F, np.cross(r, F)], axis=1)
+        M = np.where((T > 0)[:, None], np.cross(r, F), 0.0)           # a lane that adds nothing: +0, whatever its arm (NaN x 0 is NaN)
+    return np.concatenate([F, M], axis=1)
 
 
 def _magnitudes(rec, state):
