@@ -63,7 +63,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_net, HYDRO_TETH_LAYERS_MAX - up to four
  *        layers of tether records, so that bodies form chains and cables
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_peak - the running maximum of every
- *        tether's tension, per body and layer, updated inside every step */
+ *        tether's tension, per body and layer, updated inside every step
+ *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_spread, HYDRO_MOOR_LAYERS_MAX - up to four
+ *        layers of mooring records, so that a body rides on a spread of anchored lines */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -82,6 +84,7 @@ extern "C" {
 #define HYDRO_EXT_FIELDS     8   /* the extremes record of hydro_step_fused_tiled_multi_ext */
 #define HYDRO_TETH_FIELDS    7   /* the tether record of hydro_step_fused_tiled_multi_teth */
 #define HYDRO_TETH_LAYERS_MAX 4  /* tether records, one behind the other, in the net of hydro_step_fused_tiled_multi_net */
+#define HYDRO_MOOR_LAYERS_MAX 4  /* mooring records, one behind the other, in the spread of hydro_step_fused_tiled_multi_spread */
 #define HYDRO_COMP_FIELDS   24
 #define HYDRO_TILE          64   /* bodies per tile of the tiled-SoA layout = one wavefront */
 #define HYDRO_BATCH_MAX     32   /* scenes per hydro_step_wrench_tiled_batch launch */
@@ -732,7 +735,7 @@ int hydro_step_fused_tiled_multi_bed(hydro_t *h, int64_t n, const float *state, 
  * logs.  A body without a line, with a line that is not taut, or with a T that is not > 0 has its wrench left untouched:
  * +0 is NOT added, the sign of a zero survives.  Whole wavefronts without a line skip the evaluation; that changes no bit.
  * NOT MODELLED: the line's mass and catenary sag; drag on the line; the line lying on the bed; more than one line per
- * body; a line between two bodies.
+ * body by THIS entry (up to four are a spread: "Mooring spread", below); a line between two bodies ("Tether").
  *
  * hydro_mooring_wrench: writes the tiled 6-field W ([tiles][6][64] floats, tile stride out_tile_stride >= 384) of bodies
  * 0 .. n - 1 in `state` - exactly what a step that starts from `state` adds; +0 in all six fields for a body whose line adds
@@ -782,7 +785,10 @@ int hydro_step_fused_tiled_multi_moor(hydro_t *h, int64_t n, const float *state,
  *     x, y, z   s[0..2] after the step
  *     speed2    fma(v_z, v_z, fma(v_y, v_y, v_x * v_x)) of s[7..9] after the step, in fp32 (fma: rounded once)
  *     tension   the T the mooring formed IN that step, from the state the step started from ("Mooring", above); +0 where
- *               the line adds nothing: no line, a slack line, a T that is not > 0, or no mooring record at all
+ *               the line adds nothing: no line, a slack line, a T that is not > 0, or no mooring record at all.  With a
+ *               spread of L lines ("Mooring spread", below) it is the LARGEST tension of any of the body's lines in that
+ *               step: acc = +0, then acc = (t_l > acc) ? t_l : acc over the layers in ascending order, t_l the layer's T
+ *               where its line pulls and +0 where it adds nothing - with L = 1 the value above, bit for bit
  * THE UPDATE is an explicit compare-and-select, never fminf / fmaxf:
  *     m = (x < m) ? x : m            M = (x > M) ? x : M
  * so a NaN sample never enters, a NaN accumulator stays NaN, and an equal value (+0 against -0 included) leaves the
@@ -1000,6 +1006,52 @@ int hydro_step_fused_tiled_multi_peak(hydro_t *h, int64_t n, const float *state,
                                       const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
                                       float *tether_peaks, int64_t tether_peaks_tile_stride,
                                       int64_t step0, void *stream);
+
+/* Mooring spread: a body on up to four anchored lines - the three- or four-line spread that keeps a floating body on station,
+ * where one line only gives it a watch circle.  No new physics: every line is a line of "Mooring" (above), and the section
+ * states only how several of them are laid out and combined.  Only hydro_step_fused_tiled_multi_spread knows spreads.
+ *
+ * THE RECORD: a spread is L LAYERS of the mooring record, 1 <= L <= HYDRO_MOOR_LAYERS_MAX = 4, tiled as ONE record of 9 L
+ * fields: [tiles][9 L][64] floats, field f of layer l in row 9 l + f, tile stride mooring_tile_stride >= 576 L, 16-byte
+ * aligned, whole tiles.  Each layer is a complete mooring record: `mooring + 576 l` with the spread's stride is a valid
+ * argument of hydro_mooring_wrench, which is how a host sees one layer's wrenches.  A layer of zeros is a layer without
+ * lines.  The caller's device buffer, READ IN EVERY STEP of every launch (a launch must not rewrite it under a running one).
+ *
+ * IN A STEP every line is evaluated exactly as the single line is - the line's wrench above, from the TRUE state the step
+ * starts from - and the wrenches are added to the step's wrench in ASCENDING LAYER ORDER, behind the seabed's and in front
+ * of the tethers', one fp32 add per component each: f = fl(fl(f + W_0) + W_1) ..., over the layers whose line pulls.  A
+ * layer whose line adds nothing (no line, slack, a T that is not > 0) leaves the wrench untouched: +0 is NOT added.
+ * tension_max of the extremes record takes the largest tension of the body's lines in the step ("Extremes", above).
+ * RULE OF THUMB, per body: (sum of k) dt^2 / m <= 0.04 and (sum of c) dt / m <= 0.04 over the body's lines - they may all
+ * be taut at once, and the anchors are fixed (no factor 2 as in a net, where both ends move).
+ * NOT MODELLED: what "Mooring" does not model; more than four lines per body.  NOT PROVIDED: the peak tension of each line
+ * on its own (the anchored counterpart of "Link tensions") - the extremes record keeps the largest of them only.
+ *
+ * hydro_step_fused_tiled_multi_spread: the signature and the rules of hydro_step_fused_tiled_multi_peak, with
+ * `mooring_layers` between mooring_tile_stride and `extremes`.
+ *   mooring == NULL     : the launch and its bits are those of hydro_step_fused_tiled_multi_peak; mooring_layers is ignored.
+ *   mooring_layers == 1 : the bits are those of hydro_step_fused_tiled_multi_peak with the same record.
+ *   trailing layers of zeros change no bit.
+ * Every other option is still optional and adds what it adds in hydro_step_fused_tiled_multi_peak.  The refusals are those
+ * of hydro_step_fused_tiled_multi_peak, in its order (the record is first held to a single line's rules: a stride below
+ * 576), then: mooring_layers outside 1 .. HYDRO_MOOR_LAYERS_MAX; a stride below 576 mooring_layers or a misaligned record; a
+ * spread any layer of which overlaps state_out, prev_out, the log, the extremes record or tether_peaks: HYDRO_E_ARG, and
+ * nothing is launched or written.  Asynchronous, no allocation, no synchronisation, safe to capture.  Cost and registers:
+ * DESIGN.md section 28.  New functionality; the reference has no mooring of its own. */
+int hydro_step_fused_tiled_multi_spread(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                        const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                        float *state_out, int64_t out_tile_stride,
+                                        float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                        int rotational, double *ke_out_dev,
+                                        float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                        int64_t row0, int64_t *rows_written_host,
+                                        const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                        const float *control, int64_t control_tile_stride,
+                                        const float *mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                        float *extremes, int64_t extremes_tile_stride,
+                                        const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                        float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                        int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

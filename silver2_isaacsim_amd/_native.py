@@ -20,6 +20,7 @@ MOOR_FIELDS = 9                         # the mooring record of hydro_step_fused
 EXT_FIELDS = 8                          # the extremes record of hydro_step_fused_tiled_multi_ext: x, y, z min max | speed2_max | tension_max
 TETH_FIELDS = 7                         # the tether record of hydro_step_fused_tiled_multi_teth: b(3) | L0 | k | c | partner lane
 TETH_LAYERS_MAX = 4                     # layers of tether records in the net of hydro_step_fused_tiled_multi_net
+MOOR_LAYERS_MAX = 4                     # layers of mooring records in the spread of hydro_step_fused_tiled_multi_spread
 TILE = 64
 BATCH_MAX = 32
 WATCH_MAX = 65536
@@ -66,6 +67,7 @@ _REC = [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int64, POINTER(c_int6
 _APP = [c_void_p, c_int64, c_int]                                                         # applied, applied_tile_stride, applied_frame
 _CTL = _MOOR = _EXT = _TETH = _PEAK = [c_void_p, c_int64]                                 # a per-body record and its tile stride
 _LAYERS = _STEP0 = [c_int64]                                                              # tether_layers; step0
+_SPREAD = _MOOR + [c_int64]                                                               # the mooring record as a spread: + mooring_layers
 _STREAM = [c_void_p]
 
 
@@ -123,6 +125,7 @@ SIGNATURES = {
     "hydro_step_fused_tiled_multi_teth": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _STEP0),
     "hydro_step_fused_tiled_multi_net": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _LAYERS, _STEP0),
     "hydro_step_fused_tiled_multi_peak": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
+    "hydro_step_fused_tiled_multi_spread": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -1277,6 +1277,8 @@ struct NoTether {
 #define HYDRO_NET_ARGS HYDRO_TETH_ARGS, layers
 #define HYDRO_PEAK_PARAMS float* peaks, uint32_t peaks_stride
 #define HYDRO_PEAK_ARGS peaks, peaks_stride
+#define HYDRO_SPREAD_PARAMS HYDRO_MOOR_PARAMS, uint32_t mooring_layers           // (the family behind _peak: the mooring record is a spread)
+#define HYDRO_SPREAD_ARGS HYDRO_MOOR_ARGS, mooring_layers
 // The three tether families share everything in front of the tether: the groups up to the extremes, every one optional.
 #define HYDRO_UP_TO_EXT_PARAMS HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS, HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS,      \
                                HYDRO_MOOR_PARAMS, HYDRO_EXT_PARAMS
@@ -2338,6 +2340,91 @@ __global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_
     fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_UP_TO_EXT_OPTIONAL, PeakTetherNet{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr});
 }
 
+// --------------------------------------------------------------------------
+// MOORING SPREADS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_spread): `layers` mooring records, one
+// behind the other ([tiles][9 * layers][64], layer l in rows 9 l .. 9 l + 8), each a complete record of MooringLine's kind -
+// so a body has up to `layers` anchored lines, the three or four of a spread mooring.  include/hydro.h states the contract
+// ("Mooring spread").  Every line is mooring_wrench's, from the TRUE state the step starts from, and the wrenches are added
+// to f6 in ascending layer order behind the bed and in front of the tethers, one fp32 add per component, where the line
+// pulls - one layer gives OptionalMooringLine's bits.  TetherNet's design (above), applied to the anchored line:
+//   the loop    : a REAL loop over the layers, never unrolled: the peak pressure is that of one evaluation plus the fold.
+//                 The trip count is a kernel argument, wave-uniform
+//   the record  : NOT parked.  Four layers are 36 KB of LDS per block and the _peak kernels' LDS fills the CU at three blocks
+//                 as it is, so every trip reads its nine values from the caller's buffer (launch-invariant, L2 hits after
+//                 the first step): the tile's wave-uniform pointer moves on by 576 floats per trip and is made opaque
+//                 again, so no layer's loads are hoisted or shared; the quaternion likewise, so that rotation_of stays
+//                 behind the layer's ballot.  This family's LDS is the _peak kernels' less the line's nine slots
+//   the skip    : per layer, mooring_wrench's own ballot: a tile with no line in a layer pays two loads, two compares and
+//                 the branch for that layer
+//   the tension : what the extremes record takes is the LARGEST tension of any of the body's lines in the step, folded from
+//                 +0 over the layers in ascending order by extreme_max(acc, pulls ? T : +0) - TrackedMooringLine's value for
+//                 one layer, bit for bit
+// A null record evaluates nothing and reports +0.
+// --------------------------------------------------------------------------
+struct MooringSpread {
+    using GlobalFloats = const float __attribute__((address_space(1)))*;
+    const float* rec; uint32_t stride, layers;
+    GlobalFloats tile_rec; uint32_t lane4;                               // layer 0 of the tile's record: a wave-uniform pointer, in SGPRs
+    mutable float last;
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        tile_rec = (GlobalFloats)(rec + (size_t)tile * stride);
+        lane4 = lane4_;
+    }
+    __device__ __forceinline__ void end(float (&d)[3]) const             // (MooringLine::end's, for the same reason)
+    {
+        asm volatile("" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]));
+    }
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        float acc = 0.0f;
+        if (rec) {                                                       // (a kernel argument: wave-uniform)
+            GlobalFloats r = tile_rec;
+#pragma clang loop unroll(disable)
+            for (uint32_t l = 0; l < layers; ++l, r += HYDRO_MOOR_FIELDS * HYDRO_TILE) {
+                asm volatile("" : "+s"(r));
+                float t[HYDRO_STATE_FIELDS];
+#pragma unroll
+                for (int f = 0; f < HYDRO_STATE_FIELDS; ++f) t[f] = s[f];
+                asm volatile("" : "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]));
+                float W[HYDRO_WRENCH_FIELDS], T = 0.0f;
+                const bool pulls = mooring_wrench(at<float>((const float*)r, lane4), t, W, T);
+                if (pulls) {
+#pragma unroll
+                    for (int f = 0; f < HYDRO_WRENCH_FIELDS; ++f) f6[f] += W[f];
+                }
+                acc = extreme_max(acc, pulls ? T : 0.0f);
+            }
+        }
+        last = acc;
+    }
+    __device__ __forceinline__ float tension() const { return last; }
+};
+__device__ __forceinline__ MooringSpread mooring_spread(HYDRO_SPREAD_PARAMS) { return MooringSpread{HYDRO_SPREAD_ARGS, nullptr, 0u, 0.0f}; }
+
+// The net and the link tensions of the spread kernel: each optional.  No net is a net of no layers (the launch says so); no
+// record of link tensions (`peaks` - a kernel argument: wave-uniform) is TetherNet's loop, which touches no memory but the net.
+struct OptionalPeakTetherNet : PeakTetherNet {
+    __device__ __forceinline__ void add(const float (&s)[HYDRO_STATE_FIELDS], float (&f6)[HYDRO_WRENCH_FIELDS]) const
+    {
+        if (peaks) PeakTetherNet::add(s, f6);
+        else TetherNet::add(s, f6);
+    }
+};
+
+// The _peak kernel's arguments with the number of mooring layers behind the mooring record's stride.  Everything but
+// `mooring` may be null.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_spread_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                    HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                    HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   optional_sea_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), mooring_spread(HYDRO_SPREAD_ARGS),
+                                                   optional_extremes_track(HYDRO_EXT_ARGS),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
 // hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
 // nothing) and, if asked for, its tension T (+0 likewise).  The lanes >= n of the last tile leave first: the live ones
 // exchange among themselves, in uniform control flow.
@@ -3244,7 +3331,7 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// A launch of any of the eleven hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// A launch of any of the twelve hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
 // was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
 // copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
 // (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
@@ -3266,6 +3353,7 @@ struct MultiStep {
     const float* tether = nullptr; int64_t tether_tile_stride = 0;        // the _teth entry: the _ext entry, and a line between two bodies of a tile if a record is given
     int64_t tether_layers = 0;                           // the _net entry: the _teth entry with `tether` a net of that many layers (0: a single record, the _teth entry's)
     float* tether_peaks = nullptr; int64_t tether_peaks_tile_stride = 0;  // the _peak entry: the _net entry, and the running maximum of every line's tension if a record is given
+    int64_t mooring_layers = 0;                          // the _spread entry: the _peak entry with `mooring` a spread of that many layers (0: a single record, the _moor entry's)
 
     void with_recorder(float* log_, int64_t log_stride_, int64_t rows_capacity_, int fields_, int every_, int phase_, int64_t row0_, int64_t* rows_written_host_)
     {
@@ -3282,6 +3370,8 @@ struct MultiStep {
     // (a net of no layers is none of the launch's forms: it is refused as out of range, never taken for the _teth entry's record)
     void with_layers(int64_t layers) { tether_layers = layers == 0 ? -1 : layers; }
     void with_peaks(float* p, int64_t stride) { tether_peaks = p; tether_peaks_tile_stride = stride; }
+    // (a spread of no layers is refused as out of range, never taken for the _moor entry's record)
+    void with_mooring_layers(int64_t layers) { mooring_layers = layers == 0 ? -1 : layers; }
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3328,7 +3418,7 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
 
 // The refusals in the order the entries have always reported them, then ONE choice of kernel family.  The families form a
 // ladder, each taking its predecessor's argument groups and one more:
-//   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak
+//   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak < _spread
 // and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
 // the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
@@ -3401,6 +3491,21 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
             || meets(m.extremes, m.extremes_tile_stride, HYDRO_EXT_FIELDS) || (m.log && ranges_overlap(m.tether_peaks, floats, m.log, log_floats)))
             return fail(h, HYDRO_E_ARG, "tether_peaks must not overlap an output, an input record, the net, the extremes or the log");
     }
+    if (m.mooring && m.mooring_layers != 0) {
+        // the _spread entry: the record has passed as a single line's (its layer 0 is one) - now as the spread it is
+        if (m.mooring_layers < 1 || m.mooring_layers > HYDRO_MOOR_LAYERS_MAX) return fail(h, HYDRO_E_ARG, "mooring_layers must be in 1 .. HYDRO_MOOR_LAYERS_MAX");
+        const int fields = HYDRO_MOOR_FIELDS * (int)m.mooring_layers;
+        if ((rc = check_tiled(h, m.n, m.mooring, m.mooring_tile_stride, fields, "null mooring"))) return rc;
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE, floats = tiled_extent(tiles, m.mooring_tile_stride, fields);
+        const auto written = [&](const float* p, int64_t stride, int f) {
+            return p && ranges_overlap(m.mooring, floats, p, tiled_extent(tiles, stride, f));
+        };
+        if (written(m.state_out, m.out_tile_stride, HYDRO_STATE_FIELDS) || written(m.prev_out, m.prev_out_tile_stride, HYDRO_PREV_FIELDS)
+            || written(m.extremes, m.extremes_tile_stride, HYDRO_EXT_FIELDS)
+            || (m.tether_peaks && written(m.tether_peaks, m.tether_peaks_tile_stride, (int)m.tether_layers))
+            || (m.log && ranges_overlap(m.mooring, floats, m.log, log_floats)))
+            return fail(h, HYDRO_E_ARG, "the mooring spread must not overlap an output (state_out, prev_out, log, extremes, tether_peaks)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -3439,7 +3544,13 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto tracked = [&](auto kernel, auto... tail) { moored(kernel, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u, tail...); };
         const auto tethered = [&](auto kernel, auto... tail) { tracked(kernel, m.tether, (uint32_t)m.tether_tile_stride, tail...); };
         const auto netted = [&](auto kernel, auto... tail) { tethered(kernel, (uint32_t)m.tether_layers, tail...); };
-        if (m.tether_peaks) netted(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
+        // (the spread's layer count stands behind the mooring group, in front of the groups that follow it: its link takes them as its tail)
+        const auto spread_moored = [&](auto kernel, auto... tail) { on_optional_bed(kernel, m.mooring, (uint32_t)m.mooring_tile_stride, (uint32_t)m.mooring_layers, tail...); };
+        if (m.mooring && m.mooring_layers)
+            spread_moored(step_fused_multi_spread_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
+                          m.tether, m.tether ? (uint32_t)m.tether_tile_stride : 0u, m.tether ? (uint32_t)(m.tether_layers ? m.tether_layers : 1) : 0u,
+                          m.tether_peaks, m.tether_peaks ? (uint32_t)m.tether_peaks_tile_stride : 0u);
+        else if (m.tether_peaks) netted(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
         else if (m.tether && m.tether_layers) netted(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.tether) tethered(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.extremes) tracked(step_fused_multi_ext_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
@@ -3884,6 +3995,36 @@ int hydro_step_fused_tiled_multi_peak(hydro_t* h, int64_t n, const float* state,
     m.with_sea(step0);
     m.with_seabed();
     m.with_mooring(mooring, mooring_tile_stride);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_spread(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                        const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                        float* state_out, int64_t out_tile_stride,
+                                        float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                        int rotational, double* ke_out_dev,
+                                        float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                        int64_t row0, int64_t* rows_written_host,
+                                        const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                        const float* control, int64_t control_tile_stride,
+                                        const float* mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                        float* extremes, int64_t extremes_tile_stride,
+                                        const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                        float* tether_peaks, int64_t tether_peaks_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_mooring_layers(mooring_layers);
     m.with_extremes(extremes, extremes_tile_stride);
     m.with_tether(tether, tether_tile_stride);
     m.with_layers(tether_layers);

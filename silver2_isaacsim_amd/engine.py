@@ -759,6 +759,57 @@ class HydroEngine:
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream, extra)
 
+    # ------------------------------------------------------------------ mooring spreads
+    def _spread(self, spread, layers, n):
+        """(address, tile stride) of a spread of `layers` mooring records, a tiled (tiles, 9 * layers, 64) buffer."""
+        layers = int(layers)
+        if not 1 <= layers <= nat.MOOR_LAYERS_MAX:
+            raise ValueError(f"mooring_layers must be in 1 .. {nat.MOOR_LAYERS_MAX}")
+        return self._tiled(spread, nat.MOOR_FIELDS * layers, n)
+
+    def mooring_spread_wrench(self, state: torch.Tensor, spread: torch.Tensor, n: int, layers: int, stream=None) -> list:
+        """The wrench of each body's line in EACH LAYER of the spread on the tiled `state`: `spread` is a tiled
+        (tiles, 9 * layers, 64) buffer, layer l in rows 9 l .. 9 l + 8 (include/hydro.h, "Mooring spread").  One call of
+        hydro_mooring_wrench per layer, on the layer's sub-record (the spread's address + 576 l floats, the spread's tile
+        stride).  Returns a list of `layers` tiled (tiles, 6, 64) buffers - what a step of `step_fused_tiled_multi_spread`
+        that starts from `state` adds, layer by layer; zeros where a line adds nothing."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        m_ptr, m_stride = self._spread(spread, layers, n)
+        wrenches = []
+        for l in range(int(layers)):
+            out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
+            o_ptr, o_stride = self._tiled(out, nat.WRENCH_FIELDS, n)
+            self._check(self._lib.hydro_mooring_wrench(self._h, n, s_ptr, s_stride, m_ptr + 4 * nat.MOOR_FIELDS * nat.TILE * l, m_stride,
+                                                       o_ptr, o_stride, self._stream(stream)))
+            wrenches.append(out)
+        return wrenches
+
+    def step_fused_tiled_multi_spread(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                      mooring: torch.Tensor | None, mooring_layers: int = 1,
+                                      tether: torch.Tensor | None = None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                      extremes: torch.Tensor | None = None,
+                                      control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                      log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                      state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                      ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_peak with up to four anchored lines per body (hydro_step_fused_tiled_multi_spread): `mooring`
+        is a spread, the tiled (tiles, 9 * mooring_layers, 64) buffer of `mooring_spread_wrench`, read in every step.  Every
+        layer is a mooring record of its own; the lines are all evaluated from the true state the step starts from and their
+        wrenches added in ascending layer order, behind the bed and in front of the tethers; `tension_max` of the extremes
+        takes the largest tension of a body's lines.  mooring_layers=1 gives the bits of step_fused_tiled_multi_peak with the
+        same record, mooring=None IS that call (and `mooring_layers` is not looked at).  Returns the number of rows written
+        (0 without a log)."""
+        def extra():
+            tail = self._applied_control(applied, frame, control, n)
+            m_ptr, m_stride = self._spread(mooring, mooring_layers, n) if mooring is not None else (None, 0)
+            e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
+            t_ptr, t_stride = self._net(tether, layers, n) if tether is not None else (None, 0)
+            p_ptr, p_stride = self._tiled(peaks, int(layers), n) if peaks is not None else (None, 0)
+            return (*tail, m_ptr, m_stride, int(mooring_layers), e_ptr, e_stride, t_ptr, t_stride, int(layers), p_ptr, p_stride, int(step0))
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_spread,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
         if state_out is None:

@@ -27,7 +27,7 @@ from . import distributed as hd
 from . import scenes
 from .engine import HydroEngine
 from .extremes import Extremes
-from .mooring import Mooring
+from .mooring import Mooring, MooringSpread
 from .tether import LinkTensions, Tether, TetherNet
 
 
@@ -337,6 +337,9 @@ class ClosedLoopSim:
     seabed = None               # set_seabed(): the seabed.Seabed under the bodies (a class default: a sim has none until one is set)
     mooring = None              # set_mooring(): the tiled (tiles, 9, 64) record of the bodies' mooring lines while lines are set
     _mooring_buf = None         # the buffer itself (made once)
+    mooring_spread = None       # set_mooring_spread(): the tiled (tiles, 9 * layers, 64) spread of the bodies' mooring lines while a spread is set
+    mooring_layers = 0          # the layers of that spread (0 without one)
+    _mooring_spread_bufs = None # the buffers themselves, by number of layers (each made once)
     extremes = None             # track_extremes(): the extremes.Extremes view over the bodies' running extremes while they are tracked
     _extremes_view = None       # the view and its buffer (made once)
     tether = None               # set_tether(): the tiled (tiles, 7, 64) record of the bodies' tethers while tethers are set
@@ -592,6 +595,9 @@ class ClosedLoopSim:
         sees the contents of the moment."""
         if not self.fused:
             raise ValueError("mooring lines live in the fused step kernels (fused=True)")
+        if self.mooring_spread is not None:
+            raise ValueError("a mooring spread is set, and a body is moored by the spread or by set_mooring's line, not both: "
+                             "clear_mooring_spread() first")
         idx = np.arange(self.n) if bodies is None else np.asarray(bodies, dtype=np.int64).reshape(-1)
         if idx.size and (idx.min() < 0 or idx.max() >= self.n):
             raise ValueError(f"bodies must be in 0 .. {self.n - 1}")
@@ -615,6 +621,54 @@ class ClosedLoopSim:
         """Cast off: every call the sim makes is again the one it made before set_mooring."""
         if self.mooring is not None:
             self.mooring = None
+            self._graph = None
+
+    def set_mooring_spread(self, anchors, fairleads=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0, bodies=None) -> torch.Tensor:
+        """Moor the bodies on a spread: from now on every physics step of run_eager, run (graph replays included) and
+        run_resident lets up to four tension-only lines per body pull its fairleads towards their anchors
+        (hydro_step_fused_tiled_multi_spread; the model: include/hydro.h, "Mooring spread"), each evaluated INSIDE the stepping
+        kernel as set_mooring's one line is; the wrenches add up, and `tension_max` of the extremes is the largest tension of
+        any of a body's lines.  It acts together with everything a line acts with, tethers and link tensions included.
+        anchors (L, 3) or (m, L, 3): world frame, L = 1 .. 4 lines; fairleads (3,), (L, 3) or (m, L, 3): body frame; length,
+        stiffness, damping: scalars, (L,) or (m, L) - m the bodies, or the listed `bodies`; bodies that are not listed have
+        no line.  `mooring.MooringSpread` validates them, and its rule of thumb ((sum k) dt^2 / m, (sum c) dt / m <= 0.04 over
+        a body's lines) is enforced for the bodies' masses: `MooringSpread.for_body(mass, sim.dt, L)` gives stable defaults,
+        `MooringSpread.radial` a symmetric spread.  A spread and set_mooring's line exclude each other.  The spread stays until
+        the next call or `clear_mooring_spread()`.
+        Returns `sim.mooring_spread`, the tiled (tiles, 9 L, 64) device buffer the kernels read (layer l in rows 9 l .. 9 l + 8),
+        and sets `sim.mooring_layers` = L.  Its address never changes for a given L."""
+        if not self.fused:
+            raise ValueError("mooring lines live in the fused step kernels (fused=True)")
+        if self.mooring is not None:
+            raise ValueError("mooring lines are set, and a body is moored by set_mooring's line or by a spread, not both: "
+                             "clear_mooring() first")
+        idx = np.arange(self.n) if bodies is None else np.asarray(bodies, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+            raise ValueError(f"bodies must be in 0 .. {self.n - 1}")
+        spread = MooringSpread(anchors, fairleads, length=length, stiffness=stiffness, damping=damping, n=idx.size)
+        spread.check_stable(np.asarray(self.scene.params, np.float64)[idx, 10], self.dt)
+        layers = spread.lines
+        rec = np.zeros((self.n, nat.MOOR_FIELDS * layers), np.float32)
+        with np.errstate(over="ignore"):
+            rec[idx] = spread.record
+        if not np.isfinite(rec).all():
+            raise ValueError("mooring spread: a value is out of fp32 range")
+        if self._mooring_spread_bufs is None:
+            self._mooring_spread_bufs = {}
+        buf = self._mooring_spread_bufs.get(layers)
+        if buf is None:
+            buf = self._mooring_spread_bufs[layers] = self.engine.alloc_tiled(nat.MOOR_FIELDS * layers, self.n)
+        with torch.cuda.stream(self.stream):
+            buf.copy_(torch.from_numpy(scenes.to_tiled(rec)))
+        if self.mooring_spread is not buf:
+            self._graph = None                                              # captured steps are of another entry / another record
+        self.mooring_spread, self.mooring_layers = buf, layers
+        return self.mooring_spread
+
+    def clear_mooring_spread(self) -> None:
+        """Cast off: every call the sim makes is again the one it made before set_mooring_spread."""
+        if self.mooring_spread is not None:
+            self.mooring_spread, self.mooring_layers = None, 0
             self._graph = None
 
     def track_extremes(self, from_state: bool = True) -> Extremes:
@@ -786,6 +840,7 @@ class ClosedLoopSim:
             self.link_tensions.links, self.link_tensions.layer = self._tether_links
 
     # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # the mooring spread if one is set (its entry takes every other option), else with
     # the link tensions if they are tracked (over the net, or over the tethers as a net of one layer), else with
     # the tether net if one is set, else with
     # the tethers if tethers are set, else with the extremes if they are tracked, else with the mooring lines if lines are set, else over the seabed if one is set, else through the sea if one is set, else with the pose hold, else with the applied wrench, else recording, else plain.  Every entry
@@ -801,7 +856,13 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.link_tensions is not None:
+        if self.mooring_spread is not None:
+            net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
+            rows = e.step_fused_tiled_multi_spread(*args, k, self.steps_done, self.mooring_spread, self.mooring_layers, net, layers,
+                                                   self.link_tensions.buffer if self.link_tensions is not None else None,
+                                                   self.extremes.buffer if self.extremes is not None else None,
+                                                   self.control, self.applied, self.applied_frame, **kw)
+        elif self.link_tensions is not None:
             net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
             rows = e.step_fused_tiled_multi_peak(*args, k, self.steps_done, net, layers, self.link_tensions.buffer,
                                                  self.extremes.buffer if self.extremes is not None else None,
