@@ -146,7 +146,39 @@ int hydro_set_semantics(hydro_t *h, int semantics);
  * where those arrays live.  _f16 stores the seven coefficients as IEEE half in HBM (config 5:
  * 130 B per body-step instead of 144); dims and mass stay fp32; the arithmetic is fp64 either way.
  * Synchronous on the engine's private stream; the caller orders it after steps of this engine still in flight on
- * OTHER streams (they read the records this call rewrites). */
+ * OTHER streams (they read the records this call rewrites).
+ *
+ * PARAMETER RECORD - what a negative, zero, NaN or infinite constant does (tests/parameter_cases.py is this paragraph as a
+ * table; tests/test_parameter_contract_gpu.py holds every entry to it).  The constants are COMPUTED AS GIVEN: no kernel
+ * validates them.  No address, loop bound or lane index in any kernel depends on one - the record is read by tile, lane and
+ * field - so no value can fault.  A body's constants are that body's problem alone: every other body keeps the bits it has
+ * with the clean record.  The two exceptions are the kinetic-energy pair, which sums every body as given (one NaN mass makes
+ * the sum NaN), and a tether's partner, whose wrench is formed from both states.  Negative constants, -0, tiny ones (1e-20 m,
+ * 1e-30 kg) and every finite coefficient give what the reference gives.  Where a non-finite constant makes the kernels leave
+ * the reference (hydrodynamics_behavior.py:212-226, numba_hydrodynamics.py:54-105), row by row:
+ *   - mass = NaN: the UNCLAMPED wrench.  The clamp factor is fminf(1, m 500 / (|F| + 1e-6)) and fminf(1, NaN) = 1; the
+ *     reference multiplies by the NaN factor: NaN in all six.
+ *   - am_lin = NaN: NaN force, but the torque stays finite and unclamped - for the same reason (|F| = NaN, factor 1), and
+ *     because the torque does not pass through the force; the reference: NaN in all six.
+ *   - cd_lin, damp_lin or lift = +-Inf: a wrench of EXACTLY ZERO (and no implicit drag).  |F| = Inf makes the factor 0, and the
+ *     factor is applied with a multiply in which 0 wins whatever the other operand is (v_mul_legacy_f32, the instruction that
+ *     zeroes a dry body); the reference: 0 x Inf = NaN in all six.
+ *   - am_lin = +-Inf: R (k R^T a) mixes infinities of both signs.  With a NaN among the force components the factor is 1 and
+ *     the torque stays finite; without one |F| = Inf and the wrench is exactly zero.  The reference: NaN in all six.
+ *   - a NaN dimension: the submersion ratio is fmin(1, .) of the vertical extent and fmin(1, NaN) = 1 - the box is wet
+ *     WHEREVER it is, and its wrench is NaN in all six.  The reference decides on the keypoints that do not involve the
+ *     dimension: the same NaNs for a wet body, zeros for a dry one.  An infinite dimension: ratio 1 as well; every component
+ *     is +-Inf or NaN by the body's attitude - or, where |F| = Inf without a NaN, the whole wrench is zero.  Component mode
+ *     reports ratio 1 and buoyancy (0, 0, NaN or +Inf).
+ *   - a dry body (finite dimensions) never reads a coefficient or the mass: zeros, as in the reference.
+ *   - cd_ang, damp_ang, am_ang non-finite: the force is untouched, the torque NaN or +-Inf - as in the reference.
+ *   - an infinite mass: the wrench is the reference's (factor 1), but the integrator forms 1 / m and 1 / I as a hardware seed and
+ *     one Newton step, 0 + 0 (1 - Inf x 0) = NaN: the step leaves NaN in all thirteen fields.
+ * hydro_set_params_f16 stores NaN and +-Inf as such, rounds to nearest even (ties, subnormals and underflow to +-0 as IEEE half)
+ * and REFUSES what would turn a finite coefficient into an infinity: HYDRO_E_ARG if any |coefficient| is finite and >= 65520
+ * (the half format ends at 65504; a linear damping of 1e5 N s/m would otherwise become +Inf and its body's wrench exactly
+ * zero).  hydro_last_error names the field and the first such body; NOTHING is written - the previous record, f32 or f16,
+ * stays in force - and such a record belongs in hydro_set_params_f32. */
 int hydro_set_params_f32(hydro_t *h, int64_t n, const float *const params[HYDRO_PARAM_FIELDS], int on_device);
 int hydro_set_params_f16(hydro_t *h, int64_t n, const float *const params[HYDRO_PARAM_FIELDS], int on_device);
 

@@ -22,6 +22,9 @@
  * Pinned by tests/test_oracle_golden.py against tests/golden/*.npz, which hold
  * outputs of the reference itself.  Build: oracle/Makefile (-O3 -ffast-math
  * mirrors @njit(fastmath=True)).
+ * Finite inputs only: -ffast-math lets the compiler assume that no value is a NaN or an infinity, so what this file returns
+ * for a non-finite constant is not defined by its source.  tests/test_oracle_golden.py holds it to the rows of
+ * tests/golden/parameter_cases.npz on which the reference is finite; the rule for the others is hydro_oracle.py's.
  */
 #include <math.h>
 #include <stdint.h>

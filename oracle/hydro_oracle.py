@@ -82,7 +82,8 @@ BRANCH_CLAMP = BRANCH_NAMES.index("clamp")
 def lattice_keypoints(dims):
     """27 body-frame keypoints {-hx,0,hx} x {-hy,0,hy} x {-hz,0,hz} (wrapper :55-73)."""
     hx, hy, hz = (0.5 * float(d) for d in dims)
-    pts = [(i * hx, j * hy, k * hz)
+    # the middle coordinates are the literal 0 of the wrapper's table, not 0 * h: a NaN or infinite dimension stays out of them
+    pts = [(i * hx if i else 0.0, j * hy if j else 0.0, k * hz if k else 0.0)
            for k in (1, 0, -1) for j in (1, 0, -1) for i in (-1, 0, 1)]
     return np.asarray(pts, dtype=np.float64)
 
@@ -137,7 +138,9 @@ def submersion_and_cob(world_pts, position, semantics="numba"):
     CoB is the mean of whatever points are wet (warp_hydrodynamics.py:58-61), which differs from the position only when
     the top keypoint is exactly on the surface (z = 0 is not wet)."""
     z = world_pts[:, 2]
-    z_lo, z_hi = float(z.min()), float(z.max())
+    # `if pz < z_min: z_min = pz` from +inf (:62-77): a NaN height never enters, and with nothing but NaNs z_min stays +inf (dry)
+    z_lo = float(np.where(np.isnan(z), np.inf, z).min())
+    z_hi = float(np.where(np.isnan(z), -np.inf, z).max())
     if z_lo >= 0.0:
         return 0.0, position.copy()
     if z_hi <= 0.0:
@@ -149,7 +152,10 @@ def submersion_and_cob(world_pts, position, semantics="numba"):
     if height < HEIGHT_EPS:
         ratio = 1.0 if z_lo < 0.0 else 0.0
     else:
-        ratio = min(1.0, -z_lo / height)
+        with np.errstate(invalid="ignore"):
+            ratio = -z_lo / height                                       # (Inf / Inf = NaN stays: `if ratio > 1.0` is false)
+        if ratio > 1.0:
+            ratio = 1.0
     wet = z < 0.0
     n_wet = int(wet.sum())
     cob = position.copy() if n_wet == 0 else world_pts[wet].sum(axis=0) / n_wet
@@ -329,7 +335,8 @@ def solve_components(state, accel, params, rho, g, semantics="numba", dtype=np.f
         rot = _f32(rot)
 
     # A2/A3: world keypoints, extent ratio, CoB
-    local = _LATTICE_IJK[None, :, :] * half[:, None, :]              # (N,27,3)
+    # (the middle coordinates are the literal 0 of the wrapper's table, not 0 * h: a NaN or infinite dimension stays out of them)
+    local = np.where(_LATTICE_IJK[None, :, :] == 0.0, 0.0, _LATTICE_IJK[None, :, :] * half[:, None, :])          # (N,27,3)
     # R k summed in the order written, x then y then z, as any sequential evaluation of the reference's source does:
     # einsum's order is numpy's choice, and a body within 1e-8 of the dry threshold sees one ulp of a keypoint height
     world = (rot[:, None, :, 0] * local[:, :, None, 0] + rot[:, None, :, 1] * local[:, :, None, 1]
@@ -337,22 +344,24 @@ def solve_components(state, accel, params, rho, g, semantics="numba", dtype=np.f
     if "heights_f32" in mutate:
         world[:, :, 2] = _f32(world[:, :, 2])
     z = world[:, :, 2]
-    z_lo, z_hi = z.min(axis=1), z.max(axis=1)
-    height = z_hi - z_lo
+    # `if pz < z_min: z_min = pz` from +inf (:62-77): a NaN height never enters; with nothing but NaNs z_min stays +inf (dry)
+    z_lo, z_hi = np.where(np.isnan(z), np.inf, z).min(axis=1), np.where(np.isnan(z), -np.inf, z).max(axis=1)
     with np.errstate(divide="ignore", invalid="ignore"):
-        frac = np.minimum(1.0, -z_lo / height)
+        height = z_hi - z_lo
+        frac = -z_lo / height
+        frac = np.where(frac > 1.0, 1.0, frac)                          # `if ratio > 1.0: ratio = 1.0`: a NaN (Inf / Inf) stays
     frac = np.where(height < HEIGHT_EPS, np.where(z_lo < 0.0, 1.0, 0.0), frac)
     ratio = np.where(z_lo >= 0.0, 0.0, np.where(z_hi <= 0.0, 1.0, frac))
     wet = z < 0.0
     n_wet = wet.sum(axis=1)
     partial = (z_lo < 0.0) & (z_hi > 0.0) & (n_wet > 0)
-    mean_wet = (world * wet[:, :, None]).sum(axis=1) / np.maximum(n_wet, 1)[:, None]
+    mean_wet = np.where(wet[:, :, None], world, 0.0).sum(axis=1) / np.maximum(n_wet, 1)[:, None]
     # Warp twin: the mean of the wet points whenever there are any (warp_hydrodynamics.py:58-61), also for a body whose
     # top keypoint is exactly on the surface; with all 27 wet the mean is the position itself
     use_mean = (partial | ((n_wet > 0) & (n_wet < 27))) if semantics == "warp" else partial
     cob = np.where(use_mean[:, None], mean_wet, p)
 
-    live = ratio > DRY_EPS
+    live = ~(ratio <= DRY_EPS)                                           # `if sub_ratio <= 1e-9: return zeros` (:277): a NaN ratio is not dry
 
     # A5
     buoy = np.zeros((n, 3), dtype=dtype)
@@ -381,7 +390,7 @@ def solve_components(state, accel, params, rho, g, semantics="numba", dtype=np.f
             takes.append(take)
             a_f = np.where(take, alignment * face_area[:, axis], 0.0)
             area += a_f
-            weighted += c_w * a_f[:, None]
+            weighted += np.where(take[:, None], c_w * a_f[:, None], 0.0)     # (a face that is not taken adds nothing, whatever its centre)
     has_area = area > AREA_EPS
     cop = np.where(has_area[:, None], weighted / np.where(has_area, area, 1.0)[:, None], cob)
 

@@ -653,6 +653,23 @@ __global__ void __launch_bounds__(kBlock) params_to_tiled_kernel(const ParamPtrs
     }
 }
 
+// The fp16 record's one refusal (hydro_set_params_f16): a FINITE coefficient that __float2half_rn would store as +-Inf, that is
+// |x| >= 65520 (the tie between 65504 and 2^16 rounds to even: to 2^16).  A NaN or an Inf given as such is neither.  *first_bad
+// starts as all ones and ends as the smallest (body << 3 | coefficient) that overflows: one flag word for the host to read.
+__global__ void __launch_bounds__(kBlock) params_f16_range_kernel(const ParamPtrs src, unsigned long long* __restrict__ first_bad, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int f = 0; f < 7; ++f) {
+        const float a = fabsf(src.f[3 + f][i]);
+        if (a >= 65520.0f && a < __builtin_inff()) {
+            atomicMin(first_bad, ((unsigned long long)i << 3) | (unsigned long long)f);
+            return;
+        }
+    }
+}
+
 __global__ void __launch_bounds__(kBlock) params_from_tiled_kernel(const float* __restrict__ tiled, int half, float* __restrict__ soa, int64_t stride,
                                                                    __half* __restrict__ coef16, uint32_t n)
 {
@@ -2764,6 +2781,33 @@ int set_params(hydro_engine* h, int64_t n, const float* const params[], int on_d
             int rc = stage_host_fields(h, params, HYDRO_PARAM_FIELDS, n, &staged);
             if (rc) return rc;
             for (int f = 0; f < HYDRO_PARAM_FIELDS; ++f) src.f[f] = staged + (size_t)f * n;
+        }
+        if (half) {
+            // before anything is written: no finite coefficient may become +-Inf in the half record (the previous record stays)
+            unsigned long long* flag = nullptr;
+            unsigned long long first_bad = ~0ull;
+            if (hipMalloc(&flag, sizeof first_bad) != hipSuccess) {
+                if (staged) (void)hipFree(staged);
+                return fail(h, HYDRO_E_ALLOC, "hydro_set_params_f16: allocation of the range check's flag failed");
+            }
+            hipError_t e = hipMemsetAsync(flag, 0xff, sizeof first_bad, h->stream);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(params_f16_range_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, h->stream, src, flag, (uint32_t)n);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(&first_bad, flag, sizeof first_bad, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            (void)hipFree(flag);
+            if (e != hipSuccess || first_bad != ~0ull) {
+                if (staged) (void)hipFree(staged);
+                if (e != hipSuccess) return fail(h, HYDRO_E_LAUNCH, "params_f16_range_kernel", e);
+                static const char* const names[7] = {"cd_lin", "cd_ang", "damp_lin", "damp_ang", "lift", "am_lin", "am_ang"};
+                char msg[256];
+                snprintf(msg, sizeof msg, "hydro_set_params_f16: %s of body %llu is finite but at least 65520 in magnitude, which half "
+                         "precision stores as Inf; nothing was written, the previous record stays: use hydro_set_params_f32",
+                         names[first_bad & 7u], first_bad >> 3);
+                return fail(h, HYDRO_E_ARG, msg);
+            }
         }
         const uint32_t n_pad = (uint32_t)((n + 63) / 64 * 64);
         hipLaunchKernelGGL(params_to_tiled_kernel, dim3(grid_for(n_pad, kBlock)), dim3(kBlock), 0, h->stream,

@@ -4,7 +4,7 @@
 Runs only in the build container (needs /root/reference); the fixtures it
 writes are committed, the reference never travels.  Usage:
 
-    python3 -B tests/golden/make_golden.py
+    python3 -B tests/golden/make_golden.py                  (--only-ties, --only-params, --only-fuzz: those fixtures alone)
 
 How the reference is run: Numba is not installed here,
 so a stub module `numba` whose `njit(...)` is the identity decorator is placed
@@ -362,6 +362,37 @@ def save_edge_cases():
     print(f"edge_cases: {len(ec.NAMES)} cases, rest-completed {int(rest.sum())}, dry {int((ratio == 0).sum())} -> {os.path.getsize(path)} B")
 
 
+def save_parameter_cases():
+    """The parameter-record table of tests/parameter_cases.py (one constant of dims / coefficients / mass negative, zero, NaN,
+    +-Inf or at an edge of the half format, on a wet moving body and on the same body lifted dry) through the reference itself:
+    nine outputs per row and the net wrench of `_apply_behavior`, non-finite where the reference leaves them so, and `raised`
+    where it raises instead of answering (those rows hold NaN)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import parameter_cases as pc
+    names, state, prev, params = pc.table()
+    n = len(names)
+    accel = (state[:, 7:13].astype(np.float64) - prev.astype(np.float64)) / np.float64(pc.DT)
+    comps, ratio = np.full((n, 8, 3), np.nan), np.full(n, np.nan)
+    net_f, net_t = np.full((n, 3), np.nan), np.full((n, 3), np.nan)
+    rest, raised = np.zeros(n, bool), np.zeros(n, bool)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            try:
+                comps[i], ratio[i], rest[i] = reference_body(state[i], accel[i], params[i], pc.RHO, pc.G)
+                net_f[i], net_t[i] = reference_behavior_wrench(state[i], prev[i], params[i], pc.RHO, pc.G, pc.DT)
+            except Exception as e:                                     # noqa: BLE001  (whatever the reference raises is recorded)
+                raised[i] = True
+                comps[i], ratio[i], net_f[i], net_t[i] = np.nan, np.nan, np.nan, np.nan
+                print(f"  {names[i]}: the reference raises {type(e).__name__}: {e}")
+    path = os.path.join(HERE, "parameter_cases.npz")
+    np.savez_compressed(path, names=np.array(names), state=state, prev=prev, params=params, rho=np.float64(pc.RHO), g=np.float64(pc.G),
+                        dt=np.float64(pc.DT), components=comps, ratio=ratio, rest_completed=rest, net_force=net_f, net_torque=net_t,
+                        raised=raised)
+    finite = np.isfinite(net_f).all(axis=1) & np.isfinite(net_t).all(axis=1)
+    print(f"parameter_cases: {n} rows, {int(finite.sum())} with a finite net wrench, {int(raised.sum())} raised, "
+          f"dry {int((ratio == 0).sum())} -> {os.path.getsize(path)} B")
+
+
 FUZZ_SEEDS = (20251, 20252)        # tests/test_reference_fuzz.py
 FUZZ_BODIES = 3000                 # the fewest that still hold every count the test asserts (> 1000 thin plates, > 500 dry / full)
 
@@ -384,6 +415,8 @@ def main():
     if "--only-ties" in sys.argv:
         save_ties()
         return save_edge_cases()
+    if "--only-params" in sys.argv:
+        return save_parameter_cases()
     if "--only-fuzz" in sys.argv:
         for seed in FUZZ_SEEDS:
             save_fuzz(seed)
@@ -391,6 +424,7 @@ def main():
     save_known_answers()
     save_ties()
     save_edge_cases()
+    save_parameter_cases()
     sc = scenes.scene_c2()
     save_scene_fixture("c2", sc, np.arange(sc.n))
     sc = scenes.scene_c3()

@@ -92,9 +92,9 @@ def _log(rows, n):
     return torch.full((rows, 19, n), NAN, dtype=torch.float32, device=DEV)
 
 
-def _hydro_wrench(eng, cur, old, n):
+def _hydro_wrench(eng, cur, old, n, dt=DT):
     """The fp32 hydrodynamic wrench of (cur, previous velocity in old): what the fused kernels integrate (tests/test_closed_loop_gpu.py)."""
-    return eng.step_wrench_tiled(cur, n, DT, prev=old)
+    return eng.step_wrench_tiled(cur, n, dt, prev=old)
 
 
 def _report(label, worst):
@@ -104,8 +104,8 @@ def _report(label, worst):
     assert not bad, (label, bad)
 
 
-def _k(comps, st, pr, coeff, n):
-    return io.drag_jacobian(st[:n], pr[:n], {c: comps[c][:n] for c in ("ratio", "area", "scale")}, RHO, coeff)
+def _k(comps, st, pr, coeff, n, rho=RHO):
+    return io.drag_jacobian(st[:n], pr[:n], {c: comps[c][:n] for c in ("ratio", "area", "scale")}, rho, coeff)
 
 
 def _push(sc, seed, scale=5.0):
@@ -145,9 +145,9 @@ def _untouched(buf, before):
     return np.array_equal(buf.cpu().numpy(), before, equal_nan=True)
 
 
-def _relative(eng, st, pv, n, step):
-    """(s_rel, pv_rel) built on the host in fp32 from hydro_sea_sample's output."""
-    w = scenes.from_tiled(eng.sea_sample(_tiled(st[:n]), n, step, DT).cpu().numpy(), n)
+def _relative(eng, st, pv, n, step, dt=DT):
+    """(s_rel, pv_rel) built on the host in fp32 from hydro_sea_sample's output at `step` steps of `dt`."""
+    w = scenes.from_tiled(eng.sea_sample(_tiled(st[:n]), n, step, dt).cpu().numpy(), n)
     return sr.relative(st[:n], pv[:n], w[:, 0], w[:, 1:4])
 
 
@@ -167,15 +167,15 @@ ENTRIES = {
 
 
 def step(eng, entry, cur, old, n, steps, *, step0=0, applied=None, frame="world", control=None, mooring=None, extremes=None, tether=None,
-         layers=None, peaks=None, implicit=False, ke=None, **kw):
+         layers=None, peaks=None, implicit=False, ke=None, dt=DT, **kw):
     """One launch of `entry` through the engine; returns (state, prev_out): the buffer that received the final state and the six
     velocity fields of the other one.  An option the entry does not take must be None (step0: 0); `layers` is the net's, for
-    the entries that take one."""
+    the entries that take one.  dt: the step, a Python double (the scene's rho and g are the engine's: HydroEngine(n, DEV, rho, g))."""
     method, takes = ENTRIES[entry]
     given = dict(step0=step0, applied=applied, control=control, mooring=mooring, extremes=extremes, tether=tether, layers=layers, peaks=peaks)
     for name, value in given.items():
         assert name in takes or value is None or (name == "step0" and value == 0), (entry, name)
-    getattr(eng, method)(cur, old, n, DT, steps, *(given[name] for name in takes), frame, implicit_drag=implicit, ke_out=ke, **kw)
+    getattr(eng, method)(cur, old, n, dt, steps, *(given[name] for name in takes), frame, implicit_drag=implicit, ke_out=ke, **kw)
     return old, cur[:, 7:13]
 
 
@@ -249,11 +249,12 @@ def step_wrench_terms(st, hydro, *, applied=None, frame="world", ctl=None, bed_w
     return total, surrogate
 
 
-def fp64_step_errors(got, st, hydro, pr, k, **terms):
+def fp64_step_errors(got, st, hydro, pr, k, dt=DT, g=G, **terms):
     """integrator_error_ulps of one step against io.integrate of step_wrench_terms' total, with io.field_scales of its
-    surrogate; per field group the largest over the bodies.  `terms`: the keywords of step_wrench_terms."""
+    surrogate; per field group the largest over the bodies.  `terms`: the keywords of step_wrench_terms.  dt, g: the step and the
+    gravity of the launch, as doubles (rho enters through `hydro` and `k`)."""
     total, surrogate = step_wrench_terms(st, hydro, **terms)
-    ref = io.integrate(st, total, pr, G, DT, *(k or (None, None)))
-    sc = io.field_scales(st, surrogate, pr, G, DT, k, ref)
-    err = io.integrator_error_ulps(got, ref, st, total, pr, G, DT, k, scales=sc)
+    ref = io.integrate(st, total, pr, g, dt, *(k or (None, None)))
+    sc = io.field_scales(st, surrogate, pr, g, dt, k, ref)
+    err = io.integrator_error_ulps(got, ref, st, total, pr, g, dt, k, scales=sc)
     return {g: float(np.nan_to_num(e, nan=np.inf).max(initial=0.0)) for g, e in err.items()}

@@ -14,6 +14,7 @@ everything behind the wrench takes the true state.
 import numpy as np
 
 ULP = 2.0 ** -24
+VIEW_BOUND = 4.0              # units of 2^-24 of view_scales: the bound of hydro_sea_sample (tests/test_sea_gpu.py's docstring derives it)
 
 
 def _waves(sea):

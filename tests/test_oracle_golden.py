@@ -84,6 +84,67 @@ def test_fused_oracle_matches_the_reference_behavior_script(name, native_built):
     assert ho.wrench_error(fc, tc, fx["net_force"], fx["net_torque"], fx["params"], rho, g).max() < tol
 
 
+# ---- the parameter-record table (tests/parameter_cases.py): negative, zero, NaN, +-Inf constants and the edges of half ----------------
+def _same_class_and_value(got, ref, what):
+    """Finite values of the reference at TOL (of the row's largest finite value); elsewhere the same components are NaN and the
+    same components are +Inf and -Inf."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, what
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), (what, "NaN", got, ref)
+    assert np.array_equal(np.isposinf(got), np.isposinf(ref)) and np.array_equal(np.isneginf(got), np.isneginf(ref)), (what, "Inf", got, ref)
+    fin = np.isfinite(ref)
+    if fin.any():
+        assert np.abs(got[fin] - ref[fin]).max() <= TOL * max(1.0, np.abs(ref[fin]).max()), (what, got, ref)
+
+
+def test_numpy_oracle_follows_the_reference_on_the_parameter_table():
+    """Both restatements of hydro_oracle.py - vectorised and one body at a time - and the fused wrench, row by row."""
+    import parameter_cases as pc
+    fx = pc.reference_outputs()
+    assert not fx["raised"].any()                                    # (the reference answers every row; a row on which it raised would hold NaN)
+    rho, g, dt = float(fx["rho"]), float(fx["g"]), float(fx["dt"])
+    acc = accel_of(fx)
+    with np.errstate(all="ignore"):
+        out = ho.solve_components(fx["state"], acc, fx["params"], rho, g)
+        f, t, _ = ho.step_wrench(fx["state"], fx["prev"], fx["params"], rho, g, dt)
+    nonfinite = 0
+    for i, name in enumerate(str(x) for x in fx["names"]):
+        got = np.concatenate([out[k][i] for k in ho.COMPONENT_FIELDS] + [[out["ratio"][i]], f[i], t[i]])
+        ref = np.concatenate([fx["components"][i].ravel(), [fx["ratio"][i]], fx["net_force"][i], fx["net_torque"][i]])
+        _same_class_and_value(got, ref, name)
+        s = fx["state"][i]
+        with np.errstate(all="ignore"):
+            one = ho.solve_components_one(s[0:3], s[3:7], s[7:10], s[10:13], acc[i, :3], acc[i, 3:], fx["params"][i], rho, g)
+        _same_class_and_value(np.concatenate([np.asarray(x, np.float64) for x in one[:8]] + [[one[8]]]), ref[:25], (name, "one body"))
+        nonfinite += not np.isfinite(ref).all()
+    assert nonfinite >= 28                                            # (the table does reach the non-finite answers)
+
+
+def test_c_oracle_follows_the_reference_on_the_finite_rows_of_the_parameter_table(native_built):
+    """hydro_oracle.c is built with -ffast-math, which lets the compiler assume finite values: it is held to the rows on which the
+    reference's outputs are all finite (negative constants, -0, tiny ones, every edge of the half format, 65520 and 7e4)."""
+    import parameter_cases as pc
+    fx = pc.reference_outputs()
+    rho, g, dt = float(fx["rho"]), float(fx["g"]), float(fx["dt"])
+    fin = (np.isfinite(fx["components"]).all(axis=(1, 2)) & np.isfinite(fx["net_force"]).all(axis=1) & np.isfinite(fx["net_torque"]).all(axis=1)
+           & np.isfinite(fx["params"]).all(axis=1))
+    assert fin.sum() >= 150
+    comps, ratio = c_oracle.components(fx["state"][fin], accel_of(fx)[fin], fx["params"][fin], rho, g)
+    f, t = c_oracle.wrench(fx["state"][fin], fx["prev"][fin], fx["params"][fin], rho, g, dt)
+    for j, i in enumerate(np.flatnonzero(fin)):
+        got = np.concatenate([comps[j].ravel(), [ratio[j]], f[j], t[j]])
+        ref = np.concatenate([fx["components"][i].ravel(), [fx["ratio"][i]], fx["net_force"][i], fx["net_torque"][i]])
+        _same_class_and_value(got, ref, str(fx["names"][i]))
+
+
+def test_a_stale_parameter_fixture_is_refused(monkeypatch):
+    import parameter_cases as pc
+    pc.reference_outputs()
+    monkeypatch.setattr(pc, "CLEAN", pc.CLEAN + np.float32(0.25))
+    with pytest.raises(AssertionError, match="stale"):
+        pc.reference_outputs()
+
+
 # ---- K1-K5: behaviour-level known answers (SURVEY.md 8c) -------------------------------
 KAT_EXPECT = {
     "K1": dict(ratio=0.6310344827586206, buoy_z=6345.209482758621,

@@ -36,7 +36,7 @@ from resident_harness import (B, _buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, 
 
 pytestmark = pytest.mark.gpu
 WATCH = (0, 63, 64)                                               # the watched bodies, with the last one
-VIEW_BOUND = 4.0
+VIEW_BOUND = sr.VIEW_BOUND
 S_W = 4 * 64 + 52                                                 # the sample's tile stride in the guard tests
 
 
