@@ -65,7 +65,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_peak - the running maximum of every
  *        tether's tension, per body and layer, updated inside every step
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_spread, HYDRO_MOOR_LAYERS_MAX - up to four
- *        layers of mooring records, so that a body rides on a spread of anchored lines */
+ *        layers of mooring records, so that a body rides on a spread of anchored lines
+ *        added to 0.7.1 (no existing entry changed): hydro_set_sea_spectrum, hydro_sea_spectrum_sample, hydro_step_fused_tiled_multi_irr,
+ *        HYDRO_SPECTRUM_WAVES_MAX - an irregular sea of up to 64 wave components in the closed-loop steps */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -91,6 +93,7 @@ extern "C" {
 #define HYDRO_WATCH_MAX  65536   /* bodies in one watch list (hydro_set_watch) */
 #define HYDRO_SEA_WAVES_MAX   8   /* regular wave components of a sea state (hydro_set_sea) */
 #define HYDRO_SEA_FIELDS      4   /* the record of hydro_sea_sample: eta, u_x, u_y, u_z */
+#define HYDRO_SPECTRUM_WAVES_MAX 64 /* wave components of a sea spectrum (hydro_set_sea_spectrum) */
 
 typedef struct hydro_engine hydro_t;
 
@@ -1084,6 +1087,69 @@ int hydro_step_fused_tiled_multi_spread(hydro_t *h, int64_t n, const float *stat
                                         const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
                                         float *tether_peaks, int64_t tether_peaks_tile_stride,
                                         int64_t step0, void *stream);
+
+/* Sea spectrum: an irregular sea for the closed-loop steps - the model of "Sea state" (above), unchanged, with `waves` =
+ * 0 .. HYDRO_SPECTRUM_WAVES_MAX = 64 components, enough to cut a Pierson-Moskowitz or JONSWAP spectrum of a given significant
+ * wave height and peak period into bins.  The cap is a cost decision, not a design limit: a step pays for every component,
+ * and nothing in the layout or the arithmetic depends on the number.
+ *
+ * WATER AT A BODY is "Sea state"'s, statement for statement: t, x_j, m_j, tau_j in fp64, th_j, r_j, c_j, s_j, eta, z_rel, e_j
+ * and u in fp32, the sums taken in ASCENDING COMPONENT ORDER, eta starting from +0 and u from U.  For waves <= HYDRO_SEA_WAVES_MAX
+ * eta and u are therefore, bit for bit, those of hydro_set_sea with the same components.  Every body evaluates every component;
+ * c_j is formed a second time behind eta (the same instructions on the same inputs: the same bits), never stored.
+ * RELATIVE STATE and NOT MODELLED: as in "Sea state".
+ *
+ * hydro_sea_spectrum_t: `current` U (m/s, world frame), `waves` and `wave`, the caller's array of `waves` components (read
+ * during the call only; may be NULL when waves == 0).
+ *
+ * hydro_set_sea_spectrum: hydro_set_sea's rules for the current and for every component (one validator serves both), into an
+ * engine-owned device table of its own (16 + 64 * 48 = 3088 B, allocated by the first call, freed by hydro_destroy), copied on
+ * the engine's private stream and waited for.  spec == NULL clears the spectrum.  HYDRO_E_ARG for waves outside
+ * 0 .. HYDRO_SPECTRUM_WAVES_MAX, a NULL `wave` with waves > 0, and whatever hydro_set_sea refuses of a component - the
+ * previous spectrum stays in force.
+ * A SPECTRUM AND A SEA EXCLUDE EACH OTHER, at set time: hydro_set_sea_spectrum(non-NULL) returns HYDRO_E_STATE while a sea is
+ * set (clear it first: hydro_set_sea(h, NULL)), hydro_set_sea(non-NULL) returns HYDRO_E_STATE while a spectrum is set (clear it
+ * first: hydro_set_sea_spectrum(h, NULL)); what was set stays in force.  Clearing with NULL is always allowed.
+ * ONLY hydro_step_fused_tiled_multi_irr and hydro_sea_spectrum_sample know the spectrum: EVERY OTHER ENTRY IGNORES IT and steps
+ * through the water it stepped through before - the sea of hydro_set_sea where it knows one, still water otherwise - as the
+ * entries below hydro_step_fused_tiled_multi_bed ignore the bed.
+ *
+ * hydro_sea_spectrum_sample: the signature and the rules of hydro_sea_sample, read against the spectrum: the [eta, u_x, u_y, u_z]
+ * a step of hydro_step_fused_tiled_multi_irr that starts from `state` at step index `step_index` uses.  HYDRO_E_STATE without
+ * a spectrum.
+ *
+ * hydro_step_fused_tiled_multi_irr: exactly the signature, the refusals and the refusal order of
+ * hydro_step_fused_tiled_multi_spread.
+ *   no spectrum set : the launch and its bits are those of hydro_step_fused_tiled_multi_spread with the same arguments - with
+ *                     a sea of hydro_set_sea set, through that sea.
+ *   a spectrum set  : log, applied, control, the bed, the spread, the extremes, the net and the link tensions are each still
+ *                     optional and add what they add in hydro_step_fused_tiled_multi_spread; the hydrodynamic wrench is taken
+ *                     through the spectrum.  One kernel family of its own serves every combination.
+ * Trailing components of amplitude 0 change no bit.  Asynchronous, no allocation, no synchronisation, safe to capture: a
+ * captured launch replays with the step0 it was captured with, i.e. at a frozen wave phase - capture current-only spectra.
+ * Cost and registers: DESIGN.md section 29.  New functionality; the reference's water does not move. */
+typedef struct hydro_sea_spectrum {
+    double current[3];
+    int waves;
+    const hydro_sea_wave_t *wave;
+} hydro_sea_spectrum_t;
+int hydro_set_sea_spectrum(hydro_t *h, const hydro_sea_spectrum_t *spec);
+int hydro_sea_spectrum_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
+                              float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_irr(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride,
+                                     const float *mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                     float *extremes, int64_t extremes_tile_stride,
+                                     const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                     float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                     int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

@@ -26,6 +26,7 @@ BATCH_MAX = 32
 WATCH_MAX = 65536
 SEA_WAVES_MAX = 8                       # regular wave components of a sea state (hydro_set_sea)
 SEA_FIELDS = 4                          # the record of hydro_sea_sample: eta, u_x, u_y, u_z
+SPECTRUM_WAVES_MAX = 64                 # wave components of a sea spectrum (hydro_set_sea_spectrum)
 
 
 class Scene(ctypes.Structure):
@@ -44,6 +45,11 @@ class SeaWave(ctypes.Structure):
 class Sea(ctypes.Structure):
     """hydro_sea_t (include/hydro.h): the sea state hydro_set_sea takes."""
     _fields_ = [("current", c_double * 3), ("waves", c_int), ("wave", SeaWave * SEA_WAVES_MAX)]
+
+
+class SeaSpectrum(ctypes.Structure):
+    """hydro_sea_spectrum_t (include/hydro.h): the irregular sea hydro_set_sea_spectrum takes; `wave` points at `waves` SeaWave."""
+    _fields_ = [("current", c_double * 3), ("waves", c_int), ("wave", POINTER(SeaWave))]
 
 
 class Seabed(ctypes.Structure):
@@ -69,6 +75,7 @@ _CTL = _MOOR = _EXT = _TETH = _PEAK = [c_void_p, c_int64]                       
 _LAYERS = _STEP0 = [c_int64]                                                              # tether_layers; step0
 _SPREAD = _MOOR + [c_int64]                                                               # the mooring record as a spread: + mooring_layers
 _STREAM = [c_void_p]
+_SAMPLE = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]   # h, n, state (+ stride), step_index, dt, out (+ stride), stream
 
 
 def _multi(*groups):
@@ -126,6 +133,9 @@ SIGNATURES = {
     "hydro_step_fused_tiled_multi_net": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _LAYERS, _STEP0),
     "hydro_step_fused_tiled_multi_peak": _multi(_REC, _APP, _CTL, _MOOR, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
     "hydro_step_fused_tiled_multi_spread": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
+    "hydro_set_sea_spectrum": (c_int, [c_void_p, POINTER(SeaSpectrum)]),
+    "hydro_sea_spectrum_sample": (c_int, _SAMPLE),
+    "hydro_step_fused_tiled_multi_irr": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -2442,6 +2442,113 @@ __global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_
                                                    OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
 }
 
+// --------------------------------------------------------------------------
+// IRREGULAR SEAS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_irr): the sea state's model with up to
+// HYDRO_SPECTRUM_WAVES_MAX components - a JONSWAP or Pierson-Moskowitz spectrum cut into bins (hydro_set_sea_spectrum;
+// include/hydro.h, "Sea spectrum").  spectrum_water below is its ONLY implementation (the step kernel and
+// hydro_sea_spectrum_sample's kernel both call it), and for up to HYDRO_SEA_WAVES_MAX components it returns sea_water's bits:
+// the same statements on the same inputs, the sums in ascending component order, eta from +0 and u from U.
+//   the loop   : a REAL loop over the components, unrolled in groups of four so that a group's scalar loads are in flight
+//                together (one wait per group; the remainder runs one by one): cs[] and sn[] of sea_water are 128 registers at
+//                64 components, so nothing is kept per component.  The second pass needs all of eta before any exp, and forms
+//                th_j, its reduction and its cosine AGAIN - the same instructions on the same inputs, hence the same bits as
+//                the first pass (tau_j is recomputed with them: the fp64 chain is wave-uniform and short)
+//   the lanes  : every lane evaluates every component.  Dead lanes of a partial tile never reach a sea policy
+//                (fused_multi_body), so no lane may compute a phase for another
+//   the table  : SeaTable's header and records, 16 + 64 * 48 = 3088 B, read through the CONSTANT address space with a
+//                wave-uniform index: scalar loads in every trip, no vector register holds a component between trips
+// --------------------------------------------------------------------------
+struct SpectrumTable {
+    float u[3]; uint32_t waves;
+    SeaWave w[HYDRO_SPECTRUM_WAVES_MAX];
+};
+typedef const __attribute__((address_space(4))) SpectrumTable* SpectrumTablePtr;
+typedef const __attribute__((address_space(4))) SeaWave* SeaWavePtr;
+
+// r_j of include/hydro.h for component `w` at time t: th_j in revolutions, reduced to [-1/2, 1/2] - sea_water's statements.
+__device__ __forceinline__ float spectrum_revolutions(SeaWavePtr w, double t, float px, float py)
+{
+    constexpr double kInv2Pi = 0.15915494309189535, kTwoPiHi = 6.283185307179586, kTwoPiLo = 2.4492935982947064e-16;
+    const double x = __builtin_fma(-w->omega, t, w->phi);
+    const double m = __builtin_rint(x * kInv2Pi);
+    const float tau = (float)__builtin_fma(-m, kTwoPiLo, __builtin_fma(-m, kTwoPiHi, x));
+    const float th = __builtin_fmaf(w->kx, px, __builtin_fmaf(w->ky, py, tau));
+    const float rev = th * 0.15915494309189535f;
+    return rev - __builtin_rintf(rev);
+}
+
+// eta and u of the water at (px, py) for a body whose centre is at pz, at the start of step `step`: sea_water for any number
+// of components.
+__device__ __forceinline__ void spectrum_water(SpectrumTablePtr tab, uint32_t waves, int64_t step, double dt, float px, float py, float pz,
+                                               float& eta, float (&u)[3])
+{
+    const double t = (double)step * dt;
+    eta = 0.0f;
+#pragma clang loop unroll_count(4)
+    for (uint32_t j = 0; j < waves; ++j) {                   // (wave-uniform)
+        const float r = spectrum_revolutions(&tab->w[j], t, px, py);
+        eta = __builtin_fmaf(tab->w[j].a, __builtin_amdgcn_cosf(r), eta);
+    }
+    const float zc = __builtin_fminf(pz - eta, 0.0f);
+    u[0] = tab->u[0]; u[1] = tab->u[1]; u[2] = tab->u[2];
+#pragma clang loop unroll_count(4)
+    for (uint32_t j = 0; j < waves; ++j) {
+        const float r = spectrum_revolutions(&tab->w[j], t, px, py);
+        const float cs = __builtin_amdgcn_cosf(r), sn = __builtin_amdgcn_sinf(r);
+        const float e = __builtin_amdgcn_exp2f(tab->w[j].kl2 * zc);
+        const float ec = e * cs, es = e * sn;
+        u[0] = __builtin_fmaf(tab->w[j].cx, ec, u[0]);
+        u[1] = __builtin_fmaf(tab->w[j].cy, ec, u[1]);
+        u[2] = __builtin_fmaf(tab->w[j].aw, es, u[2]);
+    }
+}
+
+// SeaView with spectrum_water for the water: the same seven values parked in the same slots (the two never meet in a
+// kernel), the same restore.  Not optional: the host launches the kernel below only while a spectrum is set.
+struct SpectrumView : SeaView {
+    __device__ __forceinline__ void view(uint32_t k, float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        float eta, u[3];
+        spectrum_water((SpectrumTablePtr)tab, waves, step0 + (int64_t)k, dt, s[0], s[1], s[2], eta, u);
+        float* m = parked();
+        m[0] = s[2];
+        s[2] = s[2] - eta;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            m[(1 + i) * 64] = s[7 + i];
+            m[(4 + i) * 64] = pv[i];
+            s[7 + i] = s[7 + i] - u[i];
+            pv[i] = pv[i] - u[i];
+        }
+    }
+};
+__device__ __forceinline__ SpectrumView spectrum_view(HYDRO_SEA_PARAMS) { return SpectrumView{sea_view(HYDRO_SEA_ARGS)}; }
+
+// The _spread kernel's arguments, unchanged; the sea group carries the spectrum's table and count.  Everything else may be null.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_irr_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                 HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                 HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   spectrum_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), mooring_spread(HYDRO_SPREAD_ARGS),
+                                                   optional_extremes_track(HYDRO_EXT_ARGS),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// hydro_sea_spectrum_sample: sea_sample_kernel against the spectrum.
+__global__ void __launch_bounds__(kBlock) spectrum_sample_kernel(const float* st, uint32_t st_stride, float* out, uint32_t out_stride, uint32_t n,
+                                                                 const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float eta, u[3];
+    spectrum_water((SpectrumTablePtr)sea_table, sea_waves, step, sea_dt, *at<float>(r, lane4, 0u), *at<float>(r, lane4, 256u), *at<float>(r, lane4, 512u), eta, u);
+    const float o[HYDRO_SEA_FIELDS] = {eta, u[0], u[1], u[2]};
+    store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
+}
+
 // hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
 // nothing) and, if asked for, its tension T (+0 likewise).  The lanes >= n of the last tile leave first: the live ones
 // exchange among themselves, in uniform control flow.
@@ -2518,6 +2625,10 @@ struct hydro_engine {
     // kept until hydro_destroy.  sea_waves < 0: no sea.
     void* sea_table = nullptr;
     int sea_waves = -1;
+    // The sea spectrum (hydro_set_sea_spectrum): the device table the _irr kernels read (SpectrumTable), allocated by the first
+    // hydro_set_sea_spectrum, kept until hydro_destroy.  spectrum_waves < 0: no spectrum.  Never set together with a sea.
+    void* spectrum_table = nullptr;
+    int spectrum_waves = -1;
     // The seabed (hydro_set_seabed): the plane and the five contact constants, already rounded to fp32 - kernel arguments.
     Seabed bed = {};
     bool has_bed = false;
@@ -2992,6 +3103,7 @@ int hydro_destroy(hydro_t* h)
     if (h->watch_mask) (void)hipFree(h->watch_mask);
     if (h->watch_first) (void)hipFree(h->watch_first);
     if (h->sea_table) (void)hipFree(h->sea_table);
+    if (h->spectrum_table) (void)hipFree(h->spectrum_table);
     delete h;
     return HYDRO_OK;
 }
@@ -3375,7 +3487,7 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// A launch of any of the twelve hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// A launch of any of the thirteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
 // was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
 // copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
 // (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
@@ -3392,6 +3504,7 @@ struct MultiStep {
     const float* control = nullptr; int64_t control_tile_stride = 0;
     bool sea_entry = false; int64_t step0 = 0;           // the _sea entry: step0 is checked, and the steps go through the sea if one is set
     bool bed_entry = false;                              // the _bed entry: the _sea entry, and the steps meet the seabed if one is set
+    bool irr_entry = false;                              // the _irr entry: the _spread entry, and the steps go through the sea spectrum if one is set
     const float* mooring = nullptr; int64_t mooring_tile_stride = 0;      // the _moor entry: the _bed entry, and a line per body if a record is given
     float* extremes = nullptr; int64_t extremes_tile_stride = 0;          // the _ext entry: the _moor entry, and the running extremes if a record is given
     const float* tether = nullptr; int64_t tether_tile_stride = 0;        // the _teth entry: the _ext entry, and a line between two bodies of a tile if a record is given
@@ -3408,6 +3521,7 @@ struct MultiStep {
     void with_control(const float* p, int64_t stride) { control = p; control_tile_stride = stride; }
     void with_sea(int64_t step0_) { sea_entry = true; step0 = step0_; }
     void with_seabed() { bed_entry = true; }
+    void with_spectrum() { irr_entry = true; }
     void with_mooring(const float* p, int64_t stride) { mooring = p; mooring_tile_stride = stride; }
     void with_extremes(float* p, int64_t stride) { extremes = p; extremes_tile_stride = stride; }
     void with_tether(const float* p, int64_t stride) { tether = p; tether_tile_stride = stride; }
@@ -3463,6 +3577,7 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
 // The refusals in the order the entries have always reported them, then ONE choice of kernel family.  The families form a
 // ladder, each taking its predecessor's argument groups and one more:
 //   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak < _spread
+// (the _irr family stands beside the ladder: it is chosen while a sea spectrum is set, by the _irr entry alone, whatever the options)
 // and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
 // the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
@@ -3472,6 +3587,7 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
     if (m.sea_entry && (m.step0 < 0 || m.steps < 0 || m.step0 + (int64_t)m.steps >= ((int64_t)1 << 52) || m.step0 >= ((int64_t)1 << 52)))
         return fail(h, HYDRO_E_ARG, "step0 must be >= 0 and step0 + steps < 2^52");
     const bool rec = m.log || m.log_required, sea = m.sea_entry && h->sea_waves >= 0, bed = m.bed_entry && h->has_bed;
+    const bool irr = m.irr_entry && h->spectrum_waves >= 0;                    // (a spectrum and a sea are never set together: irr implies !sea)
     int64_t rows = 0;
     if (rec && (rc = check_recorder(h, m, rows))) return rc;
     if ((rc = check_common(h, m.n))) return rc;
@@ -3578,7 +3694,8 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
         const auto held = [&](auto kernel, auto... tail) { pushed(kernel, m.control, control_stride, tail...); };
         const auto in_sea = [&](auto kernel, auto... tail) {
-            held(kernel, sea ? (const void*)h->sea_table : (const void*)nullptr, sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
+            held(kernel, irr ? (const void*)h->spectrum_table : sea ? (const void*)h->sea_table : (const void*)nullptr,
+                 irr ? (uint32_t)h->spectrum_waves : sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
         };
         const auto on_bed = [&](auto kernel, auto... tail) {
             in_sea(kernel, h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, tail...);
@@ -3589,11 +3706,18 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto tethered = [&](auto kernel, auto... tail) { tracked(kernel, m.tether, (uint32_t)m.tether_tile_stride, tail...); };
         const auto netted = [&](auto kernel, auto... tail) { tethered(kernel, (uint32_t)m.tether_layers, tail...); };
         // (the spread's layer count stands behind the mooring group, in front of the groups that follow it: its link takes them as its tail)
-        const auto spread_moored = [&](auto kernel, auto... tail) { on_optional_bed(kernel, m.mooring, (uint32_t)m.mooring_tile_stride, (uint32_t)m.mooring_layers, tail...); };
-        if (m.mooring && m.mooring_layers)
-            spread_moored(step_fused_multi_spread_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
+        const auto spread_moored = [&](auto kernel, auto... tail) {
+            on_optional_bed(kernel, m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.mooring ? (uint32_t)m.mooring_layers : 0u, tail...);
+        };
+        // (the _spread family's groups behind the spread, every one optional: the _irr family takes them unchanged)
+        const auto spread_and_all = [&](auto kernel) {
+            spread_moored(kernel, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
                           m.tether, m.tether ? (uint32_t)m.tether_tile_stride : 0u, m.tether ? (uint32_t)(m.tether_layers ? m.tether_layers : 1) : 0u,
                           m.tether_peaks, m.tether_peaks ? (uint32_t)m.tether_peaks_tile_stride : 0u);
+        };
+        // the spectrum first: its family stands beside the ladder, not on it, and takes every option the launch has
+        if (irr) spread_and_all(step_fused_multi_irr_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        else if (m.mooring && m.mooring_layers) spread_and_all(step_fused_multi_spread_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.tether_peaks) netted(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
         else if (m.tether && m.tether_layers) netted(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.tether) tethered(step_fused_multi_teth_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
@@ -3714,36 +3838,54 @@ int hydro_step_fused_tiled_multi_ctl(hydro_t* h, int64_t n, const float* state, 
     return step_fused_tiled_multi_launch(h, m);
 }
 
-int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
+}  // extern "C"
+
+namespace {
+// What hydro_set_sea and hydro_set_sea_spectrum check of a sea and how they form its device records: `u` and `out[0 .. waves)`
+// (zeroed by the caller).  `what` ("sea" / "sea spectrum") heads the messages.
+int sea_records(hydro_t* h, const char* what, const double (&current)[3], int waves, const hydro_sea_wave_t* wave, float (&u)[3], SeaWave* out)
 {
-    if (!h) return HYDRO_E_ARG;
-    if (!sea) { h->sea_waves = -1; return HYDRO_OK; }
-    if (sea->waves < 0 || sea->waves > HYDRO_SEA_WAVES_MAX) return fail(h, HYDRO_E_ARG, "sea: waves out of range (0 .. HYDRO_SEA_WAVES_MAX)");
+    char msg[128];
+    const auto refuse = [&](const char* why) { snprintf(msg, sizeof msg, "%s: %s", what, why); return fail(h, HYDRO_E_ARG, msg); };
     for (int i = 0; i < 3; ++i)
-        if (!isfinite(sea->current[i])) return fail(h, HYDRO_E_ARG, "sea: non-finite current");
-    SeaTable tab;
-    memset(&tab, 0, sizeof tab);
-    for (int i = 0; i < 3; ++i) tab.u[i] = (float)(sea->current[i] + 0.0);      // (-0 + 0 = +0: a zero current is +0)
-    tab.waves = (uint32_t)sea->waves;
-    for (int j = 0; j < sea->waves; ++j) {
-        const hydro_sea_wave_t& w = sea->wave[j];
+        if (!isfinite(current[i])) return refuse("non-finite current");
+    for (int i = 0; i < 3; ++i) u[i] = (float)(current[i] + 0.0);              // (-0 + 0 = +0: a zero current is +0)
+    for (int j = 0; j < waves; ++j) {
+        const hydro_sea_wave_t& w = wave[j];
         if (!isfinite(w.amplitude) || !isfinite(w.kx) || !isfinite(w.ky) || !isfinite(w.omega) || !isfinite(w.phase))
-            return fail(h, HYDRO_E_ARG, "sea: non-finite wave component");
-        if (w.amplitude < 0.0) return fail(h, HYDRO_E_ARG, "sea: negative amplitude");
+            return refuse("non-finite wave component");
+        if (w.amplitude < 0.0) return refuse("negative amplitude");
         const double kappa = sqrt(w.kx * w.kx + w.ky * w.ky);
         if (!(kappa > 0.0)) {
-            if (w.amplitude != 0.0) return fail(h, HYDRO_E_ARG, "sea: a wave component with amplitude needs a wave vector (kappa > 0)");
+            if (w.amplitude != 0.0) return refuse("a wave component with amplitude needs a wave vector (kappa > 0)");
             continue;                                                          // a = 0, kappa = 0: all zeros, contributes +0
         }
-        SeaWave& d = tab.w[j];
+        SeaWave& d = out[j];
         const double aw = w.amplitude * w.omega;
         d.omega = w.omega; d.phi = w.phase;
         d.a = (float)w.amplitude; d.kx = (float)w.kx; d.ky = (float)w.ky;
         d.kl2 = (float)(kappa * 1.4426950408889634);
         d.cx = (float)(aw * w.kx / kappa); d.cy = (float)(aw * w.ky / kappa); d.aw = (float)aw;
         if (!isfinite(d.kl2) || !isfinite(d.cx) || !isfinite(d.cy) || !isfinite(d.aw) || !isfinite(d.kx) || !isfinite(d.ky) || !isfinite(d.a))
-            return fail(h, HYDRO_E_ARG, "sea: wave component out of fp32 range");
+            return refuse("wave component out of fp32 range");
     }
+    return HYDRO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!sea) { h->sea_waves = -1; return HYDRO_OK; }
+    if (h->spectrum_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea spectrum is set (clear it first: hydro_set_sea_spectrum(h, NULL))");
+    if (sea->waves < 0 || sea->waves > HYDRO_SEA_WAVES_MAX) return fail(h, HYDRO_E_ARG, "sea: waves out of range (0 .. HYDRO_SEA_WAVES_MAX)");
+    SeaTable tab;
+    memset(&tab, 0, sizeof tab);
+    int rc;
+    if ((rc = sea_records(h, "sea", sea->current, sea->waves, sea->wave, tab.u, tab.w))) return rc;
+    tab.waves = (uint32_t)sea->waves;
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     if (!h->sea_table && hipMalloc(&h->sea_table, sizeof(SeaTable)) != hipSuccess) { h->sea_table = nullptr; return fail(h, HYDRO_E_ALLOC, "sea table: allocation failed"); }
     // from here on the device table is being rewritten: a failure leaves NO sea, never half of one
@@ -3755,12 +3897,47 @@ int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
     return HYDRO_OK;
 }
 
-int hydro_sea_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
-                     float* out, int64_t out_tile_stride, void* stream)
+int hydro_set_sea_spectrum(hydro_t* h, const hydro_sea_spectrum_t* spec)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!spec) { h->spectrum_waves = -1; return HYDRO_OK; }
+    if (h->sea_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea is set (clear it first: hydro_set_sea(h, NULL))");
+    if (spec->waves < 0 || spec->waves > HYDRO_SPECTRUM_WAVES_MAX)
+        return fail(h, HYDRO_E_ARG, "sea spectrum: waves out of range (0 .. HYDRO_SPECTRUM_WAVES_MAX)");
+    if (spec->waves > 0 && !spec->wave) return fail(h, HYDRO_E_ARG, "sea spectrum: null wave with waves > 0");
+    // (3 KB: on the heap, like the watch tables)
+    SpectrumTable* tab = static_cast<SpectrumTable*>(calloc(1, sizeof(SpectrumTable)));
+    if (!tab) return fail(h, HYDRO_E_ALLOC, "sea spectrum table: host allocation failed");
+    int rc = sea_records(h, "sea spectrum", spec->current, spec->waves, spec->wave, tab->u, tab->w);
+    if (rc) { free(tab); return rc; }
+    tab->waves = (uint32_t)spec->waves;
+    if (const hipError_t e = use_device(h->device); e != hipSuccess) { free(tab); return fail(h, HYDRO_E_DEVICE, "use_device(h->device)", e); }
+    if (!h->spectrum_table && hipMalloc(&h->spectrum_table, sizeof(SpectrumTable)) != hipSuccess) {
+        h->spectrum_table = nullptr;
+        free(tab);
+        return fail(h, HYDRO_E_ALLOC, "sea spectrum table: allocation failed");
+    }
+    // from here on the device table is being rewritten: a failure leaves NO spectrum, never half of one
+    h->spectrum_waves = -1;
+    hipError_t e = hipMemcpyAsync(h->spectrum_table, tab, sizeof *tab, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    free(tab);
+    if (e != hipSuccess) return fail(h, HYDRO_E_LAUNCH, "sea spectrum table: copy to the device", e);
+    h->spectrum_waves = spec->waves;
+    return HYDRO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// hydro_sea_sample and hydro_sea_spectrum_sample: one set of rules, the table and the kernel of either.
+template <typename Kernel>
+int water_sample(hydro_t* h, Kernel kernel, const void* table, int waves, const char* none, int64_t n, const float* state, int64_t state_tile_stride,
+                 int64_t step_index, double dt, float* out, int64_t out_tile_stride, void* stream)
 {
     if (!h) return HYDRO_E_ARG;
     if (n < 0 || n > h->capacity) return fail(h, HYDRO_E_ARG, "n out of range (0 <= n <= capacity)");
-    if (h->sea_waves < 0) return fail(h, HYDRO_E_STATE, "no sea (call hydro_set_sea first)");
+    if (waves < 0) return fail(h, HYDRO_E_STATE, none);
     if (!(dt > 0.0)) return fail(h, HYDRO_E_ARG, "dt must be > 0");
     if (step_index < 0 || step_index >= ((int64_t)1 << 52)) return fail(h, HYDRO_E_ARG, "step_index must be in 0 .. 2^52 - 1");
     int rc;
@@ -3768,10 +3945,29 @@ int hydro_sea_sample(hydro_t* h, int64_t n, const float* state, int64_t state_ti
     if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_SEA_FIELDS, "null out"))) return rc;
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     if (n == 0) return HYDRO_OK;
-    hipLaunchKernelGGL(sea_sample_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
-                       out, (uint32_t)out_tile_stride, (uint32_t)n, (const void*)h->sea_table, (uint32_t)h->sea_waves, step_index, dt);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
+                       out, (uint32_t)out_tile_stride, (uint32_t)n, table, (uint32_t)waves, step_index, dt);
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hydro_sea_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
+                     float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    return water_sample(h, sea_sample_kernel, (const void*)h->sea_table, h->sea_waves, "no sea (call hydro_set_sea first)",
+                        n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream);
+}
+
+int hydro_sea_spectrum_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
+                              float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    return water_sample(h, spectrum_sample_kernel, (const void*)h->spectrum_table, h->spectrum_waves, "no sea spectrum (call hydro_set_sea_spectrum first)",
+                        n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream);
 }
 
 int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -4073,6 +4269,37 @@ int hydro_step_fused_tiled_multi_spread(hydro_t* h, int64_t n, const float* stat
     m.with_tether(tether, tether_tile_stride);
     m.with_layers(tether_layers);
     m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_irr(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride,
+                                     const float* mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                     float* extremes, int64_t extremes_tile_stride,
+                                     const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                     float* tether_peaks, int64_t tether_peaks_tile_stride, int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_mooring_layers(mooring_layers);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    m.with_spectrum();
     return step_fused_tiled_multi_launch(h, m);
 }
 

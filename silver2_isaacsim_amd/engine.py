@@ -71,6 +71,7 @@ class HydroEngine:
         self.semantics = "numba"
         self._tables: dict = {}
         self.sea_waves: int | None = None            # wave components of the sea set with set_sea; None: no sea
+        self.spectrum_waves: int | None = None       # wave components of the spectrum set with set_sea_spectrum; None: no spectrum
         self.seabed = None                           # the seabed.Seabed set with set_seabed; None: no bed
         self.set_scene(water_density, gravity)
 
@@ -539,6 +540,57 @@ class HydroEngine:
                                     (log, every, phase, row0), stream,
                                     lambda: (*self._applied_control(applied, frame, control, n), int(step0)))
 
+    # ------------------------------------------------------------------ sea spectrum
+    def set_sea_spectrum(self, spectrum) -> None:
+        """The scene's irregular sea (hydro_set_sea_spectrum; include/hydro.h, "Sea spectrum"): `spectrum` has `current` and
+        `waves`, up to `_native.SPECTRUM_WAVES_MAX` rows (amplitude, kx, ky, omega, phase) - a `sea.SeaSpectrum`.  None clears it.
+        Only `step_fused_tiled_multi_irr` and `sea_spectrum_sample` see the spectrum.  A spectrum and the sea of `set_sea`
+        exclude each other: the library refuses one while the other is set.  Synchronous, like `set_sea`."""
+        if spectrum is None:
+            self._check(self._lib.hydro_set_sea_spectrum(self._h, None))
+            self.spectrum_waves = None
+            return
+        waves = [tuple(float(x) for x in w) for w in spectrum.waves]
+        if len(waves) > nat.SPECTRUM_WAVES_MAX or any(len(w) != 5 for w in waves):
+            raise ValueError(f"a sea spectrum has at most {nat.SPECTRUM_WAVES_MAX} wave components of (amplitude, kx, ky, omega, phase)")
+        rows = (nat.SeaWave * len(waves))(*[nat.SeaWave(*w) for w in waves])     # (alive until the call returns: the library copies)
+        c = nat.SeaSpectrum()
+        c.current[:] = [float(x) for x in spectrum.current]
+        c.waves = len(waves)
+        c.wave = ctypes.cast(rows, ctypes.POINTER(nat.SeaWave)) if waves else None
+        self._check(self._lib.hydro_set_sea_spectrum(self._h, ctypes.byref(c)))
+        self.spectrum_waves = len(waves)
+
+    def sea_spectrum_sample(self, state: torch.Tensor, n: int, step_index: int, dt: float, out: torch.Tensor | None = None,
+                            stream=None) -> torch.Tensor:
+        """`sea_sample` against the spectrum set with `set_sea_spectrum` (hydro_sea_spectrum_sample): exactly the
+        [eta, u_x, u_y, u_z] `step_fused_tiled_multi_irr` uses for step `step_index`."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.SEA_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.SEA_FIELDS, n)
+        self._check(self._lib.hydro_sea_spectrum_sample(self._h, n, s_ptr, s_stride, int(step_index), float(dt), o_ptr, o_stride,
+                                                        self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_irr(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                   mooring: torch.Tensor | None = None, mooring_layers: int = 1,
+                                   tether: torch.Tensor | None = None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                   extremes: torch.Tensor | None = None,
+                                   control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                   log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_spread through the irregular sea set with `set_sea_spectrum`
+        (hydro_step_fused_tiled_multi_irr): the arguments and the rules are step_fused_tiled_multi_spread's, every option
+        optional, and the hydrodynamic wrench of every step is that of the state relative to the spectrum's water at
+        (step0 + k) * dt.  Without a spectrum the call is step_fused_tiled_multi_spread.  Returns the number of rows written
+        (0 without a log)."""
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_irr,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._spread_tail(n, step0, mooring, mooring_layers, tether, layers, peaks, extremes, control, applied, frame))
+
     # ------------------------------------------------------------------ seabed
     def set_seabed(self, bed) -> None:
         """The scene's floor (hydro_set_seabed; the model: include/hydro.h, "Seabed"): `bed` has `z`, `stiffness`, `damping`,
@@ -799,16 +851,19 @@ class HydroEngine:
         takes the largest tension of a body's lines.  mooring_layers=1 gives the bits of step_fused_tiled_multi_peak with the
         same record, mooring=None IS that call (and `mooring_layers` is not looked at).  Returns the number of rows written
         (0 without a log)."""
-        def extra():
-            tail = self._applied_control(applied, frame, control, n)
-            m_ptr, m_stride = self._spread(mooring, mooring_layers, n) if mooring is not None else (None, 0)
-            e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
-            t_ptr, t_stride = self._net(tether, layers, n) if tether is not None else (None, 0)
-            p_ptr, p_stride = self._tiled(peaks, int(layers), n) if peaks is not None else (None, 0)
-            return (*tail, m_ptr, m_stride, int(mooring_layers), e_ptr, e_stride, t_ptr, t_stride, int(layers), p_ptr, p_stride, int(step0))
         return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_spread,
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
-                                    (log, every, phase, row0), stream, extra)
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._spread_tail(n, step0, mooring, mooring_layers, tether, layers, peaks, extremes, control, applied, frame))
+
+    def _spread_tail(self, n, step0, mooring, mooring_layers, tether, layers, peaks, extremes, control, applied, frame):
+        """The arguments `applied .. step0` of `hydro_step_fused_tiled_multi_spread` / `_irr`: every buffer may be None (NULL, stride 0)."""
+        tail = self._applied_control(applied, frame, control, n)
+        m_ptr, m_stride = self._spread(mooring, mooring_layers, n) if mooring is not None else (None, 0)
+        e_ptr, e_stride = self._tiled(extremes, nat.EXT_FIELDS, n) if extremes is not None else (None, 0)
+        t_ptr, t_stride = self._net(tether, layers, n) if tether is not None else (None, 0)
+        p_ptr, p_stride = self._tiled(peaks, int(layers), n) if peaks is not None else (None, 0)
+        return (*tail, m_ptr, m_stride, int(mooring_layers), e_ptr, e_stride, t_ptr, t_stride, int(layers), p_ptr, p_stride, int(step0))
 
     def integrate_tiled(self, state_in: torch.Tensor, wrench: torch.Tensor, n: int, dt: float,
                         state_out: torch.Tensor | None = None, stream=None) -> torch.Tensor:

@@ -9,6 +9,9 @@ in fp64 NumPy - for plotting, for choosing a mooring, for checking a recorded tr
 
 with z_rel the depth of the point below the local surface (z - eta) and kappa_j = |k_j|.  The library takes omega and k
 as given; `regular` applies the deep-water dispersion relation omega^2 = g kappa.
+
+`SeaSpectrum` is the same model with up to 64 components - an irregular sea - and `pierson_moskowitz` / `jonswap` build one from
+a significant wave height and a peak period (include/hydro.h, "Sea spectrum").
 """
 from __future__ import annotations
 
@@ -17,9 +20,12 @@ import math
 import numpy as np
 
 WAVES_MAX = 8
+SPECTRUM_WAVES_MAX = 64
 
 
 class SeaState:
+    _CAP, _KIND = WAVES_MAX, "a sea"
+
     def __init__(self, current=(0.0, 0.0, 0.0)):
         cur = tuple(float(x) for x in current)
         if len(cur) != 3 or not all(math.isfinite(x) for x in cur):
@@ -36,8 +42,8 @@ class SeaState:
             raise ValueError("wave component: the amplitude must be >= 0")
         if w[0] != 0.0 and math.hypot(w[1], w[2]) == 0.0:
             raise ValueError("wave component: a wave with amplitude needs a wave vector")
-        if len(self.waves) >= WAVES_MAX:
-            raise ValueError(f"a sea has at most {WAVES_MAX} wave components")
+        if len(self.waves) >= self._CAP:
+            raise ValueError(f"{self._KIND} has at most {self._CAP} wave components")
         self.waves.append(w)
         return self
 
@@ -82,3 +88,114 @@ class SeaState:
             u[..., 1] += e * (ky / kappa) * np.cos(th)
             u[..., 2] += e * np.sin(th)
         return u
+
+
+class SeaSpectrum(SeaState):
+    """An irregular sea: the model of `SeaState` with up to 64 components, what `ClosedLoopSim.set_sea` and
+    `HydroEngine.set_sea_spectrum` take for a sea given by its spectrum (hydro_step_fused_tiled_multi_irr; include/hydro.h,
+    "Sea spectrum").  `pierson_moskowitz` and `jonswap` below cut a spectrum of significant wave height Hs and peak period Tp
+    into equal-energy bins; `add_wave` builds one by hand.  `elevation` and `velocity` are SeaState's, in fp64."""
+    _CAP, _KIND = SPECTRUM_WAVES_MAX, "a sea spectrum"
+
+    def hs(self) -> float:
+        """The significant wave height 4 sqrt(m0) of the components, m0 = sum a^2 / 2 (m)."""
+        return 4.0 * math.sqrt(sum(0.5 * w[0] * w[0] for w in self.waves))
+
+    @classmethod
+    def pierson_moskowitz(cls, hs, tp, heading_deg, **kw) -> "SeaSpectrum":
+        return pierson_moskowitz(hs, tp, heading_deg, **kw)
+
+    @classmethod
+    def jonswap(cls, hs, tp, heading_deg, **kw) -> "SeaSpectrum":
+        return jonswap(hs, tp, heading_deg, **kw)
+
+
+def pm_fraction(omega, omega_p):
+    """The Pierson-Moskowitz spectrum's cumulative energy fraction F(omega) = exp(-1.25 (omega_p / omega)^4)."""
+    omega = np.asarray(omega, np.float64)
+    with np.errstate(divide="ignore", over="ignore"):
+        return np.exp(-1.25 * (omega_p / omega) ** 4)
+
+
+def cos2_cdf(delta):
+    """The cumulative distribution of the spreading function (2 / pi) cos^2(delta) on (-pi/2, pi/2)."""
+    delta = np.asarray(delta, np.float64)
+    return 0.5 + (delta + np.sin(delta) * np.cos(delta)) / math.pi
+
+
+def cos2_offsets(n: int) -> np.ndarray:
+    """The n quantile midpoints of the cos^2 spreading function, ascending: cos2_cdf(delta_j) = (j + 1/2) / n (bisection to the
+    last bit of fp64)."""
+    target = (np.arange(n) + 0.5) / n
+    lo, hi = np.full(n, -0.5 * math.pi), np.full(n, 0.5 * math.pi)
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        below = cos2_cdf(mid) < target
+        lo, hi = np.where(below, mid, lo), np.where(below, hi, mid)
+    return 0.5 * (lo + hi)
+
+
+def jonswap_bin_medians(omega_p: float, gamma: float, n: int, grid: int = 1 << 16) -> np.ndarray:
+    """The medians of the n equal-energy bins of the JONSWAP spectrum
+        S(omega) ~ omega^-5 exp(-1.25 (omega_p / omega)^4) gamma^exp(-(omega - omega_p)^2 / (2 sigma^2 omega_p^2)),
+    sigma = 0.07 up to the peak and 0.09 above it.  The cumulative spectrum is the Pierson-Moskowitz closed form plus the
+    integral of the peak enhancement's EXCESS, S_PM (gamma^r - 1), which lives around the peak only: trapezoids on `grid` points,
+    uniform in log(omega) over omega_p / 4 .. 32 omega_p (the excess is below 1e-300 outside).  The inverse is linear
+    interpolation on that grid.  gamma = 1 has no excess and differs from the closed-form medians by the interpolation alone."""
+    w = omega_p * np.exp(np.linspace(math.log(0.25), math.log(32.0), grid))
+    sigma = np.where(w <= omega_p, 0.07, 0.09)
+    r = np.exp(-((w - omega_p) ** 2) / (2.0 * sigma * sigma * omega_p * omega_p))
+    s_pm = 5.0 * omega_p ** 4 * w ** -5.0 * np.exp(-1.25 * (omega_p / w) ** 4)        # dF / d omega
+    excess = s_pm * np.expm1(r * math.log(gamma))
+    cum = pm_fraction(w, omega_p) + np.concatenate(([0.0], np.cumsum(0.5 * (excess[1:] + excess[:-1]) * np.diff(w))))
+    total = 1.0 + (cum[-1] - pm_fraction(w[-1], omega_p))                              # (the tail above the grid is Pierson-Moskowitz's)
+    return np.interp((np.arange(n) + 0.5) / n * total, cum, w)
+
+
+def _from_bins(hs, omegas, heading_deg, seed, spread, current, g) -> SeaSpectrum:
+    n = len(omegas)
+    rng = np.random.default_rng(seed)
+    phases = rng.uniform(-math.pi, math.pi, n)
+    headings = np.full(n, math.radians(heading_deg))
+    if spread == "cos2":
+        headings = headings + cos2_offsets(n)[rng.permutation(n)]
+    elif spread is not None:
+        raise ValueError("spread must be None (long-crested) or 'cos2'")
+    a = hs / math.sqrt(8.0 * n)                                   # equal energy per bin: sum a^2 / 2 = hs^2 / 16
+    sea = SeaSpectrum(current)
+    for om, ph, hd in zip(omegas, phases, headings):
+        kappa = om * om / g
+        sea.add_wave(a, kappa * math.cos(hd), kappa * math.sin(hd), om, ph)
+    return sea
+
+
+def _check_sea(hs, tp, components, g):
+    if not hs >= 0.0 or not tp > 0.0 or not g > 0.0 or not math.isfinite(hs) or not math.isfinite(tp):
+        raise ValueError("hs must be >= 0, tp and g > 0")
+    if not 1 <= int(components) <= SPECTRUM_WAVES_MAX:
+        raise ValueError(f"components must be in 1 .. {SPECTRUM_WAVES_MAX}")
+
+
+def pierson_moskowitz(hs: float, tp: float, heading_deg: float, *, components: int = SPECTRUM_WAVES_MAX, seed: int = 0, spread=None,
+                      current=(0.0, 0.0, 0.0), g: float = 9.81) -> SeaSpectrum:
+    """A Pierson-Moskowitz sea of significant wave height `hs` (m) and peak period `tp` (s) travelling towards `heading_deg`,
+    as `components` deep-water components (kappa = omega^2 / g) of EQUAL ENERGY, in closed form: component j sits at the median
+    of bin j of the cumulative energy fraction F, omega_j = omega_p (1.25 / ln(N / (j + 1/2)))^(1/4), with amplitude
+    hs / sqrt(8 N).  Phases: numpy.random.default_rng(seed).uniform(-pi, pi, N).  spread="cos2": the headings are
+    heading + delta_j, delta_j the quantile midpoints of (2 / pi) cos^2 (`cos2_offsets`), dealt to the components by a
+    permutation drawn from the same generator, after the phases."""
+    _check_sea(hs, tp, components, g)
+    n, omega_p = int(components), 2.0 * math.pi / tp
+    omegas = omega_p * (1.25 / np.log(n / (np.arange(n) + 0.5))) ** 0.25
+    return _from_bins(hs, omegas, heading_deg, seed, spread, current, g)
+
+
+def jonswap(hs: float, tp: float, heading_deg: float, *, gamma: float = 3.3, components: int = SPECTRUM_WAVES_MAX, seed: int = 0, spread=None,
+            current=(0.0, 0.0, 0.0), g: float = 9.81) -> SeaSpectrum:
+    """`pierson_moskowitz` for the JONSWAP spectrum of peak enhancement `gamma` (>= 1): the same equal-energy binning, the bin
+    medians from the numerically integrated and inverted cumulative spectrum (`jonswap_bin_medians`); the spectrum is scaled
+    so that the components carry hs^2 / 16 exactly.  gamma = 1 is the Pierson-Moskowitz sea."""
+    _check_sea(hs, tp, components, g)
+    if not gamma >= 1.0 or not math.isfinite(gamma):
+        raise ValueError("gamma must be >= 1")
+    return _from_bins(hs, jonswap_bin_medians(2.0 * math.pi / tp, float(gamma), int(components)), heading_deg, seed, spread, current, g)

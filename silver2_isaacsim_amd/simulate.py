@@ -28,6 +28,7 @@ from . import scenes
 from .engine import HydroEngine
 from .extremes import Extremes
 from .mooring import Mooring, MooringSpread
+from .sea import SeaSpectrum
 from .tether import LinkTensions, Tether, TetherNet
 
 
@@ -544,19 +545,30 @@ class ClosedLoopSim:
         the model: include/hydro.h), with the wave phase following `steps_done` - also between the steps of a resident
         launch.  It acts together with an applied wrench, a pose hold and a recorder where those are set.  Graph replays
         (`run` with graph_steps) work for a current-only sea; with waves they raise ValueError - a captured launch would
-        replay a frozen time.  The sea stays until the next call or `clear_sea()`."""
+        replay a frozen time.  The sea stays until the next call or `clear_sea()`.
+        `sea` may also be a `sea.SeaSpectrum`, an irregular sea of up to 64 components (hydro_step_fused_tiled_multi_irr;
+        include/hydro.h, "Sea spectrum"): `sim.sea` is the one slot for either kind, every other option rides along as before,
+        and a spectrum with components stays out of graph replays like a sea with waves."""
         if not self.fused:
             raise ValueError("the sea state lives in the fused step kernels (fused=True)")
         self.synchronize()                                      # launches in flight read the table this rewrites
-        self.engine.set_sea(sea)
+        irregular = isinstance(sea, SeaSpectrum)
+        if self.sea is not None and isinstance(self.sea, SeaSpectrum) != irregular:
+            self._set_engine_sea(self.sea, None)                # the library holds a sea or a spectrum, never both: the other kind goes first
+            self.sea = None
+        self._set_engine_sea(sea, sea)
         self.sea = sea
         self._graph = None                                      # captured steps are of another entry / another sea
+
+    def _set_engine_sea(self, kind, sea) -> None:
+        """`sea` (or None: clear) to the engine call of `kind`'s kind."""
+        (self.engine.set_sea_spectrum if isinstance(kind, SeaSpectrum) else self.engine.set_sea)(sea)
 
     def clear_sea(self) -> None:
         """Back to still water: every call the sim makes is again the one it made before set_sea."""
         if self.sea is not None:
             self.synchronize()
-            self.engine.set_sea(None)
+            self._set_engine_sea(self.sea, None)
             self.sea = None
             self._graph = None
 
@@ -839,7 +851,8 @@ class ClosedLoopSim:
         if self.link_tensions is not None:
             self.link_tensions.links, self.link_tensions.layer = self._tether_links
 
-    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
+    # the sea spectrum if `sim.sea` is one (its entry takes every other option), else with
     # the mooring spread if one is set (its entry takes every other option), else with
     # the link tensions if they are tracked (over the net, or over the tethers as a net of one layer), else with
     # the tether net if one is set, else with
@@ -856,7 +869,15 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.mooring_spread is not None:
+        if isinstance(self.sea, SeaSpectrum):
+            # (the entry of the spread, every option optional: set_mooring's single record rides as a spread of one layer)
+            moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
+            net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
+            rows = e.step_fused_tiled_multi_irr(*args, k, self.steps_done, moor, moor_layers, net, layers,
+                                                self.link_tensions.buffer if self.link_tensions is not None else None,
+                                                self.extremes.buffer if self.extremes is not None else None,
+                                                self.control, self.applied, self.applied_frame, **kw)
+        elif self.mooring_spread is not None:
             net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
             rows = e.step_fused_tiled_multi_spread(*args, k, self.steps_done, self.mooring_spread, self.mooring_layers, net, layers,
                                                    self.link_tensions.buffer if self.link_tensions is not None else None,
@@ -965,7 +986,7 @@ class ClosedLoopSim:
                              "frozen at capture - use run_resident (or run_eager), or stop_recording() first")
         if self.sea is not None and len(self.sea.waves) and graph_steps and steps >= graph_steps:
             raise ValueError("a sea with waves cannot ride in graph replays: the time a captured launch steps at is frozen at "
-                             "capture - use run_resident (or run_eager); a current-only sea replays")
+                             "capture - use run_resident (or run_eager); a current-only sea replays")     # (a sea spectrum is a sea here)
         self._warm_monitor()
         if graph_steps and steps >= graph_steps:
             if self.steps_done % graph_steps and self.monitor is not None:
