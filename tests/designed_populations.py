@@ -211,9 +211,9 @@ def rest_report(bed, state, params, ratios, g=scenes.G):
             np.abs(delta.max(axis=1) - g * (1.0 - 1.0 / ratios) / (4.0 * bed.stiffness)))
 
 
-def contributing_corners(st, pr):
-    """(n,) the most corners seabed_reference counts on a body: decided in fp64 and as the kernel decides, whichever is more."""
-    return np.maximum(br.corner_count(BED, st, pr), br.corner_count(BED, st, pr, br.touching_fp32(BED, st, pr)))
+def contributing_corners(st, pr, bed=BED):
+    """(n,) the most corners seabed_reference counts on a body over `bed`: decided in fp64 and as the kernel decides, whichever is more."""
+    return np.maximum(br.corner_count(bed, st, pr), br.corner_count(bed, st, pr, br.touching_fp32(bed, st, pr)))
 
 
 def tilted_boxes(st, pv, pr, seed=2028):

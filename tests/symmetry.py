@@ -17,6 +17,20 @@ ones.  Scalars (dimensions, coefficients, mass, gains, limits, lengths, the bed'
 phases, eta, the submersion ratio, energies, tensions) do not change.  An extremes record swaps min and max of a flipped
 axis: min' = -max, max' = -min.
 
+The records of the later rungs, stated once like the rest:
+
+    record              shape       image
+    tether              (n, 7)      [b | L0 | k | c | partner]: the fairlead b (body frame) is polar; L0, k, c keep their values
+                                    and so does the partner LANE - the maps do not renumber bodies
+    net                 (n, 7 L)    a tether record per layer, each mapped as `tether`
+    spread              (n, 9 L)    a mooring record per layer, each mapped as `mooring`
+    link tensions       (n, L)      scalars: the same bits (and so is tension_max of the extremes record)
+    sea                 -           `sea()` serves BOTH kinds of sea, sea.SeaState and sea.SeaSpectrum (it builds type(s)): the
+                                    current and every component's (kx, ky) are polar, amplitude, omega and phase scalars
+
+The sums the later rungs add - over a net's or a spread's layers, over a spectrum's components - run in an order the maps do
+not permute (unlike the bed's corners), so they keep the predicate without a tolerance.
+
 One function per record kind; each returns the IMAGE of a record (the maps are involutions: the image of the image is the
 record).  `equal` is the predicate: float equality with NaN == NaN, so -0 == +0 (a dry body returns +0 and the image of +0
 is -0) - no tolerance.
@@ -70,6 +84,25 @@ def mooring(g, m):
     return _times(m, POLAR[g] + POLAR[g] + SAME3)
 
 
+def tether(g, rec):
+    """(n, 7) tether record [fairlead b (body) | L0 | k | c | partner lane]: b is polar, the rest - the partner included - unchanged."""
+    return _times(rec, POLAR[g] + (1, 1, 1, 1))
+
+
+def net(g, rec):
+    """(n, 7 L) tether net: `tether`, layer by layer."""
+    rec = np.asarray(rec)
+    assert rec.ndim == 2 and rec.shape[1] % 7 == 0, rec.shape
+    return np.concatenate([tether(g, rec[:, 7 * l:7 * l + 7]) for l in range(rec.shape[1] // 7)], axis=1)
+
+
+def spread(g, rec):
+    """(n, 9 L) mooring spread: `mooring`, layer by layer."""
+    rec = np.asarray(rec)
+    assert rec.ndim == 2 and rec.shape[1] % 9 == 0, rec.shape
+    return np.concatenate([mooring(g, rec[:, 9 * l:9 * l + 9]) for l in range(rec.shape[1] // 9)], axis=1)
+
+
 def extremes(g, e):
     """(n, 8) [x_min x_max | y_min y_max | z_min z_max | speed2_max | tension_max]: a flipped axis swaps its pair."""
     e = np.asarray(e)
@@ -81,7 +114,8 @@ def extremes(g, e):
 
 
 def sea(g, s):
-    """A sea.SeaState: the current and the wave vector (kx, ky) are polar - never a heading angle."""
+    """A sea.SeaState or a sea.SeaSpectrum (the image is of the same kind): the current and the wave vector (kx, ky) are polar -
+    never a heading angle."""
     sx, sy, sz = POLAR[g]
     out = type(s)((sx * s.current[0], sy * s.current[1], sz * s.current[2]))
     for a, kx, ky, om, ph in s.waves:
@@ -90,7 +124,7 @@ def sea(g, s):
 
 
 def sea_sample(g, w):
-    """(n, 4) [eta | u] of hydro_sea_sample."""
+    """(n, 4) [eta | u] of hydro_sea_sample and hydro_sea_spectrum_sample."""
     return _times(w, (1,) + POLAR[g])
 
 

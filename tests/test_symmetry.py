@@ -13,6 +13,14 @@
     rotation), so there the wrong hand is the vector left unturned.
 (d) The populations of tests/test_symmetry_gpu.py are what its comparisons need: shares of bodies on the bed with exactly
     one and with two or more corners, decided by seabed_reference.
+(e) The later rungs - tether, tether net, mooring spread, wave spectrum: tether_reference (wrench, tension, both decisions, the
+    fp32 emulation, the scales), tether_net_reference, mooring_spread_reference, sea_reference.water on the designed spectrum of
+    sea_spectrum_reference and closed_loop_reference.closed_loop with a tether over 7 implicit steps are all EXACTLY symmetric
+    and asserted so: the sums over layers and components keep their order under the maps, and the closed loop rounds every
+    step's wrench and state to fp32, which hides the oracle's 1e-12 on this population (observed, not derived: the assertion
+    says so if it stops holding).  Teeth: the tether's fairlead turned like an axial vector, a spread with one layer left
+    unmapped, a spectrum whose ky is not flipped under mirror_y.  And the population of the resident rungs
+    (tests/symmetry_population.py) is what tests/test_symmetry_gpu.py needs: few order-sensitive bodies, enough lines pulling.
 """
 import ctypes
 import os
@@ -23,11 +31,16 @@ import pytest
 
 import extremes_reference as er
 import mooring_reference as mr
+import mooring_spread_reference as msr
 import populations
 import pose_hold_reference as phr
 import sea_reference as sr
+import sea_spectrum_reference as ssr
 import seabed_reference as br
 import symmetry as sym
+import symmetry_population
+import tether_net_reference as tnr
+import tether_reference as tr
 from closed_loop_reference import closed_loop
 from conftest import REPO, accel_of, load_golden
 from oracle import c_oracle
@@ -355,3 +368,188 @@ def test_probe_population_has_single_and_multiple_corner_bodies(n, bed_pop):
     one, more = (count == 1).mean(), (count >= 2).mean()
     print(f"[seabed probe population, n = {n}] one corner {one:.1%}, two or more {more:.1%}, none {(count == 0).mean():.1%}")
     assert one >= 0.25 and more >= 0.10
+
+
+# ---- (e) tether, net, spread and spectrum -------------------------------------------------------------------------------------------------
+SIZES = (200, 321)
+FULL = ssr.designed_spectrum()
+
+
+@pytest.fixture(scope="module")
+def reseated():
+    return symmetry_population.reseated_population()
+
+
+def _net_states(reseated, n):
+    """The states the designed net is held on: as tether_net_population draws them, and reseated."""
+    return (("drawn", reseated["drawn"][:n]), ("reseated", reseated["st"][:n]))
+
+
+@MAPS
+@pytest.mark.parametrize("n", SIZES)
+def test_tether_reference_is_exactly_symmetric(g, n, reseated):
+    """Layers 0 and 1 of the designed net: wrench, tension, both decisions, the fp32 emulation and the scales.  The image flips the
+    fairlead as a polar vector and leaves L0, k, c and the partner lane alone."""
+    for layer, rec in enumerate(tnr.layers_of(symmetry_population.net_of(reseated, n))):
+        rec_g = sym.tether(g, rec)
+        assert np.array_equal(rec_g[:, 3:7], rec[:, 3:7]) and np.array_equal(tr.partner(rec_g), tr.partner(rec))
+        for name, st in _net_states(reseated, n):
+            image = sym.state(g, st)
+            what = (g, n, layer, name)
+            assert np.array_equal(tr.taut(rec_g, image), tr.taut(rec, st)) and np.array_equal(tr.taut_fp32(rec_g, image), tr.taut_fp32(rec, st)), what
+            assert sym.equal(tr.tension(rec_g, image), tr.tension(rec, st)), what
+            assert sym.equal(tr.wrench(rec_g, image), sym.wrench(g, tr.wrench(rec, st))), what
+            w, t = tr.wrench_fp32_emulated(rec, st, with_tension=True)
+            w_g, t_g = tr.wrench_fp32_emulated(rec_g, image, with_tension=True)
+            assert sym.equal(w_g, sym.wrench(g, w)) and sym.equal(t_g, t), what
+            assert sym.equal(tr.wrench_scales(rec_g, image), tr.wrench_scales(rec, st)) and sym.equal(tr.tension_scale(rec_g, image), tr.tension_scale(rec, st)), what
+            assert (tr.tension(rec, st) > 0).mean() >= 0.2, what
+
+
+@MAPS
+@pytest.mark.parametrize("n", SIZES)
+def test_tether_net_reference_is_exactly_symmetric(g, n, reseated):
+    """All four layers: the sum over the layers runs in layer order on the scene and on the image."""
+    net = symmetry_population.net_of(reseated, n, 4)
+    net_g = sym.net(g, net)
+    for name, st in _net_states(reseated, n):
+        image = sym.state(g, st)
+        assert sym.equal(tnr.wrench(net_g, image), sym.wrench(g, tnr.wrench(net, st))), (g, n, name)
+        assert sym.equal(tnr.tensions(net_g, image), tnr.tensions(net, st)) and np.array_equal(tnr.pulls(net_g, image), tnr.pulls(net, st)), (g, n, name)
+        assert sym.equal(tnr.wrench_scales(net_g, image), tnr.wrench_scales(net, st)), (g, n, name)
+        assert (tnr.pulls(net, st).sum(axis=0) >= 2).sum() >= 16
+
+
+@MAPS
+@pytest.mark.parametrize("n", SIZES)
+def test_mooring_spread_reference_is_exactly_symmetric(g, n, reseated):
+    """mooring_spread_reference on spread_population, all four layers (three with lines)."""
+    st, spread = reseated["st"][:n], reseated["spread"][:n]
+    image, spread_g = sym.state(g, st), sym.spread(g, spread)
+    assert sym.equal(msr.wrench(spread_g, image), sym.wrench(g, msr.wrench(spread, st)))
+    assert sym.equal(msr.tensions(spread_g, image), msr.tensions(spread, st)) and np.array_equal(msr.pulls(spread_g, image), msr.pulls(spread, st))
+    assert sym.equal(msr.wrench_scales(spread_g, image), msr.wrench_scales(spread, st))
+    on = [mr.taut_fp32(np.ascontiguousarray(rec), st) for rec in msr.layers_of(spread)]
+    on_g = [mr.taut_fp32(np.ascontiguousarray(rec), image) for rec in msr.layers_of(spread_g)]
+    assert all(np.array_equal(a, b) for a, b in zip(on_g, on))
+    assert sym.equal(msr.wrench(spread_g, image, on_g), sym.wrench(g, msr.wrench(spread, st, on)))
+    assert (msr.pulls(spread, st).sum(axis=0) >= 2).sum() >= 16
+
+
+@MAPS
+@pytest.mark.parametrize("count", [11, 64])
+def test_spectrum_reference_is_exactly_symmetric(g, count, reseated, designed):
+    """sea_reference.water of symmetry.sea(g, spectrum) - a SeaSpectrum again - at steps 0 and 10^6: the sum over the components
+    runs in component order on both sides."""
+    spec = ssr.truncated(FULL, count)
+    spec_g = sym.sea(g, spec)
+    assert type(spec_g) is type(spec) and len(spec_g.waves) == count
+    for st in (reseated["st"], designed[0]):
+        image = sym.state(g, st)
+        for step in (0, 10 ** 6):
+            eta, u = sr.water(spec, st[:, 0], st[:, 1], st[:, 2], step, DT)
+            eta_g, u_g = sr.water(spec_g, image[:, 0], image[:, 1], image[:, 2], step, DT)
+            assert sym.equal(eta_g, eta) and sym.equal(u_g, sym._times(u, sym.POLAR[g])), (g, count, step)
+            assert eta.all() and u.all()
+
+
+@MAPS
+@pytest.mark.parametrize("n", SIZES)
+def test_closed_loop_with_a_tether_is_exactly_symmetric(g, n, reseated):
+    """closed_loop_reference.closed_loop with teth= (layer 0 of the net) over 7 implicit steps: every step's state, rounded wrench and
+    tension.  The hydrodynamic oracle inside it is symmetric to 1e-12 only (its keypoint and face sums run in an order the maps
+    permute), but the loop rounds the summed wrench and the state to fp32 in every step, and on this population no rounding falls
+    the other way: exact, as observed."""
+    st, pv, pr = reseated["st"][:n], reseated["pv"][:n], reseated["params"]["f32"][:n]
+    rec = symmetry_population.net_of(reseated, n, 1)
+    ref = closed_loop(st, pv, pr, RHO, G, DT, 7, teth=rec, implicit=True)
+    got = closed_loop(sym.state(g, st), sym.prev(g, pv), pr, RHO, G, DT, 7, teth=sym.tether(g, rec), implicit=True)
+    pulled = np.zeros(n, bool)
+    for j, (a, b) in enumerate(zip(got, ref)):
+        assert sym.equal(a["state"], sym.state(g, b["state"])), (g, n, j)
+        assert sym.equal(a["wrench"], sym.wrench(g, b["wrench"])), (g, n, j)
+        assert sym.equal(a["tether_line"], sym.wrench(g, b["tether_line"])) and sym.equal(a["tether_tension"], b["tether_tension"]), (g, n, j)
+        assert np.array_equal(a["tether_taut"], b["tether_taut"]), (g, n, j)
+        pulled |= b["tether_tension"] > 0
+    assert np.isfinite(ref[-1]["state"]).all() and pulled.mean() >= 0.2
+
+
+# teeth
+@MAPS
+@pytest.mark.parametrize("n", SIZES)
+def test_teeth_an_axial_fairlead_breaks_the_tethers_equality(g, n, reseated):
+    """The image built with the tether's fairlead b turned like an axial vector (under the half turn: left unturned): wrench or
+    tension differ from the image's on at least half of the bodies whose tether pulls, in both layers."""
+    st = reseated["st"][:n]
+    image = sym.state(g, st)
+    for layer, rec in enumerate(tnr.layers_of(symmetry_population.net_of(reseated, n))):
+        wrong = sym.tether(g, rec)
+        wrong[:, 0:3] = sym._times(rec[:, 0:3], sym.AXIAL[g] if g != "half_turn" else sym.SAME3)
+        act = tr.tension(rec, st) > 0
+        assert act.sum() >= 0.2 * n
+        bad = sym.differing(tr.wrench(wrong, image), sym.wrench(g, tr.wrench(rec, st))) | sym.differing(tr.tension(wrong, image), tr.tension(rec, st))
+        print(f"[teeth, the tether's fairlead with the wrong hand, {g}, n = {n}, layer {layer}] pulling: {int(act.sum())} bodies; differing: {bad[act].mean():.1%}")
+        assert bad[act].mean() >= 0.5
+
+
+@MAPS
+@pytest.mark.parametrize("n", SIZES)
+def test_teeth_a_spread_with_one_layer_left_unmapped_breaks_the_equality(g, n, reseated):
+    """Layer 0 mapped, layer 1 left as it is: the spread's wrench differs on at least half of the bodies whose layer-1 line pulls
+    (on the scene), and on none of the others."""
+    st, spread = reseated["st"][:n], reseated["spread"][:n]
+    image = sym.state(g, st)
+    wrong = sym.spread(g, spread)
+    wrong[:, 9:18] = spread[:, 9:18]
+    act = msr.pulls(spread, st)[1]
+    assert act.sum() >= 0.3 * n
+    want = sym.wrench(g, msr.wrench(spread, st))
+    bad = sym.differing(msr.wrench(wrong, image), want)
+    print(f"[teeth, a spread whose layer 1 is not mapped, {g}, n = {n}] layer 1 pulls: {int(act.sum())} bodies; differing: {bad[act].mean():.1%}")
+    assert bad[act].mean() >= 0.5
+    assert not sym.differing(msr.wrench(sym.spread(g, spread), image), want).any()
+
+
+@pytest.mark.parametrize("count", [11, 64])
+def test_teeth_a_spectrum_whose_ky_is_not_flipped_breaks_the_equality(count, reseated):
+    """mirror_y with every component's ky left alone - a wave vector handled as if only the bodies moved: eta or u differ on at
+    least half of the bodies (all of them feel the sea)."""
+    g = "mirror_y"
+    spec = ssr.truncated(FULL, count)
+    wrong = type(spec)(sym.sea(g, spec).current)                  # the current is mapped as it should be
+    for w in spec.waves:
+        wrong.add_wave(*w)
+    st = reseated["st"]
+    image = sym.state(g, st)
+    for step in (0, 10 ** 6):
+        eta, u = sr.water(spec, st[:, 0], st[:, 1], st[:, 2], step, DT)
+        eta_w, u_w = sr.water(wrong, image[:, 0], image[:, 1], image[:, 2], step, DT)
+        bad = sym.differing(eta_w, eta) | sym.differing(u_w, sym._times(u, sym.POLAR[g]))
+        print(f"[teeth, a spectrum whose ky is not flipped, {count} components, step {step}] differing: {bad.mean():.1%} of {len(st)} bodies")
+        assert bad.mean() >= 0.5
+
+
+# the population of the resident rungs
+@pytest.mark.parametrize("n", SIZES)
+def test_reseated_population_is_what_the_resident_rungs_need(n, reseated):
+    """tests/symmetry_population.py, by the references alone: at most 25 % of the bodies stand on two or more contributing corners on
+    the scene or any of its three images (before reseating: more than half, so reseating is not optional); in each of the net's
+    two layers at least 20 % of the bodies are pulled by their tether; in each of the spread's layers 0 and 1 at least 30 % by
+    their line."""
+    st, pr = reseated["st"][:n], reseated["params"]["f32"][:n]
+    count = contributing_corners(st, pr)
+    for g in sym.MAPS:
+        count = np.maximum(count, contributing_corners(sym.state(g, st), pr))
+    many = count >= 2
+    drawn = contributing_corners(reseated["drawn"][:n], pr) >= 2
+    net = tnr.pulls(symmetry_population.net_of(reseated, n), st).mean(axis=1)
+    lines = msr.pulls(reseated["spread"][:n], st).mean(axis=1)
+    print(f"[reseated population, n = {n}] two or more corners on the scene or an image: {int(many.sum())} ({many.mean():.1%}; as drawn {drawn.mean():.1%}); "
+          f"tether pulls: layer 0 {net[0]:.1%}, layer 1 {net[1]:.1%}; line pulls: layer 0 {lines[0]:.1%}, layer 1 {lines[1]:.1%}, layer 2 {lines[2]:.1%}")
+    assert many.mean() <= 0.25 and drawn.mean() > 0.5
+    assert (net >= 0.2).all()
+    assert (lines[0:2] >= 0.3).all() and lines[2] > 0 and lines[3] == 0
+    # the spread and the lines are those of the moved states: layer 0 is the lines, and an unmoved body keeps its drawn record
+    assert np.array_equal(reseated["spread"][:n, 0:9], reseated["lines"][:n])
+    still = reseated["st"][:n, 2] == reseated["drawn"][:n, 2]
+    assert still[:8].all() and 0.1 <= still.mean() <= 0.5

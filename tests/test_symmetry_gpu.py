@@ -48,6 +48,20 @@ ON AN MI355X (f32 and f16 coefficients, both semantics, explicit and implicit dr
                         order-insensitive differs in any row.
   everything on         with non_temporal = 1 and under Warp semantics: as above (69 .. 72 of 321 left out after 7 implicit steps)
   ClosedLoopSim         64 moored buoys and their mirror_y image, 20 steps in chunks of 7: 0 bodies differ
+  later probes          hydro_tether_wrench (wrench and tension, both layers of the net; 28 % / 26 % of 200 and 29 % / 27 % of 321
+                        bodies pulled), hydro_mooring_wrench on each of the spread's four layers (37 % / 44 % / 7 % / none of 200,
+                        36 % / 46 % / 4 % / none of 321) and hydro_sea_spectrum_sample at 11 and 64 components, steps 0 and 10^6:
+                        0 differ
+  later rungs           teth, net, peak, spread, irr, everything on, on tests/symmetry_population.py.  Over FAR at 1 and 7 steps:
+                        200 / 321 exact, none left out, under implicit drag and after one explicit step - log, state, prev_out,
+                        extremes, link tensions and the energy pair; after 7 explicit steps 7 .. 14 of 200 and 8 .. 19 of 321 have
+                        been thrown through FAR's plane and are left out (test_later_rungs_are_exactly_symmetric), the others
+                        exact.  Over BED, one step: 175 / 277 exact, 25 / 44 left out (12 % / 14 %), every entry, either drag,
+                        f32 and f16.  0 bodies differ.
+  irr variants          non_temporal = 1 and Warp semantics, FAR, 7 steps, n = 321: 321 exact under implicit drag (explicit:
+                        302 / 303 exact, 19 / 18 thrown through FAR's plane)
+  teeth on the device   the net's fairleads turned like axial vectors: 48 .. 58 % of the bodies differ from the predicted image
+                        after one step; the spectrum's ky not flipped under mirror_y: 100 %
 So every device entry is exactly sign-symmetric under all three maps, but for the bed's corner sum - an order asymmetry, not
 a term of the wrong hand: no body with fewer than two contributing corners ever differs."""
 import numpy as np
@@ -56,8 +70,10 @@ import torch
 
 import populations
 import sea_reference as sr
+import sea_spectrum_reference as ssr
 import seabed_reference as br
 import symmetry as sym
+import symmetry_population
 from conftest import load_golden
 from oracle import hydro_oracle as ho
 from oracle import integrator_oracle as io
@@ -70,12 +86,14 @@ from designed_populations import BED, bed_pop, contributing_corners, FAR, hold_p
 from mooring_population import _buoys, DEPTH, line_population, moored_pop as pop  # noqa: F401  (fixtures are requested by name)
 from resident_harness import _buffers, COEFFS, DEV, DRAG, DT, _from, G, _ke, NAN, RHO, _tiled
 from seabed_reference import PROBE_BOUND
+from tether_net_population import net_for
 
 pytestmark = pytest.mark.gpu
 SIZES = (200, 321)
 STEPS = (1, 7)
 SEMANTICS = ("numba", "warp")
 STEP0 = 11
+FULL = ssr.designed_spectrum()                                    # 64 components, U = (0.5, -0.2, 0.05)
 TWO_WAVES = SeaState((0.5, -0.2, 0.05)).add_wave(*SEA.waves[0]).add_wave(*SEA.waves[1])
 
 
@@ -93,6 +111,7 @@ def engines(native_built):
         eng = made[k]
         eng.set_tuning()
         eng.set_semantics("numba")
+        eng.set_sea_spectrum(None)
         eng.set_sea(None)
         eng.set_seabed(None)
         eng.set_watch(None)
@@ -335,24 +354,55 @@ def resident_pops(pop):
 
 ENTRIES = ("rec", "app-world", "app-body", "ctl", "ctl+app", "sea", "bed", "moor", "ext", "all", "all-far")
 WITH_BED = ("bed", "moor", "ext", "all")
+LATER = ("teth", "net", "peak", "spread", "irr")                  # the rungs behind _ext: each launched with everything it takes
 
 
-def _resident(eng, entry, P, n, steps, implicit, m=None):
+def _wrong_hand(m, what, net, sea):
+    """(net, sea): the images of the scene's `net` and `sea` under m with ONE of them of the wrong hand, for the teeth.  `tether`:
+    every fairlead of the net turned like an axial vector (under the half turn, where polar and axial vectors turn alike: left
+    unturned); `ky`: the sea's ky left as the scene has it."""
+    net_g, sea_g = sym.net(m, net), sym.sea(m, sea)
+    if what == "tether":
+        hand = sym.AXIAL[m] if m != "half_turn" else sym.SAME3
+        for l in range(net.shape[1] // 7):
+            net_g[:, 7 * l:7 * l + 3] = sym._times(net[:, 7 * l:7 * l + 3], hand)
+    elif what == "ky":
+        wrong = type(sea)(sea_g.current)
+        for (a, kx, _, om, ph), (_, _, ky, _, _) in zip(sea_g.waves, sea.waves):
+            wrong.add_wave(a, kx, ky, om, ph)
+        sea_g = wrong
+    else:
+        raise ValueError(what)
+    return net_g, sea_g
+
+
+def _resident(eng, entry, P, n, steps, implicit, m=None, bed=BED, wrong=None):
     """One launch of `entry` on the population P (m: on its image under that map), every body watched and every step
     recorded with its wrench; returns the outputs MAPPED BACK (the image of the image's outputs): dict of state, prev_out,
-    log (steps, n, 19), and where the entry has them extremes and ke."""
-    st, pv, params, applied, ctl, rec = (x if isinstance(x, dict) else x[:n] for x in P)
+    log (steps, n, 19), and where the entry has them extremes, ke and the link tensions (peaks).  The LATER entries take two
+    more records of P - the tether net (all bodies, all layers: cut to n by tether_net_population.net_for) and the mooring spread -
+    and the bed they run over (`bed`); `wrong`: see _wrong_hand."""
+    st, pv, params, applied, ctl, rec = (x if isinstance(x, dict) else x[:n] for x in P[:6])
+    later = entry in LATER
+    net = net_for(P[6], n, 1 if entry == "teth" else symmetry_population.NET_LAYERS) if later else None
+    spread = np.ascontiguousarray(P[7][:n, 0:9 * symmetry_population.SPREAD_LAYERS]) if later else None
     ident = m is None
+    sea = FULL if entry == "irr" else SEA
     if not ident:
         st, pv, applied, ctl, rec = sym.state(m, st), sym.prev(m, pv), sym.applied(m, applied), sym.control(m, ctl), sym.mooring(m, rec)
-    sea = SEA if ident else sym.sea(m, SEA)
+        if wrong is not None:
+            net, sea = _wrong_hand(m, wrong, net, sea)
+        else:
+            net, sea = (sym.net(m, net) if later else None), sym.sea(m, sea)
+        spread = sym.spread(m, spread) if later else None
     eng.set_watch(list(range(n)))
     cur, old = _buffers(st, pv, n)
     log = torch.full((steps, 19, n), NAN, dtype=torch.float32, device=DEV)
     a, c17, m9 = _tiled(applied), _tiled(ctl), _tiled(rec)
     kw = dict(implicit_drag=implicit)
     rk = dict(log=log, every=1, phase=1, row0=0)
-    ke = record = None
+    ke = record = peaks = None
+    eng.set_sea_spectrum(None)
     eng.set_sea(None)
     eng.set_seabed(None)
     if entry == "rec":
@@ -371,6 +421,30 @@ def _resident(eng, entry, P, n, steps, implicit, m=None):
         eng.set_sea(sea)
         eng.set_seabed(BED)
         eng.step_fused_tiled_multi_moor(cur, old, n, DT, steps, STEP0, m9, **rk, **kw)
+    elif later:
+        # everything the entry takes: log, body-frame applied wrench, pose hold, sea (irr: the 64-component spectrum), bed, lines
+        # (spread, irr: the spread of three), extremes seeded from the state, the net (teth: one layer), link tensions, ke_out
+        if entry == "irr":
+            eng.set_sea_spectrum(sea)
+        else:
+            eng.set_sea(sea)
+        eng.set_seabed(bed)
+        record = torch.full((eng.tiles(n), 8, 64), NAN, dtype=torch.float32, device=DEV)
+        eng.extremes_reset(record, n, cur)
+        ke = _ke()
+        t7 = _tiled(net)
+        tail = dict(control=c17, applied=a, frame="body", ke_out=ke, **rk, **kw)
+        if entry == "teth":
+            eng.step_fused_tiled_multi_teth(cur, old, n, DT, steps, STEP0, t7, record, m9, **tail)
+        elif entry == "net":
+            eng.step_fused_tiled_multi_net(cur, old, n, DT, steps, STEP0, t7, net.shape[1] // 7, record, m9, **tail)
+        else:
+            peaks = eng.alloc_tiled(net.shape[1] // 7, n)
+            if entry == "peak":
+                eng.step_fused_tiled_multi_peak(cur, old, n, DT, steps, STEP0, t7, net.shape[1] // 7, peaks, record, m9, **tail)
+            else:
+                step = eng.step_fused_tiled_multi_irr if entry == "irr" else eng.step_fused_tiled_multi_spread
+                step(cur, old, n, DT, steps, STEP0, _tiled(spread), spread.shape[1] // 9, t7, net.shape[1] // 7, peaks, record, **tail)
     else:
         eng.set_sea(sea)
         eng.set_seabed(FAR if entry == "all-far" else BED)
@@ -388,6 +462,10 @@ def _resident(eng, entry, P, n, steps, implicit, m=None):
         out["extremes"] = _from(record, n)
     if ke is not None:
         out["ke"] = _np(ke)
+    if peaks is not None:
+        out["peaks"] = _from(peaks, n)                               # scalars: the image's are the scene's
+    if later:
+        eng.set_sea_spectrum(None)
     if not ident:
         out["state"], out["prev_out"], out["log"] = sym.state(m, out["state"]), sym.prev(m, out["prev_out"]), sym.log_row(m, out["log"])
         if record is not None:
@@ -395,15 +473,15 @@ def _resident(eng, entry, P, n, steps, implicit, m=None):
     return out, st
 
 
-def _sensitive_from(st0, log, pr):
-    """(n,) the first step (0-based row) whose INPUT state has two or more contributing corners; `steps` if none has.  The
-    input of row 0 is st0, of row j the state row j - 1 recorded."""
+def _sensitive_from(st0, log, pr, bed=BED):
+    """(n,) the first step (0-based row) whose INPUT state has two or more contributing corners on `bed`; `steps` if none has.
+    The input of row 0 is st0, of row j the state row j - 1 recorded."""
     steps, n = log.shape[0], log.shape[1]
     first = np.full(n, steps)
     for j in range(steps - 1, -1, -1):
         s = st0 if j == 0 else log[j - 1, :, 0:13]
         with np.errstate(all="ignore"):
-            many = contributing_corners(np.nan_to_num(s, nan=0.0, posinf=0.0, neginf=0.0), pr) >= 2
+            many = contributing_corners(np.nan_to_num(s, nan=0.0, posinf=0.0, neginf=0.0), pr, bed) >= 2
         first = np.where(many, j, first)
     return first
 
@@ -417,7 +495,7 @@ def _compare(entry, want, got, first, what):
         bad = sym.differing(got["log"][j][live], want["log"][j][live])
         assert not bad.any(), what + ("log row", j, int(bad.sum()), np.nonzero(live)[0][bad][:8])
     whole = first >= steps
-    for k in ("state", "prev_out", "extremes"):
+    for k in ("state", "prev_out", "extremes", "peaks"):
         if k in want:
             bad = sym.differing(got[k][whole], want[k][whole])
             assert not bad.any(), what + (k, int(bad.sum()), np.nonzero(whole)[0][bad][:8])
@@ -518,7 +596,164 @@ def test_everything_on_non_temporal_and_warp(variant, coeff, implicit, resident_
     print(f"[everything on, {variant} {coeff} {'implicit' if implicit else 'explicit'}] n=321 steps=7 " + "; ".join(shown))
 
 
-# ---- (e) ClosedLoopSim ------------------------------------------------------------------------------------------------------------------
+# ---- (e) the later rungs: tether, net, link tensions, spread, irregular sea ------------------------------------------------------------
+@pytest.fixture(scope="module")
+def later_pop(bed_pop):
+    """tests/symmetry_population.py (its shares are asserted in tests/test_symmetry.py, on the CPU) with the bed population's
+    applied wrench and control record, the targets following the bodies in z: (state, prev, params, applied, control, lines,
+    net (322, 28), spread (321, 36))."""
+    _, _, params, applied, ctl = bed_pop
+    P = symmetry_population.reseated_population()
+    assert all(np.array_equal(P["params"][c], params[c]) for c in ("f32", "f16"))
+    return (P["st"], P["pv"], P["params"], applied, symmetry_population.follow(ctl, P["drawn"], P["st"]), P["lines"], P["net"], P["spread"])
+
+
+@COEFFS
+def test_tether_spread_and_spectrum_probes_are_exactly_symmetric(coeff, later_pop, engines):
+    """hydro_tether_wrench (wrench and tension) on each of the net's two layers, hydro_mooring_wrench on every layer of the spread
+    (mooring_spread_wrench) and hydro_sea_spectrum_sample at 11 and 64 components and steps 0 and 10^6: the image's output is the
+    image of the output, tensions and eta keep their bits.  Alongside, what makes that say something: at least 20 % of the bodies
+    are pulled in each layer of the net, at least 30 % in each of the spread's layers 0 and 1, and eta is non-zero."""
+    st, _, params, _, _, _, net_all, spread_all = later_pop
+    for n in SIZES:
+        eng = engines("designed", params[coeff][:n], coeff)
+        s, net, spread = st[:n], net_for(net_all, n, symmetry_population.NET_LAYERS), spread_all[:n]
+        W, T = eng.tether_net_wrench(_tiled(s), _tiled(net), n, 2)
+        W, T = [_from(w, n) for w in W], [_from(t, n)[:, 0] for t in T]
+        S = [_from(w, n) for w in eng.mooring_spread_wrench(_tiled(s), _tiled(spread), n, 4)]
+        assert all((t > 0).mean() >= 0.2 for t in T), n
+        assert all(w.any(axis=1).mean() >= 0.3 for w in S[:2]) and S[2].any() and not S[3].any(), n
+        for m in sym.MAPS:
+            s_g = sym.state(m, s)
+            W_g, T_g = eng.tether_net_wrench(_tiled(s_g), _tiled(sym.net(m, net)), n, 2)
+            for l in range(2):
+                bad = sym.differing(_from(W_g[l], n), sym.wrench(m, W[l])) | sym.differing(_from(T_g[l], n)[:, 0], T[l])
+                assert not bad.any(), ("tether_wrench", n, m, l, int(bad.sum()), np.nonzero(bad)[0][:8])
+            for l, w_g in enumerate(eng.mooring_spread_wrench(_tiled(s_g), _tiled(sym.spread(m, spread)), n, 4)):
+                bad = sym.differing(_from(w_g, n), sym.wrench(m, S[l]))
+                assert not bad.any(), ("mooring_spread_wrench", n, m, l, int(bad.sum()), np.nonzero(bad)[0][:8])
+            for count in (11, 64):
+                spec = ssr.truncated(FULL, count)
+                for step in (0, 10 ** 6):
+                    eng.set_sea_spectrum(spec)
+                    want = _from(eng.sea_spectrum_sample(_tiled(s), n, step, DT), n)
+                    eng.set_sea_spectrum(sym.sea(m, spec))
+                    got = _from(eng.sea_spectrum_sample(_tiled(s_g), n, step, DT), n)
+                    bad = sym.differing(got, sym.sea_sample(m, want))
+                    assert not bad.any(), ("sea_spectrum_sample", n, m, count, step, int(bad.sum()), np.nonzero(bad)[0][:8])
+                    assert np.isfinite(want).all() and want[:, 0].all()
+            eng.set_sea_spectrum(None)
+    print(f"[probes {coeff}] hydro_tether_wrench (2 layers, wrench and tension), mooring_spread_wrench (4 layers) and hydro_sea_spectrum_sample "
+          "(11 and 64 components, steps 0 and 10^6), n = 200 and 321, 3 maps: 0 differ")
+
+
+def _later(eng, entry, P, pr, n, steps, implicit, bed, what, wrong=None):
+    """The launch of `entry` on P and on its three images, compared by `_compare`: [(map, bodies exact, bodies left out)].  A body
+    is left out from the first step whose input state has two or more contributing corners ON THE BED THAT IS SET, on the scene
+    or on the image (_sensitive_from: the reference decides).  Over FAR that is nobody - but for a body that explicit drag has
+    carried out of the scene: FAR is a plane at z = -10^6 m, and seven explicit steps take light bodies to 10^14 m and beyond
+    (the module's docstring), eight corners below any plane.  The callers assert that this happens under explicit drag only."""
+    want, st0 = _resident(eng, entry, P, n, steps, implicit, bed=bed)
+    assert not sym.equal(want["state"], st0)
+    first0 = _sensitive_from(st0, want["log"], pr[:n], bed)
+    out = []
+    for m in sym.MAPS:
+        got, st_g = _resident(eng, entry, P, n, steps, implicit, m, bed=bed)
+        first = np.minimum(first0, _sensitive_from(sym.state(m, st_g), got["log"], pr[:n], bed))
+        exact, left = _compare(entry, want, got, first, what + (n, steps, m))
+        if implicit:                                                # left out, but finite
+            gone = first < steps
+            assert np.isfinite(got["log"][:, gone]).all() and np.isfinite(want["log"][:, gone]).all(), what + (n, steps, m)
+        out.append((m, exact, left))
+    if implicit:
+        # the launch did what its name says: the lines pulled (tension_max), and where there are link tensions every layer of the net did
+        assert (want["extremes"][:, 7] > 0).mean() >= 0.3 and np.isfinite(want["ke"]).all(), what + (n, steps)
+        assert "peaks" not in want or ((want["peaks"] > 0).mean(axis=0) >= 0.2).all(), what + (n, steps)
+    return out
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("over", ["far", "bed"])
+@pytest.mark.parametrize("entry", LATER)
+def test_later_rungs_are_exactly_symmetric(entry, over, coeff, implicit, later_pop, engines):
+    """_teth, _net, _peak, _spread and _irr, each with everything it takes switched on: the log of every body with its wrench, a
+    body-frame applied wrench and the pose hold, the sea (SEA; _irr: the 64-component spectrum), the bed, the lines (_spread and
+    _irr: the spread of three), extremes seeded from the state, the net (_teth: one layer; the others two), the link tensions
+    (from _peak on) and ke_out; n = 200 and 321, under the three maps.
+      over FAR, a bed nobody reaches, at 1 and 7 steps: EVERY body exact in every log row, in state, prev_out and the extremes
+        record; the link tensions and the energy pair the same bits (with explicit drag a NaN equals a NaN).  Nobody is left out:
+        asserted at 1 step, and at 7 steps under implicit drag.  Seven EXPLICIT steps throw light bodies out of the scene (the
+        module's docstring), through FAR's plane at z = -10^6 m as through any other: such a body, eight corners below FAR by
+        the reference, is left out from that step on by the rule of the bed's corner sum - the one found (body 78 at n = 200, in
+        the sixth step at z = -5.4e14 m, its recorded wrench FAR's spring and damper at 1.9e17 N) differs from its image by one
+        ulp in that wrench and in nothing else.
+      over BED, ONE step: the bodies with at most one contributing corner on the scene and on the image exact; the others left out,
+        finite under implicit drag, and at most 25 % of the bodies.
+    Several steps over BED are deliberately not run for these rungs: a tether hands an order-sensitive body's last-bit difference to
+    its partner on the next step, that one to its own partner in the other layer on the step after, so the set that may be left
+    out grows along the chains and rings of the net by a link per step - the test would hide what it is meant to show.  In ONE step
+    every line is formed from the input states, which are exact images, so a tethered partner of an order-sensitive body is still
+    compared exactly."""
+    P = (later_pop[0], later_pop[1], later_pop[2][coeff]) + later_pop[3:]
+    pr = P[2]
+    bed = BED if over == "bed" else FAR
+    report = []
+    for n in SIZES:
+        eng = engines("designed", pr[:n], coeff)
+        for steps in (STEPS if over == "far" else (1,)):
+            runs = _later(eng, entry, P, pr, n, steps, implicit, bed, (entry, over))
+            fewest, most = min(r[1] for r in runs), max(r[2] for r in runs)
+            if over == "bed":
+                assert most <= 0.25 * n, (entry, over, n, steps, most)
+            else:                                                   # nobody reaches FAR - unless explicit drag has thrown it out of the scene
+                assert most == 0 or (not implicit and steps > 1 and most <= 0.25 * n), (entry, over, n, steps, most)
+            report.append(f"n={n} x{steps}: {fewest} exact, {most} left out ({most / n:.0%}), 0 differ")
+    print(f"[resident {entry} over {over.upper()} {coeff} {'implicit' if implicit else 'explicit'}, fewest / most over the 3 maps] " + "; ".join(report))
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("variant", ["non_temporal", "warp"])
+def test_irregular_sea_everything_on_non_temporal_and_warp(variant, coeff, implicit, later_pop, engines):
+    """The everything-on _irr launch over FAR, 7 steps, n = 321, with non_temporal = 1 and under Warp semantics (the engine's
+    settings; `_resident` leaves them alone)."""
+    P = (later_pop[0], later_pop[1], later_pop[2][coeff]) + later_pop[3:]
+    n = 321
+    eng = engines("designed", P[2][:n], coeff)
+    if variant == "warp":
+        eng.set_semantics("warp")
+    else:
+        eng.set_tuning(0, 0, 1)
+    runs = _later(eng, "irr", P, P[2], n, 7, implicit, FAR, (variant, "irr"))
+    assert not implicit or all(left == 0 for _, _, left in runs)    # (explicit: a body thrown below FAR's plane, see _later)
+    print(f"[irr, everything on, {variant} {coeff} {'implicit' if implicit else 'explicit'}] n=321 steps=7 "
+          + "; ".join(f"{m}: {exact} exact, {left} left out, 0 differ" for m, exact, left in runs))
+
+
+@COEFFS
+def test_teeth_on_the_device_wrong_hand_images_are_told_apart(coeff, later_pop, engines):
+    """Two images of the wrong hand through the same launches and the same comparison (state, prev_out or any log row): the
+    net's fairleads turned like axial vectors (_net, every map; under the half turn left unturned) and the spectrum's ky not
+    flipped under mirror_y (_irr).  At least a quarter of the bodies must differ from the predicted image - and with the right
+    hand none does.  One implicit step over FAR."""
+    P = (later_pop[0], later_pop[1], later_pop[2][coeff]) + later_pop[3:]
+    shown = []
+    for n in SIZES:
+        eng = engines("designed", P[2][:n], coeff)
+        for entry, wrong, maps in (("net", "tether", sym.MAPS), ("irr", "ky", ("mirror_y",))):
+            want, _ = _resident(eng, entry, P, n, 1, True, bed=FAR)
+            for m in maps:
+                def apart(got):
+                    return sym.differing(got["state"], want["state"]) | sym.differing(got["prev_out"], want["prev_out"]) | sym.differing(got["log"][0], want["log"][0])
+                assert not apart(_resident(eng, entry, P, n, 1, True, m, bed=FAR)[0]).any(), (entry, n, m)
+                share = apart(_resident(eng, entry, P, n, 1, True, m, bed=FAR, wrong=wrong)[0]).mean()
+                shown.append(f"{wrong} {m} n={n}: {share:.0%}")
+                assert share >= 0.25, (entry, wrong, n, m, share)
+    print(f"[teeth on the device {coeff}] bodies that differ from the predicted image: " + "; ".join(shown))
+
+
+# ---- (f) ClosedLoopSim ------------------------------------------------------------------------------------------------------------------
 def test_closed_loop_sim_builds_its_records_without_a_hand(native_built):
     """64 moored buoys at 64 headings, a current with one wave component, an off-centre fairlead and a weak pose hold towards a
     displaced, turned target - and the mirror_y image of all of it, both through ClosedLoopSim's own set_mooring / set_pose_hold
