@@ -67,7 +67,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_step_fused_tiled_multi_spread, HYDRO_MOOR_LAYERS_MAX - up to four
  *        layers of mooring records, so that a body rides on a spread of anchored lines
  *        added to 0.7.1 (no existing entry changed): hydro_set_sea_spectrum, hydro_sea_spectrum_sample, hydro_step_fused_tiled_multi_irr,
- *        HYDRO_SPECTRUM_WAVES_MAX - an irregular sea of up to 64 wave components in the closed-loop steps */
+ *        HYDRO_SPECTRUM_WAVES_MAX - an irregular sea of up to 64 wave components in the closed-loop steps
+ *        added to 0.7.1 (no existing entry changed): hydro_statistics_reset, hydro_step_fused_tiled_multi_stat, HYDRO_STAT_* -
+ *        running per-body response statistics (sum, sum of squares, up-crossings of a level) updated inside every step */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -94,6 +96,18 @@ extern "C" {
 #define HYDRO_SEA_WAVES_MAX   8   /* regular wave components of a sea state (hydro_set_sea) */
 #define HYDRO_SEA_FIELDS      4   /* the record of hydro_sea_sample: eta, u_x, u_y, u_z */
 #define HYDRO_SPECTRUM_WAVES_MAX 64 /* wave components of a sea spectrum (hydro_set_sea_spectrum) */
+/* the channels of a statistics record (hydro_step_fused_tiled_multi_stat) */
+#define HYDRO_STAT_X        0    /* s[0] */
+#define HYDRO_STAT_Y        1    /* s[1] */
+#define HYDRO_STAT_Z        2    /* s[2] */
+#define HYDRO_STAT_VX       3    /* s[7] */
+#define HYDRO_STAT_VY       4    /* s[8] */
+#define HYDRO_STAT_VZ       5    /* s[9] */
+#define HYDRO_STAT_TENSION  6    /* the tension the extremes record samples */
+#define HYDRO_STAT_CHANNELS 7
+#define HYDRO_STAT_BYTES_PER_BODY 44   /* four doubles and three words */
+#define HYDRO_STAT_TILE_BYTES  2816    /* hydro_statistics_tile_t: 64 bodies */
+#define HYDRO_STAT_LEVEL_FIELDS   2    /* the level record: one level per body and channel slot */
 
 typedef struct hydro_engine hydro_t;
 
@@ -1150,6 +1164,90 @@ int hydro_step_fused_tiled_multi_irr(hydro_t *h, int64_t n, const float *state, 
                                      const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
                                      float *tether_peaks, int64_t tether_peaks_tile_stride,
                                      int64_t step0, void *stream);
+
+/* Statistics: what a mooring designer takes from an irregular-sea run besides the peak - the mean and the standard deviation
+ * of a response and its mean up-crossing rate, from which come the mean offset and mean tension, the significant response
+ * 2 sigma, the zero-up-crossing period Tz = duration / up-crossings, the most probable maximum mu + sigma * sqrt(2 ln N_up)
+ * of a storm of any length (Rayleigh), and - on the tension channel against the level +0 - the number of slack-to-taut events
+ * of a line (snap loads).  A peak ("Extremes", above) is the largest sample of one random realisation; these are not.  Between
+ * the first and the last step of a launch the states exist in registers only and the tension is never visible at all, so the
+ * sums are kept where the extremes are kept: inside the stepping kernel, every step, for every body.  Only
+ * hydro_step_fused_tiled_multi_stat and hydro_statistics_reset know them.  Bodies stay independent.
+ *
+ * TWO CHANNELS per launch, `channel_a` and `channel_b`, each one of HYDRO_STAT_X, _Y, _Z = 0 .. 2 (s[0..2]), HYDRO_STAT_VX,
+ * _VY, _VZ = 3 .. 5 (s[7..9]) and HYDRO_STAT_TENSION = 6.  The two may be the same.  THE SAMPLE is taken where the extremes
+ * take theirs: after every step k of the launch, of the state the step produced - the values a recorder row of that step
+ * holds - and HYDRO_STAT_TENSION is EXACTLY the tension the extremes record samples in that step: the T the body's mooring
+ * line or spread formed in it (the largest of a spread's), +0 where no line pulls or there is no mooring record.
+ *
+ * THE LEVEL RECORD `levels`: HYDRO_STAT_LEVEL_FIELDS = 2 floats per body, tiled ([tiles][2][64] floats, tile stride
+ * levels_tile_stride >= 128 floats = 512 B, 16-byte aligned, addressed like `mooring`): the reference level L of the body for
+ * slot a, then for slot b.  It is the caller's read-only device buffer, read from it in every step (as a mooring spread's layers
+ * are); required whenever a statistics record is given.  L is any float: a NaN or infinite level poisons that body's slot.
+ *
+ * THE STATISTICS RECORD `statistics`: per tile of 64 bodies one hydro_statistics_tile_t,
+ *     { double sums[4][64]; uint32_t words[3][64]; }    = HYDRO_STAT_TILE_BYTES = 2 816 B, HYDRO_STAT_BYTES_PER_BODY = 44
+ *     sums  = S1_a, S2_a, S1_b, S2_b : the sum of d and of d * d of slot a, then of slot b, d the sample less its level
+ *     words = up_a, up_b, n          : the two up-crossing words (below) and the number of samples
+ * statistics_tile_stride counts 4-byte units like every stride of this header: >= 704 (2 816 B), a multiple of 4, the
+ * buffer 16-byte aligned (so every double is 8-byte aligned).  It is the caller's device buffer, READ AT THE START OF A LAUNCH AND
+ * WRITTEN AT ITS END like the extremes: it accumulates over launches, chunks and graph replays until it is reset.  Lanes >= n
+ * of the last tile are never written.  THE RECORD DOES NOT REMEMBER ITS CHANNELS OR LEVELS: a caller that changes either
+ * resets it first.
+ *
+ * THE ARITHMETIC is fixed so that a host reproduces the bits in plain IEEE double arithmetic.  Per slot and step, x the fp32
+ * sample and L the fp32 level:
+ *     d  = (double)x - (double)L          one fp64 subtraction (exact conversions)
+ *     S1 = S1 + d                         one fp64 addition
+ *     q  = d * d;   S2 = S2 + q           one fp64 product, rounded, then one fp64 addition: NO fused multiply-add anywhere
+ * UP-CROSSINGS: above = (x > L), an fp32 compare, false for a NaN.  Bit 31 of an up-crossing word says "the last sample was
+ * not above its level", bits 0 .. 30 are the count (modulo 2^31).  If bit 31 is set and `above`, the count goes up by one; then
+ * bit 31 = !above.  A reset record has bit 31 clear, so the first sample never counts, and x == L is not above.  With L = +0
+ * on the tension channel the count is the number of slack-to-taut events.
+ * n is not touched inside the loop: the end of a launch adds `steps` to the value it reads from the record.
+ * A NaN sample makes that body's S1 and S2 of that slot NaN for good and nobody else's; it is never above.
+ * NOT PROVIDED: heave relative to the moving surface; covariances between channels; more than two channels per record;
+ * statistics of the wrench; per-link statistics of tether nets.
+ *
+ * hydro_statistics_reset: sums +0.0 and words 0 for bodies 0 .. n - 1 (lanes >= n of the last tile are not written).  A small
+ * kernel of its own; asynchronous on `stream`; needs no parameters.  HYDRO_E_ARG for n > capacity, a null or misaligned buffer
+ * or a stride below 704.
+ *
+ * hydro_step_fused_tiled_multi_stat: the signature of hydro_step_fused_tiled_multi_irr with `statistics`, its stride, `levels`,
+ * its stride, `channel_a` and `channel_b` in front of step0.
+ *   statistics == NULL : the launch and its bits are those of hydro_step_fused_tiled_multi_irr with the same arguments; the
+ *                        channels are still checked (0 .. 6), `levels` is not looked at.
+ *   statistics != NULL : every other option is optional and adds what it adds in hydro_step_fused_tiled_multi_irr - through
+ *                        the sea spectrum if one is set, through the sea of hydro_set_sea or still water otherwise; state_out,
+ *                        prev_out, the kinetic-energy pair, the log, the extremes and the link tensions are bit for bit
+ *                        those of hydro_step_fused_tiled_multi_irr - nothing the record computes feeds back.
+ * The refusals are those of hydro_step_fused_tiled_multi_irr, in its order, then: a channel outside 0 .. 6; a null `levels`;
+ * a stride below 704 / 128 or a misaligned buffer; `statistics` overlapping an output (state_out, prev_out, log, extremes,
+ * tether_peaks) or - since it is written - an input (state, prev, applied, control, mooring, tether, levels); `levels`
+ * overlapping an output: HYDRO_E_ARG, and nothing is launched or written.  Asynchronous, no allocation, no synchronisation,
+ * safe to capture: a replay accumulates and adds `steps` to n.
+ * Cost and registers: DESIGN.md section 30.  New functionality; the reference keeps no statistics. */
+typedef struct hydro_statistics_tile {
+    double sums[4][HYDRO_TILE];
+    uint32_t words[3][HYDRO_TILE];
+} hydro_statistics_tile_t;
+int hydro_statistics_reset(hydro_t *h, int64_t n, void *statistics, int64_t statistics_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_stat(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                      const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float *state_out, int64_t out_tile_stride,
+                                      float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double *ke_out_dev,
+                                      float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t *rows_written_host,
+                                      const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float *control, int64_t control_tile_stride,
+                                      const float *mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                      float *extremes, int64_t extremes_tile_stride,
+                                      const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                      float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                      void *statistics, int64_t statistics_tile_stride,
+                                      const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                      int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

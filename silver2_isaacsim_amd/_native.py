@@ -27,6 +27,12 @@ WATCH_MAX = 65536
 SEA_WAVES_MAX = 8                       # regular wave components of a sea state (hydro_set_sea)
 SEA_FIELDS = 4                          # the record of hydro_sea_sample: eta, u_x, u_y, u_z
 SPECTRUM_WAVES_MAX = 64                 # wave components of a sea spectrum (hydro_set_sea_spectrum)
+# the statistics record of hydro_step_fused_tiled_multi_stat: channels, and the record in 4-byte units per body (4 doubles + 3 words)
+STAT_X, STAT_Y, STAT_Z, STAT_VX, STAT_VY, STAT_VZ, STAT_TENSION = range(7)
+STAT_CHANNELS = 7
+STAT_BYTES_PER_BODY = 44
+STAT_FIELDS = STAT_BYTES_PER_BODY // 4  # the record as a tiled buffer of 4-byte fields: (tiles, 11, 64) = 2 816 B per tile
+STAT_LEVEL_FIELDS = 2                   # the level record: one level per body and channel slot
 
 
 class Scene(ctypes.Structure):
@@ -74,6 +80,7 @@ _APP = [c_void_p, c_int64, c_int]                                               
 _CTL = _MOOR = _EXT = _TETH = _PEAK = [c_void_p, c_int64]                                 # a per-body record and its tile stride
 _LAYERS = _STEP0 = [c_int64]                                                              # tether_layers; step0
 _SPREAD = _MOOR + [c_int64]                                                               # the mooring record as a spread: + mooring_layers
+_STAT = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int]                              # statistics, levels (+ strides), channel_a, channel_b
 _STREAM = [c_void_p]
 _SAMPLE = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]   # h, n, state (+ stride), step_index, dt, out (+ stride), stream
 
@@ -136,6 +143,8 @@ SIGNATURES = {
     "hydro_set_sea_spectrum": (c_int, [c_void_p, POINTER(SeaSpectrum)]),
     "hydro_sea_spectrum_sample": (c_int, _SAMPLE),
     "hydro_step_fused_tiled_multi_irr": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
+    "hydro_statistics_reset": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "hydro_step_fused_tiled_multi_stat": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -2549,6 +2549,167 @@ __global__ void __launch_bounds__(kBlock) spectrum_sample_kernel(const float* st
     store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
 }
 
+// --------------------------------------------------------------------------
+// RESPONSE STATISTICS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_stat): what a mooring designer reads
+// off an irregular-sea run besides the peak - per body and for two channels the sum and the sum of squares of the response
+// about a reference level, and the number of times it crossed that level upwards (include/hydro.h, "Statistics", states the
+// sample, the arithmetic and the record).  Like the extremes the record is READ at the start of a launch and WRITTEN at its
+// end, so it accumulates across launches until hydro_statistics_reset.
+//   the slot    : the policy WRAPS OptionalExtremesTrack in the extremes slot of fused_multi_body: begin / after_step / end
+//                 call the extremes' own and then their own, so fused_multi_body and every existing kernel stay as they are
+//   the sample  : the extremes' - the state the step produced and the tension moor.tension() handed over.  The two channels
+//                 are kernel arguments (wave-uniform): a channel's value is picked by scalar compares, v_cndmask at most
+//   the record  : four doubles and two words per lane.  The _spread and _irr kernels stand at 156-163 VGPRs of 168, so they
+//                 are not carried through the loop: each lane parks them in LDS, [wave][10][64] floats - a double as two
+//                 planes, low word then high word, so that lane4 addresses them like every parked float (10 240 B per
+//                 block; LaneSlots' way, with the extremes' lane4 and wave offset: the loop keeps no register for this
+//                 policy's address) - and reads, updates and writes them behind the integrator.  43 008 + 10 240 = 53 248 B
+//                 per block: three blocks fit a CU
+//   the levels  : NOT parked.  Two floats per lane from the caller's buffer in every step, through the tile's wave-uniform
+//                 pointer made opaque in every step (MooringSpread's way): launch-invariant, L2 hits after the first step
+//   the sums    : fp64, one rounding per operation, NO fma: d = x - L, S1 += d, q = d * d, S2 += q.  The empty asm on q
+//                 stands between the product and the sum, so that no contraction can join them
+//   the words   : bit 31 = "the last sample was not above its level", bits 0 .. 30 the count (hydro.h states the update)
+//   n           : not touched in the loop: end() adds `steps` to the word it reads from the caller's record
+// Nothing the policy computes feeds back: state, prev_out, energy, log, extremes and link tensions are the wrapped kernel's bits.
+// --------------------------------------------------------------------------
+#define HYDRO_STAT_PARAMS void* statistics, uint32_t statistics_stride, const float* levels, uint32_t levels_stride,             \
+                          uint32_t channel_a, uint32_t channel_b
+#define HYDRO_STAT_ARGS statistics, statistics_stride, levels, levels_stride, channel_a, channel_b
+constexpr uint32_t kStatSlots = 10;                                      // four doubles as eight half planes, two words
+constexpr uint32_t kStatWordsAt = 4u * 512u;                             // the words behind the sums in the caller's record
+
+struct StatisticsTrack : OptionalExtremesTrack {
+    using GlobalFloats = const float __attribute__((address_space(1)))*;
+    using GlobalBytes = char __attribute__((address_space(1)))*;
+    void* stat; uint32_t stat_stride; const float* lev; uint32_t lev_stride, ch_a, ch_b, steps;
+    GlobalFloats tile_lev; GlobalBytes tile_stat;                        // the tile's two records: wave-uniform pointers, in SGPRs
+    static __device__ __forceinline__ float* slots()
+    {
+        __shared__ __attribute__((aligned(16))) float lds[kBlock * kStatSlots];
+        return lds;
+    }
+    // The lane's slot 0, [wave][10][64] floats: the extremes' lane4 and wave offset serve (begin sets both, whether or not there
+    // is an extremes record) - 10 / 8 of that offset is this policy's, in two scalar instructions, and no register of its own.
+    __device__ __forceinline__ float* parked() const
+    {
+        uint32_t w_off = wave_off;
+        asm volatile("" : "+s"(w_off));
+        return at<float>(slots(), lane4 + (w_off >> 3) * kStatSlots);
+    }
+    // a parked double: its low word in plane 2 j, its high word in plane 2 j + 1
+    static __device__ __forceinline__ double parked_double(const float* m, uint32_t j)
+    {
+        return __hiloint2double(__builtin_bit_cast(int, m[(2u * j + 1u) * 64u]), __builtin_bit_cast(int, m[(2u * j) * 64u]));
+    }
+    static __device__ __forceinline__ void park_double(float* m, uint32_t j, double v)
+    {
+        m[(2u * j) * 64u] = __builtin_bit_cast(float, __double2loint(v));
+        m[(2u * j + 1u) * 64u] = __builtin_bit_cast(float, __double2hiint(v));
+    }
+    // the sample of channel `ch` (wave-uniform): s[0..2], s[7..9] or the tension
+    static __device__ __forceinline__ float sample(uint32_t ch, const float (&s)[HYDRO_STATE_FIELDS], float T)
+    {
+        float x = T;
+        x = ch == HYDRO_STAT_X ? s[0] : x;
+        x = ch == HYDRO_STAT_Y ? s[1] : x;
+        x = ch == HYDRO_STAT_Z ? s[2] : x;
+        x = ch == HYDRO_STAT_VX ? s[7] : x;
+        x = ch == HYDRO_STAT_VY ? s[8] : x;
+        x = ch == HYDRO_STAT_VZ ? s[9] : x;
+        return x;
+    }
+    // one sample x of slot c (0: a, 1: b) against its level L
+    static __device__ __forceinline__ void fold(float* m, uint32_t c, float x, float L)
+    {
+        const double d = (double)x - (double)L;
+        park_double(m, 2u * c, parked_double(m, 2u * c) + d);
+        double q = d * d;
+        asm volatile("" : "+v"(q));                                      // (no fma: the product is rounded before the sum sees it)
+        park_double(m, 2u * c + 1u, parked_double(m, 2u * c + 1u) + q);
+        const bool above = x > L;                                        // (false for a NaN)
+        const uint32_t w = __builtin_bit_cast(uint32_t, m[(8u + c) * 64u]);
+        m[(8u + c) * 64u] = __builtin_bit_cast(float, ((w + ((w >> 31) & (above ? 1u : 0u))) & 0x7fffffffu) | (above ? 0u : 0x80000000u));
+    }
+    __device__ __forceinline__ void begin(uint32_t tile, uint32_t lane4_)
+    {
+        OptionalExtremesTrack::begin(tile, lane4_);
+        lane4 = lane4_;                                                  // (what ExtremesTrack::claim sets, also without an extremes record)
+        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (kExtSlots * 256u);
+        tile_lev = (GlobalFloats)(lev + (size_t)tile * lev_stride);
+        tile_stat = (GlobalBytes)(reinterpret_cast<float*>(stat) + (size_t)tile * stat_stride);
+        float* m = at<float>(slots(), lane4 + (wave_off >> 3) * kStatSlots);
+        const char* r = (const char*)tile_stat;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) park_double(m, j, *at<double>(r, lane4 * 2u, j * 512u));
+#pragma unroll
+        for (uint32_t c = 0; c < 2u; ++c) m[(8u + c) * 64u] = *at<float>(r, lane4, kStatWordsAt + c * 256u);
+    }
+    __device__ __forceinline__ void after_step(const float (&s)[HYDRO_STATE_FIELDS], float T) const
+    {
+        OptionalExtremesTrack::after_step(s, T);
+        GlobalFloats L = tile_lev;
+        asm volatile("" : "+s"(L));
+        const float la = *at<float>((const float*)L, lane4, 0u), lb = *at<float>((const float*)L, lane4, 256u);
+        float* m = parked();
+        fold(m, 0u, sample(ch_a, s, T), la);
+        fold(m, 1u, sample(ch_b, s, T), lb);
+    }
+    // Only live lanes come here (fused_multi_body): the padding lanes of the last tile are never written.
+    __device__ __forceinline__ void end(uint32_t tile, uint32_t lane4_) const
+    {
+        OptionalExtremesTrack::end(tile, lane4_);
+        const float* m = parked();
+        char* r = (char*)tile_stat;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) *at<double>(r, lane4_ * 2u, j * 512u) = parked_double(m, j);
+#pragma unroll
+        for (uint32_t c = 0; c < 2u; ++c) *at<float>(r, lane4_, kStatWordsAt + c * 256u) = m[(8u + c) * 64u];
+        uint32_t* count = at<uint32_t>(r, lane4_, kStatWordsAt + 2u * 256u);
+        *count = *count + steps;
+    }
+};
+__device__ __forceinline__ StatisticsTrack statistics_track(HYDRO_EXT_PARAMS, HYDRO_STAT_PARAMS, uint32_t steps)
+{
+    return StatisticsTrack{optional_extremes_track(HYDRO_EXT_ARGS), statistics, statistics_stride, levels, levels_stride, channel_a, channel_b, steps, nullptr, nullptr};
+}
+
+// The _spread kernel's arguments, then the statistics group.  Everything in front of the group may be null; `statistics` and `levels` may not.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_stat_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                  HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                  HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_STAT_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   optional_sea_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), mooring_spread(HYDRO_SPREAD_ARGS),
+                                                   statistics_track(HYDRO_EXT_ARGS, HYDRO_STAT_ARGS, steps),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// The same through the sea spectrum: the _irr kernel's arguments, then the statistics group.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_irr_stat_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                      HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                      HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_STAT_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   spectrum_view(HYDRO_SEA_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS), mooring_spread(HYDRO_SPREAD_ARGS),
+                                                   statistics_track(HYDRO_EXT_ARGS, HYDRO_STAT_ARGS, steps),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// hydro_statistics_reset: the empty record - sums +0.0, words 0 - for the live lanes.
+__global__ void __launch_bounds__(kBlock) statistics_reset_kernel(void* stat, uint32_t stat_stride, uint32_t n)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    char* r = reinterpret_cast<char*>(reinterpret_cast<float*>(stat) + (size_t)tile * stat_stride);
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) *at<double>(r, lane4 * 2u, j * 512u) = 0.0;
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; ++c) *at<uint32_t>(r, lane4, kStatWordsAt + c * 256u) = 0u;
+}
+
 // hydro_tether_wrench: the tether's W per body for the tiled state `st` (+0 in all six fields for a body whose line adds
 // nothing) and, if asked for, its tension T (+0 likewise).  The lanes >= n of the last tile leave first: the live ones
 // exchange among themselves, in uniform control flow.
@@ -2580,7 +2741,7 @@ constexpr bool lane_slot_counts_distinct(std::initializer_list<uint32_t> counts)
             if (*a == *b) return false;
     return true;
 }
-static_assert(lane_slot_counts_distinct({kCtlSlots, kSeaSlots, kMoorSlots, kExtSlots}),
+static_assert(lane_slot_counts_distinct({kCtlSlots, kSeaSlots, kMoorSlots, kExtSlots, kStatSlots}),
               "two LaneSlots policies of one kernel share a slot count, hence one LDS array");
 
 }  // namespace
@@ -3487,7 +3648,7 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// A launch of any of the thirteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// A launch of any of the fourteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
 // was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
 // copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
 // (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
@@ -3511,6 +3672,9 @@ struct MultiStep {
     int64_t tether_layers = 0;                           // the _net entry: the _teth entry with `tether` a net of that many layers (0: a single record, the _teth entry's)
     float* tether_peaks = nullptr; int64_t tether_peaks_tile_stride = 0;  // the _peak entry: the _net entry, and the running maximum of every line's tension if a record is given
     int64_t mooring_layers = 0;                          // the _spread entry: the _peak entry with `mooring` a spread of that many layers (0: a single record, the _moor entry's)
+    // the _stat entry: the _irr entry, and the running response statistics if a record is given
+    bool stat_entry = false; void* statistics = nullptr; int64_t statistics_tile_stride = 0;
+    const float* levels = nullptr; int64_t levels_tile_stride = 0; int channel_a = 0, channel_b = 0;
 
     void with_recorder(float* log_, int64_t log_stride_, int64_t rows_capacity_, int fields_, int every_, int phase_, int64_t row0_, int64_t* rows_written_host_)
     {
@@ -3530,6 +3694,11 @@ struct MultiStep {
     void with_peaks(float* p, int64_t stride) { tether_peaks = p; tether_peaks_tile_stride = stride; }
     // (a spread of no layers is refused as out of range, never taken for the _moor entry's record)
     void with_mooring_layers(int64_t layers) { mooring_layers = layers == 0 ? -1 : layers; }
+    void with_statistics(void* p, int64_t stride, const float* levels_, int64_t levels_stride, int a, int b)
+    {
+        stat_entry = true; statistics = p; statistics_tile_stride = stride; levels = levels_; levels_tile_stride = levels_stride;
+        channel_a = a; channel_b = b;
+    }
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3577,7 +3746,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
 // The refusals in the order the entries have always reported them, then ONE choice of kernel family.  The families form a
 // ladder, each taking its predecessor's argument groups and one more:
 //   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak < _spread
-// (the _irr family stands beside the ladder: it is chosen while a sea spectrum is set, by the _irr entry alone, whatever the options)
+// (the _irr family stands beside the ladder: it is chosen while a sea spectrum is set, by the _irr entry alone, whatever the options;
+// the two _stat families stand beside the _spread and the _irr family: chosen while a statistics record is given, whatever the options)
 // and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
 // the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
@@ -3666,6 +3836,38 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
             || (m.log && ranges_overlap(m.mooring, floats, m.log, log_floats)))
             return fail(h, HYDRO_E_ARG, "the mooring spread must not overlap an output (state_out, prev_out, log, extremes, tether_peaks)");
     }
+    if (m.stat_entry) {
+        if (m.channel_a < 0 || m.channel_a >= HYDRO_STAT_CHANNELS || m.channel_b < 0 || m.channel_b >= HYDRO_STAT_CHANNELS)
+            return fail(h, HYDRO_E_ARG, "channel_a / channel_b must be in 0 .. 6 (HYDRO_STAT_X .. HYDRO_STAT_TENSION)");
+    }
+    if (m.statistics) {
+        constexpr int kStatFloats = HYDRO_STAT_BYTES_PER_BODY / 4;                 // the record in 4-byte units per body: what check_tiled counts
+        if (!m.levels) return fail(h, HYDRO_E_ARG, "null levels (a statistics record needs its level record)");
+        if ((rc = check_tiled(h, m.n, m.statistics, m.statistics_tile_stride, kStatFloats, "null statistics"))) return rc;
+        if ((rc = check_tiled(h, m.n, m.levels, m.levels_tile_stride, HYDRO_STAT_LEVEL_FIELDS, "null levels"))) return rc;
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE;
+        const float* st = static_cast<const float*>(m.statistics);
+        const int64_t st_floats = tiled_extent(tiles, m.statistics_tile_stride, kStatFloats), lv_floats = tiled_extent(tiles, m.levels_tile_stride, HYDRO_STAT_LEVEL_FIELDS);
+        const int net_fields = HYDRO_TETH_FIELDS * (m.tether_layers > 0 ? (int)m.tether_layers : 1), peak_fields = m.tether_layers > 0 ? (int)m.tether_layers : 1;
+        const int moor_fields = HYDRO_MOOR_FIELDS * (m.mooring_layers > 0 ? (int)m.mooring_layers : 1);
+        const auto meets = [&](const float* q, int64_t q_floats, const void* p, int64_t stride, int fields) {
+            return p && ranges_overlap(q, q_floats, static_cast<const float*>(p), tiled_extent(tiles, stride, fields));
+        };
+        const auto meets_output = [&](const float* q, int64_t q_floats) {
+            return meets(q, q_floats, m.state_out, m.out_tile_stride, HYDRO_STATE_FIELDS) || meets(q, q_floats, m.prev_out, m.prev_out_tile_stride, HYDRO_PREV_FIELDS)
+                || meets(q, q_floats, m.extremes, m.extremes_tile_stride, HYDRO_EXT_FIELDS) || meets(q, q_floats, m.tether_peaks, m.tether_peaks_tile_stride, peak_fields)
+                || (m.log && ranges_overlap(q, q_floats, m.log, log_floats));
+        };
+        if (meets_output(st, st_floats))
+            return fail(h, HYDRO_E_ARG, "statistics must not overlap an output (state_out, prev_out, log, extremes, tether_peaks)");
+        if (meets(st, st_floats, m.state, m.state_tile_stride, HYDRO_STATE_FIELDS) || meets(st, st_floats, m.prev, m.prev_tile_stride, HYDRO_PREV_FIELDS)
+            || meets(st, st_floats, m.applied, m.applied_tile_stride, HYDRO_WRENCH_FIELDS) || meets(st, st_floats, m.control, m.control_tile_stride, HYDRO_CTL_FIELDS)
+            || meets(st, st_floats, m.mooring, m.mooring_tile_stride, moor_fields) || meets(st, st_floats, m.tether, m.tether_tile_stride, net_fields)
+            || meets(st, st_floats, m.levels, m.levels_tile_stride, HYDRO_STAT_LEVEL_FIELDS))
+            return fail(h, HYDRO_E_ARG, "statistics must not overlap an input (state, prev, applied, control, mooring, tether, levels)");
+        if (meets_output(m.levels, lv_floats))
+            return fail(h, HYDRO_E_ARG, "levels must not overlap an output (state_out, prev_out, log, extremes, tether_peaks)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -3710,13 +3912,22 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
             on_optional_bed(kernel, m.mooring, m.mooring ? (uint32_t)m.mooring_tile_stride : 0u, m.mooring ? (uint32_t)m.mooring_layers : 0u, tail...);
         };
         // (the _spread family's groups behind the spread, every one optional: the _irr family takes them unchanged)
-        const auto spread_and_all = [&](auto kernel) {
+        const auto spread_and_all = [&](auto kernel, auto... tail) {
             spread_moored(kernel, m.extremes, m.extremes ? (uint32_t)m.extremes_tile_stride : 0u,
                           m.tether, m.tether ? (uint32_t)m.tether_tile_stride : 0u, m.tether ? (uint32_t)(m.tether_layers ? m.tether_layers : 1) : 0u,
-                          m.tether_peaks, m.tether_peaks ? (uint32_t)m.tether_peaks_tile_stride : 0u);
+                          m.tether_peaks, m.tether_peaks ? (uint32_t)m.tether_peaks_tile_stride : 0u, tail...);
         };
-        // the spectrum first: its family stands beside the ladder, not on it, and takes every option the launch has
-        if (irr) spread_and_all(step_fused_multi_irr_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        // (the statistics group behind everything else: the two _stat families take the _spread family's groups unchanged)
+        const auto with_statistics = [&](auto kernel) {
+            spread_and_all(kernel, m.statistics, (uint32_t)m.statistics_tile_stride, m.levels, (uint32_t)m.levels_tile_stride, (uint32_t)m.channel_a, (uint32_t)m.channel_b);
+        };
+        // the statistics first, through the spectrum or not; then
+        // the spectrum: its family stands beside the ladder, not on it, and takes every option the launch has
+        if (m.statistics) {
+            if (irr) with_statistics(step_fused_multi_irr_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+            else with_statistics(step_fused_multi_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
+        }
+        else if (irr) spread_and_all(step_fused_multi_irr_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.mooring && m.mooring_layers) spread_and_all(step_fused_multi_spread_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         else if (m.tether_peaks) netted(step_fused_multi_peak_tiled_kernel<HALF, NT, IMPL, KE, WARP>, m.tether_peaks, (uint32_t)m.tether_peaks_tile_stride);
         else if (m.tether && m.tether_layers) netted(step_fused_multi_net_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
@@ -4300,6 +4511,55 @@ int hydro_step_fused_tiled_multi_irr(hydro_t* h, int64_t n, const float* state, 
     m.with_layers(tether_layers);
     m.with_peaks(tether_peaks, tether_peaks_tile_stride);
     m.with_spectrum();
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_statistics_reset(hydro_t* h, int64_t n, void* statistics, int64_t statistics_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    int rc;
+    if (n < 0 || n > h->capacity) return fail(h, HYDRO_E_ARG, "n out of range (0 .. capacity)");
+    if ((rc = check_tiled(h, n, statistics, statistics_tile_stride, HYDRO_STAT_BYTES_PER_BODY / 4, "null statistics"))) return rc;
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (n == 0) return HYDRO_OK;
+    hipLaunchKernelGGL(statistics_reset_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       statistics, (uint32_t)statistics_tile_stride, (uint32_t)n);
+    HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
+    return HYDRO_OK;
+}
+
+int hydro_step_fused_tiled_multi_stat(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                      const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                      float* state_out, int64_t out_tile_stride,
+                                      float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                      int rotational, double* ke_out_dev,
+                                      float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                      int64_t row0, int64_t* rows_written_host,
+                                      const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                      const float* control, int64_t control_tile_stride,
+                                      const float* mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                      float* extremes, int64_t extremes_tile_stride,
+                                      const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                      float* tether_peaks, int64_t tether_peaks_tile_stride,
+                                      void* statistics, int64_t statistics_tile_stride,
+                                      const float* levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                      int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_mooring_layers(mooring_layers);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    m.with_spectrum();
+    m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -591,6 +591,44 @@ class HydroEngine:
                                     (log, every, phase, row0), stream,
                                     lambda: self._spread_tail(n, step0, mooring, mooring_layers, tether, layers, peaks, extremes, control, applied, frame))
 
+    # ------------------------------------------------------------------ statistics
+    def alloc_statistics(self, n: int) -> torch.Tensor:
+        """Zeroed statistics record for n bodies - the reset record: (tiles, 11, 64) float32 = 2 816 B per tile, holding per tile
+        `{ double sums[4][64]; uint32_t words[3][64]; }` (include/hydro.h, "Statistics"; `statistics.unpack` reads it)."""
+        return self.alloc_tiled(nat.STAT_FIELDS, n)
+
+    def statistics_reset(self, statistics: torch.Tensor, n: int, stream=None) -> torch.Tensor:
+        """Empty the statistics record of bodies 0 .. n - 1: sums +0.0, words 0 (hydro_statistics_reset).  Asynchronous."""
+        p, stride = self._tiled(statistics, nat.STAT_FIELDS, n)
+        self._check(self._lib.hydro_statistics_reset(self._h, n, p, stride, self._stream(stream)))
+        return statistics
+
+    def step_fused_tiled_multi_stat(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                    statistics: torch.Tensor | None = None, levels: torch.Tensor | None = None,
+                                    channel_a: int = nat.STAT_Z, channel_b: int = nat.STAT_TENSION,
+                                    mooring: torch.Tensor | None = None, mooring_layers: int = 1,
+                                    tether: torch.Tensor | None = None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                    extremes: torch.Tensor | None = None,
+                                    control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                    log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                    state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                    ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_irr that also keeps each body's running response statistics
+        (hydro_step_fused_tiled_multi_stat): `statistics` is the record of `alloc_statistics` / `statistics_reset`, read at
+        the start of the launch and written at its end, so it accumulates over launches; `levels` the tiled (tiles, 2, 64)
+        reference levels of the two channel slots; `channel_a` / `channel_b` one of `_native.STAT_X .. STAT_TENSION`.  After
+        every step the sample of each channel enters its sums and its up-crossing count (include/hydro.h, "Statistics").
+        Nothing feeds back: everything else the launch writes is step_fused_tiled_multi_irr's bits, and statistics=None IS that
+        call.  Returns the number of rows written (0 without a log)."""
+        def extra():
+            tail = self._spread_tail(n, step0, mooring, mooring_layers, tether, layers, peaks, extremes, control, applied, frame)
+            s_ptr, s_stride = self._tiled(statistics, nat.STAT_FIELDS, n) if statistics is not None else (None, 0)
+            l_ptr, l_stride = self._tiled(levels, nat.STAT_LEVEL_FIELDS, n) if levels is not None else (None, 0)
+            return (*tail[:-1], s_ptr, s_stride, l_ptr, l_stride, int(channel_a), int(channel_b), tail[-1])
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_stat,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream, extra)
+
     # ------------------------------------------------------------------ seabed
     def set_seabed(self, bed) -> None:
         """The scene's floor (hydro_set_seabed; the model: include/hydro.h, "Seabed"): `bed` has `z`, `stiffness`, `damping`,

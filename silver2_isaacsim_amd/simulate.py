@@ -29,6 +29,7 @@ from .engine import HydroEngine
 from .extremes import Extremes
 from .mooring import Mooring, MooringSpread
 from .sea import SeaSpectrum
+from .statistics import ResponseStatistics, channel_index
 from .tether import LinkTensions, Tether, TetherNet
 
 
@@ -343,6 +344,9 @@ class ClosedLoopSim:
     _mooring_spread_bufs = None # the buffers themselves, by number of layers (each made once)
     extremes = None             # track_extremes(): the extremes.Extremes view over the bodies' running extremes while they are tracked
     _extremes_view = None       # the view and its buffer (made once)
+    statistics = None           # track_statistics(): the statistics.ResponseStatistics view over the bodies' running sums while they are tracked
+    _statistics_view = None     # the view and its two buffers (made once)
+    _statistics_dirty = False   # samples have entered the record since its last reset
     tether = None               # set_tether(): the tiled (tiles, 7, 64) record of the bodies' tethers while tethers are set
     _tether_buf = None          # the buffer itself (made once)
     tether_net = None           # set_tether_net(): the tiled (tiles, 7 * layers, 64) net of the bodies' tethers while a net is set
@@ -710,6 +714,59 @@ class ClosedLoopSim:
             self.extremes = None
             self._graph = None
 
+    def track_statistics(self, channels=("z", "tension"), levels=None, reset: bool = False) -> ResponseStatistics:
+        """Keep each body's running response statistics: from now on every physics step of run_eager, run (graph replays
+        included) and run_resident adds, INSIDE the stepping kernel, the sample of two channels to the sum and the sum of
+        squares about a reference level and counts the up-crossings of that level (hydro_step_fused_tiled_multi_stat; the
+        record: include/hydro.h, "Statistics") - 44 bytes per body, read and written once per launch whatever the chunk.
+        Nothing feeds back: states, energy, log, extremes and link tensions are bit for bit those of a run that tracks
+        nothing.  It rides with a sea or a sea spectrum, a seabed, lines, a spread, tethers, extremes, an applied wrench, a
+        pose hold and a recorder where those are set, under the rules of the extremes.
+        `channels`: two of "x", "y", "z", "vx", "vy", "vz", "tension" (or 0 .. 6).  `levels`: (n, 2), (2,) or None - None
+        takes a motion or velocity channel's level from the CURRENT state and the tension channel's as 0, so that the
+        tension count is the number of slack-to-taut events.
+        The record does not remember its channels or levels: while samples are in it, a call that changes either raises
+        ValueError unless reset=True (or `view.reset()` came first).  The first call and reset=True start from the empty
+        record; a call with the same channels and levels=None goes on accumulating.  Returns `sim.statistics`, a
+        `statistics.ResponseStatistics` view; the addresses of its buffers never change."""
+        if not self.fused:
+            raise ValueError("statistics are tracked in the fused step kernels (fused=True)")
+        if len(channels) != 2:
+            raise ValueError("track_statistics takes exactly two channels")
+        numbers = tuple(channel_index(c) for c in channels)
+        view = self._statistics_view
+        changed = view is not None and (numbers != view.channel_numbers or levels is not None)
+        if changed and self._statistics_dirty and not reset:
+            raise ValueError("the statistics record holds samples of other channels or levels: pass reset=True (or call "
+                             "sim.statistics.reset() first)")
+        if view is None or changed or reset:
+            if levels is None:
+                state = self.state()
+                lev = np.stack([state[:, (0, 1, 2, 7, 8, 9)[c]] if c < 6 else np.zeros(self.n, np.float32) for c in numbers], axis=1)
+            else:
+                lev = np.broadcast_to(np.asarray(levels, np.float32), (self.n, 2))
+            lev = np.ascontiguousarray(lev, np.float32)
+            if view is None:
+                view = self._statistics_view = ResponseStatistics(self, self.engine.alloc_statistics(self.n),
+                                                                  self.engine.alloc_tiled(nat.STAT_LEVEL_FIELDS, self.n), numbers, lev)
+            else:
+                self.synchronize()                              # launches in flight read the levels this rewrites
+                view.channels = tuple(ResponseStatistics.channel_names(numbers))
+                view.levels = lev.copy()
+            view.levels_buffer.copy_(torch.from_numpy(scenes.to_tiled(lev)))
+            view.reset()
+        if self.statistics is None or changed:
+            self._graph = None                                  # captured steps are of another entry / other channels
+        self.statistics = view
+        return view
+
+    def clear_statistics(self) -> None:
+        """Stop tracking: every call the sim makes is again the one it made before track_statistics.  The record keeps its
+        contents (the view returned by track_statistics still reads them)."""
+        if self.statistics is not None:
+            self.statistics = None
+            self._graph = None
+
     def set_tether(self, pairs, fairlead_a=(0.0, 0.0, 0.0), fairlead_b=(0.0, 0.0, 0.0), *, length, stiffness, damping=0.0) -> torch.Tensor:
         """Tie bodies to each other: from now on every physics step of run_eager, run (graph replays included) and
         run_resident lets one tension-only line per pair pull the two fairleads towards each other with equal and opposite
@@ -851,7 +908,8 @@ class ClosedLoopSim:
         if self.link_tensions is not None:
             self.link_tensions.links, self.link_tensions.layer = self._tether_links
 
-    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # the response statistics if they are tracked (their entry takes every other option, the spectrum included), else through
     # the sea spectrum if `sim.sea` is one (its entry takes every other option), else with
     # the mooring spread if one is set (its entry takes every other option), else with
     # the link tensions if they are tracked (over the net, or over the tethers as a net of one layer), else with
@@ -869,7 +927,18 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if isinstance(self.sea, SeaSpectrum):
+        if self.statistics is not None:
+            # (the entry of the spectrum, every option optional - through the spectrum if `sim.sea` is one, else as the spread's entry steps)
+            st = self.statistics
+            moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
+            net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
+            rows = e.step_fused_tiled_multi_stat(*args, k, self.steps_done, st.buffer, st.levels_buffer, *st.channel_numbers,
+                                                 moor, moor_layers, net, layers,
+                                                 self.link_tensions.buffer if self.link_tensions is not None else None,
+                                                 self.extremes.buffer if self.extremes is not None else None,
+                                                 self.control, self.applied, self.applied_frame, **kw)
+            self._statistics_dirty = True
+        elif isinstance(self.sea, SeaSpectrum):
             # (the entry of the spread, every option optional: set_mooring's single record rides as a spread of one layer)
             moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
             net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
