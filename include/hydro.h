@@ -1204,8 +1204,10 @@ int hydro_step_fused_tiled_multi_irr(hydro_t *h, int64_t n, const float *state, 
  * not above its level", bits 0 .. 30 are the count (modulo 2^31).  If bit 31 is set and `above`, the count goes up by one; then
  * bit 31 = !above.  A reset record has bit 31 clear, so the first sample never counts, and x == L is not above.  With L = +0
  * on the tension channel the count is the number of slack-to-taut events.
- * n is not touched inside the loop: the end of a launch adds `steps` to the value it reads from the record.
- * A NaN sample makes that body's S1 and S2 of that slot NaN for good and nobody else's; it is never above.
+ * n is not touched inside the loop: the end of a launch adds `steps` to the value it reads from the record.  n is a uint32_t and
+ * wraps modulo 2^32, as the count wraps modulo 2^31 without touching bit 31.
+ * A NaN sample makes that body's S1 and S2 of that slot NaN for good and nobody else's; it is never above, so it leaves bit 31
+ * set and the next sample above the level counts.  A sample equal to an infinite level gives d = NaN (Inf - Inf) likewise.
  * NOT PROVIDED: heave relative to the moving surface; covariances between channels; more than two channels per record;
  * statistics of the wrench; per-link statistics of tether nets.
  *

@@ -163,18 +163,29 @@ ENTRIES = {
     "teth": ("step_fused_tiled_multi_teth", ("step0", "tether", "extremes", "mooring", "control", "applied")),
     "net": ("step_fused_tiled_multi_net", ("step0", "tether", "layers", "extremes", "mooring", "control", "applied")),
     "peak": ("step_fused_tiled_multi_peak", ("step0", "tether", "layers", "peaks", "extremes", "mooring", "control", "applied")),
+    "spread": ("step_fused_tiled_multi_spread", ("step0", "mooring", "mooring_layers", "tether", "layers", "peaks", "extremes", "control", "applied")),
+    "irr": ("step_fused_tiled_multi_irr", ("step0", "mooring", "mooring_layers", "tether", "layers", "peaks", "extremes", "control", "applied")),
+    "stat": ("step_fused_tiled_multi_stat", ("step0", "statistics", "levels", "channel_a", "channel_b", "mooring", "mooring_layers", "tether", "layers", "peaks",
+                                             "extremes", "control", "applied")),
 }
+COUNTS = {"layers": 1, "mooring_layers": 1, "channel_a": 2, "channel_b": 6}      # what an entry that takes a count is given where the caller names none
 
 
 def step(eng, entry, cur, old, n, steps, *, step0=0, applied=None, frame="world", control=None, mooring=None, extremes=None, tether=None,
-         layers=None, peaks=None, implicit=False, ke=None, dt=DT, **kw):
+         layers=None, peaks=None, mooring_layers=None, statistics=None, levels=None, channels=None, implicit=False, ke=None, dt=DT, **kw):
     """One launch of `entry` through the engine; returns (state, prev_out): the buffer that received the final state and the six
-    velocity fields of the other one.  An option the entry does not take must be None (step0: 0); `layers` is the net's, for
-    the entries that take one.  dt: the step, a Python double (the scene's rho and g are the engine's: HydroEngine(n, DEV, rho, g))."""
+    velocity fields of the other one.  An option the entry does not take must be None (step0: 0); `layers` is the net's and
+    `mooring_layers` the spread's, for the entries that take one (1 where the caller names none); `channels` the statistics' pair
+    ((z, tension) likewise).  The sea spectrum is the engine's (set_sea_spectrum), like the sea and the bed.  dt: the step, a Python
+    double (the scene's rho and g are the engine's: HydroEngine(n, DEV, rho, g))."""
     method, takes = ENTRIES[entry]
-    given = dict(step0=step0, applied=applied, control=control, mooring=mooring, extremes=extremes, tether=tether, layers=layers, peaks=peaks)
+    given = dict(step0=step0, applied=applied, control=control, mooring=mooring, extremes=extremes, tether=tether, layers=layers, peaks=peaks,
+                 mooring_layers=mooring_layers, statistics=statistics, levels=levels, channel_a=None if channels is None else channels[0],
+                 channel_b=None if channels is None else channels[1])
     for name, value in given.items():
         assert name in takes or value is None or (name == "step0" and value == 0), (entry, name)
+        if value is None and name in takes and name in COUNTS and entry in ("spread", "irr", "stat"):
+            given[name] = COUNTS[name]
     getattr(eng, method)(cur, old, n, dt, steps, *(given[name] for name in takes), frame, implicit_drag=implicit, ke_out=ke, **kw)
     return old, cur[:, 7:13]
 
@@ -190,25 +201,32 @@ RAW_EXTRAS = {
     "moor": ("applied", "control", "mooring", "step0"),
     "ext": ("applied", "control", "mooring", "extremes", "step0"),
     "teth": ("applied", "control", "mooring", "extremes", "tether", "step0"),
+    "spread": ("applied", "control", "mooring", "mooring_layers", "extremes", "tether", "tether_layers", "peaks", "step0"),
+    "irr": ("applied", "control", "mooring", "mooring_layers", "extremes", "tether", "tether_layers", "peaks", "step0"),
+    "stat": ("applied", "control", "mooring", "mooring_layers", "extremes", "tether", "tether_layers", "peaks", "statistics", "levels", "channels", "step0"),
 }
 
 
 def raw(eng, entry, n, state, prev, out, pvo, *, steps=1, step0=0, implicit=0, log=None, fields=13, frame=0, applied=None, control=None,
-        mooring=None, extremes=None, tether=None, s_applied=S_A, s_control=S_C, s_mooring=S_M, s_extremes=None, s_tether=None):
+        mooring=None, extremes=None, tether=None, s_applied=S_A, s_control=S_C, s_mooring=S_M, s_extremes=None, s_tether=None,
+        mooring_layers=1, tether_layers=1, peaks=None, s_peaks=None, statistics=None, s_statistics=None, levels=None, s_levels=None, channels=(2, 6)):
     """hydro_step_fused_tiled_multi_<entry> with the guard tests' strides on state, prev, out and pvo; records as tensors,
-    addresses or None, each with its tile stride (the extremes' and the tether's differ between modules: no default).  The
+    addresses or None, each with its tile stride (the extremes' and the tether's differ between modules: no default; an absent
+    record's stride may be None: 0 is passed).  The counts of "spread", "irr" and "stat" follow their records, the channels the levels.  The
     recorder's arguments are fixed: 8 watched bodies at most, 4 rows, `fields` fields, every 1, phase 1, row0 0.  Returns
     (rc, rows_written); rows_written starts from the sentinel -7."""
     ptr = lambda b: b.data_ptr() if hasattr(b, "data_ptr") else b  # noqa: E731
     records = dict(applied=(applied, s_applied), control=(control, s_control), mooring=(mooring, s_mooring), extremes=(extremes, s_extremes),
-                   tether=(tether, s_tether))
+                   tether=(tether, s_tether), peaks=(peaks, s_peaks), statistics=(statistics, s_statistics), levels=(levels, s_levels))
+    scalars = dict(step0=(step0,), mooring_layers=(mooring_layers,), tether_layers=(tether_layers,), channels=tuple(channels))
     extras = []
     for name in RAW_EXTRAS[entry]:
-        if name == "step0":
-            extras.append(step0)
+        if name in scalars:
+            extras += scalars[name]
             continue
         record, stride = records.pop(name)
-        assert stride is not None, (entry, name)
+        assert stride is not None or (record is None and entry in ("spread", "irr", "stat")), (entry, name)
+        stride = 0 if stride is None else stride
         extras += [ptr(record), stride] + ([frame] if name == "applied" else [])
     assert all(record is None for record, _ in records.values()), (entry, sorted(records))
     written = ctypes.c_int64(-7)

@@ -4,7 +4,6 @@ test - config 1's buoy, copied along x, in a regular wave whose period is a few 
 
 No device is needed to import this module; the callers that launch take the engine and the tensors they are given.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -61,14 +60,12 @@ def raw_stat(eng, n, dt, state, prev, out, pvo, strides, *, steps=1, step0=0, im
              mooring=None, s_mooring=0, layers=1, extremes=None, s_extremes=0, tether=None, s_tether=0, net_layers=1, peaks=None, s_peaks=0,
              statistics=None, s_statistics=S_ST, levels=None, s_levels=S_LV, channels=(2, 6)):
     """hydro_step_fused_tiled_multi_stat; `strides` = (state, prev, out, pvo).  Returns (rc, rows_written from the sentinel -7)."""
-    ptr = lambda b: b.data_ptr() if hasattr(b, "data_ptr") else b  # noqa: E731
-    written = ctypes.c_int64(-7)
-    rc = eng._lib.hydro_step_fused_tiled_multi_stat(
-        eng._h, n, ptr(state), strides[0], ptr(prev), strides[1], dt, steps, ptr(out), strides[2], ptr(pvo), strides[3],
-        int(implicit), 1, None, ptr(log), 8, 4, 13, 1, 1, 0, ctypes.byref(written),
-        ptr(applied), s_applied, 0, ptr(control), s_control, ptr(mooring), s_mooring, layers, ptr(extremes), s_extremes, ptr(tether), s_tether, net_layers,
-        ptr(peaks), s_peaks, ptr(statistics), s_statistics, ptr(levels), s_levels, channels[0], channels[1], step0, eng._stream(None))
-    return rc, written.value
+    import resident_harness as rh                                  # (imports torch: only the callers that launch come here)
+    assert tuple(strides) == (rh.S_IN, rh.S_PV, rh.S_OUT, rh.S_PVO) and dt == rh.DT
+    return rh.raw(eng, "stat", n, state, prev, out, pvo, steps=steps, step0=step0, implicit=implicit, log=log, applied=applied, s_applied=s_applied,
+                  control=control, s_control=s_control, mooring=mooring, s_mooring=s_mooring, mooring_layers=layers, extremes=extremes, s_extremes=s_extremes,
+                  tether=tether, s_tether=s_tether, tether_layers=net_layers, peaks=peaks, s_peaks=s_peaks, statistics=statistics, s_statistics=s_statistics,
+                  levels=levels, s_levels=s_levels, channels=channels)
 
 
 # ---- the scene in which up-crossings really occur ------------------------------------------------------------------------------------------

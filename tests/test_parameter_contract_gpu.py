@@ -310,7 +310,7 @@ def _ladder(eng, pop, n, steps, implicit, *, spread, net, chunks=None):
     torch.cuda.synchronize()
     rows = np.concatenate(logs)
     return dict(state=_from(cur, n), prev=_from(old, n)[:, 7:13], log=rows.transpose(1, 0, 2).reshape(n, -1), extremes=_from(record, n),
-                peaks=_from(peaks, n))
+                peaks=_from(peaks, n), statistics=np.zeros((n, 0), np.float32))             # (the spread entry keeps no statistics)
 
 
 @COEFFS

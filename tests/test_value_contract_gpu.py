@@ -6,7 +6,9 @@ and engines fixtures, one caller per open-loop entry, `_isolated`, `_everything`
    overflows - go through every entry: step_wrench in both previous-velocity modes, step_wrench_tiled plain and _ke, the batch (one
    poisoned scene of three), step_wrench_aos in both quaternion orders, the two _sea open-loop entries, step_components and
    step_components_aos, integrate_tiled, step_fused_tiled, and the resident ladder through `peak` with sea, bed, pose hold, a
-   body-frame applied wrench, mooring, extremes, a four-layer net with peaks, the recorder on every body and ke_out.  Every other
+   body-frame applied wrench, mooring, extremes, a four-layer net with peaks, the recorder on every body and ke_out - and through
+   the rungs above it: `spread` (a spread of three layers), `irr` (a spectrum of 64 components) and `stat` in both its kernel
+   families, whose statistics words are one more per-body output.  Every other
    body's outputs have the bits of the launch on the clean population, and a clean launch on the same engine afterwards gives the
    clean bits again.  The same for poisoned rows of the control record; the f_max rows' own step is held to pose_hold_reference
    under STEP_ULP_BOUND.
@@ -50,6 +52,7 @@ import pytest
 import torch
 
 import mooring_reference as mr
+import sea_spectrum_reference as ssr
 import tether_reference as tr
 import value_contract as vc
 from silver2_isaacsim_amd import extremes as ex
@@ -60,6 +63,8 @@ from tether_net_population import net_for
 from value_contract_launches import (CURRENT, _everything, engines, _isolated, OPEN_LOOP, PER_BODY, pop, SIZES, STEP0, STEPS)  # noqa: F401  (pop, engines: fixtures)
 
 pytestmark = pytest.mark.gpu
+FULL = ssr.designed_spectrum()                                    # 64 components
+RUNGS = (("spread", None), ("irr", FULL), ("stat", None), ("stat", FULL))
 
 
 # ---- 1. a non-finite body is its own problem ---------------------------------------------------------------------------------------------
@@ -122,7 +127,9 @@ def test_a_poisoned_body_is_its_own_problem_in_the_single_step_entries(coeff, se
 @COEFFS_SEMANTICS
 @DRAG
 def test_a_poisoned_body_or_control_row_is_its_own_problem_in_the_resident_ladder(coeff, semantics, implicit, pop, engines):
-    """`peak` with everything on and ke_out given: the poison table in the state, then in the control record with the state clean."""
+    """`peak` with everything on and ke_out given: the poison table in the state, then in the control record with the state clean.
+    Then the same through `spread`, through `irr` under the 64-component spectrum, and through `stat` under the regular sea (the
+    _stat kernel family) and under the spectrum (the _irr_stat family)."""
     for n in SIZES:
         eng = engines(n, coeff, semantics)
         st, pv, ctl = pop["st"][:n], pop["pv"][:n], pop["ctl"][:n]
@@ -140,6 +147,23 @@ def test_a_poisoned_body_or_control_row_is_its_own_problem_in_the_resident_ladde
                     vc.assert_isolated(got[key], want[key], bodies, (what, key, n, steps))
                     vc.assert_same_bits(again[key], want[key], (what, key, n, steps, "the clean launch afterwards"))
                 assert not vc.same_bits(got["state"][bodies], want["state"][bodies])
+        # the rungs above `peak`, each kernel family once: the same assertions, with the spread of three layers, the 64-component
+        # spectrum and the statistics record (whose eleven words per body are one more per-body output)
+        for entry, spectrum in RUNGS:
+            for steps in STEPS:
+                run = lambda s, p, c: _everything(eng, pop, n, steps, implicit, st=s, pv=p, ctl=c, net=net, ke=True, entry=entry, spectrum=spectrum)  # noqa: E731
+                want = run(st, pv, ctl)
+                assert (want["peaks"] > 0).sum() >= n // 8 and (want["extremes"][:, 7] > 0).sum() >= n // 8
+                assert want["statistics"].shape == (n, 11 if entry == "stat" else 0)
+                for what, got in (("state", run(ps, pp, ctl)), ("control", run(st, pv, bad_ctl))):
+                    again = run(st, pv, ctl)
+                    for key in PER_BODY:
+                        vc.assert_isolated(got[key], want[key], bodies, (entry, spectrum is not None, what, key, n, steps))
+                        vc.assert_same_bits(again[key], want[key], (entry, spectrum is not None, what, key, n, steps, "the clean launch afterwards"))
+                    assert not vc.same_bits(got["state"][bodies], want["state"][bodies])
+                    if entry == "stat":                            # the poisoned bodies' records count the steps like everybody's, and differ
+                        assert (vc.bits(got["statistics"])[:, 10] == steps).all()
+                        assert not vc.same_bits(got["statistics"][bodies], want["statistics"][bodies])
 
 
 @COEFFS

@@ -1,14 +1,17 @@
 """The launches tests/test_value_contract_gpu.py and tests/test_parameter_contract_gpu.py share: the population and engines
 fixtures (the bodies, net and mooring lines of tests/test_tether_net_gpu.py, and the same with the exact-zero bodies), one caller
 per open-loop entry (`OPEN_LOOP`), `_isolated` (clean, poisoned, clean again) and `_everything` (one resident launch with every
-option on).  Nothing is asserted here but what those two modules ask through these callers."""
+option on, through `peak` or any earlier entry, or through `spread`, `irr` and `stat`: the five kernel families above _peak).  Nothing is asserted here but what those two modules ask through these callers."""
 import numpy as np
 import pytest
 import torch
 
 import mooring_population as mp
+import statistics_contract as sc
 import value_contract as vc
+from mooring_spread_population import spread_population
 from silver2_isaacsim_amd import extremes as ex
+from silver2_isaacsim_amd import statistics as stx
 from silver2_isaacsim_amd.sea import SeaState
 from designed_populations import BED, SEA
 from resident_harness import _buffers, DEV, DT, _engine, _from, _ke, _log, NAN, _rows, step, _tiled
@@ -32,6 +35,7 @@ def pop(bed_pop, hold_pop):
     zst, zpv, zapplied, zctl, zmoor = vc.exact_zero_bodies(*base.values())
     pulling = np.flatnonzero(mp.population_report(moor, st[:n])[0] & mp.OFF_TIES)
     return dict(base, params={k: v[:n] for k, v in params.items()}, net=net, rec=net[:, 0:7], groups=groups, pulling=pulling,
+                spread=spread_population(st[:n], params["f32"][:n], moor),
                 zero=dict(st=zst, pv=zpv, applied=zapplied, ctl=zctl, moor=zmoor), hold=(hold_pop[0][:n], hold_pop[1][:n], hold_pop[5]))
 
 
@@ -46,6 +50,7 @@ def engines(pop, native_built):
         eng = made[n, coeff]
         eng.set_tuning()
         eng.set_semantics(semantics)
+        eng.set_sea_spectrum(None)
         eng.set_sea(None)
         eng.set_seabed(None)
         eng.set_watch(None)
@@ -151,17 +156,40 @@ def _isolated(run, clean, poisoned, bodies, what):
     return want, got
 
 
-def _everything(eng, pop, n, steps, implicit, *, st, pv, ctl, net, moor=None, seed=None, ke=False, entry="peak", layers=4, applied=True, chunks=None, bed=BED, sea=SEA):
+STAT_CHANNELS = (2, 6)                                            # `_everything`'s statistics: z and the tension
+
+
+def _words(record, n):
+    """The statistics record's 11 words per body, (n, 11) as float32 BIT PATTERNS: value_contract's checkers compare bits."""
+    rec = stx.unpack(record.cpu().numpy(), n)
+    return np.concatenate([rec["sums"].view(np.uint32), rec["up"], rec["n"][:, None]], axis=1).view(np.float32)
+
+
+def _everything(eng, pop, n, steps, implicit, *, st, pv, ctl, net, moor=None, seed=None, ke=False, entry="peak", layers=4, applied=True, chunks=None, bed=BED, sea=SEA,
+                spectrum=None):
     """One resident launch (or `chunks` of them) with everything on: sea, bed, pose hold, a body-frame applied wrench, mooring,
-    extremes (from `seed`, default the empty record), the net with peaks, the recorder on every body.  Returns per-body arrays:
-    state (n, 13), prev_out (n, 6), log (n, steps * 19), extremes (n, 8), peaks (n, layers), and the rows (steps, n, 19)."""
-    eng.set_sea(sea)
+    extremes (from `seed`, default the empty record), the net with peaks, the recorder on every body.  `entry` "spread", "irr" and
+    "stat" take all of it with the designed spread of three layers in place of the single line; `spectrum` (a SeaSpectrum) takes the
+    place of `sea` for "irr" and "stat" - the _irr and _irr_stat kernel families -; "stat" keeps a statistics record of STAT_CHANNELS
+    from the empty record against gap levels of the CLEAN population's initial z (the same levels whatever `st` holds).  Returns
+    per-body arrays: state (n, 13), prev_out (n, 6), log (n, steps * 19), extremes (n, 8), peaks (n, layers), statistics (n, 11 words;
+    (n, 0) where the entry keeps none), and the rows (steps, n, 19)."""
+    assert spectrum is None or entry in ("irr", "stat"), entry
+    eng.set_sea_spectrum(None)
+    eng.set_sea(None if spectrum is not None else sea)
+    eng.set_sea_spectrum(spectrum)
     eng.set_seabed(bed)
     eng.set_watch(list(range(n)))
     cur, old = _buffers(st, pv, n)
-    takes = {"moor": 0, "ext": 1, "teth": 2, "net": 3, "peak": 4}[entry]
+    takes = {"moor": 0, "ext": 1, "teth": 2, "net": 3, "peak": 4, "spread": 5, "irr": 5, "stat": 6}[entry]
     kw = dict(mooring=_tiled((pop["moor"] if moor is None else moor)[:n]), control=_tiled(ctl[:n]) if ctl is not None else None, applied=_tiled(pop["applied"][:n]) if applied else None, frame="body")
-    record = peaks = None
+    record = peaks = statistics = None
+    if takes >= 5:
+        kw.update(mooring=_tiled((pop["spread"][:, 0:27] if moor is None else moor)[:n]), mooring_layers=3)
+    if takes >= 6:
+        statistics = eng.statistics_reset(eng.alloc_statistics(n), n)
+        levels = sc.gap_levels(np.stack([pop["st"][:n, 2], np.zeros(n, np.float32)], axis=1), 27)
+        kw.update(statistics=statistics, levels=_tiled(levels), channels=STAT_CHANNELS)
     if takes >= 1:
         record = kw["extremes"] = _tiled(ex.Extremes.empty(n) if seed is None else seed)
     if takes >= 2:
@@ -184,7 +212,9 @@ def _everything(eng, pop, n, steps, implicit, *, st, pv, ctl, net, moor=None, se
         out["extremes"] = _from(record, n)
     if peaks is not None:
         out["peaks"] = _from(peaks, n)
+    out["statistics"] = _words(statistics, n) if statistics is not None else np.zeros((n, 0), np.float32)
+    eng.set_sea_spectrum(None)
     return out
 
 
-PER_BODY = ("state", "prev", "log", "extremes", "peaks")
+PER_BODY = ("state", "prev", "log", "extremes", "peaks", "statistics")
