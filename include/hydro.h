@@ -69,7 +69,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_set_sea_spectrum, hydro_sea_spectrum_sample, hydro_step_fused_tiled_multi_irr,
  *        HYDRO_SPECTRUM_WAVES_MAX - an irregular sea of up to 64 wave components in the closed-loop steps
  *        added to 0.7.1 (no existing entry changed): hydro_statistics_reset, hydro_step_fused_tiled_multi_stat, HYDRO_STAT_* -
- *        running per-body response statistics (sum, sum of squares, up-crossings of a level) updated inside every step */
+ *        running per-body response statistics (sum, sum of squares, up-crossings of a level) updated inside every step
+ *        added to 0.7.1 (no existing entry changed): hydro_set_sea_ensemble, hydro_sea_ensemble_sample, hydro_step_fused_tiled_multi_ens,
+ *        HYDRO_SEA_ENSEMBLE_MAX - up to 1024 sea spectra in one launch, block m of the bodies stepping through member m */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -96,6 +98,7 @@ extern "C" {
 #define HYDRO_SEA_WAVES_MAX   8   /* regular wave components of a sea state (hydro_set_sea) */
 #define HYDRO_SEA_FIELDS      4   /* the record of hydro_sea_sample: eta, u_x, u_y, u_z */
 #define HYDRO_SPECTRUM_WAVES_MAX 64 /* wave components of a sea spectrum (hydro_set_sea_spectrum) */
+#define HYDRO_SEA_ENSEMBLE_MAX 1024 /* members of a sea ensemble (hydro_set_sea_ensemble) */
 /* the channels of a statistics record (hydro_step_fused_tiled_multi_stat) */
 #define HYDRO_STAT_X        0    /* s[0] */
 #define HYDRO_STAT_Y        1    /* s[1] */
@@ -1250,6 +1253,73 @@ int hydro_step_fused_tiled_multi_stat(hydro_t *h, int64_t n, const float *state,
                                       void *statistics, int64_t statistics_tile_stride,
                                       const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
                                       int64_t step0, void *stream);
+
+/* Sea ensemble: `count` sea spectra ("Sea spectrum", above) in one launch, each over a block of the bodies - the realisations
+ * (seeds), headings and currents a design extreme is taken over, stepped together instead of one run after the other.  A single
+ * realisation of a few thousand bodies leaves most of the device idle; sixteen of them in one launch cost little more than one.
+ *
+ * MAPPING: body i belongs to tile i / 64, and tile T steps through member  sea(T) = T / tiles_per_sea,  tiles_per_sea =
+ * bodies_per_sea / 64 - so member m has the bodies m * bodies_per_sea .. (m + 1) * bodies_per_sea - 1.  bodies_per_sea is a
+ * positive multiple of 64.  A member's block may lie partly or wholly past n (the last one usually does): what is past n is not
+ * stepped, as ever.  A launch needs ceil(tiles(n) / tiles_per_sea) members, tiles(n) = ceil(n / 64).
+ * WATER AT A BODY is "Sea spectrum"'s, statement for statement, read against the body's member.  So, bit for bit, a body of
+ * member m takes the step it takes in hydro_step_fused_tiled_multi_stat under hydro_set_sea_spectrum(member m) - the ensemble
+ * changes which table a wavefront reads and nothing else.
+ * MEMBERS: every member has its own current U and its own components; all members have the SAME `waves`, 0 .. 64.  At most
+ * HYDRO_SEA_ENSEMBLE_MAX = 1024 members.  The device table is count * 3088 B, engine-owned (it grows when a call needs more
+ * members than any before, and is freed by hydro_destroy).
+ *
+ * hydro_set_sea_ensemble: `members` is the caller's array of `count` hydro_sea_spectrum_t (read, with their components, during
+ * the call only).  hydro_set_sea_spectrum's validator is applied to every member; the table is copied on the engine's private
+ * stream and waited for.  members == NULL clears the ensemble (count and bodies_per_sea are not looked at).  HYDRO_E_ARG for
+ * count outside 1 .. HYDRO_SEA_ENSEMBLE_MAX, bodies_per_sea below 64 or not a multiple of 64, members of unequal `waves`, and
+ * whatever hydro_set_sea_spectrum refuses of any member - the previous ensemble stays in force.
+ * AN ENSEMBLE, A SPECTRUM AND A SEA EXCLUDE EACH OTHER, at set time: each of hydro_set_sea, hydro_set_sea_spectrum and
+ * hydro_set_sea_ensemble (non-NULL) returns HYDRO_E_STATE while another kind is set, and its message names the call that clears
+ * that kind (an ensemble: hydro_set_sea_ensemble(h, NULL, 0, 0)); what was set stays in force.  Clearing with NULL is always
+ * allowed.  ONLY hydro_step_fused_tiled_multi_ens and hydro_sea_ensemble_sample know the ensemble: EVERY OTHER ENTRY IGNORES IT,
+ * as every entry but hydro_step_fused_tiled_multi_irr and _stat ignores a spectrum.
+ *
+ * hydro_sea_ensemble_sample: the signature and the rules of hydro_sea_spectrum_sample, each body read against its member.
+ * HYDRO_E_STATE without an ensemble; HYDRO_E_ARG, last, if n needs more members than `count`.
+ *
+ * hydro_step_fused_tiled_multi_ens: exactly the signature, the refusals and the refusal order of
+ * hydro_step_fused_tiled_multi_stat.
+ *   no ensemble set : the launch and its bits are those of hydro_step_fused_tiled_multi_stat with the same arguments.
+ *   an ensemble set : every other option is still optional and adds what it adds in hydro_step_fused_tiled_multi_stat;
+ *                     statistics == NULL gives the family without statistics.  One further refusal comes LAST:
+ *                     ceil(tiles(n) / tiles_per_sea) > count returns HYDRO_E_ARG, and nothing is launched or written.
+ * Asynchronous, no allocation, no synchronisation, safe to capture under the spectrum's rule: a captured launch replays at a
+ * frozen step0 - capture current-only members.
+ * COST: with tiles_per_sea a multiple of 4 the four wavefronts of a block read one member, as they read one spectrum; with
+ * tiles_per_sea = 1 every wavefront streams its own 3 KB table through the scalar cache.  Measured on an MI355X at 65 536 bodies
+ * and 64 components: 16 members of 4 096 bodies cost 0.99 - 1.01 times the single spectrum's step, and 16
+ * seeds of 4 096 bodies in one launch 1 / 16 of sixteen launches; SMALL BLOCKS ARE MARKEDLY SLOWER - members of 256 bodies 1.01
+ * (nothing but the sea) to 1.17 times (a spread, extremes and statistics), members of 64 bodies 1.11 to 1.42 times.  Guidance, not a
+ * rule: give each member as many bodies as the study has, a multiple of 256 bodies.
+ * NOT PROVIDED: members with different component counts; a per-body index table (the mapping is by block); ensembles in the
+ * open-loop entries (hydro_step_wrench_*_sea) and the plugin; a sign-symmetry statement for the ensemble (each member's is
+ * "Sea spectrum"'s).
+ * New functionality; the reference's water does not move. */
+int hydro_set_sea_ensemble(hydro_t *h, const hydro_sea_spectrum_t *members, int64_t count, int64_t bodies_per_sea);
+int hydro_sea_ensemble_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
+                              float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_ens(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                     const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float *state_out, int64_t out_tile_stride,
+                                     float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double *ke_out_dev,
+                                     float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t *rows_written_host,
+                                     const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float *control, int64_t control_tile_stride,
+                                     const float *mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                     float *extremes, int64_t extremes_tile_stride,
+                                     const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                     float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                     void *statistics, int64_t statistics_tile_stride,
+                                     const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                     int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

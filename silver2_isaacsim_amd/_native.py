@@ -27,6 +27,7 @@ WATCH_MAX = 65536
 SEA_WAVES_MAX = 8                       # regular wave components of a sea state (hydro_set_sea)
 SEA_FIELDS = 4                          # the record of hydro_sea_sample: eta, u_x, u_y, u_z
 SPECTRUM_WAVES_MAX = 64                 # wave components of a sea spectrum (hydro_set_sea_spectrum)
+SEA_ENSEMBLE_MAX = 1024                 # members of a sea ensemble (hydro_set_sea_ensemble)
 # the statistics record of hydro_step_fused_tiled_multi_stat: channels, and the record in 4-byte units per body (4 doubles + 3 words)
 STAT_X, STAT_Y, STAT_Z, STAT_VX, STAT_VY, STAT_VZ, STAT_TENSION = range(7)
 STAT_CHANNELS = 7
@@ -145,6 +146,9 @@ SIGNATURES = {
     "hydro_step_fused_tiled_multi_irr": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STEP0),
     "hydro_statistics_reset": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "hydro_step_fused_tiled_multi_stat": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
+    "hydro_set_sea_ensemble": (c_int, [c_void_p, POINTER(SeaSpectrum), c_int64, c_int64]),
+    "hydro_sea_ensemble_sample": (c_int, _SAMPLE),
+    "hydro_step_fused_tiled_multi_ens": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

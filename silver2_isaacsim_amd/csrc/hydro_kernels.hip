@@ -2698,6 +2698,86 @@ __global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_
                                                    OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
 }
 
+// --------------------------------------------------------------------------
+// SEA ENSEMBLES in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_ens): `count` spectra of the model above,
+// one SpectrumTable behind the other in an engine-owned device table, and block m of `tiles_per_sea` tiles steps through
+// member m (hydro_set_sea_ensemble; include/hydro.h, "Sea ensemble").  The water is spectrum_water's, statement for
+// statement: the ONLY thing an ensemble changes is where the wave's table pointer points.
+//   the member : tile / tiles_per_sea, formed ONCE in begin from the wave's tile (wave-uniform, told to the compiler with
+//                v_readfirstlane) - four waves of a block may read four different members (tiles_per_sea = 1)
+//   the pointer: SeaView::tab moved on by member * sizeof(SpectrumTable): a scalar 64-bit add in front of the step loop.
+//                The component loops read through it with scalar loads as before; nothing new is live in the step loop
+//   dead waves : a wave whose lanes are all >= n never reaches a sea policy (fused_multi_body), so a member index past
+//                `count` is never formed into an address that is read: the host refuses a launch whose LIVE tiles need more
+//                members than the table holds
+// view and restore are SpectrumView's; fused_multi_body is not touched.
+// --------------------------------------------------------------------------
+#define HYDRO_ENS_PARAMS uint32_t tiles_per_sea
+#define HYDRO_ENS_ARGS tiles_per_sea
+// the table of the member that `tile` steps through (both wave-uniform)
+__device__ __forceinline__ SpectrumTablePtr ensemble_member(SpectrumTablePtr table, uint32_t tile, uint32_t tiles_per_sea)
+{
+    // (there is no scalar divide: the quotient of two scalars is formed with vector instructions whichever way it is written.  Left
+    // to itself the compiler fails on it here ("illegal VGPR to SGPR copy" in every instantiation), so both operands are handed
+    // over as vector values, the quotient is taken as one, and it comes back through v_readfirstlane like wave_tile's index)
+    uint32_t t = tile, d = tiles_per_sea;
+    asm volatile("" : "+v"(t), "+v"(d));
+    uint32_t q = t / d;
+    asm volatile("" : "+v"(q));
+    return table + __builtin_amdgcn_readfirstlane(q);
+}
+struct SpectrumEnsembleView : SpectrumView {
+    uint32_t tiles_per_sea;
+    __device__ __forceinline__ void begin(uint32_t lane4_)
+    {
+        SpectrumView::begin(lane4_);
+        tab = (SeaTablePtr)ensemble_member((SpectrumTablePtr)tab, wave_tile<kBlock>(blockIdx.x), tiles_per_sea);
+    }
+};
+__device__ __forceinline__ SpectrumEnsembleView spectrum_ensemble_view(HYDRO_SEA_PARAMS, HYDRO_ENS_PARAMS)
+{
+    return SpectrumEnsembleView{spectrum_view(HYDRO_SEA_ARGS), HYDRO_ENS_ARGS};
+}
+
+// The _irr kernel's arguments, then the ensemble's; the sea group carries the ensemble's table and the members' count of components.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_ens_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                 HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                 HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_ENS_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   spectrum_ensemble_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS),
+                                                   mooring_spread(HYDRO_SPREAD_ARGS), optional_extremes_track(HYDRO_EXT_ARGS),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// The _irr_stat kernel's arguments, then the ensemble's.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_ens_stat_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                      HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                      HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_STAT_PARAMS,
+                                                                                                      HYDRO_ENS_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   spectrum_ensemble_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS),
+                                                   mooring_spread(HYDRO_SPREAD_ARGS), statistics_track(HYDRO_EXT_ARGS, HYDRO_STAT_ARGS, steps),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// hydro_sea_ensemble_sample: spectrum_sample_kernel with every tile read against its member.
+__global__ void __launch_bounds__(kBlock) ensemble_sample_kernel(const float* st, uint32_t st_stride, float* out, uint32_t out_stride, uint32_t n,
+                                                                 const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt, HYDRO_ENS_PARAMS)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float eta, u[3];
+    spectrum_water(ensemble_member((SpectrumTablePtr)sea_table, tile, tiles_per_sea), sea_waves, step, sea_dt, *at<float>(r, lane4, 0u), *at<float>(r, lane4, 256u),
+                   *at<float>(r, lane4, 512u), eta, u);
+    const float o[HYDRO_SEA_FIELDS] = {eta, u[0], u[1], u[2]};
+    store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
+}
+
 // hydro_statistics_reset: the empty record - sums +0.0, words 0 - for the live lanes.
 __global__ void __launch_bounds__(kBlock) statistics_reset_kernel(void* stat, uint32_t stat_stride, uint32_t n)
 {
@@ -2790,6 +2870,12 @@ struct hydro_engine {
     // hydro_set_sea_spectrum, kept until hydro_destroy.  spectrum_waves < 0: no spectrum.  Never set together with a sea.
     void* spectrum_table = nullptr;
     int spectrum_waves = -1;
+    // The sea ensemble (hydro_set_sea_ensemble): `ensemble_count` SpectrumTables one behind the other, the device table allocated
+    // for `ensemble_capacity` members by the first call that needs as many, kept until hydro_destroy.  ensemble_waves < 0: no
+    // ensemble.  Never set together with a sea or a spectrum.
+    void* ensemble_table = nullptr;
+    int64_t ensemble_capacity = 0, ensemble_count = 0, ensemble_tiles_per_sea = 0;
+    int ensemble_waves = -1;
     // The seabed (hydro_set_seabed): the plane and the five contact constants, already rounded to fp32 - kernel arguments.
     Seabed bed = {};
     bool has_bed = false;
@@ -3265,6 +3351,7 @@ int hydro_destroy(hydro_t* h)
     if (h->watch_first) (void)hipFree(h->watch_first);
     if (h->sea_table) (void)hipFree(h->sea_table);
     if (h->spectrum_table) (void)hipFree(h->spectrum_table);
+    if (h->ensemble_table) (void)hipFree(h->ensemble_table);
     delete h;
     return HYDRO_OK;
 }
@@ -3648,7 +3735,7 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// A launch of any of the fourteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// A launch of any of the fifteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
 // was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
 // copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
 // (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
@@ -3675,6 +3762,7 @@ struct MultiStep {
     // the _stat entry: the _irr entry, and the running response statistics if a record is given
     bool stat_entry = false; void* statistics = nullptr; int64_t statistics_tile_stride = 0;
     const float* levels = nullptr; int64_t levels_tile_stride = 0; int channel_a = 0, channel_b = 0;
+    bool ens_entry = false;                              // the _ens entry: the _stat entry, and block m of the bodies steps through member m of the sea ensemble if one is set
 
     void with_recorder(float* log_, int64_t log_stride_, int64_t rows_capacity_, int fields_, int every_, int phase_, int64_t row0_, int64_t* rows_written_host_)
     {
@@ -3699,6 +3787,7 @@ struct MultiStep {
         stat_entry = true; statistics = p; statistics_tile_stride = stride; levels = levels_; levels_tile_stride = levels_stride;
         channel_a = a; channel_b = b;
     }
+    void with_ensemble() { ens_entry = true; }
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3747,7 +3836,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
 // ladder, each taking its predecessor's argument groups and one more:
 //   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak < _spread
 // (the _irr family stands beside the ladder: it is chosen while a sea spectrum is set, by the _irr entry alone, whatever the options;
-// the two _stat families stand beside the _spread and the _irr family: chosen while a statistics record is given, whatever the options)
+// the two _stat families stand beside the _spread and the _irr family: chosen while a statistics record is given, whatever the options;
+// the two _ens families stand beside the _irr and the _irr_stat family: chosen while a sea ensemble is set, by the _ens entry alone)
 // and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
 // the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
@@ -3758,6 +3848,7 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         return fail(h, HYDRO_E_ARG, "step0 must be >= 0 and step0 + steps < 2^52");
     const bool rec = m.log || m.log_required, sea = m.sea_entry && h->sea_waves >= 0, bed = m.bed_entry && h->has_bed;
     const bool irr = m.irr_entry && h->spectrum_waves >= 0;                    // (a spectrum and a sea are never set together: irr implies !sea)
+    const bool ens = m.ens_entry && h->ensemble_waves >= 0;                    // (nor an ensemble with either: ens implies !irr and !sea)
     int64_t rows = 0;
     if (rec && (rc = check_recorder(h, m, rows))) return rc;
     if ((rc = check_common(h, m.n))) return rc;
@@ -3868,6 +3959,12 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         if (meets_output(m.levels, lv_floats))
             return fail(h, HYDRO_E_ARG, "levels must not overlap an output (state_out, prev_out, log, extremes, tether_peaks)");
     }
+    if (ens) {
+        // the last refusal: every LIVE tile's member must be in the table (the kernels index it by tile / tiles_per_sea, unchecked)
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE;
+        if ((tiles + h->ensemble_tiles_per_sea - 1) / h->ensemble_tiles_per_sea > h->ensemble_count)
+            return fail(h, HYDRO_E_ARG, "n needs more members than the sea ensemble has (count * bodies_per_sea < n)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -3896,8 +3993,8 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
         const auto held = [&](auto kernel, auto... tail) { pushed(kernel, m.control, control_stride, tail...); };
         const auto in_sea = [&](auto kernel, auto... tail) {
-            held(kernel, irr ? (const void*)h->spectrum_table : sea ? (const void*)h->sea_table : (const void*)nullptr,
-                 irr ? (uint32_t)h->spectrum_waves : sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
+            held(kernel, ens ? (const void*)h->ensemble_table : irr ? (const void*)h->spectrum_table : sea ? (const void*)h->sea_table : (const void*)nullptr,
+                 ens ? (uint32_t)h->ensemble_waves : irr ? (uint32_t)h->spectrum_waves : sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
         };
         const auto on_bed = [&](auto kernel, auto... tail) {
             in_sea(kernel, h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, tail...);
@@ -3918,12 +4015,18 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
                           m.tether_peaks, m.tether_peaks ? (uint32_t)m.tether_peaks_tile_stride : 0u, tail...);
         };
         // (the statistics group behind everything else: the two _stat families take the _spread family's groups unchanged)
-        const auto with_statistics = [&](auto kernel) {
-            spread_and_all(kernel, m.statistics, (uint32_t)m.statistics_tile_stride, m.levels, (uint32_t)m.levels_tile_stride, (uint32_t)m.channel_a, (uint32_t)m.channel_b);
+        const auto with_statistics = [&](auto kernel, auto... tail) {
+            spread_and_all(kernel, m.statistics, (uint32_t)m.statistics_tile_stride, m.levels, (uint32_t)m.levels_tile_stride, (uint32_t)m.channel_a, (uint32_t)m.channel_b, tail...);
         };
-        // the statistics first, through the spectrum or not; then
+        // the ensemble first: its group stands behind everything else, and its two families take every option the launch has; then
+        // the statistics, through the spectrum or not; then
         // the spectrum: its family stands beside the ladder, not on it, and takes every option the launch has
-        if (m.statistics) {
+        if (ens) {
+            const uint32_t tiles_per_sea = (uint32_t)h->ensemble_tiles_per_sea;
+            if (m.statistics) with_statistics(step_fused_multi_ens_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea);
+            else spread_and_all(step_fused_multi_ens_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea);
+        }
+        else if (m.statistics) {
             if (irr) with_statistics(step_fused_multi_irr_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
             else with_statistics(step_fused_multi_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>);
         }
@@ -4091,6 +4194,7 @@ int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
     if (!h) return HYDRO_E_ARG;
     if (!sea) { h->sea_waves = -1; return HYDRO_OK; }
     if (h->spectrum_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea spectrum is set (clear it first: hydro_set_sea_spectrum(h, NULL))");
+    if (h->ensemble_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea ensemble is set (clear it first: hydro_set_sea_ensemble(h, NULL, 0, 0))");
     if (sea->waves < 0 || sea->waves > HYDRO_SEA_WAVES_MAX) return fail(h, HYDRO_E_ARG, "sea: waves out of range (0 .. HYDRO_SEA_WAVES_MAX)");
     SeaTable tab;
     memset(&tab, 0, sizeof tab);
@@ -4113,6 +4217,7 @@ int hydro_set_sea_spectrum(hydro_t* h, const hydro_sea_spectrum_t* spec)
     if (!h) return HYDRO_E_ARG;
     if (!spec) { h->spectrum_waves = -1; return HYDRO_OK; }
     if (h->sea_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea is set (clear it first: hydro_set_sea(h, NULL))");
+    if (h->ensemble_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea ensemble is set (clear it first: hydro_set_sea_ensemble(h, NULL, 0, 0))");
     if (spec->waves < 0 || spec->waves > HYDRO_SPECTRUM_WAVES_MAX)
         return fail(h, HYDRO_E_ARG, "sea spectrum: waves out of range (0 .. HYDRO_SPECTRUM_WAVES_MAX)");
     if (spec->waves > 0 && !spec->wave) return fail(h, HYDRO_E_ARG, "sea spectrum: null wave with waves > 0");
@@ -4138,13 +4243,64 @@ int hydro_set_sea_spectrum(hydro_t* h, const hydro_sea_spectrum_t* spec)
     return HYDRO_OK;
 }
 
+int hydro_set_sea_ensemble(hydro_t* h, const hydro_sea_spectrum_t* members, int64_t count, int64_t bodies_per_sea)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!members) { h->ensemble_waves = -1; return HYDRO_OK; }
+    if (h->sea_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea is set (clear it first: hydro_set_sea(h, NULL))");
+    if (h->spectrum_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea spectrum is set (clear it first: hydro_set_sea_spectrum(h, NULL))");
+    if (count < 1 || count > HYDRO_SEA_ENSEMBLE_MAX) return fail(h, HYDRO_E_ARG, "sea ensemble: count out of range (1 .. HYDRO_SEA_ENSEMBLE_MAX)");
+    if (bodies_per_sea < HYDRO_TILE || bodies_per_sea % HYDRO_TILE != 0 || bodies_per_sea >= ((int64_t)1 << 31))
+        return fail(h, HYDRO_E_ARG, "sea ensemble: bodies_per_sea must be a positive multiple of 64 (and < 2^31)");
+    const int waves = members[0].waves;
+    if (waves < 0 || waves > HYDRO_SPECTRUM_WAVES_MAX)
+        return fail(h, HYDRO_E_ARG, "sea ensemble: waves out of range (0 .. HYDRO_SPECTRUM_WAVES_MAX)");
+    for (int64_t m = 0; m < count; ++m) {
+        if (members[m].waves != waves) return fail(h, HYDRO_E_ARG, "sea ensemble: every member must have the same number of waves");
+        if (waves > 0 && !members[m].wave) return fail(h, HYDRO_E_ARG, "sea ensemble: null wave with waves > 0");
+    }
+    // (up to 3 MB: on the heap.  Everything is checked and formed here, before the device table is touched)
+    SpectrumTable* tab = static_cast<SpectrumTable*>(calloc((size_t)count, sizeof(SpectrumTable)));
+    if (!tab) return fail(h, HYDRO_E_ALLOC, "sea ensemble table: host allocation failed");
+    for (int64_t m = 0; m < count; ++m) {
+        char what[48];
+        snprintf(what, sizeof what, "sea ensemble member %lld", (long long)m);
+        const int rc = sea_records(h, what, members[m].current, waves, members[m].wave, tab[m].u, tab[m].w);
+        if (rc) { free(tab); return rc; }
+        tab[m].waves = (uint32_t)waves;
+    }
+    if (const hipError_t e = use_device(h->device); e != hipSuccess) { free(tab); return fail(h, HYDRO_E_DEVICE, "use_device(h->device)", e); }
+    if (count > h->ensemble_capacity) {
+        // a larger table: the new one first, so that a failure leaves the previous ensemble in force
+        void* grown = nullptr;
+        if (hipMalloc(&grown, (size_t)count * sizeof(SpectrumTable)) != hipSuccess) {
+            free(tab);
+            return fail(h, HYDRO_E_ALLOC, "sea ensemble table: allocation failed");
+        }
+        if (h->ensemble_table) (void)hipFree(h->ensemble_table);
+        h->ensemble_table = grown;
+        h->ensemble_capacity = count;
+    }
+    // from here on the device table is being rewritten: a failure leaves NO ensemble, never half of one
+    h->ensemble_waves = -1;
+    hipError_t e = hipMemcpyAsync(h->ensemble_table, tab, (size_t)count * sizeof(SpectrumTable), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    free(tab);
+    if (e != hipSuccess) return fail(h, HYDRO_E_LAUNCH, "sea ensemble table: copy to the device", e);
+    h->ensemble_count = count;
+    h->ensemble_tiles_per_sea = bodies_per_sea / HYDRO_TILE;
+    h->ensemble_waves = waves;
+    return HYDRO_OK;
+}
+
 }  // extern "C"
 
 namespace {
-// hydro_sea_sample and hydro_sea_spectrum_sample: one set of rules, the table and the kernel of either.
-template <typename Kernel>
+// hydro_sea_sample, hydro_sea_spectrum_sample and hydro_sea_ensemble_sample: one set of rules, the table and the kernel of each;
+// `members` (the ensemble's only: the others pass none) are count and tiles_per_sea - a refusal of its own, last, and the kernel's last argument.
+template <typename Kernel, typename... Members>
 int water_sample(hydro_t* h, Kernel kernel, const void* table, int waves, const char* none, int64_t n, const float* state, int64_t state_tile_stride,
-                 int64_t step_index, double dt, float* out, int64_t out_tile_stride, void* stream)
+                 int64_t step_index, double dt, float* out, int64_t out_tile_stride, void* stream, Members... members)
 {
     if (!h) return HYDRO_E_ARG;
     if (n < 0 || n > h->capacity) return fail(h, HYDRO_E_ARG, "n out of range (0 <= n <= capacity)");
@@ -4154,10 +4310,21 @@ int water_sample(hydro_t* h, Kernel kernel, const void* table, int waves, const 
     int rc;
     if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
     if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_SEA_FIELDS, "null out"))) return rc;
+    if constexpr (sizeof...(Members) != 0) {
+        const int64_t count_and_tiles[] = {members...}, tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE;
+        if ((tiles + count_and_tiles[1] - 1) / count_and_tiles[1] > count_and_tiles[0])
+            return fail(h, HYDRO_E_ARG, "n needs more members than the sea ensemble has (count * bodies_per_sea < n)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     if (n == 0) return HYDRO_OK;
-    hipLaunchKernelGGL(kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
-                       out, (uint32_t)out_tile_stride, (uint32_t)n, table, (uint32_t)waves, step_index, dt);
+    const auto launch = [&](auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
+                           out, (uint32_t)out_tile_stride, (uint32_t)n, table, (uint32_t)waves, step_index, dt, tail...);
+    };
+    if constexpr (sizeof...(Members) != 0) {
+        const int64_t count_and_tiles[] = {members...};
+        launch((uint32_t)count_and_tiles[1]);
+    } else launch();
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }
@@ -4179,6 +4346,14 @@ int hydro_sea_spectrum_sample(hydro_t* h, int64_t n, const float* state, int64_t
     if (!h) return HYDRO_E_ARG;
     return water_sample(h, spectrum_sample_kernel, (const void*)h->spectrum_table, h->spectrum_waves, "no sea spectrum (call hydro_set_sea_spectrum first)",
                         n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream);
+}
+
+int hydro_sea_ensemble_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
+                              float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    return water_sample(h, ensemble_sample_kernel, (const void*)h->ensemble_table, h->ensemble_waves, "no sea ensemble (call hydro_set_sea_ensemble first)",
+                        n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream, h->ensemble_count, h->ensemble_tiles_per_sea);
 }
 
 int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -4560,6 +4735,42 @@ int hydro_step_fused_tiled_multi_stat(hydro_t* h, int64_t n, const float* state,
     m.with_peaks(tether_peaks, tether_peaks_tile_stride);
     m.with_spectrum();
     m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_ens(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                     const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                     float* state_out, int64_t out_tile_stride,
+                                     float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                     int rotational, double* ke_out_dev,
+                                     float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                     int64_t row0, int64_t* rows_written_host,
+                                     const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                     const float* control, int64_t control_tile_stride,
+                                     const float* mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                     float* extremes, int64_t extremes_tile_stride,
+                                     const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                     float* tether_peaks, int64_t tether_peaks_tile_stride,
+                                     void* statistics, int64_t statistics_tile_stride,
+                                     const float* levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                     int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_mooring_layers(mooring_layers);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    m.with_spectrum();
+    m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
+    m.with_ensemble();
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -72,6 +72,7 @@ class HydroEngine:
         self._tables: dict = {}
         self.sea_waves: int | None = None            # wave components of the sea set with set_sea; None: no sea
         self.spectrum_waves: int | None = None       # wave components of the spectrum set with set_sea_spectrum; None: no spectrum
+        self.ensemble_count: int | None = None       # members of the ensemble set with set_sea_ensemble; None: no ensemble
         self.seabed = None                           # the seabed.Seabed set with set_seabed; None: no bed
         self.set_scene(water_density, gravity)
 
@@ -620,14 +621,77 @@ class HydroEngine:
         every step the sample of each channel enters its sums and its up-crossing count (include/hydro.h, "Statistics").
         Nothing feeds back: everything else the launch writes is step_fused_tiled_multi_irr's bits, and statistics=None IS that
         call.  Returns the number of rows written (0 without a log)."""
-        def extra():
-            tail = self._spread_tail(n, step0, mooring, mooring_layers, tether, layers, peaks, extremes, control, applied, frame)
-            s_ptr, s_stride = self._tiled(statistics, nat.STAT_FIELDS, n) if statistics is not None else (None, 0)
-            l_ptr, l_stride = self._tiled(levels, nat.STAT_LEVEL_FIELDS, n) if levels is not None else (None, 0)
-            return (*tail[:-1], s_ptr, s_stride, l_ptr, l_stride, int(channel_a), int(channel_b), tail[-1])
         return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_stat,
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
-                                    (log, every, phase, row0), stream, extra)
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._stat_tail(n, step0, statistics, levels, channel_a, channel_b, mooring, mooring_layers, tether, layers,
+                                                            peaks, extremes, control, applied, frame))
+
+    def _stat_tail(self, n, step0, statistics, levels, channel_a, channel_b, *spread):
+        """The arguments `applied .. step0` of `hydro_step_fused_tiled_multi_stat` / `_ens`: `_spread_tail`'s with the statistics
+        group in front of step0."""
+        tail = self._spread_tail(n, step0, *spread)
+        s_ptr, s_stride = self._tiled(statistics, nat.STAT_FIELDS, n) if statistics is not None else (None, 0)
+        l_ptr, l_stride = self._tiled(levels, nat.STAT_LEVEL_FIELDS, n) if levels is not None else (None, 0)
+        return (*tail[:-1], s_ptr, s_stride, l_ptr, l_stride, int(channel_a), int(channel_b), tail[-1])
+
+    # ------------------------------------------------------------------ sea ensemble
+    def set_sea_ensemble(self, ensemble) -> None:
+        """The scene's sea ensemble (hydro_set_sea_ensemble; include/hydro.h, "Sea ensemble"): `ensemble` has `members`, up to
+        `_native.SEA_ENSEMBLE_MAX` spectra of equally many components (each with `current` and `waves`, as `set_sea_spectrum` takes
+        them), and `bodies_per_sea`, a multiple of 64 - a `sea.SeaEnsemble`.  Bodies m * bodies_per_sea .. step through member m.
+        None clears it.  Only `step_fused_tiled_multi_ens` and `sea_ensemble_sample` see the ensemble; an ensemble, a spectrum and
+        the sea of `set_sea` exclude each other.  Synchronous, like `set_sea`."""
+        if ensemble is None:
+            self._check(self._lib.hydro_set_sea_ensemble(self._h, None, 0, 0))
+            self.ensemble_count = None
+            return
+        members = list(ensemble.members)
+        rows = []                                                                  # (alive until the call returns: the library copies)
+        c = (nat.SeaSpectrum * max(len(members), 1))()
+        for m, member in enumerate(members):
+            waves = [tuple(float(x) for x in w) for w in member.waves]
+            if len(waves) > nat.SPECTRUM_WAVES_MAX or any(len(w) != 5 for w in waves):
+                raise ValueError(f"a sea spectrum has at most {nat.SPECTRUM_WAVES_MAX} wave components of (amplitude, kx, ky, omega, phase)")
+            rows.append((nat.SeaWave * max(len(waves), 1))(*[nat.SeaWave(*w) for w in waves]))
+            c[m].current[:] = [float(x) for x in member.current]
+            c[m].waves = len(waves)
+            c[m].wave = ctypes.cast(rows[-1], ctypes.POINTER(nat.SeaWave)) if waves else None
+        self._check(self._lib.hydro_set_sea_ensemble(self._h, c, len(members), int(ensemble.bodies_per_sea)))
+        self.ensemble_count = len(members)
+
+    def sea_ensemble_sample(self, state: torch.Tensor, n: int, step_index: int, dt: float, out: torch.Tensor | None = None,
+                            stream=None) -> torch.Tensor:
+        """`sea_spectrum_sample` with each body read against its member of the ensemble set with `set_sea_ensemble`
+        (hydro_sea_ensemble_sample): exactly the [eta, u_x, u_y, u_z] `step_fused_tiled_multi_ens` uses for step `step_index`."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.SEA_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.SEA_FIELDS, n)
+        self._check(self._lib.hydro_sea_ensemble_sample(self._h, n, s_ptr, s_stride, int(step_index), float(dt), o_ptr, o_stride,
+                                                        self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_ens(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                   statistics: torch.Tensor | None = None, levels: torch.Tensor | None = None,
+                                   channel_a: int = nat.STAT_Z, channel_b: int = nat.STAT_TENSION,
+                                   mooring: torch.Tensor | None = None, mooring_layers: int = 1,
+                                   tether: torch.Tensor | None = None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                   extremes: torch.Tensor | None = None,
+                                   control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                   log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                   state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                   ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_stat through the sea ensemble set with `set_sea_ensemble` (hydro_step_fused_tiled_multi_ens):
+        the arguments and the rules are step_fused_tiled_multi_stat's, every option optional, and each block of
+        `bodies_per_sea` bodies steps through its own member - bit for bit the step it takes in step_fused_tiled_multi_stat
+        under `set_sea_spectrum(member)`.  Without an ensemble the call IS step_fused_tiled_multi_stat.  Returns the number of
+        rows written (0 without a log)."""
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_ens,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._stat_tail(n, step0, statistics, levels, channel_a, channel_b, mooring, mooring_layers, tether, layers,
+                                                            peaks, extremes, control, applied, frame))
 
     # ------------------------------------------------------------------ seabed
     def set_seabed(self, bed) -> None:

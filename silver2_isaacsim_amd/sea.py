@@ -12,6 +12,9 @@ as given; `regular` applies the deep-water dispersion relation omega^2 = g kappa
 
 `SeaSpectrum` is the same model with up to 64 components - an irregular sea - and `pierson_moskowitz` / `jonswap` build one from
 a significant wave height and a peak period (include/hydro.h, "Sea spectrum").
+
+`SeaEnsemble` is several such spectra in one run, each over its own block of the bodies - `jonswap_ensemble` and
+`pierson_moskowitz_ensemble` build one sea per seed (include/hydro.h, "Sea ensemble").
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import numpy as np
 
 WAVES_MAX = 8
 SPECTRUM_WAVES_MAX = 64
+ENSEMBLE_MAX = 1024
 
 
 class SeaState:
@@ -199,3 +203,99 @@ def jonswap(hs: float, tp: float, heading_deg: float, *, gamma: float = 3.3, com
     if not gamma >= 1.0 or not math.isfinite(gamma):
         raise ValueError("gamma must be >= 1")
     return _from_bins(hs, jonswap_bin_medians(2.0 * math.pi / tp, float(gamma), int(components)), heading_deg, seed, spread, current, g)
+
+
+class SeaEnsemble:
+    """Several seas in one run: `members` are `SeaSpectrum`s of equally many components, and block m of `bodies_per_sea` bodies
+    (a multiple of 64) steps through member m - the seeds, headings and currents a design extreme is taken over, in ONE resident
+    launch (`ClosedLoopSim.set_sea`, `HydroEngine.set_sea_ensemble`; hydro_step_fused_tiled_multi_ens; include/hydro.h, "Sea
+    ensemble").  Lay the bodies out member by member: the same `bodies_per_sea` designs once per member.  Not a `SeaSpectrum`:
+    the water depends on the body.  `split` turns any per-body array into (count, bodies_per_sea, ...), so that
+    `ens.split(extremes.tension_max())` is seeds x designs, and `mean_of_maxima` / `std_of_maxima` reduce it over the members."""
+
+    def __init__(self, members, bodies_per_sea: int):
+        members = list(members)
+        if not 1 <= len(members) <= ENSEMBLE_MAX:
+            raise ValueError(f"a sea ensemble has 1 .. {ENSEMBLE_MAX} members")
+        if not all(isinstance(m, SeaSpectrum) for m in members):
+            raise ValueError("the members of a sea ensemble are SeaSpectrum objects")
+        if len({len(m.waves) for m in members}) != 1:
+            raise ValueError("every member of a sea ensemble must have the same number of wave components")
+        if int(bodies_per_sea) != bodies_per_sea or bodies_per_sea < 64 or bodies_per_sea % 64:
+            raise ValueError("bodies_per_sea must be a positive multiple of 64")
+        self.members = members
+        self.bodies_per_sea = int(bodies_per_sea)
+
+    @property
+    def count(self) -> int:
+        return len(self.members)
+
+    @property
+    def waves(self) -> list:
+        """Every member's components, one behind the other: empty exactly when every member is current-only."""
+        return [w for m in self.members for w in m.waves]
+
+    def sea_of(self, body):
+        """The member (index) body `body` steps through; `body` may be an array."""
+        return np.asarray(body, np.int64) // self.bodies_per_sea
+
+    def split(self, values) -> np.ndarray:
+        """A per-body array (n, ...) as (count, bodies_per_sea, ...): row m holds member m's bodies.  A view where `values` has
+        all count * bodies_per_sea bodies; with fewer (the last member's block is partial) the missing bodies are NaN (floats
+        only)."""
+        v = np.asarray(values)
+        full = self.count * self.bodies_per_sea
+        if v.shape[0] > full:
+            raise ValueError(f"{v.shape[0]} bodies are more than the ensemble's {self.count} x {self.bodies_per_sea}")
+        if v.shape[0] < full:
+            if not np.issubdtype(v.dtype, np.floating):
+                raise ValueError("a partial last member needs a floating-point array (the missing bodies become NaN)")
+            v = np.concatenate([v, np.full((full - v.shape[0],) + v.shape[1:], np.nan, v.dtype)])
+        return v.reshape((self.count, self.bodies_per_sea) + v.shape[1:])
+
+    def mean_of_maxima(self, values) -> np.ndarray:
+        """Per design (position within a member's block), the mean over the members of a per-body maximum (bodies_per_sea, ...)."""
+        return self.split(values).mean(axis=0)
+
+    def std_of_maxima(self, values) -> np.ndarray:
+        """Per design, the sample standard deviation (ddof = 1; 0 for a single member) over the members."""
+        s = self.split(values)
+        return s.std(axis=0, ddof=1) if self.count > 1 else np.zeros(s.shape[1:], s.dtype)
+
+    def elevation(self, x, y, t, body) -> np.ndarray:
+        """Surface elevation eta (m) at (x, y) and time t of the member that `body` steps through; the arguments broadcast."""
+        x, y, t, member = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(t, np.float64), self.sea_of(body))
+        eta = np.zeros(x.shape, np.float64)
+        for m in np.unique(member):
+            at = member == m
+            eta[at] = self.members[int(m)].elevation(x[at], y[at], t[at])
+        return eta
+
+
+def _per_member(value, count, scalar):
+    """`value` as one value per member: a single one (`scalar(value)` says so) for all, or a sequence of `count`."""
+    if scalar(value):
+        return [value] * count
+    value = list(value)
+    if len(value) != count:
+        raise ValueError(f"expected one value or one per member ({count}), got {len(value)}")
+    return value
+
+
+def _ensemble(one, hs, tp, heading_deg, seeds, bodies_per_sea, current, kw) -> SeaEnsemble:
+    seeds = list(seeds)
+    headings = _per_member(heading_deg, len(seeds), lambda v: np.ndim(v) == 0)
+    currents = _per_member(current, len(seeds), lambda v: np.ndim(v) == 1)
+    return SeaEnsemble([one(hs, tp, float(hd), seed=sd, current=tuple(cu), **kw) for sd, hd, cu in zip(seeds, headings, currents)], bodies_per_sea)
+
+
+def jonswap_ensemble(hs: float, tp: float, heading_deg, *, seeds=range(16), bodies_per_sea: int, current=(0.0, 0.0, 0.0), **kw) -> SeaEnsemble:
+    """One `jonswap` sea per seed: member i is exactly `jonswap(hs, tp, heading, seed=seeds[i], current=current, **kw)`.
+    `heading_deg` and `current` may each be one value for every member or a sequence of one per member."""
+    return _ensemble(jonswap, hs, tp, heading_deg, seeds, bodies_per_sea, current, kw)
+
+
+def pierson_moskowitz_ensemble(hs: float, tp: float, heading_deg, *, seeds=range(16), bodies_per_sea: int, current=(0.0, 0.0, 0.0),
+                               **kw) -> SeaEnsemble:
+    """`jonswap_ensemble` for `pierson_moskowitz`."""
+    return _ensemble(pierson_moskowitz, hs, tp, heading_deg, seeds, bodies_per_sea, current, kw)

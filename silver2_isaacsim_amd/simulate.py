@@ -28,7 +28,7 @@ from . import scenes
 from .engine import HydroEngine
 from .extremes import Extremes
 from .mooring import Mooring, MooringSpread
-from .sea import SeaSpectrum
+from .sea import SeaEnsemble, SeaSpectrum
 from .statistics import ResponseStatistics, channel_index
 from .tether import LinkTensions, Tether, TetherNet
 
@@ -552,21 +552,30 @@ class ClosedLoopSim:
         replay a frozen time.  The sea stays until the next call or `clear_sea()`.
         `sea` may also be a `sea.SeaSpectrum`, an irregular sea of up to 64 components (hydro_step_fused_tiled_multi_irr;
         include/hydro.h, "Sea spectrum"): `sim.sea` is the one slot for either kind, every other option rides along as before,
-        and a spectrum with components stays out of graph replays like a sea with waves."""
+        and a spectrum with components stays out of graph replays like a sea with waves.
+        Or a `sea.SeaEnsemble`, several spectra with block m of `bodies_per_sea` bodies stepping through member m
+        (hydro_step_fused_tiled_multi_ens; include/hydro.h, "Sea ensemble"): the same one slot, every other option rides along,
+        count * bodies_per_sea must cover the sim's bodies, and only an ensemble of current-only members replays."""
         if not self.fused:
             raise ValueError("the sea state lives in the fused step kernels (fused=True)")
+        if isinstance(sea, SeaEnsemble) and sea.count * sea.bodies_per_sea < self.n:
+            raise ValueError(f"the ensemble's {sea.count} members of {sea.bodies_per_sea} bodies do not cover the sim's {self.n} bodies")
         self.synchronize()                                      # launches in flight read the table this rewrites
-        irregular = isinstance(sea, SeaSpectrum)
-        if self.sea is not None and isinstance(self.sea, SeaSpectrum) != irregular:
-            self._set_engine_sea(self.sea, None)                # the library holds a sea or a spectrum, never both: the other kind goes first
+        if self.sea is not None and self._sea_setter(self.sea) != self._sea_setter(sea):
+            self._set_engine_sea(self.sea, None)                # the library holds a sea, a spectrum or an ensemble, never two: the other kind goes first
             self.sea = None
         self._set_engine_sea(sea, sea)
         self.sea = sea
         self._graph = None                                      # captured steps are of another entry / another sea
 
+    @staticmethod
+    def _sea_setter(kind) -> str:
+        """The engine call that takes a sea of `kind`'s kind."""
+        return "set_sea_ensemble" if isinstance(kind, SeaEnsemble) else "set_sea_spectrum" if isinstance(kind, SeaSpectrum) else "set_sea"
+
     def _set_engine_sea(self, kind, sea) -> None:
         """`sea` (or None: clear) to the engine call of `kind`'s kind."""
-        (self.engine.set_sea_spectrum if isinstance(kind, SeaSpectrum) else self.engine.set_sea)(sea)
+        getattr(self.engine, self._sea_setter(kind))(sea)
 
     def clear_sea(self) -> None:
         """Back to still water: every call the sim makes is again the one it made before set_sea."""
@@ -908,7 +917,8 @@ class ClosedLoopSim:
         if self.link_tensions is not None:
             self.link_tensions.links, self.link_tensions.layer = self._tether_links
 
-    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
+    # the sea ensemble if `sim.sea` is one (its entry takes every other option, the statistics included), else with
     # the response statistics if they are tracked (their entry takes every other option, the spectrum included), else through
     # the sea spectrum if `sim.sea` is one (its entry takes every other option), else with
     # the mooring spread if one is set (its entry takes every other option), else with
@@ -927,7 +937,20 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if self.statistics is not None:
+        if isinstance(self.sea, SeaEnsemble):
+            # (the entry of the statistics, every option optional, the statistics too)
+            st = self.statistics
+            moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
+            net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
+            rows = e.step_fused_tiled_multi_ens(*args, k, self.steps_done, *((st.buffer, st.levels_buffer, *st.channel_numbers) if st is not None
+                                                                             else (None, None, nat.STAT_Z, nat.STAT_TENSION)),
+                                                moor, moor_layers, net, layers,
+                                                self.link_tensions.buffer if self.link_tensions is not None else None,
+                                                self.extremes.buffer if self.extremes is not None else None,
+                                                self.control, self.applied, self.applied_frame, **kw)
+            if st is not None:
+                self._statistics_dirty = True
+        elif self.statistics is not None:
             # (the entry of the spectrum, every option optional - through the spectrum if `sim.sea` is one, else as the spread's entry steps)
             st = self.statistics
             moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
