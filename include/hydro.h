@@ -71,7 +71,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_statistics_reset, hydro_step_fused_tiled_multi_stat, HYDRO_STAT_* -
  *        running per-body response statistics (sum, sum of squares, up-crossings of a level) updated inside every step
  *        added to 0.7.1 (no existing entry changed): hydro_set_sea_ensemble, hydro_sea_ensemble_sample, hydro_step_fused_tiled_multi_ens,
- *        HYDRO_SEA_ENSEMBLE_MAX - up to 1024 sea spectra in one launch, block m of the bodies stepping through member m */
+ *        HYDRO_SEA_ENSEMBLE_MAX - up to 1024 sea spectra in one launch, block m of the bodies stepping through member m
+ *        added to 0.7.1 (no existing entry changed): hydro_set_sea_finite_depth, hydro_sea_finite_depth_sample,
+ *        hydro_step_fused_tiled_multi_fd - the ensemble's spectra in water of finite depth h: waves that feel the bottom */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -1320,6 +1322,79 @@ int hydro_step_fused_tiled_multi_ens(hydro_t *h, int64_t n, const float *state, 
                                      void *statistics, int64_t statistics_tile_stride,
                                      const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
                                      int64_t step0, void *stream);
+
+/* Finite-depth sea: the spectra of "Sea ensemble" in water of still-water depth h > 0 (m) - linear (Airy) waves that feel the
+ * bottom.  Moorings are a shallow- and intermediate-water business: a Tp = 7 s wave is 76 m long in deep water, and over h = 20 m
+ * its kappa h is about 1.7.  There the horizontal orbital velocity at the surface is larger by coth(kappa h), and it does not
+ * die off with depth as e^{kappa z}: it goes to a purely horizontal, non-zero motion at the bed - where the lower end of a cable,
+ * a bottom-sitting box and an ROV on a tether live.  "Sea spectrum"'s model is unchanged except for the depth profile.
+ *
+ * WATER AT A BODY of member m (the mapping is "Sea ensemble"'s), component j of wavenumber kappa_j, q_j = e^{-2 kappa_j h}:
+ *   eta, tau_j, th_j, r_j, c_j, s_j      exactly "Sea spectrum"'s WATER AT A BODY (the surface does not change)
+ *   z_rel = p_z - eta
+ *   zc    = max(min(z_rel, 0), -h)       fp32; h rounded once to fp32.  No growth above the surface, nothing below the bed
+ *   E_j   = exp2(kl2_j * zc)             as in deep water
+ *   G_j   = exp2(fma(-kl2_j, zc, gl_j))  gl_j = -2 kappa_j h log2(e), formed in fp64, rounded once
+ *   u_x = fma(cx_j, (E_j + G_j) * c_j, u_x)   u_y likewise with cy_j   u_z = fma(aw_j, (E_j - G_j) * s_j, u_z)
+ * CONSTANTS: cx_j, cy_j and aw_j are "Sea spectrum"'s constants times 1 / (1 - q_j), formed in fp64 on the host and rounded once.
+ * PROFILES: (E + G) / (1 - q) = cosh(kappa (zc + h)) / sinh(kappa h) and (E - G) / (1 - q) = sinh(kappa (zc + h)) / sinh(kappa h):
+ * linear theory, evaluated at the stretched depth z_rel as the deep model is.  u_z = 0 on the bed; below it the water is the bed's.
+ * ORDER: the sums run in ascending j, eta from +0 and u from U; the relative state and everything behind the wrench are unchanged.
+ * DISPERSION: omega and the wave vector are TAKEN AS GIVEN, as ever.  omega^2 = g kappa tanh(kappa h) is the caller's business
+ * (the Python constructors solve it: sea.wavenumber, depth= on pierson_moskowitz / jonswap and their ensembles).
+ * CLAMP: the clamp at -h makes zc finite for every p_z, +-inf and NaN included (min and max return the number): a finite table
+ * never produces a NaN that the deep model would not.
+ * DEEP WATER: where q_j = 0 in fp64 and gl_j - kl2_j zc is below -149 for every body (kappa_j h beyond a few hundred), G_j = +0,
+ * the constants are the deep ones and every statement returns "Sea ensemble"'s bits.
+ *
+ * hydro_set_sea_finite_depth: hydro_set_sea_ensemble's arguments and rules (members, count 1 .. HYDRO_SEA_ENSEMBLE_MAX,
+ * bodies_per_sea a positive multiple of 64, equal `waves`, the spectrum's validator on every member, the table engine-owned and
+ * of its own, the copy waited for) plus `depth`, ONE depth for all members.  A lone spectrum is an ensemble of one member whose
+ * block covers n.  HYDRO_E_ARG also for a depth that is non-finite or <= 0 (or not a positive finite fp32), and for a depth at
+ * which a scaled constant or gl_j leaves fp32 range (kappa_j h so small that 1 / (1 - q_j) overflows the component) - the
+ * previous table stays in force on every refusal.  members == NULL clears (count, bodies_per_sea and depth are not looked at).
+ * IT IS THE FOURTH KIND OF SEA: it and a sea, a spectrum and an ensemble exclude each other at set time - each of the four setters
+ * (non-NULL) returns HYDRO_E_STATE while another kind is set, and its message names the call that clears that kind (this one:
+ * hydro_set_sea_finite_depth(h, NULL, 0, 0, 0)); what was set stays in force.  ONLY hydro_step_fused_tiled_multi_fd and
+ * hydro_sea_finite_depth_sample know it: EVERY OTHER ENTRY IGNORES A FINITE-DEPTH SEA.
+ *
+ * hydro_sea_finite_depth_sample: the signature and the rules of hydro_sea_ensemble_sample.  HYDRO_E_STATE without a finite-depth
+ * sea; HYDRO_E_ARG, last, if n needs more members than `count`.
+ *
+ * hydro_step_fused_tiled_multi_fd: exactly the signature, the refusals and the refusal order of hydro_step_fused_tiled_multi_ens.
+ *   no finite-depth sea set : the launch and its bits are those of hydro_step_fused_tiled_multi_ens with the same arguments.
+ *   a finite-depth sea set  : every option stays optional; statistics == NULL gives the family without statistics; the
+ *                             ensemble's last refusal (n needs more members than `count`) is read against this table.
+ * Asynchronous, no allocation, no synchronisation, safe to capture under the ensemble's rule (capture current-only members).
+ * THE SEABED IS INDEPENDENT: h and hydro_set_seabed's z_b know nothing of each other.  Set z_b = -h for a scene whose bodies
+ * rest on the bottom the waves feel.
+ * COST: one more v_exp_f32 and four more vector instructions per component and body in the second pass (42 for 37); nothing more is
+ * loaded.  Measured on an MI355X at 64 components against the ensemble's step on the same bodies: 1.09 times
+ * at 4 096 bodies and 1.11 times at 1 048 576 with nothing but the sea, 1.07 and 1.09 times with a spread, extremes and statistics.
+ * A run in deep water pays nothing: leave the depth away and the kernels are the ensemble's.
+ * NOT MODELLED / NOT PROVIDED: a depth-limited spectral shape (TMA); shoaling, breaking and a sloping bed; depth in the 8-wave
+ * hydro_set_sea, in the open-loop entries (hydro_step_wrench_*_sea) and the plugin; members of different depths; any coupling
+ * between h and the seabed's z_b; a sign-symmetry statement for this rung.
+ * New functionality; the reference's water does not move. */
+int hydro_set_sea_finite_depth(hydro_t *h, const hydro_sea_spectrum_t *members, int64_t count, int64_t bodies_per_sea, double depth);
+int hydro_sea_finite_depth_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
+                                  float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_fd(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                    const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                    float *state_out, int64_t out_tile_stride,
+                                    float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                    int rotational, double *ke_out_dev,
+                                    float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                    int64_t row0, int64_t *rows_written_host,
+                                    const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                    const float *control, int64_t control_tile_stride,
+                                    const float *mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                    float *extremes, int64_t extremes_tile_stride,
+                                    const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                    float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                    void *statistics, int64_t statistics_tile_stride,
+                                    const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                    int64_t step0, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

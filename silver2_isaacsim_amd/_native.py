@@ -83,6 +83,7 @@ _LAYERS = _STEP0 = [c_int64]                                                    
 _SPREAD = _MOOR + [c_int64]                                                               # the mooring record as a spread: + mooring_layers
 _STAT = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int]                              # statistics, levels (+ strides), channel_a, channel_b
 _STREAM = [c_void_p]
+_SET_FD = [c_void_p, POINTER(SeaSpectrum), c_int64, c_int64, c_double]                       # h, members, count, bodies_per_sea, depth
 _SAMPLE = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_double, c_void_p, c_int64, c_void_p]   # h, n, state (+ stride), step_index, dt, out (+ stride), stream
 
 
@@ -149,6 +150,9 @@ SIGNATURES = {
     "hydro_set_sea_ensemble": (c_int, [c_void_p, POINTER(SeaSpectrum), c_int64, c_int64]),
     "hydro_sea_ensemble_sample": (c_int, _SAMPLE),
     "hydro_step_fused_tiled_multi_ens": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
+    "hydro_set_sea_finite_depth": (c_int, _SET_FD),
+    "hydro_sea_finite_depth_sample": (c_int, _SAMPLE),
+    "hydro_step_fused_tiled_multi_fd": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

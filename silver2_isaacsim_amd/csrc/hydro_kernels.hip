@@ -2778,6 +2778,113 @@ __global__ void __launch_bounds__(kBlock) ensemble_sample_kernel(const float* st
     store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
 }
 
+// --------------------------------------------------------------------------
+// FINITE-DEPTH SEAS in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_fd): the ensemble's spectra in water of
+// still-water depth h, where the orbital velocity goes with cosh / sinh of the height above the bed instead of e^{kappa z}
+// (hydro_set_sea_finite_depth; include/hydro.h, "Finite-depth sea").  depth_water below is its ONLY implementation (the step
+// kernels and hydro_sea_finite_depth_sample's kernel both call it): spectrum_water with a second exponential per component.
+//   the record : SeaWave stays at 48 B - `pad` holds gl_j = -2 kappa_j h log2(e), and cx, cy, aw arrive already divided by
+//                1 - e^{-2 kappa_j h} (the host, in fp64).  The table has SpectrumTable's layout but is one of its own: the deep
+//                kernels never see scaled constants
+//   the profile: E = exp2(kl2 zc), G = exp2(gl - kl2 zc): (E + G) / (1 - q) = cosh(kappa (zc + h)) / sinh(kappa h) under the
+//                horizontal velocity, (E - G) / (1 - q) = sinh(..) / sinh(kappa h) under the vertical one.  One more v_exp_f32,
+//                one fma, an add and a subtract per component; nothing more is loaded
+//   the clamp  : zc = max(min(z_rel, 0), -h) - nothing below the bed, and zc is finite whatever p_z is.  -h is ONE kernel
+//                argument (HYDRO_FD_PARAMS), wave-uniform
+//   deep water : with q_j = 0 and G = 0 (kappa_j h beyond a few hundred) every statement returns spectrum_water's bits
+// The first pass, spectrum_revolutions and the member's table pointer are the ensemble's; a lone spectrum is an ensemble of one.
+// --------------------------------------------------------------------------
+#define HYDRO_FD_PARAMS float neg_depth
+#define HYDRO_FD_ARGS neg_depth
+__device__ __forceinline__ void depth_water(SpectrumTablePtr tab, uint32_t waves, int64_t step, double dt, float px, float py, float pz, HYDRO_FD_PARAMS,
+                                            float& eta, float (&u)[3])
+{
+    const double t = (double)step * dt;
+    eta = 0.0f;
+#pragma clang loop unroll_count(4)
+    for (uint32_t j = 0; j < waves; ++j) {                   // (wave-uniform)
+        const float r = spectrum_revolutions(&tab->w[j], t, px, py);
+        eta = __builtin_fmaf(tab->w[j].a, __builtin_amdgcn_cosf(r), eta);
+    }
+    const float zc = __builtin_fmaxf(__builtin_fminf(pz - eta, 0.0f), neg_depth);
+    u[0] = tab->u[0]; u[1] = tab->u[1]; u[2] = tab->u[2];
+#pragma clang loop unroll_count(4)
+    for (uint32_t j = 0; j < waves; ++j) {
+        const float r = spectrum_revolutions(&tab->w[j], t, px, py);
+        const float cs = __builtin_amdgcn_cosf(r), sn = __builtin_amdgcn_sinf(r);
+        const float e = __builtin_amdgcn_exp2f(tab->w[j].kl2 * zc);
+        const float g = __builtin_amdgcn_exp2f(__builtin_fmaf(-tab->w[j].kl2, zc, tab->w[j].pad));
+        const float ec = (e + g) * cs, es = (e - g) * sn;
+        u[0] = __builtin_fmaf(tab->w[j].cx, ec, u[0]);
+        u[1] = __builtin_fmaf(tab->w[j].cy, ec, u[1]);
+        u[2] = __builtin_fmaf(tab->w[j].aw, es, u[2]);
+    }
+}
+
+// SpectrumEnsembleView with depth_water for the water: begin (the member's table) and restore are inherited.
+struct DepthEnsembleView : SpectrumEnsembleView {
+    float neg_depth;
+    __device__ __forceinline__ void view(uint32_t k, float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        float eta, u[3];
+        depth_water((SpectrumTablePtr)tab, waves, step0 + (int64_t)k, dt, s[0], s[1], s[2], HYDRO_FD_ARGS, eta, u);
+        float* m = parked();
+        m[0] = s[2];
+        s[2] = s[2] - eta;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            m[(1 + i) * 64] = s[7 + i];
+            m[(4 + i) * 64] = pv[i];
+            s[7 + i] = s[7 + i] - u[i];
+            pv[i] = pv[i] - u[i];
+        }
+    }
+};
+__device__ __forceinline__ DepthEnsembleView depth_ensemble_view(HYDRO_SEA_PARAMS, HYDRO_ENS_PARAMS, HYDRO_FD_PARAMS)
+{
+    return DepthEnsembleView{spectrum_ensemble_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS), HYDRO_FD_ARGS};
+}
+
+// The _ens kernel's arguments, then the depth; the sea group carries the finite-depth table and the members' count of components.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_fd_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_ENS_PARAMS,
+                                                                                                HYDRO_FD_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   depth_ensemble_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS, HYDRO_FD_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS),
+                                                   mooring_spread(HYDRO_SPREAD_ARGS), optional_extremes_track(HYDRO_EXT_ARGS),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// The _ens_stat kernel's arguments, then the depth.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_fd_stat_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                     HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                     HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_STAT_PARAMS,
+                                                                                                     HYDRO_ENS_PARAMS, HYDRO_FD_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   depth_ensemble_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS, HYDRO_FD_ARGS), optional_seabed_contact(HYDRO_OPT_BED_ARGS),
+                                                   mooring_spread(HYDRO_SPREAD_ARGS), statistics_track(HYDRO_EXT_ARGS, HYDRO_STAT_ARGS, steps),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// hydro_sea_finite_depth_sample: ensemble_sample_kernel calling depth_water.
+__global__ void __launch_bounds__(kBlock) depth_sample_kernel(const float* st, uint32_t st_stride, float* out, uint32_t out_stride, uint32_t n,
+                                                              const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt, HYDRO_ENS_PARAMS, HYDRO_FD_PARAMS)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float eta, u[3];
+    depth_water(ensemble_member((SpectrumTablePtr)sea_table, tile, tiles_per_sea), sea_waves, step, sea_dt, *at<float>(r, lane4, 0u), *at<float>(r, lane4, 256u),
+                *at<float>(r, lane4, 512u), HYDRO_FD_ARGS, eta, u);
+    const float o[HYDRO_SEA_FIELDS] = {eta, u[0], u[1], u[2]};
+    store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
+}
+
 // hydro_statistics_reset: the empty record - sums +0.0, words 0 - for the live lanes.
 __global__ void __launch_bounds__(kBlock) statistics_reset_kernel(void* stat, uint32_t stat_stride, uint32_t n)
 {
@@ -2876,6 +2983,13 @@ struct hydro_engine {
     void* ensemble_table = nullptr;
     int64_t ensemble_capacity = 0, ensemble_count = 0, ensemble_tiles_per_sea = 0;
     int ensemble_waves = -1;
+    // The finite-depth sea (hydro_set_sea_finite_depth): the ensemble's table over again, of its own - the records hold the
+    // constants scaled by 1 / (1 - q_j) and gl_j in `pad` - with -h rounded once to fp32, a kernel argument.  fd_waves < 0: no
+    // finite-depth sea.  Never set together with a sea, a spectrum or an ensemble.
+    void* fd_table = nullptr;
+    int64_t fd_capacity = 0, fd_count = 0, fd_tiles_per_sea = 0;
+    int fd_waves = -1;
+    float fd_neg_depth = 0.0f;
     // The seabed (hydro_set_seabed): the plane and the five contact constants, already rounded to fp32 - kernel arguments.
     Seabed bed = {};
     bool has_bed = false;
@@ -3352,6 +3466,7 @@ int hydro_destroy(hydro_t* h)
     if (h->sea_table) (void)hipFree(h->sea_table);
     if (h->spectrum_table) (void)hipFree(h->spectrum_table);
     if (h->ensemble_table) (void)hipFree(h->ensemble_table);
+    if (h->fd_table) (void)hipFree(h->fd_table);
     delete h;
     return HYDRO_OK;
 }
@@ -3735,7 +3850,7 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// A launch of any of the fifteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// A launch of any of the sixteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
 // was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
 // copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
 // (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
@@ -3763,6 +3878,7 @@ struct MultiStep {
     bool stat_entry = false; void* statistics = nullptr; int64_t statistics_tile_stride = 0;
     const float* levels = nullptr; int64_t levels_tile_stride = 0; int channel_a = 0, channel_b = 0;
     bool ens_entry = false;                              // the _ens entry: the _stat entry, and block m of the bodies steps through member m of the sea ensemble if one is set
+    bool fd_entry = false;                               // the _fd entry: the _ens entry, and the finite-depth sea's water if one is set
 
     void with_recorder(float* log_, int64_t log_stride_, int64_t rows_capacity_, int fields_, int every_, int phase_, int64_t row0_, int64_t* rows_written_host_)
     {
@@ -3788,6 +3904,7 @@ struct MultiStep {
         channel_a = a; channel_b = b;
     }
     void with_ensemble() { ens_entry = true; }
+    void with_finite_depth() { fd_entry = true; }
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -3837,7 +3954,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
 //   plain < _rec < _app < _ctl < _sea < _bed < _moor < _ext < _teth < _net < _peak < _spread
 // (the _irr family stands beside the ladder: it is chosen while a sea spectrum is set, by the _irr entry alone, whatever the options;
 // the two _stat families stand beside the _spread and the _irr family: chosen while a statistics record is given, whatever the options;
-// the two _ens families stand beside the _irr and the _irr_stat family: chosen while a sea ensemble is set, by the _ens entry alone)
+// the two _ens families stand beside the _irr and the _irr_stat family: chosen while a sea ensemble is set, by the _ens entry alone;
+// the two _fd families stand beside the two _ens families: chosen while a finite-depth sea is set, by the _fd entry alone)
 // and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
 // the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
@@ -3849,6 +3967,7 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
     const bool rec = m.log || m.log_required, sea = m.sea_entry && h->sea_waves >= 0, bed = m.bed_entry && h->has_bed;
     const bool irr = m.irr_entry && h->spectrum_waves >= 0;                    // (a spectrum and a sea are never set together: irr implies !sea)
     const bool ens = m.ens_entry && h->ensemble_waves >= 0;                    // (nor an ensemble with either: ens implies !irr and !sea)
+    const bool fd = m.fd_entry && h->fd_waves >= 0;                            // (nor a finite-depth sea with any of them: fd implies !ens, !irr and !sea)
     int64_t rows = 0;
     if (rec && (rc = check_recorder(h, m, rows))) return rc;
     if ((rc = check_common(h, m.n))) return rc;
@@ -3965,6 +4084,11 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         if ((tiles + h->ensemble_tiles_per_sea - 1) / h->ensemble_tiles_per_sea > h->ensemble_count)
             return fail(h, HYDRO_E_ARG, "n needs more members than the sea ensemble has (count * bodies_per_sea < n)");
     }
+    if (fd) {
+        const int64_t tiles = (m.n + HYDRO_TILE - 1) / HYDRO_TILE;
+        if ((tiles + h->fd_tiles_per_sea - 1) / h->fd_tiles_per_sea > h->fd_count)
+            return fail(h, HYDRO_E_ARG, "n needs more members than the finite-depth sea has (count * bodies_per_sea < n)");
+    }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -3993,8 +4117,8 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto pushed = [&](auto kernel, auto... tail) { recording(kernel, m.applied, applied_stride, frame, tail...); };
         const auto held = [&](auto kernel, auto... tail) { pushed(kernel, m.control, control_stride, tail...); };
         const auto in_sea = [&](auto kernel, auto... tail) {
-            held(kernel, ens ? (const void*)h->ensemble_table : irr ? (const void*)h->spectrum_table : sea ? (const void*)h->sea_table : (const void*)nullptr,
-                 ens ? (uint32_t)h->ensemble_waves : irr ? (uint32_t)h->spectrum_waves : sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
+            held(kernel, fd ? (const void*)h->fd_table : ens ? (const void*)h->ensemble_table : irr ? (const void*)h->spectrum_table : sea ? (const void*)h->sea_table : (const void*)nullptr,
+                 fd ? (uint32_t)h->fd_waves : ens ? (uint32_t)h->ensemble_waves : irr ? (uint32_t)h->spectrum_waves : sea ? (uint32_t)h->sea_waves : 0u, m.step0, m.dt, tail...);
         };
         const auto on_bed = [&](auto kernel, auto... tail) {
             in_sea(kernel, h->bed.z, h->bed.stiffness, h->bed.damping, h->bed.friction, h->bed.slip_speed, h->bed.friction_rate, tail...);
@@ -4018,10 +4142,16 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto with_statistics = [&](auto kernel, auto... tail) {
             spread_and_all(kernel, m.statistics, (uint32_t)m.statistics_tile_stride, m.levels, (uint32_t)m.levels_tile_stride, (uint32_t)m.channel_a, (uint32_t)m.channel_b, tail...);
         };
-        // the ensemble first: its group stands behind everything else, and its two families take every option the launch has; then
+        // the finite-depth sea first: the ensemble's group and the depth behind everything else, every option the launch has; then
+        // the ensemble: its group stands behind everything else, and its two families take every option the launch has; then
         // the statistics, through the spectrum or not; then
         // the spectrum: its family stands beside the ladder, not on it, and takes every option the launch has
-        if (ens) {
+        if (fd) {
+            const uint32_t tiles_per_sea = (uint32_t)h->fd_tiles_per_sea;
+            if (m.statistics) with_statistics(step_fused_multi_fd_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea, h->fd_neg_depth);
+            else spread_and_all(step_fused_multi_fd_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea, h->fd_neg_depth);
+        }
+        else if (ens) {
             const uint32_t tiles_per_sea = (uint32_t)h->ensemble_tiles_per_sea;
             if (m.statistics) with_statistics(step_fused_multi_ens_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea);
             else spread_and_all(step_fused_multi_ens_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea);
@@ -4185,6 +4315,27 @@ int sea_records(hydro_t* h, const char* what, const double (&current)[3], int wa
     }
     return HYDRO_OK;
 }
+
+// What hydro_set_sea_finite_depth adds to the records sea_records formed: cx, cy and aw over again from the caller's fp64 values,
+// times 1 / (1 - q_j), q_j = e^{-2 kappa_j h}, rounded once; gl_j = -2 kappa_j h log2(e) into `pad`.  (q_j = 0: the deep constants.)
+int depth_records(hydro_t* h, const char* what, double depth, int waves, const hydro_sea_wave_t* wave, SeaWave* out)
+{
+    char msg[128];
+    for (int j = 0; j < waves; ++j) {
+        const hydro_sea_wave_t& w = wave[j];
+        const double kappa = sqrt(w.kx * w.kx + w.ky * w.ky);
+        if (!(kappa > 0.0)) continue;                                          // a = 0, kappa = 0: all zeros, contributes +0
+        SeaWave& d = out[j];
+        const double aw = w.amplitude * w.omega, scale = 1.0 / (1.0 - exp(-2.0 * kappa * depth));
+        d.cx = (float)(aw * w.kx / kappa * scale); d.cy = (float)(aw * w.ky / kappa * scale); d.aw = (float)(aw * scale);
+        d.pad = (float)(-2.0 * kappa * depth * 1.4426950408889634);
+        if (!isfinite(d.cx) || !isfinite(d.cy) || !isfinite(d.aw) || !isfinite(d.pad)) {
+            snprintf(msg, sizeof msg, "%s: wave component out of fp32 range at this depth", what);
+            return fail(h, HYDRO_E_ARG, msg);
+        }
+    }
+    return HYDRO_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -4195,6 +4346,7 @@ int hydro_set_sea(hydro_t* h, const hydro_sea_t* sea)
     if (!sea) { h->sea_waves = -1; return HYDRO_OK; }
     if (h->spectrum_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea spectrum is set (clear it first: hydro_set_sea_spectrum(h, NULL))");
     if (h->ensemble_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea ensemble is set (clear it first: hydro_set_sea_ensemble(h, NULL, 0, 0))");
+    if (h->fd_waves >= 0) return fail(h, HYDRO_E_STATE, "a finite-depth sea is set (clear it first: hydro_set_sea_finite_depth(h, NULL, 0, 0, 0))");
     if (sea->waves < 0 || sea->waves > HYDRO_SEA_WAVES_MAX) return fail(h, HYDRO_E_ARG, "sea: waves out of range (0 .. HYDRO_SEA_WAVES_MAX)");
     SeaTable tab;
     memset(&tab, 0, sizeof tab);
@@ -4218,6 +4370,7 @@ int hydro_set_sea_spectrum(hydro_t* h, const hydro_sea_spectrum_t* spec)
     if (!spec) { h->spectrum_waves = -1; return HYDRO_OK; }
     if (h->sea_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea is set (clear it first: hydro_set_sea(h, NULL))");
     if (h->ensemble_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea ensemble is set (clear it first: hydro_set_sea_ensemble(h, NULL, 0, 0))");
+    if (h->fd_waves >= 0) return fail(h, HYDRO_E_STATE, "a finite-depth sea is set (clear it first: hydro_set_sea_finite_depth(h, NULL, 0, 0, 0))");
     if (spec->waves < 0 || spec->waves > HYDRO_SPECTRUM_WAVES_MAX)
         return fail(h, HYDRO_E_ARG, "sea spectrum: waves out of range (0 .. HYDRO_SPECTRUM_WAVES_MAX)");
     if (spec->waves > 0 && !spec->wave) return fail(h, HYDRO_E_ARG, "sea spectrum: null wave with waves > 0");
@@ -4249,6 +4402,7 @@ int hydro_set_sea_ensemble(hydro_t* h, const hydro_sea_spectrum_t* members, int6
     if (!members) { h->ensemble_waves = -1; return HYDRO_OK; }
     if (h->sea_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea is set (clear it first: hydro_set_sea(h, NULL))");
     if (h->spectrum_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea spectrum is set (clear it first: hydro_set_sea_spectrum(h, NULL))");
+    if (h->fd_waves >= 0) return fail(h, HYDRO_E_STATE, "a finite-depth sea is set (clear it first: hydro_set_sea_finite_depth(h, NULL, 0, 0, 0))");
     if (count < 1 || count > HYDRO_SEA_ENSEMBLE_MAX) return fail(h, HYDRO_E_ARG, "sea ensemble: count out of range (1 .. HYDRO_SEA_ENSEMBLE_MAX)");
     if (bodies_per_sea < HYDRO_TILE || bodies_per_sea % HYDRO_TILE != 0 || bodies_per_sea >= ((int64_t)1 << 31))
         return fail(h, HYDRO_E_ARG, "sea ensemble: bodies_per_sea must be a positive multiple of 64 (and < 2^31)");
@@ -4293,11 +4447,68 @@ int hydro_set_sea_ensemble(hydro_t* h, const hydro_sea_spectrum_t* members, int6
     return HYDRO_OK;
 }
 
+int hydro_set_sea_finite_depth(hydro_t* h, const hydro_sea_spectrum_t* members, int64_t count, int64_t bodies_per_sea, double depth)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!members) { h->fd_waves = -1; return HYDRO_OK; }
+    if (h->sea_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea is set (clear it first: hydro_set_sea(h, NULL))");
+    if (h->spectrum_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea spectrum is set (clear it first: hydro_set_sea_spectrum(h, NULL))");
+    if (h->ensemble_waves >= 0) return fail(h, HYDRO_E_STATE, "a sea ensemble is set (clear it first: hydro_set_sea_ensemble(h, NULL, 0, 0))");
+    if (count < 1 || count > HYDRO_SEA_ENSEMBLE_MAX) return fail(h, HYDRO_E_ARG, "finite-depth sea: count out of range (1 .. HYDRO_SEA_ENSEMBLE_MAX)");
+    if (bodies_per_sea < HYDRO_TILE || bodies_per_sea % HYDRO_TILE != 0 || bodies_per_sea >= ((int64_t)1 << 31))
+        return fail(h, HYDRO_E_ARG, "finite-depth sea: bodies_per_sea must be a positive multiple of 64 (and < 2^31)");
+    const float neg_depth = (float)-depth;                                     // -h, rounded once
+    if (!isfinite(depth) || !(depth > 0.0) || !isfinite(neg_depth) || !(neg_depth < 0.0f))
+        return fail(h, HYDRO_E_ARG, "finite-depth sea: depth must be finite and > 0 (and in fp32 range)");
+    const int waves = members[0].waves;
+    if (waves < 0 || waves > HYDRO_SPECTRUM_WAVES_MAX)
+        return fail(h, HYDRO_E_ARG, "finite-depth sea: waves out of range (0 .. HYDRO_SPECTRUM_WAVES_MAX)");
+    for (int64_t m = 0; m < count; ++m) {
+        if (members[m].waves != waves) return fail(h, HYDRO_E_ARG, "finite-depth sea: every member must have the same number of waves");
+        if (waves > 0 && !members[m].wave) return fail(h, HYDRO_E_ARG, "finite-depth sea: null wave with waves > 0");
+    }
+    // (everything is checked and formed on the host, before the device table is touched)
+    SpectrumTable* tab = static_cast<SpectrumTable*>(calloc((size_t)count, sizeof(SpectrumTable)));
+    if (!tab) return fail(h, HYDRO_E_ALLOC, "finite-depth sea table: host allocation failed");
+    for (int64_t m = 0; m < count; ++m) {
+        char what[48];
+        snprintf(what, sizeof what, "finite-depth sea member %lld", (long long)m);
+        int rc = sea_records(h, what, members[m].current, waves, members[m].wave, tab[m].u, tab[m].w);
+        if (!rc) rc = depth_records(h, what, depth, waves, members[m].wave, tab[m].w);
+        if (rc) { free(tab); return rc; }
+        tab[m].waves = (uint32_t)waves;
+    }
+    if (const hipError_t e = use_device(h->device); e != hipSuccess) { free(tab); return fail(h, HYDRO_E_DEVICE, "use_device(h->device)", e); }
+    if (count > h->fd_capacity) {
+        // a larger table: the new one first, so that a failure leaves the previous sea in force
+        void* grown = nullptr;
+        if (hipMalloc(&grown, (size_t)count * sizeof(SpectrumTable)) != hipSuccess) {
+            free(tab);
+            return fail(h, HYDRO_E_ALLOC, "finite-depth sea table: allocation failed");
+        }
+        if (h->fd_table) (void)hipFree(h->fd_table);
+        h->fd_table = grown;
+        h->fd_capacity = count;
+    }
+    // from here on the device table is being rewritten: a failure leaves NO finite-depth sea, never half of one
+    h->fd_waves = -1;
+    hipError_t e = hipMemcpyAsync(h->fd_table, tab, (size_t)count * sizeof(SpectrumTable), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    free(tab);
+    if (e != hipSuccess) return fail(h, HYDRO_E_LAUNCH, "finite-depth sea table: copy to the device", e);
+    h->fd_count = count;
+    h->fd_tiles_per_sea = bodies_per_sea / HYDRO_TILE;
+    h->fd_neg_depth = neg_depth;
+    h->fd_waves = waves;
+    return HYDRO_OK;
+}
+
 }  // extern "C"
 
 namespace {
 // hydro_sea_sample, hydro_sea_spectrum_sample and hydro_sea_ensemble_sample: one set of rules, the table and the kernel of each;
-// `members` (the ensemble's only: the others pass none) are count and tiles_per_sea - a refusal of its own, last, and the kernel's last argument.
+// `members` (the ensemble's and the finite-depth sea's only: the others pass none) are count and tiles_per_sea - a refusal of its own,
+// last, and the kernel's next argument - and then whatever else the kernel takes (the finite-depth sea's -h).
 template <typename Kernel, typename... Members>
 int water_sample(hydro_t* h, Kernel kernel, const void* table, int waves, const char* none, int64_t n, const float* state, int64_t state_tile_stride,
                  int64_t step_index, double dt, float* out, int64_t out_tile_stride, void* stream, Members... members)
@@ -4311,9 +4522,12 @@ int water_sample(hydro_t* h, Kernel kernel, const void* table, int waves, const 
     if ((rc = check_tiled(h, n, state, state_tile_stride, HYDRO_STATE_FIELDS, "null state"))) return rc;
     if ((rc = check_tiled(h, n, out, out_tile_stride, HYDRO_SEA_FIELDS, "null out"))) return rc;
     if constexpr (sizeof...(Members) != 0) {
-        const int64_t count_and_tiles[] = {members...}, tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE;
-        if ((tiles + count_and_tiles[1] - 1) / count_and_tiles[1] > count_and_tiles[0])
-            return fail(h, HYDRO_E_ARG, "n needs more members than the sea ensemble has (count * bodies_per_sea < n)");
+        const bool covered = [&](int64_t count, int64_t tiles_per_sea, auto...) {
+            return ((n + HYDRO_TILE - 1) / HYDRO_TILE + tiles_per_sea - 1) / tiles_per_sea <= count;
+        }(members...);
+        if (!covered)
+            return fail(h, HYDRO_E_ARG, sizeof...(Members) > 2 ? "n needs more members than the finite-depth sea has (count * bodies_per_sea < n)"
+                                                               : "n needs more members than the sea ensemble has (count * bodies_per_sea < n)");
     }
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     if (n == 0) return HYDRO_OK;
@@ -4321,10 +4535,9 @@ int water_sample(hydro_t* h, Kernel kernel, const void* table, int waves, const 
         hipLaunchKernelGGL(kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), state, (uint32_t)state_tile_stride,
                            out, (uint32_t)out_tile_stride, (uint32_t)n, table, (uint32_t)waves, step_index, dt, tail...);
     };
-    if constexpr (sizeof...(Members) != 0) {
-        const int64_t count_and_tiles[] = {members...};
-        launch((uint32_t)count_and_tiles[1]);
-    } else launch();
+    if constexpr (sizeof...(Members) != 0)
+        [&](int64_t, int64_t tiles_per_sea, auto... more) { launch((uint32_t)tiles_per_sea, more...); }(members...);
+    else launch();
     HYDRO_HIP(h, hipGetLastError(), HYDRO_E_LAUNCH);
     return HYDRO_OK;
 }
@@ -4354,6 +4567,14 @@ int hydro_sea_ensemble_sample(hydro_t* h, int64_t n, const float* state, int64_t
     if (!h) return HYDRO_E_ARG;
     return water_sample(h, ensemble_sample_kernel, (const void*)h->ensemble_table, h->ensemble_waves, "no sea ensemble (call hydro_set_sea_ensemble first)",
                         n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream, h->ensemble_count, h->ensemble_tiles_per_sea);
+}
+
+int hydro_sea_finite_depth_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
+                                  float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    return water_sample(h, depth_sample_kernel, (const void*)h->fd_table, h->fd_waves, "no finite-depth sea (call hydro_set_sea_finite_depth first)",
+                        n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream, h->fd_count, h->fd_tiles_per_sea, h->fd_neg_depth);
 }
 
 int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -4771,6 +4992,43 @@ int hydro_step_fused_tiled_multi_ens(hydro_t* h, int64_t n, const float* state, 
     m.with_spectrum();
     m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
     m.with_ensemble();
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_fd(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                    const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                    float* state_out, int64_t out_tile_stride,
+                                    float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                    int rotational, double* ke_out_dev,
+                                    float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                    int64_t row0, int64_t* rows_written_host,
+                                    const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                    const float* control, int64_t control_tile_stride,
+                                    const float* mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                    float* extremes, int64_t extremes_tile_stride,
+                                    const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                    float* tether_peaks, int64_t tether_peaks_tile_stride,
+                                    void* statistics, int64_t statistics_tile_stride,
+                                    const float* levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                    int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_mooring_layers(mooring_layers);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    m.with_spectrum();
+    m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
+    m.with_ensemble();
+    m.with_finite_depth();
     return step_fused_tiled_multi_launch(h, m);
 }
 

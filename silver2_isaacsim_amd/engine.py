@@ -73,6 +73,7 @@ class HydroEngine:
         self.sea_waves: int | None = None            # wave components of the sea set with set_sea; None: no sea
         self.spectrum_waves: int | None = None       # wave components of the spectrum set with set_sea_spectrum; None: no spectrum
         self.ensemble_count: int | None = None       # members of the ensemble set with set_sea_ensemble; None: no ensemble
+        self.finite_depth: float | None = None       # the depth (m) of the sea set with set_sea_finite_depth; None: no finite-depth sea
         self.seabed = None                           # the seabed.Seabed set with set_seabed; None: no bed
         self.set_scene(water_density, gravity)
 
@@ -646,8 +647,15 @@ class HydroEngine:
             self._check(self._lib.hydro_set_sea_ensemble(self._h, None, 0, 0))
             self.ensemble_count = None
             return
-        members = list(ensemble.members)
-        rows = []                                                                  # (alive until the call returns: the library copies)
+        c, rows = self._c_members(ensemble.members)                                # (alive until the call returns: the library copies)
+        self._check(self._lib.hydro_set_sea_ensemble(self._h, c, len(rows), int(ensemble.bodies_per_sea)))
+        self.ensemble_count = len(rows)
+
+    @staticmethod
+    def _c_members(members):
+        """(the array of hydro_sea_spectrum_t that `hydro_set_sea_ensemble` / `_finite_depth` take, the rows that keep it alive)."""
+        members = list(members)
+        rows = []
         c = (nat.SeaSpectrum * max(len(members), 1))()
         for m, member in enumerate(members):
             waves = [tuple(float(x) for x in w) for w in member.waves]
@@ -657,8 +665,7 @@ class HydroEngine:
             c[m].current[:] = [float(x) for x in member.current]
             c[m].waves = len(waves)
             c[m].wave = ctypes.cast(rows[-1], ctypes.POINTER(nat.SeaWave)) if waves else None
-        self._check(self._lib.hydro_set_sea_ensemble(self._h, c, len(members), int(ensemble.bodies_per_sea)))
-        self.ensemble_count = len(members)
+        return c, rows
 
     def sea_ensemble_sample(self, state: torch.Tensor, n: int, step_index: int, dt: float, out: torch.Tensor | None = None,
                             stream=None) -> torch.Tensor:
@@ -688,6 +695,60 @@ class HydroEngine:
         under `set_sea_spectrum(member)`.  Without an ensemble the call IS step_fused_tiled_multi_stat.  Returns the number of
         rows written (0 without a log)."""
         return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_ens,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._stat_tail(n, step0, statistics, levels, channel_a, channel_b, mooring, mooring_layers, tether, layers,
+                                                            peaks, extremes, control, applied, frame))
+
+    # ------------------------------------------------------------------ finite-depth sea
+    def set_sea_finite_depth(self, sea, n: int | None = None) -> None:
+        """The scene's finite-depth sea (hydro_set_sea_finite_depth; include/hydro.h, "Finite-depth sea"): `sea` is a
+        `sea.SeaEnsemble` with a `depth` - its members, its `bodies_per_sea` - or a `sea.SeaSpectrum` with a `depth`, which rides as
+        ONE member whose block covers `n` bodies (default: the engine's capacity).  The orbital velocity follows cosh / sinh of
+        the height above the bed; the surface is the deep model's.  None clears it.  Only `step_fused_tiled_multi_fd` and
+        `sea_finite_depth_sample` see it; it, an ensemble, a spectrum and the sea of `set_sea` exclude each other.  Synchronous,
+        like `set_sea`."""
+        if sea is None:
+            self._check(self._lib.hydro_set_sea_finite_depth(self._h, None, 0, 0, 0.0))
+            self.finite_depth = None
+            return
+        if getattr(sea, "depth", None) is None:
+            raise ValueError("a finite-depth sea needs a depth (SeaSpectrum(depth=), jonswap(..., depth=))")
+        if hasattr(sea, "members"):
+            members, per_sea = sea.members, int(sea.bodies_per_sea)
+        else:
+            members, per_sea = [sea], 64 * max(1, -(-(self.capacity if n is None else int(n)) // 64))
+        c, rows = self._c_members(members)                                         # (alive until the call returns: the library copies)
+        self._check(self._lib.hydro_set_sea_finite_depth(self._h, c, len(rows), per_sea, float(sea.depth)))
+        self.finite_depth = float(sea.depth)
+
+    def sea_finite_depth_sample(self, state: torch.Tensor, n: int, step_index: int, dt: float, out: torch.Tensor | None = None,
+                                stream=None) -> torch.Tensor:
+        """`sea_ensemble_sample` against the finite-depth sea set with `set_sea_finite_depth` (hydro_sea_finite_depth_sample):
+        exactly the [eta, u_x, u_y, u_z] `step_fused_tiled_multi_fd` uses for step `step_index`."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.SEA_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.SEA_FIELDS, n)
+        self._check(self._lib.hydro_sea_finite_depth_sample(self._h, n, s_ptr, s_stride, int(step_index), float(dt), o_ptr, o_stride,
+                                                            self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_fd(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                  statistics: torch.Tensor | None = None, levels: torch.Tensor | None = None,
+                                  channel_a: int = nat.STAT_Z, channel_b: int = nat.STAT_TENSION,
+                                  mooring: torch.Tensor | None = None, mooring_layers: int = 1,
+                                  tether: torch.Tensor | None = None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                  extremes: torch.Tensor | None = None,
+                                  control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                  log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                  state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                  ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_ens through the finite-depth sea set with `set_sea_finite_depth`
+        (hydro_step_fused_tiled_multi_fd): the arguments and the rules are step_fused_tiled_multi_ens's, every option optional.
+        Without a finite-depth sea the call IS step_fused_tiled_multi_ens.  Returns the number of rows written (0 without a
+        log)."""
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_fd,
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream,
                                     lambda: self._stat_tail(n, step0, statistics, levels, channel_a, channel_b, mooring, mooring_layers, tether, layers,

@@ -15,6 +15,11 @@ a significant wave height and a peak period (include/hydro.h, "Sea spectrum"; DE
 
 `SeaEnsemble` is several such spectra in one run, each over its own block of the bodies - `jonswap_ensemble` and
 `pierson_moskowitz_ensemble` build one sea per seed (include/hydro.h, "Sea ensemble").
+
+A `SeaSpectrum` or `SeaEnsemble` with a `depth` (m) is a FINITE-DEPTH sea: the same surface, the orbital velocity with the profiles
+cosh(kappa (z + h)) / sinh(kappa h) and sinh(kappa (z + h)) / sinh(kappa h) in place of exp(kappa z), nothing below the bed
+(include/hydro.h, "Finite-depth sea").  `wavenumber` solves omega^2 = g kappa tanh(kappa h), and `depth=` on
+the four constructors places the same bins and amplitudes on the shorter waves of that depth.
 """
 from __future__ import annotations
 
@@ -94,12 +99,77 @@ class SeaState:
         return u
 
 
+def wavenumber(omega, depth: float, g: float = 9.81):
+    """kappa (rad/m) of a linear wave of angular frequency `omega` (rad/s; a number or an array, >= 0) over still water of `depth`
+    (m): the root of omega^2 = g kappa tanh(kappa depth).  Newton's iteration on f(x) = x tanh x - omega^2 depth / g in x = kappa
+    depth, started from the deep-water root or the shallow-water one, whichever is larger - f is convex and increasing for x > 0
+    and both starts lie at or above the root, so the iteration descends monotonically; it stops when x no longer changes."""
+    if not (depth > 0.0 and math.isfinite(depth) and g > 0.0):
+        raise ValueError("depth must be finite and > 0, g > 0")
+    om = np.asarray(omega, np.float64)
+    if not (np.isfinite(om).all() and (om >= 0.0).all()):
+        raise ValueError("omega must be finite and >= 0")
+    c = om * om * (depth / g)
+    x = np.maximum(c, np.sqrt(c))
+    for _ in range(64):
+        th = np.tanh(x)
+        slope = th + x * (1.0 - th * th)
+        step = np.divide(x * th - c, slope, out=np.zeros_like(x), where=slope > 0.0)
+        nxt = x - step
+        if np.array_equal(nxt, x):
+            break
+        x = nxt
+    kappa = x / depth
+    return float(kappa) if np.ndim(omega) == 0 else kappa
+
+
+def _depth(depth):
+    """None (deep water) or a finite depth > 0 as a float."""
+    if depth is None:
+        return None
+    depth = float(depth)
+    if not (depth > 0.0 and math.isfinite(depth)):
+        raise ValueError("depth must be None (deep water) or finite and > 0 (m)")
+    return depth
+
+
 class SeaSpectrum(SeaState):
     """An irregular sea: the model of `SeaState` with up to 64 components, what `ClosedLoopSim.set_sea` and
     `HydroEngine.set_sea_spectrum` take for a sea given by its spectrum (hydro_step_fused_tiled_multi_irr; include/hydro.h,
     "Sea spectrum").  `pierson_moskowitz` and `jonswap` below cut a spectrum of significant wave height Hs and peak period Tp
-    into equal-energy bins; `add_wave` builds one by hand.  `elevation` and `velocity` are SeaState's, in fp64."""
+    into equal-energy bins; `add_wave` builds one by hand.  `elevation` and `velocity` are SeaState's, in fp64.
+    `depth` (m; None: deep water) makes it a finite-depth sea (hydro_step_fused_tiled_multi_fd; include/hydro.h, "Finite-depth
+    sea"): `ClosedLoopSim.set_sea` then takes it through `HydroEngine.set_sea_finite_depth`, `velocity` follows the depth,
+    `elevation` is unchanged.  The components are taken as given: `wavenumber` is the dispersion relation of a depth."""
     _CAP, _KIND = SPECTRUM_WAVES_MAX, "a sea spectrum"
+
+    def __init__(self, current=(0.0, 0.0, 0.0), depth=None):
+        super().__init__(current)
+        self.depth = _depth(depth)
+
+    def velocity(self, x, y, z_rel, t) -> np.ndarray:
+        """`SeaState.velocity` in deep water; with a `depth` h the profiles of linear theory - horizontal a omega cosh(kappa (zc +
+        h)) / sinh(kappa h), vertical a omega sinh(kappa (zc + h)) / sinh(kappa h), zc = z_rel clamped to -h .. 0 - evaluated as
+        (E +- G) / (1 - q), E = exp(kappa zc), G = exp(-kappa (zc + 2 h)), q = exp(-2 kappa h), which neither overflows nor
+        cancels in deep water."""
+        if self.depth is None:
+            return super().velocity(x, y, z_rel, t)
+        h = self.depth
+        x, y, z, t = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(z_rel, np.float64),
+                                         np.asarray(t, np.float64))
+        u = np.empty(x.shape + (3,), np.float64)
+        u[...] = self.current
+        zc = np.maximum(np.minimum(z, 0.0), -h)
+        for (a, kx, ky, om, _), th in zip(self.waves, self._phases(x, y, t)):
+            kappa = math.hypot(kx, ky)
+            if kappa == 0.0:
+                continue
+            e, g_ = np.exp(kappa * zc), np.exp(-kappa * (zc + 2.0 * h))
+            scale = a * om / -math.expm1(-2.0 * kappa * h)
+            u[..., 0] += scale * (e + g_) * (kx / kappa) * np.cos(th)
+            u[..., 1] += scale * (e + g_) * (ky / kappa) * np.cos(th)
+            u[..., 2] += scale * (e - g_) * np.sin(th)
+        return u
 
     def hs(self) -> float:
         """The significant wave height 4 sqrt(m0) of the components, m0 = sum a^2 / 2 (m)."""
@@ -156,7 +226,7 @@ def jonswap_bin_medians(omega_p: float, gamma: float, n: int, grid: int = 1 << 1
     return np.interp((np.arange(n) + 0.5) / n * total, cum, w)
 
 
-def _from_bins(hs, omegas, heading_deg, seed, spread, current, g) -> SeaSpectrum:
+def _from_bins(hs, omegas, heading_deg, seed, spread, current, g, depth=None) -> SeaSpectrum:
     n = len(omegas)
     rng = np.random.default_rng(seed)
     phases = rng.uniform(-math.pi, math.pi, n)
@@ -166,9 +236,9 @@ def _from_bins(hs, omegas, heading_deg, seed, spread, current, g) -> SeaSpectrum
     elif spread is not None:
         raise ValueError("spread must be None (long-crested) or 'cos2'")
     a = hs / math.sqrt(8.0 * n)                                   # equal energy per bin: sum a^2 / 2 = hs^2 / 16
-    sea = SeaSpectrum(current)
+    sea = SeaSpectrum(current, depth)
     for om, ph, hd in zip(omegas, phases, headings):
-        kappa = om * om / g
+        kappa = om * om / g if sea.depth is None else wavenumber(float(om), sea.depth, g)
         sea.add_wave(a, kappa * math.cos(hd), kappa * math.sin(hd), om, ph)
     return sea
 
@@ -181,28 +251,29 @@ def _check_sea(hs, tp, components, g):
 
 
 def pierson_moskowitz(hs: float, tp: float, heading_deg: float, *, components: int = SPECTRUM_WAVES_MAX, seed: int = 0, spread=None,
-                      current=(0.0, 0.0, 0.0), g: float = 9.81) -> SeaSpectrum:
+                      current=(0.0, 0.0, 0.0), g: float = 9.81, depth=None) -> SeaSpectrum:
     """A Pierson-Moskowitz sea of significant wave height `hs` (m) and peak period `tp` (s) travelling towards `heading_deg`,
     as `components` deep-water components (kappa = omega^2 / g) of EQUAL ENERGY, in closed form: component j sits at the median
     of bin j of the cumulative energy fraction F, omega_j = omega_p (1.25 / ln(N / (j + 1/2)))^(1/4), with amplitude
     hs / sqrt(8 N).  Phases: numpy.random.default_rng(seed).uniform(-pi, pi, N).  spread="cos2": the headings are
     heading + delta_j, delta_j the quantile midpoints of (2 / pi) cos^2 (`cos2_offsets`), dealt to the components by a
-    permutation drawn from the same generator, after the phases."""
+    permutation drawn from the same generator, after the phases.  `depth` (m): the same bins, amplitudes, phases and headings
+    on the wavenumbers of that depth (`wavenumber`), and a finite-depth sea (`SeaSpectrum.depth`)."""
     _check_sea(hs, tp, components, g)
     n, omega_p = int(components), 2.0 * math.pi / tp
     omegas = omega_p * (1.25 / np.log(n / (np.arange(n) + 0.5))) ** 0.25
-    return _from_bins(hs, omegas, heading_deg, seed, spread, current, g)
+    return _from_bins(hs, omegas, heading_deg, seed, spread, current, g, depth)
 
 
 def jonswap(hs: float, tp: float, heading_deg: float, *, gamma: float = 3.3, components: int = SPECTRUM_WAVES_MAX, seed: int = 0, spread=None,
-            current=(0.0, 0.0, 0.0), g: float = 9.81) -> SeaSpectrum:
+            current=(0.0, 0.0, 0.0), g: float = 9.81, depth=None) -> SeaSpectrum:
     """`pierson_moskowitz` for the JONSWAP spectrum of peak enhancement `gamma` (>= 1): the same equal-energy binning, the bin
     medians from the numerically integrated and inverted cumulative spectrum (`jonswap_bin_medians`); the spectrum is scaled
     so that the components carry hs^2 / 16 exactly.  gamma = 1 is the Pierson-Moskowitz sea."""
     _check_sea(hs, tp, components, g)
     if not gamma >= 1.0 or not math.isfinite(gamma):
         raise ValueError("gamma must be >= 1")
-    return _from_bins(hs, jonswap_bin_medians(2.0 * math.pi / tp, float(gamma), int(components)), heading_deg, seed, spread, current, g)
+    return _from_bins(hs, jonswap_bin_medians(2.0 * math.pi / tp, float(gamma), int(components)), heading_deg, seed, spread, current, g, depth)
 
 
 class SeaEnsemble:
@@ -223,12 +294,19 @@ class SeaEnsemble:
             raise ValueError("every member of a sea ensemble must have the same number of wave components")
         if int(bodies_per_sea) != bodies_per_sea or bodies_per_sea < 64 or bodies_per_sea % 64:
             raise ValueError("bodies_per_sea must be a positive multiple of 64")
+        if len({m.depth for m in members}) != 1:
+            raise ValueError("every member of a sea ensemble must have the same depth (or none)")
         self.members = members
         self.bodies_per_sea = int(bodies_per_sea)
 
     @property
     def count(self) -> int:
         return len(self.members)
+
+    @property
+    def depth(self):
+        """The members' common depth (m), or None in deep water: with a depth the ensemble is a finite-depth sea."""
+        return self.members[0].depth
 
     @property
     def waves(self) -> list:

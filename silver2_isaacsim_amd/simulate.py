@@ -555,14 +555,18 @@ class ClosedLoopSim:
         and a spectrum with components stays out of graph replays like a sea with waves.
         Or a `sea.SeaEnsemble`, several spectra with block m of `bodies_per_sea` bodies stepping through member m
         (hydro_step_fused_tiled_multi_ens; include/hydro.h, "Sea ensemble"): the same one slot, every other option rides along,
-        count * bodies_per_sea must cover the sim's bodies, and only an ensemble of current-only members replays."""
+        count * bodies_per_sea must cover the sim's bodies, and only an ensemble of current-only members replays.
+        A spectrum or an ensemble WITH A `depth` is a finite-depth sea (hydro_step_fused_tiled_multi_fd; include/hydro.h,
+        "Finite-depth sea"): the same slot, the orbital velocity feels the bottom at that depth; a spectrum rides as one member
+        that covers the sim's bodies, and the replay rules are the ensemble's.  The seabed is independent of it: set its z to
+        -depth for bodies that rest on the bottom the waves feel."""
         if not self.fused:
             raise ValueError("the sea state lives in the fused step kernels (fused=True)")
         if isinstance(sea, SeaEnsemble) and sea.count * sea.bodies_per_sea < self.n:
             raise ValueError(f"the ensemble's {sea.count} members of {sea.bodies_per_sea} bodies do not cover the sim's {self.n} bodies")
         self.synchronize()                                      # launches in flight read the table this rewrites
         if self.sea is not None and self._sea_setter(self.sea) != self._sea_setter(sea):
-            self._set_engine_sea(self.sea, None)                # the library holds a sea, a spectrum or an ensemble, never two: the other kind goes first
+            self._set_engine_sea(self.sea, None)                # the library holds ONE kind of sea, never two: the other kind goes first
             self.sea = None
         self._set_engine_sea(sea, sea)
         self.sea = sea
@@ -571,6 +575,8 @@ class ClosedLoopSim:
     @staticmethod
     def _sea_setter(kind) -> str:
         """The engine call that takes a sea of `kind`'s kind."""
+        if isinstance(kind, (SeaEnsemble, SeaSpectrum)) and kind.depth is not None:
+            return "set_sea_finite_depth"
         return "set_sea_ensemble" if isinstance(kind, SeaEnsemble) else "set_sea_spectrum" if isinstance(kind, SeaSpectrum) else "set_sea"
 
     def _set_engine_sea(self, kind, sea) -> None:
@@ -918,6 +924,7 @@ class ClosedLoopSim:
             self.link_tensions.links, self.link_tensions.layer = self._tether_links
 
     # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
+    # the finite-depth sea if `sim.sea` has a depth (its entry is the ensemble's, every other option optional), else through
     # the sea ensemble if `sim.sea` is one (its entry takes every other option, the statistics included), else with
     # the response statistics if they are tracked (their entry takes every other option, the spectrum included), else through
     # the sea spectrum if `sim.sea` is one (its entry takes every other option), else with
@@ -937,17 +944,19 @@ class ClosedLoopSim:
         if rec is not None:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
-        if isinstance(self.sea, SeaEnsemble):
-            # (the entry of the statistics, every option optional, the statistics too)
+        finite_depth = self.sea is not None and self._sea_setter(self.sea) == "set_sea_finite_depth"
+        if finite_depth or isinstance(self.sea, SeaEnsemble):
+            # (the entry of the statistics, every option optional, the statistics too; _fd first)
             st = self.statistics
             moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
             net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
-            rows = e.step_fused_tiled_multi_ens(*args, k, self.steps_done, *((st.buffer, st.levels_buffer, *st.channel_numbers) if st is not None
-                                                                             else (None, None, nat.STAT_Z, nat.STAT_TENSION)),
-                                                moor, moor_layers, net, layers,
-                                                self.link_tensions.buffer if self.link_tensions is not None else None,
-                                                self.extremes.buffer if self.extremes is not None else None,
-                                                self.control, self.applied, self.applied_frame, **kw)
+            step = e.step_fused_tiled_multi_fd if finite_depth else e.step_fused_tiled_multi_ens
+            rows = step(*args, k, self.steps_done, *((st.buffer, st.levels_buffer, *st.channel_numbers) if st is not None
+                                                     else (None, None, nat.STAT_Z, nat.STAT_TENSION)),
+                        moor, moor_layers, net, layers,
+                        self.link_tensions.buffer if self.link_tensions is not None else None,
+                        self.extremes.buffer if self.extremes is not None else None,
+                        self.control, self.applied, self.applied_frame, **kw)
             if st is not None:
                 self._statistics_dirty = True
         elif self.statistics is not None:

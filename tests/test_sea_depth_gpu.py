@@ -1,0 +1,479 @@
+"""Finite-depth seas on the device (hydro_set_sea_finite_depth, hydro_sea_finite_depth_sample, hydro_step_fused_tiled_multi_fd).
+
+THE IDENTITY (no tolerance): at h = 1e6 m with every kappa_j >= 0.01 rad/m, q_j = e^{-2 kappa_j h} is 0.0 in fp64 - the scaled
+constants ARE the deep ones - and every G exponent gl_j - kl2_j zc is below -200 for bodies within 1 000 m of the surface, so
+G_j = +0 and every statement of include/hydro.h's "Finite-depth sea" returns "Sea ensemble"'s bits: the _fd launch must equal the
+parent's _ens launch in state, prev_out, the log, the extremes, the link tensions, every word of the statistics record and the
+energy pair.  The test asserts the two host conditions first.
+THE COMPOSITION: at h = 9 m (kappa_p h = 1) one explicit step equals hydro_step_wrench_tiled on the relative state built from
+hydro_sea_finite_depth_sample followed by hydro_integrate_tiled on the true state, bit for bit - after the parent's _ens run of the
+same bodies has shown that the bottom moves at least 3 in 4 of them, and some body of every tile.
+THE SAMPLE is held to tests/sea_depth_reference.py's DEPTH_VIEW_BOUND = 8 units of 2^-24, derived on the host beforehand (the
+emulation stands at 3.18; the device at eta 2.83, u 3.18), and the same fp64 reference without the G term misses the device by 8e5 units.
+
+Shapes: n = 65, 200 and 321 at tiles_per_sea = 1, n = 321 at 2 (tests/test_sea_ensemble_gpu.py's cases); f32 and f16, both drag
+forms, 1 and 7 steps, 11 and 64 components; 9, 10, 11, 63 and 64 components for the remainder trips of the component loops."""
+import ctypes
+import math
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import sea_depth_reference as sdr
+import sea_ensemble_harness as seh
+import statistics_reference as sx
+import value_contract as vc
+from conftest import REPO
+from silver2_isaacsim_amd import _native as nat
+from silver2_isaacsim_amd import scenes
+from silver2_isaacsim_amd import statistics as stx
+from silver2_isaacsim_amd.extremes import Extremes
+from silver2_isaacsim_amd.sea import SeaEnsemble, SeaSpectrum, SeaState, jonswap, wavenumber
+from silver2_isaacsim_amd.simulate import ClosedLoopSim
+from designed_populations import BED, bed_pop, hold_pop, SEA  # noqa: F401  (fixtures are requested by name)
+from resident_harness import (_buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, _from, _guarded, _ke, NAN, S_A, S_C, S_IN, S_OUT, S_PV, S_PVO,
+                              _same_bits, _tiled, _unguard, _untouched, _watched)
+from sea_reference import relative
+from test_sea_ensemble_gpu import (_buoy_field, _c_members, _equal, _everything, _levels_for, _moored_sim, pop, _record, _same_or_nan,  # noqa: F401
+                                   S_E, S_P2, S_SP3, S_T2)
+from tether_net_population import net_for
+
+pytestmark = pytest.mark.gpu
+CASES = ((65, 1), (200, 1), (321, 1), (321, 2))                   # (n, tiles_per_sea)
+STEPS = (1, 7)
+WAVES = pytest.mark.parametrize("waves", [11, 64])
+FAR = 1e6                                                         # m: deep water for every component of the harness members
+H = sdr.DEPTH                                                     # m: kappa_p h = 1 at the members' Tp = 7 s
+E_ARG, E_STATE = -1, -5
+S_W = 4 * 64 + 12
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _return_the_cached_blocks():
+    """The guard tests of tests/test_statistics_gpu.py hand a small input buffer over as a LARGER record and expect the refusal that
+    names an input: which refusal comes first depends on what lies behind that buffer, hence on the blocks earlier modules left in
+    torch's caching allocator.  This module leaves none behind."""
+    yield
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+
+
+def _fd(sea, depth):
+    """`sea` (a spectrum or an ensemble, its components taken as given) at `depth`."""
+    if isinstance(sea, SeaEnsemble):
+        return SeaEnsemble([sdr.with_depth(m, depth) for m in sea.members], sea.bodies_per_sea)
+    return sdr.with_depth(sea, depth)
+
+
+def _water(eng, water, n=None):
+    """The engine's water: None, a SeaState, a SeaSpectrum, a SeaEnsemble, or either of the two with a depth - whatever was set
+    before is cleared first."""
+    eng.set_sea(None)
+    eng.set_sea_spectrum(None)
+    eng.set_sea_ensemble(None)
+    eng.set_sea_finite_depth(None)
+    if water is None:
+        return
+    if getattr(water, "depth", None) is not None:
+        eng.set_sea_finite_depth(water, n)
+    elif isinstance(water, SeaEnsemble):
+        eng.set_sea_ensemble(water)
+    elif isinstance(water, SeaSpectrum):
+        eng.set_sea_spectrum(water)
+    else:
+        eng.set_sea(water)
+
+
+# ---- 1. the identity --------------------------------------------------------------------------------------------------------------------------
+@COEFFS
+@DRAG
+@WAVES
+def test_in_deep_water_the_launch_is_the_ens_launch_bit_for_bit(waves, coeff, implicit, pop, native_built):
+    assert (np.abs(pop["st"][:, 2]) < 1000.0).all()
+    for m in seh.members(waves):
+        consts, q = sdr.device_constants(m, FAR)
+        assert min(math.hypot(w[1], w[2]) for w in m.waves) >= 0.01 and all(x == 0.0 for x in q)
+        assert all(float(c[7]) + float(c[3]) * 1000.0 < -200.0 for c in consts)           # gl_j - kl2_j zc for zc >= -1 000 m
+    for n in sorted({n for n, _ in CASES}):
+        eng = _engine(n, pop["params"][coeff], coeff)
+        eng.set_seabed(BED)
+        for tps in (t for m, t in CASES if m == n):
+            ens = seh.ensemble(waves, n, tps)
+            for bare in (False, True):
+                for steps in STEPS:
+                    ke = dict(ke=_ke()) if steps == 7 else {}
+                    _water(eng, ens)
+                    want = _everything(eng, "ens", pop, n, steps, 5, implicit, bare=bare, **ke)
+                    want_plain = _everything(eng, "ens", pop, n, steps, 5, implicit, bare=bare, record=False)
+                    _water(eng, _fd(ens, FAR))
+                    ke = dict(ke=_ke()) if steps == 7 else {}
+                    got = _everything(eng, "fd", pop, n, steps, 5, implicit, bare=bare, **ke)
+                    assert set(got) == set(want) and _equal(got, want, n) is None, (n, tps, bare, steps, _equal(got, want, n))
+                    assert (stx.unpack(got["record"].cpu().numpy(), n)["n"] == steps).all()
+                    if steps == 7:
+                        assert _same_bits(got["ke"], want["ke"]) and torch.isfinite(got["ke"]).all() == torch.isfinite(want["ke"]).all()
+                    # without a statistics record: the family without statistics
+                    plain = _everything(eng, "fd", pop, n, steps, 5, implicit, bare=bare, record=False)
+                    assert set(plain) == set(want_plain) and all(_same_or_nan(plain[k], want_plain[k]) for k in plain), (n, tps, bare, steps)
+        # a lone spectrum is an ensemble of one member that covers n
+        member = seh.members(waves)[3]
+        _water(eng, SeaEnsemble([member], 64 * eng.tiles(n)))
+        want = _everything(eng, "ens", pop, n, 7, 5, implicit)
+        _water(eng, _fd(member, FAR), n)
+        assert _equal(_everything(eng, "fd", pop, n, 7, 5, implicit), want, n) is None, n
+        eng.close()
+
+
+def test_without_a_finite_depth_sea_the_launch_is_the_ens_entrys_with_each_option_alone(pop, native_built):
+    """n = 65, 2 steps, f32, explicit, with the kinetic energy - each option alone, and none, with and without a record, in still
+    water, in a regular sea, under a spectrum and under an ensemble."""
+    n, steps, step0 = 65, 2, 3
+    st, pv = pop["st"], pop["pv"]
+    lev = _tiled(_levels_for(st, n))
+    spec = seh.members(11)[2]
+    for option in (None, "log", "applied", "control", "sea", "spectrum", "ensemble", "seabed", "spread", "extremes", "net", "peaks"):
+        eng = _engine(n, pop["params"]["f32"], "f32")
+        eng.set_watch([0, 5, 63, 64])
+        _water(eng, SEA if option == "sea" else spec if option == "spectrum" else seh.ensemble(11, n, 1) if option == "ensemble" else None)
+        eng.set_seabed(BED if option == "seabed" else None)
+        layers = 2 if option in ("net", "peaks") else 1
+
+        def run(entry, with_record):
+            cur, old = _buffers(st, pv, n)
+            ke = _ke()
+            log = torch.full((steps, 19, 4), NAN, dtype=torch.float32, device=DEV) if option == "log" else None
+            extremes = eng.extremes_reset(eng.alloc_tiled(8, n), n) if option == "extremes" else None
+            peaks = eng.alloc_tiled(layers, n) if option == "peaks" else None
+            record = _record(eng, n) if with_record else None
+            kw = dict(step0=step0, spread=_tiled(pop["spread"][:n, 0:27]) if option == "spread" else None, layers=3,
+                      tether=_tiled(net_for(pop["net"], n, layers)) if option in ("net", "peaks") else None, net_layers=layers, peaks=peaks,
+                      extremes=extremes, applied=_tiled(pop["applied"][:n]) if option == "applied" else None,
+                      control=_tiled(pop["ctl"][:n]) if option == "control" else None, frame="body", ke=ke,
+                      statistics=record, levels=lev if with_record else None, channels=(2, 6))
+            if log is not None:
+                kw.update(log=log, every=1, phase=1, row0=0)
+            state, prev = seh.launch(eng, cur, old, n, steps, entry=entry, **kw)
+            torch.cuda.synchronize()
+            return [state, prev, ke] + [x for x in (log, extremes, peaks, record) if x is not None]
+        for with_record in (False, True):
+            want, got = run("ens", with_record), run("fd", with_record)
+            assert len(got) == len(want) and all(_same_bits(x, y) for x, y in zip(got, want)), (option, with_record)
+        eng.close()
+
+
+def test_every_other_entry_ignores_a_finite_depth_sea(pop, native_built):
+    """With a finite-depth sea set, the _ens and the _stat entries step in still water: their bits are those without any sea."""
+    n = 200
+    eng = _engine(n, pop["params"]["f32"], "f32")
+    for entry in ("ens", "stat"):
+        _water(eng, None)
+        want = _everything(eng, entry, pop, n, 2, 5, False, bare=True)
+        _water(eng, _fd(seh.ensemble(11, n, 1), H))
+        got = _everything(eng, entry, pop, n, 2, 5, False, bare=True)
+        assert _equal(got, want, n) is None, entry
+    moved = _everything(eng, "fd", pop, n, 2, 5, False, bare=True)
+    assert not _same_or_nan(moved["state"], want["state"])         # (and the _fd entry does see it)
+    eng.close()
+
+
+# ---- 2. the composition, and the condition that makes it mean something ---------------------------------------------------------------------
+@COEFFS_SEMANTICS
+def test_explicit_step_is_wrench_of_the_relative_state_then_integrator_of_the_true_one(coeff, semantics, pop, native_built):
+    n = 65
+    st, pv = pop["st"], pop["pv"]
+    assert 0.9 <= wavenumber(2.0 * math.pi / seh.TP, H) * H <= 1.1
+    eng = _engine(n, pop["params"][coeff], coeff, semantics)
+    watched = _watched(n, (0, 63, 64))
+    eng.set_watch(watched)
+    for count in (9, 10, 11, 63, 64):                              # one, two and three remainder trips behind the groups of four, and none
+        ens = seh.ensemble(count, n, 1)
+        assert len(ens.members[0].waves) == count and ens.count == 2
+        # the condition, on the parent's _ens run of the same bodies: the bottom moves nearly every body
+        _water(eng, ens)
+        cur, old = _buffers(st, pv, n)
+        deep, _ = seh.launch(eng, cur, old, n, 1, step0=7)
+        deep = _from(deep, n)
+        _water(eng, _fd(ens, H))
+        for step0 in (0, 7):
+            w = _from(eng.sea_finite_depth_sample(_tiled(st[:n]), n, step0, DT), n)
+            s_rel, pv_rel = relative(st[:n], pv[:n], w[:, 0], w[:, 1:4])
+            wrench = eng.step_wrench_tiled(_tiled(s_rel), n, DT, prev=_tiled(pv_rel))
+            cur, old = _buffers(st, pv, n)
+            want = eng.integrate_tiled(cur, wrench, n, DT)
+            log = torch.full((1, 19, len(watched)), NAN, dtype=torch.float32, device=DEV)
+            got, got_prev = seh.launch(eng, cur, old, n, 1, step0=step0, entry="fd", log=log, every=1, phase=1, row0=0)
+            torch.cuda.synchronize()
+            if step0 == 7:
+                fraction, every_tile = sdr.differs(_from(want, n), deep, n)
+                assert fraction >= 0.75 and every_tile, (count, fraction, every_tile)
+            assert _same_bits(got, want), (count, step0)
+            assert np.array_equal(got_prev.cpu().numpy().view(np.uint32), scenes.to_tiled(st[:n, 7:13]).view(np.uint32))    # the TRUE velocity
+            host = log.cpu().numpy()[0]
+            assert np.array_equal(host[:13].T.view(np.uint32), _from(want, n)[watched].view(np.uint32)), (count, step0)
+            assert np.array_equal(host[13:].T.view(np.uint32), _from(wrench, n)[watched].view(np.uint32)), (count, step0)
+    eng.close()
+
+
+@COEFFS
+@DRAG
+def test_one_launch_equals_single_steps_and_chunks(coeff, implicit, pop, native_built):
+    n = 321
+    eng = _engine(n, pop["params"][coeff], coeff)
+    eng.set_seabed(BED)
+    for tps in (1, 2):
+        ens = seh.ensemble(64, n, tps)
+        _water(eng, ens)
+        deep = _everything(eng, "ens", pop, n, 1, 5, implicit)
+        _water(eng, _fd(ens, H))
+        fraction, every_tile = sdr.differs(_from(_everything(eng, "fd", pop, n, 1, 5, implicit)["state"], n), _from(deep["state"], n), n)
+        assert fraction >= 0.75 and every_tile, (tps, fraction, every_tile)
+        for step0 in (0, 10 ** 6):
+            whole = _everything(eng, "fd", pop, n, 7, step0, implicit)
+            for chunks in ([1] * 7, [2, 5]):
+                parts = _everything(eng, "fd", pop, n, 7, step0, implicit, chunks=chunks)
+                assert _equal(parts, whole, n) is None, (tps, step0, chunks, _equal(parts, whole, n))
+            assert (stx.unpack(whole["record"].cpu().numpy(), n)["n"] == 7).all()
+    eng.close()
+
+
+# ---- 3. the sample against fp64 ------------------------------------------------------------------------------------------------------------
+def test_sample_against_fp64_cosh_and_sinh(pop, native_built):
+    st = sdr.population()
+    n = len(st)
+    full = sdr.designed_sea()
+    worst, missed = {"eta": 0.0, "u": 0.0}, np.inf
+    eng = _engine(n, pop["params"]["f32"], "f32")
+    state = _tiled(st)
+    for count in (9, 10, 11, 63, 64):
+        sea = sdr.truncated(full, count)
+        _water(eng, sea, n)
+        for step in sdr.VIEW_STEPS:
+            got = _from(eng.sea_finite_depth_sample(state, n, step, DT), n)
+            assert np.isfinite(got).all()
+            for k, v in sdr.view_errors(sea, st, step, DT, got[:, 0], got[:, 1:4]).items():
+                worst[k] = max(worst[k], v)
+            missed = min(missed, sdr.view_errors(sea, st, step, DT, got[:, 0], got[:, 1:4], without_g=True)["u"])
+            # the water below the bed is the bed's, and its vertical velocity the current's
+            if step == 0 and count == 64:
+                lower = st.copy()
+                lower[:, 2] = np.where(st[:, 2] <= -H - 1.0, st[:, 2] - 50.0, st[:, 2])
+                again = _from(eng.sea_finite_depth_sample(_tiled(lower), n, step, DT), n)
+                assert np.array_equal(again.view(np.uint32), got.view(np.uint32)) and (st[:, 2] <= -H - 1.0).sum() >= 10
+                # (E - G vanishes there in exact arithmetic; in fp32 gl_j and kl2_j h are rounded apart, so u_z is the current's to the bound)
+                below = st[:, 2] <= -H - 1.0
+                assert (np.abs(got[below, 3].astype(np.float64) - sea.current[2]) <= sdr.DEPTH_VIEW_BOUND * 2.0 ** -24 * sdr.scales(sea, H)[1][2]).all()
+    eng.close()
+    print("[depth view] largest error in units of 2^-24 of the scale: " + "  ".join(f"{k} {v:.2f}" for k, v in worst.items())
+          + f"  (bound {sdr.DEPTH_VIEW_BOUND:g}); without the G term the reference misses by {missed:.3g}")
+    assert max(worst.values()) <= sdr.DEPTH_VIEW_BOUND, worst
+    assert missed > 10 * sdr.DEPTH_VIEW_BOUND
+
+
+# ---- 4. value rules --------------------------------------------------------------------------------------------------------------------------
+def test_a_body_at_infinity_or_nan_has_finite_water_and_poisons_nobody(pop, native_built):
+    n = 321
+    eng = _engine(n, pop["params"]["f32"], "f32")
+    ens = _fd(seh.ensemble(64, n, 1), H)
+    _water(eng, ens)
+    bodies = vc.poisoned_bodies(n)
+    rows = [r for r in vc.POISONS if r[0] in ("nan_z", "+inf_z", "-inf_z")]
+    assert len(rows) == 3
+    st = pop["st"][:n].copy()
+    clean = _from(eng.sea_finite_depth_sample(_tiled(st), n, 7, DT), n)
+    cur, old = _buffers(pop["st"], pop["pv"], n)
+    clean_state = _from(seh.launch(eng, cur, old, n, 2, step0=7, entry="fd")[0], n)
+    for name, _, cols, value in rows:
+        bad = st.copy()
+        bad[np.ix_(bodies, cols)] = value
+        got = _from(eng.sea_finite_depth_sample(_tiled(bad), n, 7, DT), n)
+        assert np.isfinite(got).all(), name
+        others = np.setdiff1d(np.arange(n), bodies)
+        assert np.array_equal(got[others].view(np.uint32), clean[others].view(np.uint32)), name
+        assert np.array_equal(got[bodies, 0].view(np.uint32), clean[bodies, 0].view(np.uint32)), name            # the surface does not ask for p_z
+        cur, old = _buffers(bad, pop["pv"], n)
+        stepped = _from(seh.launch(eng, cur, old, n, 2, step0=7, entry="fd")[0], n)
+        assert np.array_equal(stepped[others].view(np.uint32), clean_state[others].view(np.uint32)), name
+    eng.close()
+
+
+# ---- 5. refusals -------------------------------------------------------------------------------------------------------------------------------
+def _raw_set(eng, members, count=None, bodies_per_sea=64, depth=H):
+    arr, keep = _c_members(members)
+    return eng._lib.hydro_set_sea_finite_depth(eng._h, arr, len(members) if count is None else count, bodies_per_sea, depth)
+
+
+def test_refusals_launch_nothing_write_nothing_and_keep_the_previous_sea(pop, native_built):
+    n = 321
+    tiles = (n + 63) // 64
+    eng = _engine(n, pop["params"]["f32"], "f32")
+    last = lambda: eng._lib.hydro_last_error(eng._h).decode()  # noqa: E731
+    members = seh.members(11)
+    st, pv = pop["st"], pop["pv"]
+    lev = _levels_for(st, n)
+    state, prev, lv = _guarded(st[:n], S_IN), _guarded(pv[:n], S_PV), _guarded(lev, sx.S_LV)
+    a, c17 = _guarded(pop["applied"][:n], S_A), _guarded(pop["ctl"][:n], S_C)
+    m27, net = _guarded(pop["spread"][:n, 0:27], S_SP3), _guarded(net_for(pop["net"], n, 2), S_T2)
+    fresh = lambda stride: torch.full((tiles * stride,), NAN, device=DEV)  # noqa: E731
+    e8, p2, out, pvo, record, water = fresh(S_E), fresh(S_P2), fresh(S_OUT), fresh(S_PVO), fresh(sx.S_ST), fresh(S_W)
+    everything = dict(applied=a, s_applied=S_A, control=c17, s_control=S_C, mooring=m27, s_mooring=S_SP3, layers=3, extremes=e8, s_extremes=S_E,
+                      tether=net, s_tether=S_T2, net_layers=2, peaks=p2, s_peaks=S_P2, statistics=record, s_statistics=sx.S_ST, levels=lv, s_levels=sx.S_LV)
+
+    def step(n_=n, **kw):
+        args = dict(everything)
+        args.update(kw)
+        return seh.raw_ens(eng, n_, state, prev, out, pvo, entry="fd", **args)
+
+    def sample(n_=n):
+        return eng._lib.hydro_sea_finite_depth_sample(eng._h, n_, state.data_ptr(), S_IN, 3, DT, water.data_ptr(), S_W, eng._stream(None))
+    # the sample without a finite-depth sea
+    assert sample() == E_STATE and "hydro_set_sea_finite_depth" in last()
+    # the setter's own refusals, with nothing set before: nothing becomes set
+    assert _raw_set(eng, members, count=0) == E_ARG and "count" in last()
+    assert _raw_set(eng, members, count=1025) == E_ARG and "count" in last()
+    for bad in (0, 63, 96):
+        assert _raw_set(eng, members, bodies_per_sea=bad) == E_ARG and "bodies_per_sea" in last(), bad
+    for bad in (0.0, -9.0, float("nan"), float("inf"), -float("inf"), 1e39, 1e-60):
+        assert _raw_set(eng, members, depth=bad) == E_ARG and "depth" in last(), bad
+    # a depth at which a scaled constant leaves fp32 range: kappa h = 1e-36 under an amplitude of 1 000 m
+    tiny = SeaSpectrum().add_wave(1000.0, 1e-30, 0.0, 1.0, 0.0)
+    assert _raw_set(eng, [tiny], depth=1e-6) == E_ARG and "member 0" in last() and "fp32 range" in last()
+    assert _raw_set(eng, [members[0], seh.members(64)[1]]) == E_ARG and "same number of waves" in last()
+    assert sample() == E_STATE
+    # six members at one tile each; then a bad component in member 2, and every other refusal: the previous sea stays in force
+    good = _fd(seh.ensemble(11, n, 1), H)
+    eng.set_sea_finite_depth(good)
+    before = eng.sea_finite_depth_sample(_tiled(st[:n]), n, 3, DT).clone()
+    bad = seh.members(11)
+    bad[2] = SeaSpectrum(bad[2].current)
+    bad[2].waves = list(members[2].waves[:10]) + [(float("nan"), 0.1, 0.0, 1.0, 0.0)]
+    assert _raw_set(eng, bad) == E_ARG and "member 2" in last() and "non-finite" in last()
+    bad[2].waves[10] = (-0.1, 0.1, 0.0, 1.0, 0.0)
+    assert _raw_set(eng, bad) == E_ARG and "member 2" in last() and "negative amplitude" in last()
+    arr, keep = _c_members(members)
+    arr[4].wave = None                                             # a NULL wave with waves > 0
+    assert eng._lib.hydro_set_sea_finite_depth(eng._h, arr, 6, 64, H) == E_ARG and "null wave" in last()
+    assert _raw_set(eng, members, depth=0.0) == E_ARG and _raw_set(eng, members, bodies_per_sea=96) == E_ARG and _raw_set(eng, members, count=0) == E_ARG
+    assert _raw_set(eng, [tiny], depth=1e-6) == E_ARG
+    assert _same_bits(eng.sea_finite_depth_sample(_tiled(st[:n]), n, 3, DT), before)
+    # the four-way exclusion, each message naming the call that clears the other kind; clearing with NULL is always allowed
+    spec, sea = members[0], SeaState((0.3, 0.0, 0.0)).add_wave(0.1, 0.2, 0.0, 1.4)
+    c_spec, keep_spec = _c_members([spec])
+    c_sea = nat.Sea()
+    c_sea.current[:] = [0.3, 0.0, 0.0]
+    clear_fd = "hydro_set_sea_finite_depth(h, NULL, 0, 0, 0)"
+    assert eng._lib.hydro_set_sea_spectrum(eng._h, ctypes.byref(c_spec[0])) == E_STATE and clear_fd in last()
+    assert eng._lib.hydro_set_sea(eng._h, ctypes.byref(c_sea)) == E_STATE and clear_fd in last()
+    assert eng._lib.hydro_set_sea_ensemble(eng._h, c_spec, 1, 64) == E_STATE and clear_fd in last()
+    assert _same_bits(eng.sea_finite_depth_sample(_tiled(st[:n]), n, 3, DT), before)
+    assert eng._lib.hydro_set_sea(eng._h, None) == 0 and eng._lib.hydro_set_sea_spectrum(eng._h, None) == 0       # clearing what is not set
+    assert eng._lib.hydro_set_sea_ensemble(eng._h, None, 0, 0) == 0
+    eng.set_sea_finite_depth(None)
+    eng.set_sea_spectrum(spec)
+    assert _raw_set(eng, members) == E_STATE and "hydro_set_sea_spectrum(h, NULL)" in last()
+    assert eng._lib.hydro_set_sea_finite_depth(eng._h, None, 0, 0, 0.0) == 0
+    eng.set_sea_spectrum(None)
+    eng.set_sea(sea)
+    assert _raw_set(eng, members) == E_STATE and "hydro_set_sea(h, NULL)" in last()
+    eng.set_sea(None)
+    eng.set_sea_ensemble(seh.ensemble(11, n, 1))
+    assert _raw_set(eng, members) == E_STATE and "hydro_set_sea_ensemble(h, NULL, 0, 0)" in last()
+    assert sample() == E_STATE
+    eng.set_sea_ensemble(None)
+    # n needing more members than count: five members at one tile each do not cover six tiles
+    eng.set_sea_finite_depth(SeaEnsemble([sdr.with_depth(m, H) for m in members[:5]], 64))
+    assert step() == (E_ARG, -7) and "more members" in last()
+    assert step(statistics=None, levels=None) == (E_ARG, -7) and "more members" in last()
+    assert sample() == E_ARG and "more members" in last()
+    # it comes last: the _ens entry's refusals are reported in front of it
+    assert step(channels=(7, 0)) == (E_ARG, -7) and "channel" in last()
+    assert step(levels=None) == (E_ARG, -7) and "levels" in last()
+    assert step(step0=-1) == (E_ARG, -7) and "step0" in last()
+    torch.cuda.synchronize()
+    assert all(torch.isnan(x).all() for x in (out, pvo, e8, p2, record, water))
+    # the legal launches next to them: 320 bodies are five tiles; and three members of two tiles cover 321
+    e8, p2 = _guarded(Extremes.empty(n), S_E), _guarded(np.zeros((n, 2), np.float32), S_P2)
+    assert eng._lib.hydro_statistics_reset(eng._h, n, record.data_ptr(), sx.S_ST, eng._stream(None)) == 0
+    inputs = (state, prev, lv, a, c17, m27, net)
+    was = [b.cpu().numpy() for b in inputs]
+    assert step(n_=320, steps=3, extremes=e8, peaks=p2) == (0, 0) and sample(320) == 0
+    eng.set_sea_finite_depth(SeaEnsemble([sdr.with_depth(m, H) for m in members[:3]], 128))
+    assert step(steps=3, extremes=e8, peaks=p2) == (0, 0) and sample() == 0
+    torch.cuda.synchronize()
+    # guard bands round every output and the padding lanes
+    got, rest = sx.unguard(record.cpu().numpy().view(np.uint32), n)
+    assert (got["n"][:320] == 6).all() and got["n"][320] == 3 and (rest == sx.NAN_BITS).all()
+    for buf, fields, stride in ((out, 13, S_OUT), (pvo, 6, S_PVO), (e8, 8, S_E), (p2, 2, S_P2), (water, 4, S_W)):
+        bodies, rest = _unguard(buf, n, fields, stride)
+        assert np.isnan(rest).all(), "a sentinel of an output was overwritten"
+    assert np.isfinite(_unguard(water, n, 4, S_W)[0]).all()
+    assert all(_untouched(b, w) for b, w in zip(inputs, was))
+    eng.close()
+
+
+# ---- 6. the Python paths --------------------------------------------------------------------------------------------------------------------------
+def test_sim_resident_equals_eager_and_the_depth_changes_the_run(native_built):
+    """300 moored buoys under a JONSWAP sea built for h = 9 m (the dispersion relation solved): resident, chunked and eager runs
+    agree in state, extremes and statistics, as a lone spectrum and as an ensemble of three seeds; the deep sea of the same bins
+    gives another run."""
+    sc = _buoy_field(300)
+    kw = dict(spread="cos2", current=(0.4, 0.0, 0.0), g=sc.g)
+    lone = jonswap(1.5, 7.0, 25.0, seed=3, depth=H, **kw)
+    three = SeaEnsemble([jonswap(1.5, 7.0, 25.0, seed=s, depth=H, **kw) for s in (3, 4, 5)], 128)
+    for sea in (lone, three):
+        records, finals, extremes = {}, {}, {}
+        for name, go in (("eager", lambda s: s.run_eager(20)), ("resident", lambda s: s.run_resident(20)), ("chunks", lambda s: s.run_resident(20, chunk=7))):
+            sim = _moored_sim(sc, sea)
+            assert sim.sea is sea and sim.engine.finite_depth == H and sim.engine.ensemble_count is None and sim.engine.spectrum_waves is None
+            ext, stat = sim.track_extremes(), sim.track_statistics()
+            go(sim)
+            records[name], finals[name], extremes[name] = stat.record(), sim.state(), ext.bodies()
+            if name == "resident":
+                assert (stat.count() == 20).all() and np.isfinite(finals[name]).all()
+            sim.close()
+        for k in ("resident", "chunks"):
+            assert sx.same_record(records["eager"], records[k], nan_equal=False), k
+            assert np.array_equal(finals["eager"], finals[k]) and np.array_equal(extremes["eager"], extremes[k])
+        if sea is lone:
+            lone_final = finals["resident"]
+        else:
+            assert np.array_equal(finals["resident"][:128], lone_final[:128])        # member 0 IS the lone spectrum, bit for bit
+            assert not np.array_equal(finals["resident"][128:256], lone_final[128:256])
+    deep = _moored_sim(sc, jonswap(1.5, 7.0, 25.0, seed=3, **kw))
+    deep.run_resident(20)
+    assert deep.engine.finite_depth is None and not np.array_equal(deep.state(), lone_final)
+    deep.set_sea(lone)                                             # the kinds swap in the one slot
+    assert deep.engine.finite_depth == H and deep.engine.spectrum_waves is None
+    deep.clear_sea()
+    assert deep.sea is None and deep.engine.finite_depth is None
+    deep.close()
+
+
+def test_sim_replays_a_current_only_table_and_refuses_components(native_built):
+    sc = _buoy_field(300)
+    currents = SeaEnsemble([SeaSpectrum((0.4, -0.1, 0.0), H), SeaSpectrum((-0.2, 0.3, 0.0), H), SeaSpectrum((0.0, 0.0, 0.0), H)], 128)
+    g, r = _moored_sim(sc, currents), _moored_sim(sc, currents)
+    gs, rs = g.track_statistics(("x", "tension")), r.track_statistics(("x", "tension"))
+    g.run(64, graph_steps=32)
+    r.run_resident(64)
+    assert g._graph is not None and sx.same_record(gs.record(), rs.record(), nan_equal=False) and (gs.count() == 64).all()
+    assert np.array_equal(g.state(), r.state())
+    assert not np.array_equal(g.state()[0:44, 0:2] - sc.state[0:44, 0:2], g.state()[256:300, 0:2] - sc.state[256:300, 0:2])       # the currents differ
+    waves = _moored_sim(sc, jonswap(1.0, 7.0, 0.0, seed=1, depth=H, g=sc.g))
+    with pytest.raises(ValueError, match="graph replays"):
+        waves.run(64, graph_steps=32)
+    for s in (g, r, waves):
+        s.close()
+
+
+def test_shallow_water_design_loads_example(native_built):
+    res = subprocess.run([sys.executable, os.path.join(REPO, "examples", "shallow_water_design_loads.py"), "--steps", "240"], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-2000:]
+    print(res.stdout)
+    rows = re.findall(r"peak tension +([\d.]+) N deep +([\d.]+) N at h = 20 m .*sigma +([\d.]+) N deep +([\d.]+) N at h = 20 m", res.stdout)
+    assert len(rows) == 9 and all(float(x) > 0.0 for row in rows for x in row[:2])
+    assert any(row[0] != row[1] for row in rows) and "h = 20 m" in res.stdout
