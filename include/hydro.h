@@ -1131,7 +1131,8 @@ int hydro_step_fused_tiled_multi_spread(hydro_t *h, int64_t n, const float *stat
  * first: hydro_set_sea_spectrum(h, NULL)); what was set stays in force.  Clearing with NULL is always allowed.
  * ONLY hydro_step_fused_tiled_multi_irr and hydro_sea_spectrum_sample know the spectrum: EVERY OTHER ENTRY IGNORES IT and steps
  * through the water it stepped through before - the sea of hydro_set_sea where it knows one, still water otherwise - as the
- * entries below hydro_step_fused_tiled_multi_bed ignore the bed.
+ * entries below hydro_step_fused_tiled_multi_bed ignore the bed.  (Besides them the two open-loop entries
+ * hydro_step_wrench_tiled_irr and hydro_step_wrench_aos_irr know the spectrum: "Irregular sea in the open-loop steps" below.)
  *
  * hydro_sea_spectrum_sample: the signature and the rules of hydro_sea_sample, read against the spectrum: the [eta, u_x, u_y, u_z]
  * a step of hydro_step_fused_tiled_multi_irr that starts from `state` at step index `step_index` uses.  HYDRO_E_STATE without
@@ -1280,7 +1281,9 @@ int hydro_step_fused_tiled_multi_stat(hydro_t *h, int64_t n, const float *state,
  * hydro_set_sea_ensemble (non-NULL) returns HYDRO_E_STATE while another kind is set, and its message names the call that clears
  * that kind (an ensemble: hydro_set_sea_ensemble(h, NULL, 0, 0)); what was set stays in force.  Clearing with NULL is always
  * allowed.  ONLY hydro_step_fused_tiled_multi_ens and hydro_sea_ensemble_sample know the ensemble: EVERY OTHER ENTRY IGNORES IT,
- * as every entry but hydro_step_fused_tiled_multi_irr and _stat ignores a spectrum.
+ * as every entry but hydro_step_fused_tiled_multi_irr and _stat ignores a spectrum.  (Besides them the two open-loop entries
+ * hydro_step_wrench_tiled_irr and hydro_step_wrench_aos_irr know a spectrum, an ensemble and a finite-depth sea: "Irregular sea
+ * in the open-loop steps" below.)
  *
  * hydro_sea_ensemble_sample: the signature and the rules of hydro_sea_spectrum_sample, each body read against its member.
  * HYDRO_E_STATE without an ensemble; HYDRO_E_ARG, last, if n needs more members than `count`.
@@ -1356,7 +1359,8 @@ int hydro_step_fused_tiled_multi_ens(hydro_t *h, int64_t n, const float *state, 
  * IT IS THE FOURTH KIND OF SEA: it and a sea, a spectrum and an ensemble exclude each other at set time - each of the four setters
  * (non-NULL) returns HYDRO_E_STATE while another kind is set, and its message names the call that clears that kind (this one:
  * hydro_set_sea_finite_depth(h, NULL, 0, 0, 0)); what was set stays in force.  ONLY hydro_step_fused_tiled_multi_fd and
- * hydro_sea_finite_depth_sample know it: EVERY OTHER ENTRY IGNORES A FINITE-DEPTH SEA.
+ * hydro_sea_finite_depth_sample know it: EVERY OTHER ENTRY IGNORES A FINITE-DEPTH SEA.  (Besides them the two open-loop entries
+ * hydro_step_wrench_tiled_irr and hydro_step_wrench_aos_irr: "Irregular sea in the open-loop steps" below.)
  *
  * hydro_sea_finite_depth_sample: the signature and the rules of hydro_sea_ensemble_sample.  HYDRO_E_STATE without a finite-depth
  * sea; HYDRO_E_ARG, last, if n needs more members than `count`.
@@ -1395,6 +1399,47 @@ int hydro_step_fused_tiled_multi_fd(hydro_t *h, int64_t n, const float *state, i
                                     void *statistics, int64_t statistics_tile_stride,
                                     const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
                                     int64_t step0, void *stream);
+
+/* Irregular sea in the open-loop steps: the spectrum, the ensemble and the finite-depth sea for the caller who integrates - a
+ * simulator behind the plugin, or an integrator of one's own around hydro_step_wrench_tiled.  Two entries, each with exactly the
+ * prototype of its _sea sibling ("Sea state, open loop"), `double time` in front of `stream`:
+ *     hydro_step_wrench_tiled_irr = hydro_step_wrench_tiled_sea    hydro_step_wrench_aos_irr = hydro_step_wrench_aos_sea
+ * WHICH WATER.  The four kinds of sea exclude each other at set time, so the engine holds at most one, and the step goes through it:
+ *   a finite-depth sea : "Finite-depth sea"'s WATER AT A BODY; the bodies of block m step through member m (tile T through
+ *                        member T / tiles_per_sea), as in hydro_step_fused_tiled_multi_fd
+ *   an ensemble        : "Sea spectrum"'s WATER AT A BODY read against the body's member, as in hydro_step_fused_tiled_multi_ens
+ *   a lone spectrum    : "Sea spectrum"'s WATER AT A BODY - in the ensemble's kernels, as an ensemble of one member
+ *   an 8-wave sea      : the launch and its bits are those of the _sea sibling with the same arguments
+ *   no sea             : the launch and its bits are those of the parent entry (`time` is validated all the same)
+ * MODEL.  As in "Sea state, open loop", with ONE change to the stated WATER AT A BODY: t = time, in seconds, an fp64 value taken
+ * as given, replaces t = (step0 + k) * dt.  The wrench is that of the state with p_z - eta and v - u and of the previous velocity
+ * with pv[0:3] - u: fp32 subtractions with the same u.
+ * IDENTITY.  (double)1 * time == time exactly, so hydro_sea_spectrum_sample, hydro_sea_ensemble_sample and
+ * hydro_sea_finite_depth_sample with (step_index = 1, dt = time) write exactly the [eta, u] these entries use at time > 0; at
+ * time == 0 it is step_index = 0 (with any dt > 0).  A step is therefore, bit for bit, the parent entry on the relative state
+ * built from that sample; and one explicit step of hydro_step_fused_tiled_multi_fd at step0 (no option set) is this entry at
+ * time = step0 * dt followed by hydro_integrate_tiled of the true state.
+ * PREVIOUS VELOCITY.  "Sea state, open loop"'s rule: the engine-owned previous velocity receives the TRUE velocity, never the
+ * relative one; with a caller-owned `prev` nothing is written but the wrench.
+ * A spectrum with no current and no components (or components of amplitude 0) gives the parent's bits, sign of zero included; a
+ * spectrum of up to HYDRO_SEA_WAVES_MAX components gives the bits of the _sea sibling under the same components set with
+ * hydro_set_sea; a finite-depth sea in deep water ("DEEP WATER" above) gives the ensemble's.
+ * REFUSALS.  HYDRO_E_ARG for a non-finite time, time < 0 or time > 2^52, first; after that the parent's refusals in the parent's
+ * order; then, LAST and with an ensemble or a finite-depth sea only, ceil(tiles(n) / tiles_per_sea) > count with the message of
+ * hydro_step_fused_tiled_multi_ens (_fd) - all before anything is launched or written.  Asynchronous, no allocation, no
+ * synchronisation, safe to capture: a captured launch replays at the frozen `time` it was captured with, and reads the table at
+ * replay time with the number of components, the mapping and the depth of the moment it was captured.
+ * EVERY EXISTING ENTRY BEHAVES AS BEFORE, the _sea entries included: with a spectrum, an ensemble or a finite-depth sea set they
+ * issue the parent's launch.  Kernels of their own beside the _sea kernels (256-thread blocks whatever hydro_set_tuning's
+ * block_threads says).
+ * NOT COVERED - these step through still water whatever is set: hydro_step_wrench_tiled_ke, hydro_step_wrench_tiled_batch, the
+ * plain-SoA hydro_step_wrench[_ext], and the component / calculator entries hydro_step_components[_aos].
+ * Cost and registers: DESIGN.md section 33.  New functionality; the reference's water does not move. */
+int hydro_step_wrench_tiled_irr(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                const float *prev, int64_t prev_tile_stride, double dt,
+                                float *wrench, int64_t wrench_tile_stride, double time, void *stream);
+int hydro_step_wrench_aos_irr(hydro_t *h, int64_t n, const float *positions, const float *orientations, int quat_xyzw,
+                              const float *velocities, double dt, float *forces, float *torques, double time, void *stream);
 
 /* Kernel-variant selection for tuning: bodies per lane (0 = default, 1, 2), threads per block
  * (0 = chosen by size, 128, 256), streaming accesses - non-temporal loads, write-through stores - (-1 = chosen by size, 0, 1), resident waves per

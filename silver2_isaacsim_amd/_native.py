@@ -130,6 +130,10 @@ SIGNATURES = {
                                             c_void_p, c_int64, c_double, c_void_p]),
     "hydro_step_wrench_aos_sea": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_double,
                                           c_void_p, c_void_p, c_double, c_void_p]),
+    "hydro_step_wrench_tiled_irr": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
+                                            c_void_p, c_int64, c_double, c_void_p]),
+    "hydro_step_wrench_aos_irr": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_double,
+                                          c_void_p, c_void_p, c_double, c_void_p]),
     "hydro_set_seabed": (c_int, [c_void_p, POINTER(Seabed)]),
     "hydro_seabed_wrench": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "hydro_step_fused_tiled_multi_bed": _multi(_REC, _APP, _CTL, _STEP0),

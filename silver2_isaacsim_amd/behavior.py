@@ -36,6 +36,7 @@ import torch
 
 from . import config as cfg
 from .engine import HydroEngine, HydroError
+from .sea import SeaEnsemble, SeaSpectrum
 
 log = logging.getLogger("silver2_isaacsim_amd")
 
@@ -130,7 +131,8 @@ class _AosStepper:
         return p
 
     def launch(self, dt: float, time: float | None = None) -> None:
-        """time None: `hydro_step_wrench_aos`, the call made without a sea; otherwise the `_sea` entry at `time` seconds."""
+        """time None: `hydro_step_wrench_aos`, the call made without a sea; otherwise the `_sea` entry at `time` seconds - the
+        `_irr` entry while the engine holds a spectrum or a finite-depth sea (the prepared step picks the one that matches)."""
         if time is None:
             self._step(dt)
         else:
@@ -140,6 +142,23 @@ class _AosStepper:
         p = self.accept(positions, orientations, velocities)
         self.launch(dt, time)
         return p
+
+
+def _sea_kind(sea) -> str | None:
+    """Which of an engine's kinds of sea `sea` is: "sea" (SeaState), "spectrum" (SeaSpectrum), "depth" (SeaSpectrum with a
+    depth), or None."""
+    if sea is None:
+        return None
+    if isinstance(sea, SeaSpectrum):
+        return "spectrum" if sea.depth is None else "depth"
+    return "sea"
+
+
+# how an engine is given each kind, and how it is cleared of it (the kinds exclude each other in the library)
+_SET_SEA = {"sea": lambda e, sea: e.set_sea(sea), "spectrum": lambda e, sea: e.set_sea_spectrum(sea),
+            "depth": lambda e, sea: e.set_sea_finite_depth(sea, n=e.capacity)}
+_CLEAR_SEA = {"sea": lambda e: e.set_sea(None), "spectrum": lambda e: e.set_sea_spectrum(None),
+              "depth": lambda e: e.set_sea_finite_depth(None)}
 
 
 class _SeaClock:
@@ -153,6 +172,7 @@ class _SeaClock:
         self.sea_time = 0.0
         self._sea_seen = 0                  # the registry's sea_version this unit's engine was last given (0: never any)
         self._sea_set = False
+        self._kind = None                   # the kind of sea the unit's engine holds (_sea_kind)
 
     def start(self) -> None:
         self.sea_time = 0.0
@@ -164,16 +184,22 @@ class _SeaClock:
         return now
 
     def new_engine(self) -> None:
-        self._sea_seen, self._sea_set = 0, False
+        self._sea_seen, self._sea_set, self._kind = 0, False, None
 
     def sea_for(self, engine, now: float) -> float | None:
-        """Bring `engine` up to the registry's sea if that changed (or the engine is new); `now` if a sea is set, else None."""
+        """Bring `engine` up to the registry's sea if that changed (or the engine is new); `now` if a sea is set, else None.
+        The step stream is drained, a sea of ANOTHER kind is cleared first (the library refuses one kind while another is
+        set), then the new one is set; the clock is not touched."""
         if self._sea_seen != REGISTRY.sea_version:
             sea = REGISTRY.sea
+            kind = _sea_kind(sea)
             if sea is not None or self._sea_set:
-                engine.sync()               # hydro_set_sea runs on the engine's own stream: earlier steps have to be done
-                engine.set_sea(sea)
-            self._sea_seen, self._sea_set = REGISTRY.sea_version, sea is not None
+                engine.sync()               # the setters run on the engine's own stream: earlier steps have to be done
+                if self._kind is not None and kind != self._kind:
+                    _CLEAR_SEA[self._kind](engine)
+                if kind is not None:
+                    _SET_SEA[kind](engine, sea)
+            self._sea_seen, self._sea_set, self._kind = REGISTRY.sea_version, sea is not None, kind
         return now if self._sea_set else None
 
 
@@ -330,15 +356,18 @@ class EngineRegistry:
 
     def __init__(self):
         self._groups: dict[tuple, _Group] = {}
-        # the scene's sea (sea.SeaState or None), scene-wide like rho and g; every stepping unit compares sea_version with
-        # the one its engine holds, once per step.  0: no sea has ever been set - the units make today's calls
+        # the scene's sea (sea.SeaState, sea.SeaSpectrum - with or without a depth - or None), scene-wide like rho and g; every
+        # stepping unit compares sea_version with the one its engine holds, once per step.  0: no sea has ever been set - the units make today's calls
         self.sea = None
         self.sea_version = 0
         self._sea_source = None             # "python" (set_sea) or "config" (the JSON's "sea" block)
 
     def set_sea(self, sea, source: str = "python") -> bool:
         """The sea of every engine the plugin owns, now and later; None clears it.  A sea from the JSON configuration
-        (source="config") yields to one set from Python, and only the first block found counts.  Returns whether it was taken."""
+        (source="config") yields to one set from Python, and only the first block found counts.  Returns whether it was taken.
+        A `sea.SeaEnsemble` is refused: its members belong to blocks of one engine's bodies, and a scene has one sea."""
+        if isinstance(sea, SeaEnsemble):
+            raise ValueError("a scene has one sea: a SeaEnsemble is for ClosedLoopSim and the engine calls (pass one of its members)")
         if source == "config" and self._sea_source is not None:
             return False
         self.sea, self._sea_source = sea, source
@@ -419,10 +448,11 @@ class HydrodynamicsBehavior:
 
     @staticmethod
     def set_sea(sea) -> None:
-        """The scene's moving water (sea.SeaState: a current and up to 8 regular waves; None clears it), scene-wide like the
-        water density and gravity: it applies to every engine the plugin owns - the groups', those of batched=False
-        behaviours, and engines built later - and may change between physics steps.  Every stepping unit evaluates it at its
-        own clock: the sum of the delta_time of its earlier physics-step callbacks since it started."""
+        """The scene's moving water - a sea.SeaState (a current and up to 8 regular waves), or a sea.SeaSpectrum (an irregular sea of
+        up to 64 components: sea.jonswap, sea.pierson_moskowitz; with `depth=` a finite-depth sea); None clears it; a
+        sea.SeaEnsemble is refused with a ValueError (a scene has one sea).  Scene-wide like the water density and gravity: it
+        applies to every engine the plugin owns - the groups', those of batched=False behaviours, and engines built later -
+        and may change between physics steps.  Every stepping unit evaluates it at its own clock: the sum of the delta_time of its earlier physics-step callbacks since it started."""
         REGISTRY.set_sea(sea)
 
     @property

@@ -102,7 +102,12 @@ def sea_from_config(data: Mapping[str, Any]):
     """The optional top-level "sea" block of the configuration file as a `sea.SeaState`, or None without one:
         {"current": [x, y, z], "waves": [{"height": m, "period": s, "heading_deg": deg, "phase": rad}, ...]}
     Both keys are optional; every wave is built by `SeaState.regular` (deep-water dispersion relation) with the file's gravity
-    (`globals.gravity`, default 9.81).  The reference reads `globals` and `parts` only and ignores the block.  Raises
+    (`globals.gravity`, default 9.81).  Instead of "waves" the block may carry an irregular sea, which gives a `sea.SeaSpectrum`:
+        {"current": [x, y, z], "spectrum": {"kind": "jonswap" | "pierson_moskowitz", "hs": m, "tp": s, "heading_deg": deg,
+                                            "gamma": 3.3, "components": 64, "seed": 0, "spread": "cos2", "depth": m}}
+    kind, hs, tp and heading_deg are required; gamma (JONSWAP only), components, seed, spread and depth are optional and go to
+    `sea.jonswap` / `sea.pierson_moskowitz` with the file's gravity and the block's current.  "waves" and "spectrum" together are
+    malformed.  The reference reads `globals` and `parts` only and ignores the block.  Raises
     ValueError / TypeError / KeyError on a malformed block - the plugin logs that and keeps going, like other JSON errors."""
     from .sea import SeaState
     block = data.get("sea")
@@ -110,10 +115,14 @@ def sea_from_config(data: Mapping[str, Any]):
         return None
     if not isinstance(block, Mapping):
         raise ValueError('"sea" must be an object')
-    unknown = set(block) - {"current", "waves"}
+    unknown = set(block) - {"current", "waves", "spectrum"}
     if unknown:
         raise ValueError(f'"sea": unknown keys {sorted(unknown)}')
     g = float(data.get("globals", {}).get("gravity", GLOBALS["gravity"]))
+    if "spectrum" in block:
+        if "waves" in block:
+            raise ValueError('"sea": "waves" and "spectrum" exclude each other')
+        return _spectrum_from_config(block["spectrum"], tuple(block.get("current", (0.0, 0.0, 0.0))), g)
     sea = SeaState(tuple(block.get("current", (0.0, 0.0, 0.0))))
     waves = block.get("waves", [])
     if not isinstance(waves, (list, tuple)):
@@ -126,6 +135,30 @@ def sea_from_config(data: Mapping[str, Any]):
                                float(w.get("phase", 0.0)), g=g)
         sea.add_wave(*one.waves[0])
     return sea
+
+
+def _spectrum_from_config(spec, current, g: float):
+    """The "spectrum" object of the "sea" block as a `sea.SeaSpectrum` (see `sea_from_config`)."""
+    from . import sea
+    if not isinstance(spec, Mapping):
+        raise ValueError('"sea.spectrum" must be an object')
+    unknown = set(spec) - {"kind", "hs", "tp", "heading_deg", "gamma", "components", "seed", "spread", "depth"}
+    if unknown:
+        raise ValueError(f'"sea.spectrum": unknown keys {sorted(unknown)}')
+    kinds = {"jonswap": sea.jonswap, "pierson_moskowitz": sea.pierson_moskowitz}
+    if spec["kind"] not in kinds:
+        raise ValueError(f'"sea.spectrum.kind" must be one of {sorted(kinds)}')
+    if len(current) != 3:
+        raise ValueError('"sea.current" must have three components')
+    kw = {"current": tuple(float(x) for x in current), "g": g}
+    if "gamma" in spec:
+        if spec["kind"] != "jonswap":
+            raise ValueError('"sea.spectrum.gamma" belongs to kind "jonswap"')
+        kw["gamma"] = float(spec["gamma"])
+    for key, conv in (("components", int), ("seed", int), ("spread", str), ("depth", float)):
+        if key in spec:
+            kw[key] = conv(spec[key])
+    return kinds[spec["kind"]](float(spec["hs"]), float(spec["tp"]), float(spec["heading_deg"]), **kw)
 
 
 def match_part(prim_name: str, parts: Mapping[str, Any]) -> str | None:

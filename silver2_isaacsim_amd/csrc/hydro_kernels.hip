@@ -2885,6 +2885,92 @@ __global__ void __launch_bounds__(kBlock) depth_sample_kernel(const float* st, u
     store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
 }
 
+// --------------------------------------------------------------------------
+// IRREGULAR and FINITE-DEPTH seas in the OPEN-LOOP steps (hydro_step_wrench_tiled_irr, hydro_step_wrench_aos_irr): the two
+// open-loop sea kernels over again with spectrum_water or depth_water (DEPTH) for the water, against the table of the member
+// the wave's tile steps through.  New kernels beside wrench_tiled_sea_kernel and wrench_aos_sea_kernel, which stay as they
+// are; the host launches these only while a spectrum, an ensemble or a finite-depth sea is set.
+//   time   : as in the _sea kernels, (step, sea_dt) = (1, time) or (0, time): spectrum_water and depth_water stay the only
+//            implementations of the water, and the three *_sample kernels give the same bits
+//   member : ensemble_member of the wave's tile; a lone spectrum is an ensemble of one, launched with a tiles_per_sea that no
+//            tile index reaches (member 0 for every wave)
+//   table  : stays in the constant address space: scalar loads in every trip of the component loops, nothing kept per component
+//   prev   : the _sea kernels' rule - the TRUE velocity goes to the engine's record before the relative values are formed
+// --------------------------------------------------------------------------
+// (Depth: HYDRO_FD_PARAMS' one float with DEPTH, nothing without - the deep kernels take no depth argument)
+template <bool DEPTH, typename... Depth>
+__device__ __forceinline__ void irregular_relative(SpectrumTablePtr tab, uint32_t waves, int64_t step, double sea_dt,
+                                                   float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS], Depth... neg_depth)
+{
+    static_assert(sizeof...(Depth) == (DEPTH ? 1 : 0), "HYDRO_FD_PARAMS with DEPTH only");
+    float eta, u[3];
+    if constexpr (DEPTH) depth_water(tab, waves, step, sea_dt, s[0], s[1], s[2], neg_depth..., eta, u);
+    else spectrum_water(tab, waves, step, sea_dt, s[0], s[1], s[2], eta, u);
+    s[2] = s[2] - eta;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        s[7 + i] = s[7 + i] - u[i];
+        pv[i] = pv[i] - u[i];
+    }
+}
+
+// wrench_tiled_sea_kernel's frame and first arguments (the same 16 preloaded dwords), then the sea's, the ensemble's and, with DEPTH, the depth (HYDRO_FD_PARAMS).
+template <bool HALF, bool ENGINE_PREV, bool NT, bool WARP, bool DEPTH, typename... Depth>
+__global__ void __launch_bounds__(kBlock) HYDRO_TILED_OCC_ATTR wrench_tiled_irr_kernel(const float* k_st, const float* k_pv, const float* k_prm, float* k_out, float* k_pv_out,
+                                                             uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
+                                                             uint32_t n, int warp, double rho, double g, double inv_dt,
+                                                             HYDRO_SEA_PARAMS, HYDRO_ENS_PARAMS, Depth... neg_depth)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u;
+    const uint32_t first = tile * 64u;
+    const uint32_t left = n - __builtin_amdgcn_readfirstlane(n < first ? n : first);       // (scalar, see wrench_tiled_kernel)
+    if (lane >= left) return;
+    const uint32_t lane4 = lane * 4u;
+    float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass, f6[HYDRO_WRENCH_FIELDS];
+    load_tile_records<HALF, NT>(k_st + (size_t)tile * st_stride, k_pv + (size_t)tile * pv_stride, k_prm, tile, lane4, s, pv, d, c, mass);
+    if constexpr (ENGINE_PREV) store_record<HYDRO_PREV_FIELDS, NT>(k_pv_out + (size_t)tile * pvo_stride, lane4, s + 7);
+    const SpectrumTablePtr tab = ensemble_member((SpectrumTablePtr)sea_table, tile, HYDRO_ENS_ARGS);
+    irregular_relative<DEPTH>(tab, sea_waves, step0, sea_dt, s, pv, HYDRO_FD_ARGS...);
+    wrench_fields(body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP), f6);
+    store_record<HYDRO_WRENCH_FIELDS, NT>(k_out + (size_t)tile * out_stride, lane4, f6);
+}
+
+// wrench_aos_sea_kernel's frame and first arguments, then the sea's, the ensemble's and, with DEPTH, the depth (HYDRO_FD_PARAMS).
+template <bool HALF, bool NT, bool WARP, bool DEPTH, typename... Depth>
+__global__ void __launch_bounds__(kBlock) wrench_aos_irr_kernel(const float* k_pos, const float* k_quat, const float* k_vel, float* k_force, float* k_torque,
+                                                               float* k_pv, const float* k_prm, int quat_xyzw, uint32_t n,      // 16 dwords: preloaded
+                                                               int warp, double rho, double g, double inv_dt,
+                                                               HYDRO_SEA_PARAMS, HYDRO_ENS_PARAMS, Depth... neg_depth)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const size_t first = (size_t)tile * 64u;
+    const float* t_pos = k_pos + first * 3; const float* t_quat = k_quat + first * 4; const float* t_vel = k_vel + first * 6;
+    float s[HYDRO_STATE_FIELDS], pv[HYDRO_PREV_FIELDS], d[3], c[7], mass;
+    constexpr bool RNT = false;                              // (the simulator's rows: temporal, see wrench_aos_direct_kernel)
+    const f3_a4 p = ld_f3_a4<RNT>(t_pos, lane * 12u);
+    const f4_a16 q = ld_f4_a16<RNT>(t_quat, lane * 16u);
+    const f4_a8 v0 = ld_f4_a8<RNT>(t_vel, lane * 24u);
+    const f2_a8 v1 = ld_f2_a8<RNT>(t_vel, lane * 24u + 16u);
+    s[0] = p.x; s[1] = p.y; s[2] = p.z;
+    if (quat_xyzw) { s[3] = q.x; s[4] = q.y; s[5] = q.z; s[6] = q.w; }
+    else           { s[3] = q.y; s[4] = q.z; s[5] = q.w; s[6] = q.x; }
+    s[7] = v0.x; s[8] = v0.y; s[9] = v0.z; s[10] = v0.w; s[11] = v1.x; s[12] = v1.y;
+    float* t_pv = k_pv + (size_t)tile * (HYDRO_PREV_FIELDS * HYDRO_TILE);
+#pragma unroll
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) pv[f] = ldg<NT>(at<float>(t_pv, lane4, f * 256u));
+    load_param_record<HALF, NT>(k_prm, tile, lane4, d, c, mass);
+#pragma unroll
+    for (int f = 0; f < HYDRO_PREV_FIELDS; ++f) stg_aos<NT>(at<float>(t_pv, lane4, f * 256u), s[7 + f]);     // the TRUE velocity
+    const SpectrumTablePtr tab = ensemble_member((SpectrumTablePtr)sea_table, tile, HYDRO_ENS_ARGS);
+    irregular_relative<DEPTH>(tab, sea_waves, step0, sea_dt, s, pv, HYDRO_FD_ARGS...);
+    const hydro::Wrench w = body_wrench(s, pv, d, c, mass, rho, g, inv_dt, WARP);
+    f3_a4 fo, to;
+    fo.x = w.fx; fo.y = w.fy; fo.z = w.fz; to.x = w.tx; to.y = w.ty; to.z = w.tz;
+    st_f3_a4<NT>(k_force + first * 3, lane * 12u, fo);
+    st_f3_a4<NT>(k_torque + first * 3, lane * 12u, to);
+}
+
 // hydro_statistics_reset: the empty record - sums +0.0, words 0 - for the live lanes.
 __global__ void __launch_bounds__(kBlock) statistics_reset_kernel(void* stat, uint32_t stat_stride, uint32_t n)
 {
@@ -3624,13 +3710,45 @@ void launch_wrench_tiled_sea(hydro_engine* h, dim3 grid, dim3 blk, size_t lds, h
 void launch_wrench_aos_sea(hydro_engine* h, hipStream_t s, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
                            const float* velocities, double dt, float* forces, float* torques, double time);
 
+// The open-loop _irr entries (hydro_step_wrench_tiled_irr, hydro_step_wrench_aos_irr): the _sea entries, and the step goes
+// through whichever kind of sea the engine holds - the four exclude each other at set time.  What irregular_water finds:
+//   table != nullptr : a finite-depth sea (depth), an ensemble, or a lone spectrum as an ensemble of one - tiles_per_sea is then
+//                      2^32 - 1, which no tile index reaches, so ensemble_member gives member 0 to every wave
+//   table == nullptr : an 8-wave sea or none - the _sea entry's launch
+struct IrregularWater { const void* table = nullptr; uint32_t waves = 0, tiles_per_sea = 0; bool depth = false; float neg_depth = 0.0f; };
+// 0 and `w` filled, or the refusal of a launch whose LIVE tiles need more members than the table holds (_ens's and _fd's own)
+int irregular_water(hydro_engine* h, int64_t n, IrregularWater& w)
+{
+    const int64_t tiles = (n + HYDRO_TILE - 1) / HYDRO_TILE;
+    if (h->fd_waves >= 0) {
+        if ((tiles + h->fd_tiles_per_sea - 1) / h->fd_tiles_per_sea > h->fd_count)
+            return fail(h, HYDRO_E_ARG, "n needs more members than the finite-depth sea has (count * bodies_per_sea < n)");
+        w = IrregularWater{h->fd_table, (uint32_t)h->fd_waves, (uint32_t)h->fd_tiles_per_sea, true, h->fd_neg_depth};
+    } else if (h->ensemble_waves >= 0) {
+        if ((tiles + h->ensemble_tiles_per_sea - 1) / h->ensemble_tiles_per_sea > h->ensemble_count)
+            return fail(h, HYDRO_E_ARG, "n needs more members than the sea ensemble has (count * bodies_per_sea < n)");
+        w = IrregularWater{h->ensemble_table, (uint32_t)h->ensemble_waves, (uint32_t)h->ensemble_tiles_per_sea, false, 0.0f};
+    } else if (h->spectrum_waves >= 0) {
+        w = IrregularWater{h->spectrum_table, (uint32_t)h->spectrum_waves, 0xffffffffu, false, 0.0f};
+    }
+    return HYDRO_OK;
+}
+// The launches of the two _irr kernels: defined behind launch_wrench_aos_sea, for the same reason - 48 instantiations that
+// come behind every kernel the library had before them.
+void launch_wrench_tiled_irr(hydro_engine* h, dim3 grid, dim3 blk, size_t lds, hipStream_t s, const float* state, const float* pv,
+                             float* wrench, float* pv_out, uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
+                             int64_t n, double dt, bool own_prev, double time, const IrregularWater& w);
+void launch_wrench_aos_irr(hydro_engine* h, hipStream_t s, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                           const float* velocities, double dt, float* forces, float* torques, double time, const IrregularWater& w);
+
 // hydro_step_wrench_tiled, optionally sampling the kinetic energy of the state it reads (ke_out != nullptr)
 int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
                            const float* prev, int64_t prev_tile_stride, double dt,
                            float* wrench, int64_t wrench_tile_stride, int ke_rotational, double* ke_out, void* stream,
-                           const double* sea_time = nullptr)
+                           const double* sea_time = nullptr, bool irr_entry = false)
 {
     // sea_time: the _sea entry - the time is checked first, and the step goes through the sea if one is set
+    // irr_entry: the _irr entry - the _sea entry, and a spectrum, an ensemble or a finite-depth sea counts as well
     int rc = sea_time ? check_sea_time(h, *sea_time) : HYDRO_OK;
     if (rc) return rc;
     if ((rc = check_common(h, n))) return rc;
@@ -3646,10 +3764,12 @@ int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t st
     float* pv_out = own_prev ? h->prev_tiled : nullptr;
     const uint32_t pv_stride = own_prev ? HYDRO_PREV_FIELDS * HYDRO_TILE : (uint32_t)prev_tile_stride, pvo_stride = own_prev ? pv_stride : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    IrregularWater irr;                                                     // (the last refusal, before anything is written)
+    if (irr_entry && (rc = irregular_water(h, n, irr))) return rc;
     if (own_prev && (rc = prev_acquire(h, hydro_engine::kPrevTiled, n, s))) return rc;
     if (ke_out && (rc = ke_prepare(h, s))) return rc;
-    const bool sea = sea_time && h->sea_waves >= 0;
-    const int block = (h->block && !ke_out && !sea) ? h->block : 256;       // (the energy partials are one per 256 bodies; the sea kernel exists for 256 only)
+    const bool sea = (sea_time && h->sea_waves >= 0) || irr.table;
+    const int block = (h->block && !ke_out && !sea) ? h->block : 256;       // (the energy partials are one per 256 bodies; the sea kernels exist for 256 only)
     const dim3 grid(grid_for(n, block)), blk(block);
     // Occupancy shaping: the kernel uses no LDS, so a dynamic-LDS request is a pure residency cap
     // (160 KB per CU / blocks per CU).  Fewer resident waves = fewer DRAM streams in flight.
@@ -3662,7 +3782,9 @@ int step_wrench_tiled_impl(hydro_t* h, int64_t n, const float* state, int64_t st
     }
     // ke_out: the sampling variant - same body, same bits, plus one fp64 pair per block and the fixed-order final sum (same
     // launch).  It exists for 256-thread blocks only, which is what `block` is whenever it is asked for.
-    if (sea) launch_wrench_tiled_sea(h, grid, blk, lds, s, state, pv, wrench, pv_out, (uint32_t)state_tile_stride, pv_stride,
+    if (irr.table) launch_wrench_tiled_irr(h, grid, blk, lds, s, state, pv, wrench, pv_out, (uint32_t)state_tile_stride, pv_stride,
+                                           (uint32_t)wrench_tile_stride, pvo_stride, n, dt, own_prev, *sea_time, irr);
+    else if (sea) launch_wrench_tiled_sea(h, grid, blk, lds, s, state, pv, wrench, pv_out, (uint32_t)state_tile_stride, pv_stride,
                                      (uint32_t)wrench_tile_stride, pvo_stride, n, dt, own_prev, *sea_time);
     else dispatch_flags([&](auto BIG, auto HALF, auto WP, auto NT, auto KE, auto WARP) {
         if constexpr (BIG || !KE)
@@ -3698,6 +3820,13 @@ int hydro_step_wrench_tiled_sea(hydro_t* h, int64_t n, const float* state, int64
                                 float* wrench, int64_t wrench_tile_stride, double time, void* stream)
 {
     return step_wrench_tiled_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, wrench, wrench_tile_stride, 0, nullptr, stream, &time);
+}
+
+int hydro_step_wrench_tiled_irr(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                const float* prev, int64_t prev_tile_stride, double dt,
+                                float* wrench, int64_t wrench_tile_stride, double time, void* stream)
+{
+    return step_wrench_tiled_impl(h, n, state, state_tile_stride, prev, prev_tile_stride, dt, wrench, wrench_tile_stride, 0, nullptr, stream, &time, true);
 }
 
 int hydro_step_wrench_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -5086,9 +5215,11 @@ int hydro_repack(hydro_t* h, int64_t n, int fields, float* const soa[], float* t
 }  // extern "C"
 
 namespace {
-// hydro_step_wrench_aos; sea_time: the _sea entry - the time is checked first, and the step goes through the sea if one is set
+// hydro_step_wrench_aos; sea_time: the _sea entry - the time is checked first, and the step goes through the sea if one is set;
+// irr_entry: the _irr entry - the _sea entry, and a spectrum, an ensemble or a finite-depth sea counts as well
 int step_wrench_aos_impl(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
-                         const float* velocities, double dt, float* forces, float* torques, void* stream, const double* sea_time)
+                         const float* velocities, double dt, float* forces, float* torques, void* stream, const double* sea_time,
+                         bool irr_entry = false)
 {
     const float* orientations_wxyz = orientations;
     if (sea_time) { const int bad = check_sea_time(h, *sea_time); if (bad) return bad; }
@@ -5103,8 +5234,11 @@ int step_wrench_aos_impl(hydro_t* h, int64_t n, const float* positions, const fl
     if (n == 0) return HYDRO_OK;
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    IrregularWater irr;                                                     // (the last refusal, before anything is written)
+    if (irr_entry && (rc = irregular_water(h, n, irr))) return rc;
     if ((rc = prev_acquire(h, hydro_engine::kPrevTiled, n, s))) return rc;
-    if (sea_time && h->sea_waves >= 0) launch_wrench_aos_sea(h, s, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, *sea_time);
+    if (irr.table) launch_wrench_aos_irr(h, s, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, *sea_time, irr);
+    else if (sea_time && h->sea_waves >= 0) launch_wrench_aos_sea(h, s, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, *sea_time);
     else dispatch_flags([&](auto HALF, auto NT, auto WARP) {
         hipLaunchKernelGGL((wrench_aos_direct_kernel<HALF, NT, WARP>), dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
                            positions, orientations, velocities, forces, torques, h->prev_tiled, h->params_tiled, quat_xyzw ? 1 : 0, (uint32_t)n,
@@ -5127,6 +5261,12 @@ int hydro_step_wrench_aos_sea(hydro_t* h, int64_t n, const float* positions, con
                               const float* velocities, double dt, float* forces, float* torques, double time, void* stream)
 {
     return step_wrench_aos_impl(h, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, stream, &time);
+}
+
+int hydro_step_wrench_aos_irr(hydro_t* h, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                              const float* velocities, double dt, float* forces, float* torques, double time, void* stream)
+{
+    return step_wrench_aos_impl(h, n, positions, orientations, quat_xyzw, velocities, dt, forces, torques, stream, &time, true);
 }
 
 int hydro_step_components(hydro_t* h, int64_t n, const float* const state[HYDRO_STATE_FIELDS],
@@ -5432,5 +5572,38 @@ void launch_wrench_aos_sea(hydro_engine* h, hipStream_t s, int64_t n, const floa
                            h->semantics, h->rho, h->g, 1.0 / dt,
                            (const void*)h->sea_table, (uint32_t)h->sea_waves, sea_step(time), time);
     }, h->half_coeffs, streaming(h, n), is_warp(h));
+}
+
+void launch_wrench_tiled_irr(hydro_engine* h, dim3 grid, dim3 blk, size_t lds, hipStream_t s, const float* state, const float* pv,
+                             float* wrench, float* pv_out, uint32_t st_stride, uint32_t pv_stride, uint32_t out_stride, uint32_t pvo_stride,
+                             int64_t n, double dt, bool own_prev, double time, const IrregularWater& w)
+{
+    dispatch_flags([&](auto HALF, auto WP, auto NT, auto WARP, auto DEPTH) {
+        const auto launch = [&](auto kernel, auto... depth) {
+            hipLaunchKernelGGL(kernel, grid, blk, lds, s,
+                               state, pv, h->params_tiled, wrench, pv_out, st_stride, pv_stride, out_stride, pvo_stride,
+                               (uint32_t)n, h->semantics, h->rho, h->g, 1.0 / dt,
+                               w.table, w.waves, sea_step(time), time, w.tiles_per_sea, depth...);
+        };
+        // (the kernels take HYDRO_FD_PARAMS with DEPTH only: <..., true, float> has the depth as its last argument, <..., false> none)
+        if constexpr (DEPTH) launch(wrench_tiled_irr_kernel<HALF, WP, NT, WARP, true, float>, w.neg_depth);
+        else launch(wrench_tiled_irr_kernel<HALF, WP, NT, WARP, false>);
+    }, h->half_coeffs, own_prev, streaming(h, n), is_warp(h), w.depth);
+}
+
+void launch_wrench_aos_irr(hydro_engine* h, hipStream_t s, int64_t n, const float* positions, const float* orientations, int quat_xyzw,
+                           const float* velocities, double dt, float* forces, float* torques, double time, const IrregularWater& w)
+{
+    dispatch_flags([&](auto HALF, auto NT, auto WARP, auto DEPTH) {
+        const auto launch = [&](auto kernel, auto... depth) {
+            hipLaunchKernelGGL(kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s,
+                               positions, orientations, velocities, forces, torques, h->prev_tiled, h->params_tiled, quat_xyzw ? 1 : 0, (uint32_t)n,
+                               h->semantics, h->rho, h->g, 1.0 / dt,
+                               w.table, w.waves, sea_step(time), time, w.tiles_per_sea, depth...);
+        };
+        // (as above: <..., true, float> takes the depth, <..., false> does not)
+        if constexpr (DEPTH) launch(wrench_aos_irr_kernel<HALF, NT, WARP, true, float>, w.neg_depth);
+        else launch(wrench_aos_irr_kernel<HALF, NT, WARP, false>);
+    }, h->half_coeffs, streaming(h, n), is_warp(h), w.depth);
 }
 }  // namespace

@@ -230,9 +230,10 @@ class HydroEngine:
         if ke_out.dtype != torch.float64 or ke_out.device != self.device or ke_out.numel() < 2 or not ke_out.is_contiguous():
             raise ValueError(f"ke_out: expected a contiguous float64 tensor of 2 elements on {self.device}")
 
-    def _wrench_tiled_call(self, state, n, dt, out, prev, stream, ke_out, rotational, time=None):
-        """(name, args, out) of one `hydro_step_wrench_tiled[_ke | _sea]` launch: the buffers validated, `out` allocated when
-        None, the stream resolved now.  `time` (seconds) selects the `_sea` entry, which takes it in front of the stream."""
+    def _wrench_tiled_call(self, state, n, dt, out, prev, stream, ke_out, rotational, time=None, irr=False):
+        """(name, args, out) of one `hydro_step_wrench_tiled[_ke | _sea | _irr]` launch: the buffers validated, `out` allocated
+        when None, the stream resolved now.  `time` (seconds) selects the `_sea` entry - with `irr` its `_irr` sibling - which
+        takes it in front of the stream."""
         s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
         if out is None:
             out = self.alloc_tiled(nat.WRENCH_FIELDS, n)
@@ -242,7 +243,7 @@ class HydroEngine:
         if time is not None:
             if ke_out is not None:
                 raise ValueError("the sea entry does not sample the kinetic energy (ke_out must be None)")
-            return "hydro_step_wrench_tiled_sea", args + (float(time), self._stream(stream)), out
+            return "hydro_step_wrench_tiled_irr" if irr else "hydro_step_wrench_tiled_sea", args + (float(time), self._stream(stream)), out
         if ke_out is None:
             return "hydro_step_wrench_tiled", args + (self._stream(stream),), out
         self._check_ke_out(ke_out)                      # the variant that samples the kinetic energy of `state` on the way
@@ -271,6 +272,21 @@ class HydroEngine:
         self._check(getattr(self._lib, name)(*args))
         return out
 
+    def step_wrench_tiled_irr(self, state: torch.Tensor, n: int, dt: float, time: float, out: torch.Tensor | None = None,
+                              prev: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """`step_wrench_tiled_sea` through whichever sea the engine holds, at `time` seconds (hydro_step_wrench_tiled_irr): the
+        finite-depth sea of `set_sea_finite_depth`, the ensemble of `set_sea_ensemble` (block m of the bodies against member m),
+        the spectrum of `set_sea_spectrum`, or the sea of `set_sea`.  The engine-owned previous velocity (prev=None) receives
+        the TRUE velocity; a caller-owned `prev` is only read.  Without any sea the call is step_wrench_tiled."""
+        name, args, out = self._wrench_tiled_call(state, n, dt, out, prev, stream, None, True, time, irr=True)
+        self._check(getattr(self._lib, name)(*args))
+        return out
+
+    def holds_irregular_sea(self) -> bool:
+        """Whether the last seas set successfully through this object leave a spectrum, an ensemble or a finite-depth sea in
+        the engine: the prepared steps then issue the `_irr` entries for a `time`, the `_sea` entries otherwise."""
+        return self.spectrum_waves is not None or self.ensemble_count is not None or self.finite_depth is not None
+
     def prepare_step_wrench_tiled(self, state: torch.Tensor, n: int, dt: float, out: torch.Tensor | None = None,
                                   prev: torch.Tensor | None = None, stream=None, ke_out: torch.Tensor | None = None,
                                   rotational: bool = True):
@@ -279,14 +295,16 @@ class HydroEngine:
         `stream` is None).  For step loops over small scenes, where the per-call Python work (shape checks, ctypes
         conversions: ~10 us) exceeds the kernel (~3 us at 4 096 bodies): the prepared call costs ~4 us of host time.
         `step()` is that launch, argument for argument; `step(time)` is `step_wrench_tiled_sea` at `time` seconds on the
-        same buffers (not with ke_out).  The callable returns `out`; errors raise HydroError as usual."""
+        same buffers (not with ke_out) - `step_wrench_tiled_irr` while the engine holds a spectrum, an ensemble or a
+        finite-depth sea (`holds_irregular_sea`, asked at every step).  The callable returns `out`; errors raise HydroError as usual."""
         name, args, out = self._wrench_tiled_call(state, n, dt, out, prev, stream, ke_out, rotational)
         fn, args = getattr(self._lib, name), _prebuilt(name, args)
         keep = (state, prev, out, ke_out)               # the buffers must outlive the callable
         check = self._check
-        sea_fn, sea_args = None, None
+        sea_fn, irr_fn, sea_args = None, None, None
         if ke_out is None:                              # the same argument list with the time in front of the stream
-            sea_fn, sea_args = self._lib.hydro_step_wrench_tiled_sea, (args[:-1], args[-1])
+            sea_fn, irr_fn, sea_args = self._lib.hydro_step_wrench_tiled_sea, self._lib.hydro_step_wrench_tiled_irr, (args[:-1], args[-1])
+        irregular = self.holds_irregular_sea
 
         def step(time=None):
             if self._h is None:                         # engine closed: the captured handle is gone
@@ -296,7 +314,7 @@ class HydroEngine:
             elif sea_fn is None:
                 raise ValueError("the sea entry does not sample the kinetic energy (prepared with ke_out)")
             else:
-                rc = sea_fn(*sea_args[0], ctypes.c_double(time), sea_args[1])
+                rc = (irr_fn if irregular() else sea_fn)(*sea_args[0], ctypes.c_double(time), sea_args[1])
             if rc:
                 check(rc)
             return keep[2]
@@ -526,6 +544,16 @@ class HydroEngine:
         time = float(time)
         return self.sea_sample(state, n, *((1, time) if time > 0.0 else (0, 1.0)), out=out, stream=stream)
 
+    def irregular_sea_sample_at(self, state: torch.Tensor, n: int, time: float, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The water each body of the tiled `state` meets at `time` seconds in the spectrum, the ensemble or the finite-depth sea
+        the engine holds: exactly the [eta, u_x, u_y, u_z] that `step_wrench_tiled_irr` / `step_wrench_aos_irr` use at that time.
+        The matching `sea_finite_depth_sample`, `sea_ensemble_sample` or `sea_spectrum_sample` with (step_index, dt) = (1, time) -
+        (double)1 * time == time exactly - or (0, 1.0) at time 0 (include/hydro.h, "Irregular sea in the open-loop steps")."""
+        time = float(time)
+        sample = (self.sea_finite_depth_sample if self.finite_depth is not None
+                  else self.sea_ensemble_sample if self.ensemble_count is not None else self.sea_spectrum_sample)
+        return sample(state, n, *((1, time) if time > 0.0 else (0, 1.0)), out=out, stream=stream)
+
     def step_fused_tiled_multi_sea(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
                                    control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
                                    log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
@@ -546,7 +574,8 @@ class HydroEngine:
     def set_sea_spectrum(self, spectrum) -> None:
         """The scene's irregular sea (hydro_set_sea_spectrum; include/hydro.h, "Sea spectrum"): `spectrum` has `current` and
         `waves`, up to `_native.SPECTRUM_WAVES_MAX` rows (amplitude, kx, ky, omega, phase) - a `sea.SeaSpectrum`.  None clears it.
-        Only `step_fused_tiled_multi_irr` and `sea_spectrum_sample` see the spectrum.  A spectrum and the sea of `set_sea`
+        `step_fused_tiled_multi_irr` (and the rungs above it), `sea_spectrum_sample`, `step_wrench_tiled_irr` and
+        `step_wrench_aos_irr` see the spectrum.  A spectrum and the sea of `set_sea`
         exclude each other: the library refuses one while the other is set.  Synchronous, like `set_sea`."""
         if spectrum is None:
             self._check(self._lib.hydro_set_sea_spectrum(self._h, None))
@@ -641,7 +670,8 @@ class HydroEngine:
         """The scene's sea ensemble (hydro_set_sea_ensemble; include/hydro.h, "Sea ensemble"): `ensemble` has `members`, up to
         `_native.SEA_ENSEMBLE_MAX` spectra of equally many components (each with `current` and `waves`, as `set_sea_spectrum` takes
         them), and `bodies_per_sea`, a multiple of 64 - a `sea.SeaEnsemble`.  Bodies m * bodies_per_sea .. step through member m.
-        None clears it.  Only `step_fused_tiled_multi_ens` and `sea_ensemble_sample` see the ensemble; an ensemble, a spectrum and
+        None clears it.  `step_fused_tiled_multi_ens`, `sea_ensemble_sample`, `step_wrench_tiled_irr` and `step_wrench_aos_irr` see
+        the ensemble; an ensemble, a spectrum and
         the sea of `set_sea` exclude each other.  Synchronous, like `set_sea`."""
         if ensemble is None:
             self._check(self._lib.hydro_set_sea_ensemble(self._h, None, 0, 0))
@@ -705,9 +735,9 @@ class HydroEngine:
         """The scene's finite-depth sea (hydro_set_sea_finite_depth; include/hydro.h, "Finite-depth sea"): `sea` is a
         `sea.SeaEnsemble` with a `depth` - its members, its `bodies_per_sea` - or a `sea.SeaSpectrum` with a `depth`, which rides as
         ONE member whose block covers `n` bodies (default: the engine's capacity).  The orbital velocity follows cosh / sinh of
-        the height above the bed; the surface is the deep model's.  None clears it.  Only `step_fused_tiled_multi_fd` and
-        `sea_finite_depth_sample` see it; it, an ensemble, a spectrum and the sea of `set_sea` exclude each other.  Synchronous,
-        like `set_sea`."""
+        the height above the bed; the surface is the deep model's.  None clears it.  `step_fused_tiled_multi_fd`,
+        `sea_finite_depth_sample`, `step_wrench_tiled_irr` and `step_wrench_aos_irr` see it; it, an ensemble, a spectrum and the sea
+        of `set_sea` exclude each other.  Synchronous, like `set_sea`."""
         if sea is None:
             self._check(self._lib.hydro_set_sea_finite_depth(self._h, None, 0, 0, 0.0))
             self.finite_depth = None
@@ -1099,6 +1129,16 @@ class HydroEngine:
         self._check(self._lib.hydro_step_wrench_aos_sea(*head, float(dt), *tail, float(time), self._stream(stream)))
         return forces, torques
 
+    def step_wrench_aos_irr(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
+                            dt: float, time: float, forces: torch.Tensor | None = None, torques: torch.Tensor | None = None,
+                            quat_xyzw: bool = False, stream=None):
+        """`step_wrench_aos_sea` through whichever sea the engine holds, at `time` seconds (hydro_step_wrench_aos_irr): a
+        finite-depth sea, an ensemble, a spectrum, or the sea of `set_sea`.  The engine's previous-velocity state receives the
+        TRUE velocity.  Without any sea the call is step_wrench_aos."""
+        head, tail, forces, torques = self._wrench_aos_call(positions, orientations, velocities, forces, torques, quat_xyzw)
+        self._check(self._lib.hydro_step_wrench_aos_irr(*head, float(dt), *tail, float(time), self._stream(stream)))
+        return forces, torques
+
     def prepare_step_wrench_aos(self, positions: torch.Tensor, orientations: torch.Tensor, velocities: torch.Tensor,
                                 forces: torch.Tensor | None = None, torques: torch.Tensor | None = None,
                                 quat_xyzw: bool = False):
@@ -1107,11 +1147,13 @@ class HydroEngine:
         simulator's tensor API hands out views of the same device buffers every physics step).  For the plugin path,
         where the per-call Python work of `step_wrench_aos` (tensor checks, pointer conversions) is several times the
         kernel at 20 bodies.  `time` None: `hydro_step_wrench_aos`, argument for argument; otherwise the `_sea` entry at
-        `time` seconds.  `stream`: a torch stream / raw handle; None = the stream current at the time of the call."""
+        `time` seconds - the `_irr` entry while the engine holds a spectrum, an ensemble or a finite-depth sea
+        (`holds_irregular_sea`, asked at every step).  `stream`: a torch stream / raw handle; None = the stream current at the time of the call."""
         head, tail, forces, torques = self._wrench_aos_call(positions, orientations, velocities, forces, torques, quat_xyzw)
         self._rows((forces, torques), (3, 3), positions.shape[0], "output")
         head, tail = _prebuilt("hydro_step_wrench_aos", head), _prebuilt("hydro_step_wrench_aos", tail, len(head) + 1)
         fn, sea_fn, check = self._lib.hydro_step_wrench_aos, self._lib.hydro_step_wrench_aos_sea, self._check
+        irr_fn, irregular = self._lib.hydro_step_wrench_aos_irr, self.holds_irregular_sea
         keep = (positions, orientations, velocities, forces, torques)          # the buffers must outlive the callable
         dev, cur = self.device, torch.cuda.current_stream
         # the current stream's raw handle without building a torch.cuda.Stream object (0.2 instead of 1 us per step)
@@ -1127,7 +1169,10 @@ class HydroEngine:
                 sp = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
             if dt != last[0]:
                 last[0], last[1] = dt, ctypes.c_double(dt)
-            rc = fn(*head, last[1], *tail, sp) if time is None else sea_fn(*head, last[1], *tail, ctypes.c_double(time), sp)
+            if time is None:
+                rc = fn(*head, last[1], *tail, sp)
+            else:
+                rc = (irr_fn if irregular() else sea_fn)(*head, last[1], *tail, ctypes.c_double(time), sp)
             if rc:
                 check(rc)
             return keep[3], keep[4]
