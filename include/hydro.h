@@ -73,7 +73,9 @@ extern "C" {
  *        added to 0.7.1 (no existing entry changed): hydro_set_sea_ensemble, hydro_sea_ensemble_sample, hydro_step_fused_tiled_multi_ens,
  *        HYDRO_SEA_ENSEMBLE_MAX - up to 1024 sea spectra in one launch, block m of the bodies stepping through member m
  *        added to 0.7.1 (no existing entry changed): hydro_set_sea_finite_depth, hydro_sea_finite_depth_sample,
- *        hydro_step_fused_tiled_multi_fd - the ensemble's spectra in water of finite depth h: waves that feel the bottom */
+ *        hydro_step_fused_tiled_multi_fd - the ensemble's spectra in water of finite depth h: waves that feel the bottom
+ *        added to 0.7.1 (no existing entry changed): hydro_set_current_profile, hydro_current_profile_sample,
+ *        hydro_step_fused_tiled_multi_shear, HYDRO_CURRENT_KNOTS_MAX - a sheared current: a profile over depth of up to 16 knots */
 #define HYDRO_VERSION 0x000701
 
 #define HYDRO_OK         0
@@ -101,6 +103,7 @@ extern "C" {
 #define HYDRO_SEA_FIELDS      4   /* the record of hydro_sea_sample: eta, u_x, u_y, u_z */
 #define HYDRO_SPECTRUM_WAVES_MAX 64 /* wave components of a sea spectrum (hydro_set_sea_spectrum) */
 #define HYDRO_SEA_ENSEMBLE_MAX 1024 /* members of a sea ensemble (hydro_set_sea_ensemble) */
+#define HYDRO_CURRENT_KNOTS_MAX 16 /* knots of a current profile (hydro_set_current_profile) */
 /* the channels of a statistics record (hydro_step_fused_tiled_multi_stat) */
 #define HYDRO_STAT_X        0    /* s[0] */
 #define HYDRO_STAT_Y        1    /* s[1] */
@@ -1399,6 +1402,82 @@ int hydro_step_fused_tiled_multi_fd(hydro_t *h, int64_t n, const float *state, i
                                     void *statistics, int64_t statistics_tile_stride,
                                     const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
                                     int64_t step0, void *stream);
+
+/* Current profile: a sheared current - the steady current as a PROFILE OVER DEPTH, scene-wide, on top of "Finite-depth sea".
+ * A real current is strongest at the surface and close to zero at the bed, and design codes give it as a profile (DNV-RP-C205
+ * 4.1: a 1/7 power law over the depth for the tidal part, a wind-driven slab that dies out linearly over the top 50 m, often on
+ * another heading).  A cable's bow and a mooring's load below the surface are set by that shear; one vector U over-loads both.
+ *
+ * THE PROFILE: K = 0 .. HYDRO_CURRENT_KNOTS_MAX knots (z_l, V_l), z_l in m (<= 0, 0 the still-water surface), strictly ascending
+ * as fp32 values, V_l a 3-vector in m/s.  Piecewise linear between the knots; V_0 below the lowest, V_{K-1} above the highest.
+ * WATER AT A BODY of member m, behind "Finite-depth sea"'s WATER AT A BODY (eta and u_fd are that section's, bit for bit):
+ *   zc  = max(min(p_z - eta, 0), -h)                 fp32: "Finite-depth sea"'s statement over again from the same eta - the
+ *                                                    profile rides with the instantaneous surface; zc is finite for every p_z
+ *   P   = V_0
+ *   t_l = min(max((zc - z_l) * inv_l, 0), 1)         l = 0 .. K-2 in ascending order; a subtraction, a product, two clamps
+ *   P_i = fma(D_l,i, t_l, P_i)                       i = x, y, z
+ *   u_i = u_fd,i + P_i                               one fp32 add per component
+ * Branch-free: a segment below the body adds all of D_l, a segment above it adds D_l * +-0.
+ * CONSTANTS: inv_l = 1 / (z_{l+1} - z_l) and D_l = V_{l+1} - V_l are formed in fp64 on the host from the fp32 knots and rounded
+ * once each.  ROUNDING: every statement above is ONE fp32 operation (the fma one rounding); the sum over the segments telescopes to
+ * the knot values only up to these roundings - DESIGN.md section 34 bounds the distance to the exact profile (PROFILE_BOUND).
+ * THE MEMBER'S OWN U STAYS: it is inside u_fd, and the profile is added to EVERY member.  The relative state, restore and
+ * everything behind the wrench are "Finite-depth sea"'s.
+ * SCOPE: the profile takes effect ONLY WHILE THE ENGINE HOLDS A FINITE-DEPTH SEA (a profile is defined over a water column: it
+ * needs h).  Deep water is depth = 1e6, where the _fd kernels return the ensemble's bits; a current-only scene is a member with
+ * waves = 0.
+ *
+ * hydro_set_current_profile: the engine copies the knots into a table of its own (synchronous, like hydro_set_sea).  NULL or
+ * knots = 0 clears.  Settable whether or not a sea of any kind is set.  HYDRO_E_ARG for knots outside 0 .. HYDRO_CURRENT_KNOTS_MAX,
+ * NULL z or v with knots > 0, a non-finite value, a z_l > 0, knots not strictly ascending, an inv_l or a D_l outside fp32 range -
+ * the previous profile stays in force on every refusal.  ONLY hydro_step_fused_tiled_multi_shear and hydro_current_profile_sample
+ * know it: EVERY EXISTING ENTRY IGNORES A PROFILE - hydro_step_fused_tiled_multi_fd, hydro_step_wrench_tiled_irr,
+ * hydro_step_wrench_aos_irr and every *_sample included.
+ *
+ * hydro_current_profile_sample: the signature and the rules of hydro_sea_finite_depth_sample (HYDRO_E_STATE without a
+ * finite-depth sea); it writes [eta, u] with the profile in u.  Without a profile it writes hydro_sea_finite_depth_sample's bits.
+ *
+ * hydro_step_fused_tiled_multi_shear: exactly the signature, the refusals and the refusal order of hydro_step_fused_tiled_multi_fd.
+ *   no profile set                       : the launch and its bits are those of hydro_step_fused_tiled_multi_fd with the same arguments.
+ *   a profile and a finite-depth sea set : every option stays optional; the water is the one above.
+ *   a profile and NO finite-depth sea    : HYDRO_E_STATE, behind every other refusal; the message names hydro_set_sea_finite_depth.
+ *                                          Nothing is launched or written.
+ * Asynchronous, no allocation, no synchronisation, safe to capture under the ensemble's rule (capture current-only members; a
+ * profile over current-only members is steady, so it replays exactly).
+ * COST: per segment and body five vector instructions (a subtraction, a product that carries both clamps, three fmas) behind two
+ * scalar loads, 75 at 16 knots; no more registers than the _fd kernels (0 or 1 VGPR), no LDS, no scratch.  Expected before measuring:
+ * about 6 per segment, +18 % on a current-only step and +3 % in a full sea of 64 components where the step is issue-bound, less
+ * elsewhere.  Measured on an MI355X with 16 knots against the _fd step on the same bodies: 1.15 times
+ * current-only and 1.05 times in a full sea at 1 048 576 bodies; 1.44 and 1.04 times at 4 096 bodies, where a step is latency and the
+ * 15 dependent trips, each behind its scalar load, show in full (+0.57 us per step).  A run without a profile pays nothing.
+ * NOT MODELLED / NOT PROVIDED: a profile in the open-loop entries (hydro_step_wrench_*) and the plugin; in the 8-wave hydro_set_sea
+ * and in the deep kinds of sea without a depth (spectrum, ensemble); a profile per member; a profile that varies in time; the
+ * Doppler shift of the waves by the current (omega and the wave vector are taken as given, as ever).
+ * New functionality; the reference's water does not move. */
+typedef struct hydro_current_profile {
+    int knots;
+    const float *z;
+    const float *v; /* knots x 3 */
+} hydro_current_profile_t;
+int hydro_set_current_profile(hydro_t *h, const hydro_current_profile_t *profile);
+int hydro_current_profile_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
+                                 float *out, int64_t out_tile_stride, void *stream);
+int hydro_step_fused_tiled_multi_shear(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
+                                       const float *prev, int64_t prev_tile_stride, double dt, int steps,
+                                       float *state_out, int64_t out_tile_stride,
+                                       float *prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                       int rotational, double *ke_out_dev,
+                                       float *log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                       int64_t row0, int64_t *rows_written_host,
+                                       const float *applied, int64_t applied_tile_stride, int applied_frame,
+                                       const float *control, int64_t control_tile_stride,
+                                       const float *mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                       float *extremes, int64_t extremes_tile_stride,
+                                       const float *tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                       float *tether_peaks, int64_t tether_peaks_tile_stride,
+                                       void *statistics, int64_t statistics_tile_stride,
+                                       const float *levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                       int64_t step0, void *stream);
 
 /* Irregular sea in the open-loop steps: the spectrum, the ensemble and the finite-depth sea for the caller who integrates - a
  * simulator behind the plugin, or an integrator of one's own around hydro_step_wrench_tiled.  Two entries, each with exactly the

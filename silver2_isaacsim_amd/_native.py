@@ -28,6 +28,7 @@ SEA_WAVES_MAX = 8                       # regular wave components of a sea state
 SEA_FIELDS = 4                          # the record of hydro_sea_sample: eta, u_x, u_y, u_z
 SPECTRUM_WAVES_MAX = 64                 # wave components of a sea spectrum (hydro_set_sea_spectrum)
 SEA_ENSEMBLE_MAX = 1024                 # members of a sea ensemble (hydro_set_sea_ensemble)
+CURRENT_KNOTS_MAX = 16                  # knots of a current profile (hydro_set_current_profile)
 # the statistics record of hydro_step_fused_tiled_multi_stat: channels, and the record in 4-byte units per body (4 doubles + 3 words)
 STAT_X, STAT_Y, STAT_Z, STAT_VX, STAT_VY, STAT_VZ, STAT_TENSION = range(7)
 STAT_CHANNELS = 7
@@ -57,6 +58,12 @@ class Sea(ctypes.Structure):
 class SeaSpectrum(ctypes.Structure):
     """hydro_sea_spectrum_t (include/hydro.h): the irregular sea hydro_set_sea_spectrum takes; `wave` points at `waves` SeaWave."""
     _fields_ = [("current", c_double * 3), ("waves", c_int), ("wave", POINTER(SeaWave))]
+
+
+class CurrentProfile(ctypes.Structure):
+    """hydro_current_profile_t (include/hydro.h): the sheared current hydro_set_current_profile takes; `z` points at `knots`
+    floats, `v` at `knots` x 3."""
+    _fields_ = [("knots", c_int), ("z", POINTER(ctypes.c_float)), ("v", POINTER(ctypes.c_float))]
 
 
 class Seabed(ctypes.Structure):
@@ -157,6 +164,9 @@ SIGNATURES = {
     "hydro_set_sea_finite_depth": (c_int, _SET_FD),
     "hydro_sea_finite_depth_sample": (c_int, _SAMPLE),
     "hydro_step_fused_tiled_multi_fd": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
+    "hydro_set_current_profile": (c_int, [c_void_p, POINTER(CurrentProfile)]),
+    "hydro_current_profile_sample": (c_int, _SAMPLE),
+    "hydro_step_fused_tiled_multi_shear": _multi(_REC, _APP, _CTL, _SPREAD, _EXT, _TETH, _LAYERS, _PEAK, _STAT, _STEP0),
     "hydro_reserve_soa": (c_int, [c_void_p]),
     "hydro_integrate_tiled": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double,
                                       c_void_p, c_int64, c_void_p]),

@@ -2886,6 +2886,115 @@ __global__ void __launch_bounds__(kBlock) depth_sample_kernel(const float* st, u
 }
 
 // --------------------------------------------------------------------------
+// A SHEARED CURRENT in the loop of the multi-step kernel (hydro_step_fused_tiled_multi_shear): a scene-wide current profile over
+// depth, piecewise linear between up to HYDRO_CURRENT_KNOTS_MAX knots (z_l, V_l), added to the finite-depth sea's water
+// (hydro_set_current_profile; include/hydro.h, "Current profile").  sheared_water below is its ONLY implementation (the step
+// kernels and hydro_current_profile_sample's kernel both call it): depth_water, UNEDITED, then the knot loop, then one add per
+// component.
+//   the depth  : zc = max(min(p_z - eta, 0), -h) over again from depth_water's eta - the statement and the inputs of the orbital
+//                velocities' zc, hence its bits: the profile rides with the instantaneous surface, and zc is finite for every p_z
+//   the loop   : P = V_0, then per segment t = min(max((zc - z_l) * inv_l, 0), 1) and P_i = fma(D_l,i, t, P_i), in ascending l.
+//                Branch-free: a segment below the body adds all of D_l, one above it adds +-0 * D_l.  A REAL loop over the
+//                segments (wave-uniform count), its values dead once u is formed
+//   the table  : a 16-byte header (V_0, the knot count) and 16 records of z_l, inv_l, D_l padded to 32 B: 528 B, engine-owned,
+//                read through the CONSTANT address space with a wave-uniform index as the spectrum table is: scalar loads, no
+//                LDS staging, no vector register holds a knot between trips
+//   the add    : u_i = u_fd,i + P_i behind everything depth_water does; eta, the relative state and restore are the _fd rung's
+// The host launches these kernels only while a profile (knots >= 1) AND a finite-depth sea are set.
+// --------------------------------------------------------------------------
+struct CurrentKnot { float z, inv, d[3], pad[3]; };
+struct CurrentTable {
+    float v0[3]; uint32_t knots;
+    CurrentKnot k[HYDRO_CURRENT_KNOTS_MAX];
+};
+static_assert(sizeof(CurrentKnot) == 32 && sizeof(CurrentTable) == 16 + 32 * HYDRO_CURRENT_KNOTS_MAX, "the knot table's layout");
+typedef const __attribute__((address_space(4))) CurrentTable* CurrentTablePtr;
+#define HYDRO_SHEAR_PARAMS const void* knot_table, uint32_t knots
+#define HYDRO_SHEAR_ARGS knot_table, knots
+__device__ __forceinline__ void sheared_water(SpectrumTablePtr tab, uint32_t waves, int64_t step, double dt, float px, float py, float pz, HYDRO_FD_PARAMS,
+                                              CurrentTablePtr prof, uint32_t knots, float& eta, float (&u)[3])
+{
+    depth_water(tab, waves, step, dt, px, py, pz, HYDRO_FD_ARGS, eta, u);
+    const float zc = __builtin_fmaxf(__builtin_fminf(pz - eta, 0.0f), neg_depth);
+    float p[3] = {prof->v0[0], prof->v0[1], prof->v0[2]};
+    for (uint32_t l = 0; l + 1u < knots; ++l) {              // (wave-uniform)
+        const float t = __builtin_fminf(__builtin_fmaxf((zc - prof->k[l].z) * prof->k[l].inv, 0.0f), 1.0f);
+        p[0] = __builtin_fmaf(prof->k[l].d[0], t, p[0]);
+        p[1] = __builtin_fmaf(prof->k[l].d[1], t, p[1]);
+        p[2] = __builtin_fmaf(prof->k[l].d[2], t, p[2]);
+    }
+    u[0] = u[0] + p[0]; u[1] = u[1] + p[1]; u[2] = u[2] + p[2];
+}
+
+// DepthEnsembleView with sheared_water for the water: begin (the member's table) and restore are inherited.
+struct ShearedDepthView : DepthEnsembleView {
+    const void* knot_table;
+    uint32_t knots;
+    __device__ __forceinline__ void view(uint32_t k, float (&s)[HYDRO_STATE_FIELDS], float (&pv)[HYDRO_PREV_FIELDS]) const
+    {
+        float eta, u[3];
+        sheared_water((SpectrumTablePtr)tab, waves, step0 + (int64_t)k, dt, s[0], s[1], s[2], HYDRO_FD_ARGS, (CurrentTablePtr)knot_table, knots, eta, u);
+        float* m = parked();
+        m[0] = s[2];
+        s[2] = s[2] - eta;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            m[(1 + i) * 64] = s[7 + i];
+            m[(4 + i) * 64] = pv[i];
+            s[7 + i] = s[7 + i] - u[i];
+            pv[i] = pv[i] - u[i];
+        }
+    }
+};
+__device__ __forceinline__ ShearedDepthView sheared_depth_view(HYDRO_SEA_PARAMS, HYDRO_ENS_PARAMS, HYDRO_FD_PARAMS, HYDRO_SHEAR_PARAMS)
+{
+    return ShearedDepthView{depth_ensemble_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS, HYDRO_FD_ARGS), HYDRO_SHEAR_ARGS};
+}
+
+// The _fd kernel's arguments, then the knot table and its count.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_shear_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                   HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                   HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_ENS_PARAMS,
+                                                                                                   HYDRO_FD_PARAMS, HYDRO_SHEAR_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   sheared_depth_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS, HYDRO_FD_ARGS, HYDRO_SHEAR_ARGS),
+                                                   optional_seabed_contact(HYDRO_OPT_BED_ARGS),
+                                                   mooring_spread(HYDRO_SPREAD_ARGS), optional_extremes_track(HYDRO_EXT_ARGS),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// The _fd_stat kernel's arguments, then the knot table and its count.
+template <bool HALF, bool NT, bool IMPLICIT, bool KE, bool WARP>
+__global__ void __launch_bounds__(kBlock) HYDRO_MULTI_OCC_ATTR step_fused_multi_shear_stat_tiled_kernel(HYDRO_BASE_PARAMS, HYDRO_REC_PARAMS, HYDRO_APP_PARAMS, HYDRO_CTL_PARAMS,
+                                                                                                        HYDRO_SEA_PARAMS, HYDRO_OPT_BED_PARAMS, HYDRO_SPREAD_PARAMS,
+                                                                                                        HYDRO_EXT_PARAMS, HYDRO_NET_PARAMS, HYDRO_PEAK_PARAMS, HYDRO_STAT_PARAMS,
+                                                                                                        HYDRO_ENS_PARAMS, HYDRO_FD_PARAMS, HYDRO_SHEAR_PARAMS)
+{
+    fused_multi_body<HALF, NT, IMPLICIT, KE, WARP>(HYDRO_BASE_ARGS, optional_recorder(HYDRO_REC_ARGS), optional_pose_hold(HYDRO_APP_ARGS, HYDRO_CTL_ARGS),
+                                                   sheared_depth_view(HYDRO_SEA_ARGS, HYDRO_ENS_ARGS, HYDRO_FD_ARGS, HYDRO_SHEAR_ARGS),
+                                                   optional_seabed_contact(HYDRO_OPT_BED_ARGS),
+                                                   mooring_spread(HYDRO_SPREAD_ARGS), statistics_track(HYDRO_EXT_ARGS, HYDRO_STAT_ARGS, steps),
+                                                   OptionalPeakTetherNet{{{HYDRO_NET_ARGS, nullptr, 0u}, HYDRO_PEAK_ARGS, nullptr}});
+}
+
+// hydro_current_profile_sample: depth_sample_kernel calling sheared_water.
+__global__ void __launch_bounds__(kBlock) shear_sample_kernel(const float* st, uint32_t st_stride, float* out, uint32_t out_stride, uint32_t n,
+                                                              const void* sea_table, uint32_t sea_waves, int64_t step, double sea_dt, HYDRO_ENS_PARAMS, HYDRO_FD_PARAMS,
+                                                              HYDRO_SHEAR_PARAMS)
+{
+    const uint32_t tile = wave_tile<kBlock>(blockIdx.x), lane = threadIdx.x & 63u, lane4 = lane * 4u;
+    if (tile * 64u + lane >= n) return;
+    const float* r = st + (size_t)tile * st_stride;
+    float eta, u[3];
+    sheared_water(ensemble_member((SpectrumTablePtr)sea_table, tile, tiles_per_sea), sea_waves, step, sea_dt, *at<float>(r, lane4, 0u), *at<float>(r, lane4, 256u),
+                  *at<float>(r, lane4, 512u), HYDRO_FD_ARGS, (CurrentTablePtr)knot_table, knots, eta, u);
+    const float o[HYDRO_SEA_FIELDS] = {eta, u[0], u[1], u[2]};
+    store_record<HYDRO_SEA_FIELDS, false>(out + (size_t)tile * out_stride, lane4, o);
+}
+
+// --------------------------------------------------------------------------
 // IRREGULAR and FINITE-DEPTH seas in the OPEN-LOOP steps (hydro_step_wrench_tiled_irr, hydro_step_wrench_aos_irr): the two
 // open-loop sea kernels over again with spectrum_water or depth_water (DEPTH) for the water, against the table of the member
 // the wave's tile steps through.  New kernels beside wrench_tiled_sea_kernel and wrench_aos_sea_kernel, which stay as they
@@ -3076,6 +3185,10 @@ struct hydro_engine {
     int64_t fd_capacity = 0, fd_count = 0, fd_tiles_per_sea = 0;
     int fd_waves = -1;
     float fd_neg_depth = 0.0f;
+    // The current profile (hydro_set_current_profile): the device table the _shear kernels read (CurrentTable), allocated by the
+    // first hydro_set_current_profile, kept until hydro_destroy.  shear_knots == 0: no profile.  Independent of the kind of sea.
+    void* shear_table = nullptr;
+    int shear_knots = 0;
     // The seabed (hydro_set_seabed): the plane and the five contact constants, already rounded to fp32 - kernel arguments.
     Seabed bed = {};
     bool has_bed = false;
@@ -3553,6 +3666,7 @@ int hydro_destroy(hydro_t* h)
     if (h->spectrum_table) (void)hipFree(h->spectrum_table);
     if (h->ensemble_table) (void)hipFree(h->ensemble_table);
     if (h->fd_table) (void)hipFree(h->fd_table);
+    if (h->shear_table) (void)hipFree(h->shear_table);
     delete h;
     return HYDRO_OK;
 }
@@ -3979,7 +4093,7 @@ int hydro_step_fused_tiled_ke(hydro_t* h, int64_t n, const float* state, int64_t
 
 namespace {
 
-// A launch of any of the sixteen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
+// A launch of any of the seventeen hydro_step_fused_tiled_multi* entries, described ONCE: an entry fills a MultiStep with what it
 // was given - the fifteen base members by the braces, every further group by its with_*() below, which is the only place that
 // copies the group - and step_fused_tiled_multi_launch validates and launches it.  An option is absent by its pointer
 // (log, applied, control, mooring, extremes, tether, tether_peaks: nullptr is "without"); the sea and the seabed are the
@@ -4034,6 +4148,8 @@ struct MultiStep {
     }
     void with_ensemble() { ens_entry = true; }
     void with_finite_depth() { fd_entry = true; }
+    bool shear_entry = false;                            // the _shear entry: the _fd entry, and the current profile's water if one is set
+    void with_current_profile() { shear_entry = true; }
 };
 // [p, p + floats) and [q, q + floats_q) share an element
 inline bool ranges_overlap(const float* p, int64_t floats, const float* q, int64_t floats_q)
@@ -4084,7 +4200,8 @@ int check_recorder(hydro_t* h, const MultiStep& m, int64_t& rows_out)
 // (the _irr family stands beside the ladder: it is chosen while a sea spectrum is set, by the _irr entry alone, whatever the options;
 // the two _stat families stand beside the _spread and the _irr family: chosen while a statistics record is given, whatever the options;
 // the two _ens families stand beside the _irr and the _irr_stat family: chosen while a sea ensemble is set, by the _ens entry alone;
-// the two _fd families stand beside the two _ens families: chosen while a finite-depth sea is set, by the _fd entry alone)
+// the two _fd families stand beside the two _ens families: chosen while a finite-depth sea is set, by the _fd entry alone;
+// the two _shear families stand beside the two _fd families: chosen while a current profile AND a finite-depth sea are set, by the _shear entry alone)
 // and a launch goes to the LOWEST family that takes every option it has (the higher ones compute the same bits, slower for
 // the lesser cases); the options below the chosen one that the launch goes without are handed over as absent ones.
 int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
@@ -4097,6 +4214,7 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
     const bool irr = m.irr_entry && h->spectrum_waves >= 0;                    // (a spectrum and a sea are never set together: irr implies !sea)
     const bool ens = m.ens_entry && h->ensemble_waves >= 0;                    // (nor an ensemble with either: ens implies !irr and !sea)
     const bool fd = m.fd_entry && h->fd_waves >= 0;                            // (nor a finite-depth sea with any of them: fd implies !ens, !irr and !sea)
+    const bool shear = m.shear_entry && h->shear_knots > 0;                    // (a profile needs a water column: refused below without fd)
     int64_t rows = 0;
     if (rec && (rc = check_recorder(h, m, rows))) return rc;
     if ((rc = check_common(h, m.n))) return rc;
@@ -4218,6 +4336,8 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         if ((tiles + h->fd_tiles_per_sea - 1) / h->fd_tiles_per_sea > h->fd_count)
             return fail(h, HYDRO_E_ARG, "n needs more members than the finite-depth sea has (count * bodies_per_sea < n)");
     }
+    if (shear && !fd)
+        return fail(h, HYDRO_E_STATE, "a current profile is set without a finite-depth sea (call hydro_set_sea_finite_depth first, or clear the profile: hydro_set_current_profile(h, NULL))");
     HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
     hipStream_t s = static_cast<hipStream_t>(m.stream);
     if (m.rows_written_host) *m.rows_written_host = m.n == 0 ? 0 : rows;
@@ -4271,11 +4391,17 @@ int step_fused_tiled_multi_launch(hydro_t* h, const MultiStep& m)
         const auto with_statistics = [&](auto kernel, auto... tail) {
             spread_and_all(kernel, m.statistics, (uint32_t)m.statistics_tile_stride, m.levels, (uint32_t)m.levels_tile_stride, (uint32_t)m.channel_a, (uint32_t)m.channel_b, tail...);
         };
-        // the finite-depth sea first: the ensemble's group and the depth behind everything else, every option the launch has; then
+        // the current profile first: the finite-depth sea's groups and the knot table behind everything else; then
+        // the finite-depth sea: the ensemble's group and the depth behind everything else, every option the launch has; then
         // the ensemble: its group stands behind everything else, and its two families take every option the launch has; then
         // the statistics, through the spectrum or not; then
         // the spectrum: its family stands beside the ladder, not on it, and takes every option the launch has
-        if (fd) {
+        if (shear) {
+            const uint32_t tiles_per_sea = (uint32_t)h->fd_tiles_per_sea, knots = (uint32_t)h->shear_knots;
+            if (m.statistics) with_statistics(step_fused_multi_shear_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea, h->fd_neg_depth, (const void*)h->shear_table, knots);
+            else spread_and_all(step_fused_multi_shear_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea, h->fd_neg_depth, (const void*)h->shear_table, knots);
+        }
+        else if (fd) {
             const uint32_t tiles_per_sea = (uint32_t)h->fd_tiles_per_sea;
             if (m.statistics) with_statistics(step_fused_multi_fd_stat_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea, h->fd_neg_depth);
             else spread_and_all(step_fused_multi_fd_tiled_kernel<HALF, NT, IMPL, KE, WARP>, tiles_per_sea, h->fd_neg_depth);
@@ -4632,6 +4758,42 @@ int hydro_set_sea_finite_depth(hydro_t* h, const hydro_sea_spectrum_t* members, 
     return HYDRO_OK;
 }
 
+int hydro_set_current_profile(hydro_t* h, const hydro_current_profile_t* profile)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (!profile || profile->knots == 0) { h->shear_knots = 0; return HYDRO_OK; }
+    const int knots = profile->knots;
+    if (knots < 0 || knots > HYDRO_CURRENT_KNOTS_MAX) return fail(h, HYDRO_E_ARG, "current profile: knots out of range (0 .. HYDRO_CURRENT_KNOTS_MAX)");
+    if (!profile->z || !profile->v) return fail(h, HYDRO_E_ARG, "current profile: null z or v with knots > 0");
+    // (everything is checked and formed on the host, before the device table is touched)
+    CurrentTable tab;
+    memset(&tab, 0, sizeof tab);
+    for (int l = 0; l < knots; ++l) {
+        const float z = profile->z[l], *v = profile->v + 3 * l;
+        if (!isfinite(z) || !isfinite(v[0]) || !isfinite(v[1]) || !isfinite(v[2])) return fail(h, HYDRO_E_ARG, "current profile: non-finite knot");
+        if (z > 0.0f) return fail(h, HYDRO_E_ARG, "current profile: a knot above the still-water surface (z > 0)");
+        if (l > 0 && !(z > profile->z[l - 1])) return fail(h, HYDRO_E_ARG, "current profile: z must be strictly ascending (in fp32)");
+    }
+    tab.v0[0] = profile->v[0]; tab.v0[1] = profile->v[1]; tab.v0[2] = profile->v[2];
+    tab.knots = (uint32_t)knots;
+    for (int l = 0; l + 1 < knots; ++l) {
+        CurrentKnot& k = tab.k[l];
+        k.z = profile->z[l];
+        k.inv = (float)(1.0 / ((double)profile->z[l + 1] - (double)profile->z[l]));
+        for (int i = 0; i < 3; ++i) k.d[i] = (float)((double)profile->v[3 * (l + 1) + i] - (double)profile->v[3 * l + i]);
+        if (!isfinite(k.inv) || !isfinite(k.d[0]) || !isfinite(k.d[1]) || !isfinite(k.d[2]))
+            return fail(h, HYDRO_E_ARG, "current profile: a segment's 1 / (z_{l+1} - z_l) or V_{l+1} - V_l is out of fp32 range");
+    }
+    HYDRO_HIP(h, use_device(h->device), HYDRO_E_DEVICE);
+    if (!h->shear_table) HYDRO_HIP(h, hipMalloc(&h->shear_table, sizeof(CurrentTable)), HYDRO_E_ALLOC);
+    // from here on the device table is being rewritten: a failure leaves NO profile, never half of one
+    h->shear_knots = 0;
+    HYDRO_HIP(h, hipMemcpyAsync(h->shear_table, &tab, sizeof tab, hipMemcpyHostToDevice, h->stream), HYDRO_E_LAUNCH);
+    HYDRO_HIP(h, hipStreamSynchronize(h->stream), HYDRO_E_LAUNCH);
+    h->shear_knots = knots;
+    return HYDRO_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -4704,6 +4866,17 @@ int hydro_sea_finite_depth_sample(hydro_t* h, int64_t n, const float* state, int
     if (!h) return HYDRO_E_ARG;
     return water_sample(h, depth_sample_kernel, (const void*)h->fd_table, h->fd_waves, "no finite-depth sea (call hydro_set_sea_finite_depth first)",
                         n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream, h->fd_count, h->fd_tiles_per_sea, h->fd_neg_depth);
+}
+
+int hydro_current_profile_sample(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride, int64_t step_index, double dt,
+                                 float* out, int64_t out_tile_stride, void* stream)
+{
+    if (!h) return HYDRO_E_ARG;
+    if (h->shear_knots == 0)                                                   // no profile: the _fd sample, its launch and its bits
+        return hydro_sea_finite_depth_sample(h, n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream);
+    return water_sample(h, shear_sample_kernel, (const void*)h->fd_table, h->fd_waves, "no finite-depth sea (call hydro_set_sea_finite_depth first)",
+                        n, state, state_tile_stride, step_index, dt, out, out_tile_stride, stream, h->fd_count, h->fd_tiles_per_sea, h->fd_neg_depth,
+                        (const void*)h->shear_table, (uint32_t)h->shear_knots);
 }
 
 int hydro_step_fused_tiled_multi_sea(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
@@ -5158,6 +5331,44 @@ int hydro_step_fused_tiled_multi_fd(hydro_t* h, int64_t n, const float* state, i
     m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
     m.with_ensemble();
     m.with_finite_depth();
+    return step_fused_tiled_multi_launch(h, m);
+}
+
+int hydro_step_fused_tiled_multi_shear(hydro_t* h, int64_t n, const float* state, int64_t state_tile_stride,
+                                       const float* prev, int64_t prev_tile_stride, double dt, int steps,
+                                       float* state_out, int64_t out_tile_stride,
+                                       float* prev_out, int64_t prev_out_tile_stride, int implicit_drag,
+                                       int rotational, double* ke_out_dev,
+                                       float* log, int64_t log_stride, int64_t rows_capacity, int fields, int every, int phase,
+                                       int64_t row0, int64_t* rows_written_host,
+                                       const float* applied, int64_t applied_tile_stride, int applied_frame,
+                                       const float* control, int64_t control_tile_stride,
+                                       const float* mooring, int64_t mooring_tile_stride, int64_t mooring_layers,
+                                       float* extremes, int64_t extremes_tile_stride,
+                                       const float* tether, int64_t tether_tile_stride, int64_t tether_layers,
+                                       float* tether_peaks, int64_t tether_peaks_tile_stride,
+                                       void* statistics, int64_t statistics_tile_stride,
+                                       const float* levels, int64_t levels_tile_stride, int channel_a, int channel_b,
+                                       int64_t step0, void* stream)
+{
+    MultiStep m = {n, state, state_tile_stride, prev, prev_tile_stride, dt, steps, state_out, out_tile_stride, prev_out, prev_out_tile_stride,
+                   implicit_drag, rotational, ke_out_dev, stream};
+    m.with_recorder(log, log_stride, rows_capacity, fields, every, phase, row0, rows_written_host);
+    m.with_applied(applied, applied_tile_stride, applied_frame);
+    m.with_control(control, control_tile_stride);
+    m.with_sea(step0);
+    m.with_seabed();
+    m.with_mooring(mooring, mooring_tile_stride);
+    m.with_mooring_layers(mooring_layers);
+    m.with_extremes(extremes, extremes_tile_stride);
+    m.with_tether(tether, tether_tile_stride);
+    m.with_layers(tether_layers);
+    m.with_peaks(tether_peaks, tether_peaks_tile_stride);
+    m.with_spectrum();
+    m.with_statistics(statistics, statistics_tile_stride, levels, levels_tile_stride, channel_a, channel_b);
+    m.with_ensemble();
+    m.with_finite_depth();
+    m.with_current_profile();
     return step_fused_tiled_multi_launch(h, m);
 }
 

@@ -74,6 +74,7 @@ class HydroEngine:
         self.spectrum_waves: int | None = None       # wave components of the spectrum set with set_sea_spectrum; None: no spectrum
         self.ensemble_count: int | None = None       # members of the ensemble set with set_sea_ensemble; None: no ensemble
         self.finite_depth: float | None = None       # the depth (m) of the sea set with set_sea_finite_depth; None: no finite-depth sea
+        self.current_profile = None                  # the sea.CurrentProfile set with set_current_profile; None: no profile
         self.seabed = None                           # the seabed.Seabed set with set_seabed; None: no bed
         self.set_scene(water_density, gravity)
 
@@ -779,6 +780,56 @@ class HydroEngine:
         Without a finite-depth sea the call IS step_fused_tiled_multi_ens.  Returns the number of rows written (0 without a
         log)."""
         return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_fd,
+                                    (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
+                                    (log, every, phase, row0), stream,
+                                    lambda: self._stat_tail(n, step0, statistics, levels, channel_a, channel_b, mooring, mooring_layers, tether, layers,
+                                                            peaks, extremes, control, applied, frame))
+
+    # ------------------------------------------------------------------ current profile
+    def set_current_profile(self, profile) -> None:
+        """The scene's sheared current (hydro_set_current_profile; include/hydro.h, "Current profile"): `profile` is a
+        `sea.CurrentProfile` - up to 16 knots (z_l, V_l), piecewise linear, constant beyond the ends - added to the water of the
+        finite-depth sea for every member.  None (or a profile without knots) clears it.  Only `step_fused_tiled_multi_shear` and
+        `current_profile_sample` see it, and only while a finite-depth sea is set.  Synchronous, like `set_sea`."""
+        if profile is None or len(profile.z) == 0:
+            self._check(self._lib.hydro_set_current_profile(self._h, None))
+            self.current_profile = None
+            return
+        knots = len(profile.z)
+        z = (ctypes.c_float * knots)(*[float(x) for x in profile.z])               # (alive until the call returns: the library copies)
+        v = (ctypes.c_float * (3 * knots))(*[float(x) for row in profile.v for x in row])
+        c = nat.CurrentProfile(knots, ctypes.cast(z, ctypes.POINTER(ctypes.c_float)), ctypes.cast(v, ctypes.POINTER(ctypes.c_float)))
+        self._check(self._lib.hydro_set_current_profile(self._h, ctypes.byref(c)))
+        self.current_profile = profile
+
+    def current_profile_sample(self, state: torch.Tensor, n: int, step_index: int, dt: float, out: torch.Tensor | None = None,
+                               stream=None) -> torch.Tensor:
+        """`sea_finite_depth_sample` with the current profile in u (hydro_current_profile_sample): exactly the
+        [eta, u_x, u_y, u_z] `step_fused_tiled_multi_shear` uses for step `step_index`.  Without a profile, the bits of
+        `sea_finite_depth_sample`."""
+        s_ptr, s_stride = self._tiled(state, nat.STATE_FIELDS, n)
+        if out is None:
+            out = self.alloc_tiled(nat.SEA_FIELDS, n)
+        o_ptr, o_stride = self._tiled(out, nat.SEA_FIELDS, n)
+        self._check(self._lib.hydro_current_profile_sample(self._h, n, s_ptr, s_stride, int(step_index), float(dt), o_ptr, o_stride,
+                                                           self._stream(stream)))
+        return out
+
+    def step_fused_tiled_multi_shear(self, state: torch.Tensor, prev_state: torch.Tensor, n: int, dt: float, steps: int, step0: int,
+                                     statistics: torch.Tensor | None = None, levels: torch.Tensor | None = None,
+                                     channel_a: int = nat.STAT_Z, channel_b: int = nat.STAT_TENSION,
+                                     mooring: torch.Tensor | None = None, mooring_layers: int = 1,
+                                     tether: torch.Tensor | None = None, layers: int = 1, peaks: torch.Tensor | None = None,
+                                     extremes: torch.Tensor | None = None,
+                                     control: torch.Tensor | None = None, applied: torch.Tensor | None = None, frame: str = "body",
+                                     log: torch.Tensor | None = None, every: int = 1, phase: int = 1, row0: int = 0,
+                                     state_out: torch.Tensor | None = None, implicit_drag: bool = False, stream=None,
+                                     ke_out: torch.Tensor | None = None, rotational: bool = True) -> int:
+        """step_fused_tiled_multi_fd with the current profile set with `set_current_profile` added to the water
+        (hydro_step_fused_tiled_multi_shear): the arguments and the rules are step_fused_tiled_multi_fd's, every option optional.
+        Without a profile the call IS step_fused_tiled_multi_fd; with a profile and no finite-depth sea it is refused.  Returns
+        the number of rows written (0 without a log)."""
+        return self._recorded_multi(self._lib.hydro_step_fused_tiled_multi_shear,
                                     (state, prev_state, n, dt, steps, state_out, implicit_drag, ke_out, rotational),
                                     (log, every, phase, row0), stream,
                                     lambda: self._stat_tail(n, step0, statistics, levels, channel_a, channel_b, mooring, mooring_layers, tether, layers,

@@ -20,6 +20,10 @@ A `SeaSpectrum` or `SeaEnsemble` with a `depth` (m) is a FINITE-DEPTH sea: the s
 cosh(kappa (z + h)) / sinh(kappa h) and sinh(kappa (z + h)) / sinh(kappa h) in place of exp(kappa z), nothing below the bed
 (include/hydro.h, "Finite-depth sea").  `wavenumber` solves omega^2 = g kappa tanh(kappa h), and `depth=` on
 the four constructors places the same bins and amplitudes on the shorter waves of that depth.
+
+`CurrentProfile` is a SHEARED current: up to 16 knots (z_l, V_l), piecewise linear over the depth below the instantaneous surface,
+added to the water of a finite-depth sea (include/hydro.h, "Current profile").  `power_law` and `slab` are
+the two profiles design codes name; `+` superposes them.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ import numpy as np
 WAVES_MAX = 8
 SPECTRUM_WAVES_MAX = 64
 ENSEMBLE_MAX = 1024
+CURRENT_KNOTS_MAX = 16
 
 
 class SeaState:
@@ -377,3 +382,94 @@ def pierson_moskowitz_ensemble(hs: float, tp: float, heading_deg, *, seeds=range
                                **kw) -> SeaEnsemble:
     """`jonswap_ensemble` for `pierson_moskowitz`."""
     return _ensemble(pierson_moskowitz, hs, tp, heading_deg, seeds, bodies_per_sea, current, kw)
+
+
+class CurrentProfile:
+    """A current that varies with depth: knots (z_l, V_l) - z_l <= 0 in m below the local surface, strictly ascending, V_l a
+    3-vector in m/s, world frame - piecewise linear between the knots, V_0 below the lowest and V_{K-1} above the highest; what
+    `ClosedLoopSim.set_current_profile` and `HydroEngine.set_current_profile` take (hydro_step_fused_tiled_multi_shear;
+    include/hydro.h, "Current profile").  The knots are kept AS THE ENGINE SEES THEM, rounded to fp32 (`z`, `v`: float64 arrays of
+    fp32 values), and must still ascend strictly after that rounding.  It is added to every member's own steady current, and
+    takes effect only in a sea that has a depth.  No knots: no current."""
+
+    def __init__(self, z=(), v=()):
+        z64, v64 = np.asarray(z, np.float64).reshape(-1), np.asarray(v, np.float64).reshape(-1, 3)
+        if len(z64) != len(v64):
+            raise ValueError("a current profile needs one velocity (three numbers) per knot")
+        if len(z64) > CURRENT_KNOTS_MAX:
+            raise ValueError(f"a current profile has at most {CURRENT_KNOTS_MAX} knots")
+        if not (np.isfinite(z64).all() and np.isfinite(v64).all()):
+            raise ValueError("current profile: non-finite knot")
+        with np.errstate(over="ignore"):
+            zf, vf = z64.astype(np.float32), v64.astype(np.float32)
+        if not (np.isfinite(zf).all() and np.isfinite(vf).all()):
+            raise ValueError("current profile: a knot out of fp32 range")
+        if (zf > 0.0).any():
+            raise ValueError("current profile: the knots lie at or below the surface (z <= 0)")
+        if not (np.diff(zf) > 0.0).all():
+            raise ValueError("current profile: z must be strictly ascending (after rounding to fp32)")
+        self.z, self.v = zf.astype(np.float64), vf.astype(np.float64)
+        inv, d = self.table()[2:]
+        if not (np.isfinite(inv).all() and np.isfinite(d).all()):
+            raise ValueError("current profile: a segment's 1 / (z_{l+1} - z_l) or V_{l+1} - V_l is out of fp32 range")
+
+    @property
+    def knots(self) -> int:
+        return len(self.z)
+
+    def velocity(self, z_rel, depth=None) -> np.ndarray:
+        """The profile (..., 3) in m/s at `z_rel` below the local surface, in fp64: linear between the knots, constant beyond
+        them.  `depth` (m): z_rel is clamped to -depth first, as the kernels do with the sea's depth."""
+        z = np.asarray(z_rel, np.float64)
+        if depth is not None:
+            z = np.maximum(z, -float(depth))
+        out = np.zeros(z.shape + (3,), np.float64)
+        if self.knots:
+            for i in range(3):
+                out[..., i] = np.interp(z, self.z, self.v[:, i])
+        return out
+
+    def table(self):
+        """The constants the kernels read, as fp32 arrays: (V_0 (3,), z_l (K-1,), inv_l = 1 / (z_{l+1} - z_l) (K-1,),
+        D_l = V_{l+1} - V_l (K-1, 3)) - the differences formed in fp64 from the fp32 knots and rounded once."""
+        if not self.knots:
+            return np.zeros(3, np.float32), np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros((0, 3), np.float32)
+        with np.errstate(over="ignore", divide="ignore"):
+            inv = (1.0 / np.diff(self.z)).astype(np.float32)
+            d = np.diff(self.v, axis=0).astype(np.float32)
+        return self.v[0].astype(np.float32), self.z[:-1].astype(np.float32), inv, d
+
+    def __add__(self, other: "CurrentProfile") -> "CurrentProfile":
+        """The sum of two profiles on the union of their knots (exact: both are linear between neighbouring knots of the union)."""
+        if not isinstance(other, CurrentProfile):
+            return NotImplemented
+        z = np.union1d(self.z, other.z)
+        if len(z) > CURRENT_KNOTS_MAX:
+            raise ValueError(f"the sum has {len(z)} knots: a current profile has at most {CURRENT_KNOTS_MAX}")
+        return CurrentProfile(z, self.velocity(z) + other.velocity(z))
+
+    @classmethod
+    def power_law(cls, speed: float, heading_deg: float, depth: float, exponent: float = 1.0 / 7.0, knots: int = CURRENT_KNOTS_MAX) -> "CurrentProfile":
+        """The tidal profile of the design codes (DNV-RP-C205 4.1.4): `speed` (m/s, at the surface) times ((z + depth) / depth) **
+        exponent, flowing towards `heading_deg` (degrees from +x towards +y), zero at the bed.  The knots sit at
+        z_l = -depth (1 - (l / (knots - 1)) ** 4): dense at the bed, where the power law is steep - with 16 knots the piecewise
+        linear profile stays within 0.5 % of the surface speed of the closed form above the lowest 1 % of the depth (uniform knots
+        miss by 1.5 %)."""
+        depth, knots = _depth(depth), int(knots)
+        if depth is None or not 2 <= knots <= CURRENT_KNOTS_MAX:
+            raise ValueError(f"power_law needs a depth and 2 .. {CURRENT_KNOTS_MAX} knots")
+        if not (math.isfinite(speed) and exponent > 0.0 and math.isfinite(exponent)):
+            raise ValueError("speed must be finite, exponent finite and > 0")
+        frac = (np.arange(knots) / (knots - 1.0)) ** 4                       # (z + depth) / depth at the knots
+        hd = math.radians(heading_deg)
+        mag = float(speed) * frac ** float(exponent)
+        return cls(-depth * (1.0 - frac), np.stack([mag * math.cos(hd), mag * math.sin(hd), np.zeros(knots)], axis=1))
+
+    @classmethod
+    def slab(cls, speed: float, heading_deg: float, thickness: float = 50.0) -> "CurrentProfile":
+        """The wind-driven profile of the design codes (DNV-RP-C205 4.1.4): `speed` (m/s) at the surface towards `heading_deg`,
+        linear to zero at -thickness (m), nothing below."""
+        if not (math.isfinite(speed) and thickness > 0.0 and math.isfinite(thickness)):
+            raise ValueError("speed must be finite, thickness finite and > 0")
+        hd = math.radians(heading_deg)
+        return cls([-float(thickness), 0.0], [[0.0, 0.0, 0.0], [speed * math.cos(hd), speed * math.sin(hd), 0.0]])

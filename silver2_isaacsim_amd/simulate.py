@@ -337,6 +337,7 @@ class TrajectoryRecorder:
 
 class ClosedLoopSim:
     seabed = None               # set_seabed(): the seabed.Seabed under the bodies (a class default: a sim has none until one is set)
+    current_profile = None      # set_current_profile(): the sea.CurrentProfile added to the finite-depth sea's water while one is set
     mooring = None              # set_mooring(): the tiled (tiles, 9, 64) record of the bodies' mooring lines while lines are set
     _mooring_buf = None         # the buffer itself (made once)
     mooring_spread = None       # set_mooring_spread(): the tiled (tiles, 9 * layers, 64) spread of the bodies' mooring lines while a spread is set
@@ -589,6 +590,31 @@ class ClosedLoopSim:
             self.synchronize()
             self._set_engine_sea(self.sea, None)
             self.sea = None
+            self._graph = None
+
+    def set_current_profile(self, profile) -> None:
+        """A sheared current: from now on every physics step of run_eager and run_resident adds `profile` (a
+        `sea.CurrentProfile`: knots over the depth below the instantaneous surface, piecewise linear) to the water of the
+        finite-depth sea, for every member and on top of each member's own steady current
+        (hydro_step_fused_tiled_multi_shear; include/hydro.h, "Current profile").  A profile is defined over a water column:
+        while one is set, a step raises ValueError unless `sim.sea` has a `depth` (deep water: depth=1e6; current only: a
+        spectrum without components).  Graph replays (`run` with graph_steps) refuse a profile.  Every other option rides
+        along as in a finite-depth sea.  The profile stays until the next call or `clear_current_profile()`."""
+        if not self.fused:
+            raise ValueError("the current profile lives in the fused step kernels (fused=True)")
+        if profile is None or not profile.knots:
+            return self.clear_current_profile()
+        self.synchronize()                                      # launches in flight read the table this rewrites
+        self.engine.set_current_profile(profile)
+        self.current_profile = profile
+        self._graph = None                                      # captured steps are of another entry
+
+    def clear_current_profile(self) -> None:
+        """No sheared current: every call the sim makes is again the one it made before set_current_profile."""
+        if self.current_profile is not None:
+            self.synchronize()
+            self.engine.set_current_profile(None)
+            self.current_profile = None
             self._graph = None
 
     def set_seabed(self, bed) -> None:
@@ -923,7 +949,8 @@ class ClosedLoopSim:
         if self.link_tensions is not None:
             self.link_tensions.links, self.link_tensions.layer = self._tether_links
 
-    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: through
+    # `k` physics steps in ONE call of the engine, on the current stream context - the only place that picks the call: with
+    # the current profile if one is set (its entry is the finite-depth sea's; refused unless `sim.sea` has a depth), else through
     # the finite-depth sea if `sim.sea` has a depth (its entry is the ensemble's, every other option optional), else through
     # the sea ensemble if `sim.sea` is one (its entry takes every other option, the statistics included), else with
     # the response statistics if they are tracked (their entry takes every other option, the spectrum included), else through
@@ -945,12 +972,16 @@ class ClosedLoopSim:
             phase, row0, _ = rec.launch(self.steps_done, k)
             kw.update(log=rec.log, every=rec.every, phase=phase, row0=row0)
         finite_depth = self.sea is not None and self._sea_setter(self.sea) == "set_sea_finite_depth"
+        if self.current_profile is not None and not finite_depth:
+            raise ValueError("a current profile needs a water column: set a sea with a depth first (set_sea(SeaSpectrum(depth=h)) for a "
+                             "current-only scene, depth=1e6 for deep water), or clear_current_profile()")
         if finite_depth or isinstance(self.sea, SeaEnsemble):
             # (the entry of the statistics, every option optional, the statistics too; _fd first)
             st = self.statistics
             moor, moor_layers = (self.mooring_spread, self.mooring_layers) if self.mooring_spread is not None else (self.mooring, 1)
             net, layers = (self.tether_net, self.tether_layers) if self.tether_net is not None else (self.tether, 1)
-            step = e.step_fused_tiled_multi_fd if finite_depth else e.step_fused_tiled_multi_ens
+            step = (e.step_fused_tiled_multi_shear if self.current_profile is not None else e.step_fused_tiled_multi_fd if finite_depth
+                    else e.step_fused_tiled_multi_ens)
             rows = step(*args, k, self.steps_done, *((st.buffer, st.levels_buffer, *st.channel_numbers) if st is not None
                                                      else (None, None, nat.STAT_Z, nat.STAT_TENSION)),
                         moor, moor_layers, net, layers,
@@ -1088,6 +1119,9 @@ class ClosedLoopSim:
         if self.sea is not None and len(self.sea.waves) and graph_steps and steps >= graph_steps:
             raise ValueError("a sea with waves cannot ride in graph replays: the time a captured launch steps at is frozen at "
                              "capture - use run_resident (or run_eager); a current-only sea replays")     # (a sea spectrum is a sea here)
+        if self.current_profile is not None and graph_steps and steps >= graph_steps:
+            raise ValueError("a current profile does not ride in graph replays - use run_resident (or run_eager), or "
+                             "clear_current_profile() first")
         self._warm_monitor()
         if graph_steps and steps >= graph_steps:
             if self.steps_done % graph_steps and self.monitor is not None:
