@@ -1219,6 +1219,11 @@ int hydro_step_fused_tiled_multi_irr(hydro_t *h, int64_t n, const float *state, 
  * set and the next sample above the level counts.  A sample equal to an infinite level gives d = NaN (Inf - Inf) likewise.
  * NOT PROVIDED: heave relative to the moving surface; covariances between channels; more than two channels per record;
  * statistics of the wrench; per-link statistics of tether nets.
+ * SIGN SYMMETRY: exact, WITH ONE EXCEPTION.  A channel the map does not flip - z, vz and tension always,
+ * and whichever of x, y, vx, vy it leaves alone - keeps every word of its slot.  A flipped channel, taken against the level
+ * L' = -L, has d' = -d exactly: S1' = -S1 and S2 keeps its bits.  n keeps its bits.  The exception is the UP-CROSSING WORD OF A
+ * FLIPPED CHANNEL: an up-crossing of L by x is a DOWN-crossing of -L by -x, which the record does not count - the image's word is
+ * the scene's count of down-crossings, not its image (tests/symmetry.py, tests/test_symmetry_gpu.py).
  *
  * hydro_statistics_reset: sums +0.0 and words 0 for bodies 0 .. n - 1 (lanes >= n of the last tile are not written).  A small
  * kernel of its own; asynchronous on `stream`; needs no parameters.  HYDRO_E_ARG for n > capacity, a null or misaligned buffer
@@ -1306,8 +1311,11 @@ int hydro_step_fused_tiled_multi_stat(hydro_t *h, int64_t n, const float *state,
  * (nothing but the sea) to 1.17 times (a spread, extremes and statistics), members of 64 bodies 1.11 to 1.42 times.  Guidance, not a
  * rule: give each member as many bodies as the study has, a multiple of 256 bodies.
  * NOT PROVIDED: members with different component counts; a per-body index table (the mapping is by block); ensembles in the
- * open-loop entries (hydro_step_wrench_*_sea) and the plugin; a sign-symmetry statement for the ensemble (each member's is
- * "Sea spectrum"'s).
+ * open-loop entries (hydro_step_wrench_*_sea) and the plugin.
+ * SIGN SYMMETRY: exact, member by member.  Under the mirror in y = 0, the mirror in x = 0 and the half turn about z (DESIGN.md
+ * section 21) the image of an ensemble is the image of each member - current and (kx, ky) polar, everything else unchanged - in
+ * the members' ORDER and over the same bodies_per_sea: the maps do not renumber bodies.  A launch over the image of a scene then
+ * writes the image of what it wrote, by float equality, eta and every scalar the same bits (tests/test_symmetry_gpu.py).
  * New functionality; the reference's water does not move. */
 int hydro_set_sea_ensemble(hydro_t *h, const hydro_sea_spectrum_t *members, int64_t count, int64_t bodies_per_sea);
 int hydro_sea_ensemble_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
@@ -1381,7 +1389,11 @@ int hydro_step_fused_tiled_multi_ens(hydro_t *h, int64_t n, const float *state, 
  * A run in deep water pays nothing: leave the depth away and the kernels are the ensemble's.
  * NOT MODELLED / NOT PROVIDED: a depth-limited spectral shape (TMA); shoaling, breaking and a sloping bed; depth in the 8-wave
  * hydro_set_sea, in the open-loop entries (hydro_step_wrench_*_sea) and the plugin; members of different depths; any coupling
- * between h and the seabed's z_b; a sign-symmetry statement for this rung.
+ * between h and the seabed's z_b.
+ * SIGN SYMMETRY: exact at any depth.  h is a scalar and so are kl2_j, gl_j, aw_j times 1 / (1 - q_j), zc, E_j and G_j; cx_j and
+ * cy_j times 1 / (1 - q_j) are formed from kx_j and ky_j by products and a division - exact negations under a map that flips
+ * them - and the phase keeps its bits.  So the image of a scene (the image of the sea has the same depth)
+ * gives the image of its outputs by float equality, eta the same bits (tests/test_symmetry_gpu.py).
  * New functionality; the reference's water does not move. */
 int hydro_set_sea_finite_depth(hydro_t *h, const hydro_sea_spectrum_t *members, int64_t count, int64_t bodies_per_sea, double depth);
 int hydro_sea_finite_depth_sample(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride, int64_t step_index, double dt,
@@ -1453,6 +1465,10 @@ int hydro_step_fused_tiled_multi_fd(hydro_t *h, int64_t n, const float *state, i
  * NOT MODELLED / NOT PROVIDED: a profile in the open-loop entries (hydro_step_wrench_*) and the plugin; in the 8-wave hydro_set_sea
  * and in the deep kinds of sea without a depth (spectrum, ensemble); a profile per member; a profile that varies in time; the
  * Doppler shift of the waves by the current (omega and the wave vector are taken as given, as ever).
+ * SIGN SYMMETRY: exact.  The knots' z_l and inv_l are scalars and so is t_l; V_0 and every D_l are polar - D_l is rounded once from
+ * a difference of fp32 values, an exact negation under a map that flips the component - and the knots are summed in ascending l on
+ * the scene and on its image.  So the image of a scene (the image of the profile has the same z_l) gives the
+ * image of its outputs by float equality (tests/test_symmetry_gpu.py).
  * New functionality; the reference's water does not move. */
 typedef struct hydro_current_profile {
     int knots;
@@ -1513,6 +1529,9 @@ int hydro_step_fused_tiled_multi_shear(hydro_t *h, int64_t n, const float *state
  * block_threads says).
  * NOT COVERED - these step through still water whatever is set: hydro_step_wrench_tiled_ke, hydro_step_wrench_tiled_batch, the
  * plain-SoA hydro_step_wrench[_ext], and the component / calculator entries hydro_step_components[_aos].
+ * SIGN SYMMETRY: exact, whichever sea the engine holds, for both entries (hydro_step_wrench_aos_irr in either quaternion order),
+ * their _sea siblings and the samples at a time: the image's wrench is the image of the wrench, the engine-owned previous
+ * velocity afterwards the image of the scene's, eta the same bits (tests/test_symmetry_gpu.py).
  * Cost and registers: DESIGN.md section 33.  New functionality; the reference's water does not move. */
 int hydro_step_wrench_tiled_irr(hydro_t *h, int64_t n, const float *state, int64_t state_tile_stride,
                                 const float *prev, int64_t prev_tile_stride, double dt,

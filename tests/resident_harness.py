@@ -140,6 +140,30 @@ def _unguard(buf, n, fields, stride):
     return flat[:n].copy(), np.concatenate([flat[n:].reshape(-1), host[:, fields * 64:].reshape(-1)])
 
 
+ARENA_GAP = 8192                                                  # floats between two buffers of an arena: see _in_one_allocation
+
+
+def _in_one_allocation(*bufs):
+    """Flat fp32 device buffers -> views of the same sizes and contents inside ONE allocation, in the order given, ARENA_GAP
+    floats of NaN in front of, between and behind them.  For the refusal tests: a call that hands a buffer to the library as
+    ANOTHER record makes the library claim that record's extent from the buffer's address - the statistics record's
+    (tiles - 1) * stride + 704 floats, 4 404 at six tiles of stride 740, from a `prev` of 2 424 floats - and what lies behind a
+    buffer of its own allocation is wherever the allocator put the next one: an output, and the refusal "overlaps an output"
+    fires in front of the one the test is about.  Inside the arena a claim of up to ARENA_GAP floats past a buffer's end meets
+    only the gap, so every call's only overlap is the intended one, wherever the allocator places the arena."""
+    sizes = [b.numel() for b in bufs]
+    offsets, at = [], ARENA_GAP
+    for size in sizes:
+        offsets.append(at)
+        at += -(-size // 64) * 64 + ARENA_GAP                       # (every view starts on a 256-byte boundary of the arena)
+    arena = torch.full((at,), NAN, dtype=torch.float32, device=DEV)
+    views = [arena[o:o + size] for o, size in zip(offsets, sizes)]
+    for view, buf in zip(views, bufs):
+        assert buf.dtype == torch.float32 and buf.dim() == 1
+        view.copy_(buf)
+    return views
+
+
 def _untouched(buf, before):
     """An input buffer, sentinels included, is bit for bit what it was."""
     return np.array_equal(buf.cpu().numpy(), before, equal_nan=True)

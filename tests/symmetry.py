@@ -25,11 +25,25 @@ The records of the later rungs, stated once like the rest:
     net                 (n, 7 L)    a tether record per layer, each mapped as `tether`
     spread              (n, 9 L)    a mooring record per layer, each mapped as `mooring`
     link tensions       (n, L)      scalars: the same bits (and so is tension_max of the extremes record)
-    sea                 -           `sea()` serves BOTH kinds of sea, sea.SeaState and sea.SeaSpectrum (it builds type(s)): the
-                                    current and every component's (kx, ky) are polar, amplitude, omega and phase scalars
+    sea                 -           `sea()` serves every kind of sea, sea.SeaState, sea.SeaSpectrum and sea.SeaEnsemble (it builds
+                                    type(s)): the current and every component's (kx, ky) are polar, amplitude, omega and phase
+                                    scalars - and so is a spectrum's DEPTH, which the image carries
+    sea ensemble        -           member by member, the member ORDER and bodies_per_sea unchanged: block m of the bodies steps
+                                    through the image of member m - the maps do not renumber bodies
+    current profile     -           `current_profile()`: the knots' z_l are scalars, the V_l polar (so V_0 and every slope D_l
+                                    change sign only)
+    levels              (n, 2)      `levels()`: the level of a channel the map flips changes sign, L' = -L; the others keep theirs
+    statistics          dict        `statistics()`: sums (n, 4) [S1_a S2_a S1_b S2_b], up (n, 2), n (n,).  A channel the map does not
+                                    flip - z, vz and tension always, and whichever of x, y, vx, vy the map leaves alone - keeps
+                                    every word.  A flipped channel, against L' = -L: d' = -d exactly, so S1' = -S1 and S2 keeps
+                                    its bits.  n keeps its bits.  THE UP-CROSSING WORD OF A FLIPPED CHANNEL IS NOT COMPARABLE: an
+                                    up-crossing of L by x is a DOWN-crossing of -L by -x, and the record counts no down-crossings.
+                                    That one word, of that slot only, is left out (`statistics_left_out`); `statistics()` puts 0
+                                    in its place
 
-The sums the later rungs add - over a net's or a spread's layers, over a spectrum's components - run in an order the maps do
-not permute (unlike the bed's corners), so they keep the predicate without a tolerance.
+The sums the later rungs add - over a net's or a spread's layers, over a spectrum's components, over a profile's knots, over
+the steps of a statistics record - run in an order the maps do not permute (unlike the bed's corners), so they keep the
+predicate without a tolerance.
 
 One function per record kind; each returns the IMAGE of a record (the maps are involutions: the image of the image is the
 record).  `equal` is the predicate: float equality with NaN == NaN, so -0 == +0 (a dry body returns +0 and the image of +0
@@ -114,13 +128,63 @@ def extremes(g, e):
 
 
 def sea(g, s):
-    """A sea.SeaState or a sea.SeaSpectrum (the image is of the same kind): the current and the wave vector (kx, ky) are polar -
-    never a heading angle."""
+    """A sea.SeaState, a sea.SeaSpectrum or a sea.SeaEnsemble (the image is of the same kind): the current and the wave vector
+    (kx, ky) are polar - never a heading angle; a spectrum's depth is a scalar and the image has it; an ensemble maps member by
+    member, in the members' order, over the same bodies_per_sea."""
+    if hasattr(s, "members"):
+        return type(s)([sea(g, member) for member in s.members], s.bodies_per_sea)
     sx, sy, sz = POLAR[g]
-    out = type(s)((sx * s.current[0], sy * s.current[1], sz * s.current[2]))
+    current = (sx * s.current[0], sy * s.current[1], sz * s.current[2])
+    out = type(s)(current, s.depth) if hasattr(s, "depth") else type(s)(current)
     for a, kx, ky, om, ph in s.waves:
         out.add_wave(a, sx * kx, sy * ky, om, ph)
     return out
+
+
+def current_profile(g, p):
+    """A sea.CurrentProfile: the knots' z_l are scalars, the V_l polar."""
+    return type(p)(p.z, _times(p.v, POLAR[g]))
+
+
+def flips(g, channel):
+    """Whether the map changes the sign of a statistics channel (0 .. 6: x, y, z, vx, vy, vz, tension)."""
+    return channel < 6 and POLAR[g][channel % 3] < 0
+
+
+def levels(g, lev, channels):
+    """(n, 2) reference levels of the two channel slots: the level of a flipped channel changes sign."""
+    return _times(lev, tuple(-1 if flips(g, c) else 1 for c in channels))
+
+
+def statistics(g, rec, channels):
+    """The statistics record as statistics.unpack gives it - sums (n, 4), up (n, 2), n (n,) - taken against `levels()`: a flipped
+    slot's S1 changes sign and its S2 keeps its bits; its up-crossing word is NOT predicted (an up-crossing of L by x is a
+    down-crossing of -L by -x) and 0 stands in its place: compare through `statistics_words` and `statistics_left_out`."""
+    sums, up = np.array(rec["sums"], np.float64, copy=True), np.array(rec["up"], np.uint32, copy=True)
+    for slot, c in enumerate(channels):
+        if flips(g, c):
+            sums[:, 2 * slot] = -sums[:, 2 * slot]
+            up[:, slot] = 0
+    return {"sums": sums, "up": up, "n": np.array(rec["n"], np.uint32, copy=True)}
+
+
+def statistics_words(rec):
+    """(n, 7) float64 [S1_a S2_a S1_b S2_b | up_a up_b | n] of a statistics record (a uint32 is exact in a double)."""
+    return np.concatenate([np.asarray(rec["sums"], np.float64), np.asarray(rec["up"], np.float64), np.asarray(rec["n"], np.float64)[:, None]], axis=1)
+
+
+def statistics_left_out(g, channels):
+    """The columns of `statistics_words` that are not comparable under g: the up-crossing word of each flipped slot."""
+    return [4 + slot for slot, c in enumerate(channels) if flips(g, c)]
+
+
+def statistics_differing(g, got, want, channels):
+    """(n,) bool: the bodies on which the record `got` of the image, mapped back by `statistics`, differs from the scene's `want` -
+    the up-crossing word of a flipped slot left out on both sides."""
+    a, b = statistics_words(got), statistics_words(want)
+    cols = statistics_left_out(g, channels)
+    a[:, cols], b[:, cols] = 0.0, 0.0
+    return differing(a, b)
 
 
 def sea_sample(g, w):

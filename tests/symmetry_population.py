@@ -8,6 +8,10 @@ the device (tests/test_symmetry_gpu.py) and 59 % of the population as drawn stan
 the spread are drawn anew from the moved states (every anchored line is built from its own body's state; the ties at bodies
 0 .. 7 are not moved and keep their records); the controller's targets follow the bodies in z.  The tether net is NOT drawn anew:
 its lines join two bodies, and the moved population keeps enough of them pulling (asserted in tests/test_symmetry.py).
+
+For the rungs that know a depth (finite-depth sea, sheared current) the module also says in which water the population stands
+(`FD_DEPTH`, `fd_sea`, `fd_ensemble`), measures its water column by the fp64 reference (`column_shares`) and builds the probe
+population that holds a body in every knot interval of a profile (`knot_population`).
 """
 import numpy as np
 
@@ -47,3 +51,58 @@ def follow(ctl, drawn, moved):
 def net_of(pop, n, layers=NET_LAYERS):
     """The net of the first n bodies: tether_net_population.net_for."""
     return net_for(pop["net"], n, layers)
+
+
+# ---- the water column of the finite-depth and sheared-current rungs ---------------------------------------------------------------------
+# The reseated population lies between z = -3.6 m and z = -2.0 m, over the bed of the bed tests at z = -3 m: in water of THAT depth
+# 70 % of it sits strictly inside the column and 28 .. 30 % on the clamp zc = -h (tests/test_symmetry.py asserts both and prints
+# the rest).  Nobody reaches the surface clamp zc = 0 at any depth - the bodies are two metres down and the designed sea's
+# amplitudes sum to less - so the probes also run on sea_depth_reference.population(), which covers the column by construction,
+# and on `knot_population`, which puts a body into every knot interval.
+FD_DEPTH = 3.0
+
+
+def fd_sea(components=64, depth=FD_DEPTH):
+    """sea_depth_reference.designed_sea in the depth the resident rungs run at."""
+    import sea_depth_reference as sdr
+    return sdr.designed_sea(components, depth)
+
+
+def fd_ensemble(waves, n, tiles_per_sea, depth=FD_DEPTH):
+    """sea_ensemble_harness.ensemble(waves, n, tiles_per_sea), every member given `depth`."""
+    import sea_depth_reference as sdr
+    import sea_ensemble_harness as seh
+    from silver2_isaacsim_amd.sea import SeaEnsemble
+    ens = seh.ensemble(waves, n, tiles_per_sea)
+    return SeaEnsemble([sdr.with_depth(m, depth) for m in ens.members], ens.bodies_per_sea)
+
+
+def column_shares(sea, profile, st, step, dt):
+    """By the fp64 reference: dict(inside, surface, bed: the shares of bodies with -h < zc < 0, zc = 0, zc = -h; intervals: the
+    number of the profile's knot intervals that hold a body strictly inside; eta: whether eta is non-zero for every body)."""
+    import sea_depth_reference as sdr
+    h = sea.depth
+    eta, _ = sdr.water(sea, st[:, 0], st[:, 1], st[:, 2], step, dt)
+    zc = np.clip(st[:, 2].astype(np.float64) - eta, -h, 0.0)
+    inside = (zc > -h) & (zc < 0.0)
+    held = np.histogram(zc[inside], bins=profile.z)[0] if profile is not None and profile.knots > 1 else np.zeros(0, int)
+    return dict(inside=float(inside.mean()), surface=float((zc == 0.0).mean()), bed=float((zc == -h).mean()), intervals=int((held > 0).sum()),
+                eta=bool((eta != 0.0).all()))
+
+
+def knot_population(profile, sea, step, dt, per_interval=2):
+    """(n, 13) fp32 states within 40 m of the origin with `per_interval` bodies in EVERY knot interval of `profile` at `step`: eta
+    does not depend on p_z, so p_z = eta(x, y) + (a point of the interval) in fp64, rounded once.  The lowest interval of the
+    16-knot turning profile is 0.06 mm wide at h = 3 m; an fp32 p_z near 3 m resolves 0.2 micrometres."""
+    import sea_depth_reference as sdr
+    rng = np.random.default_rng(35)
+    lo, hi = profile.z[:-1], profile.z[1:]
+    frac = (np.arange(per_interval) + 1.0) / (per_interval + 1.0)
+    zc = (lo[:, None] + frac[None, :] * (hi - lo)[:, None]).reshape(-1)
+    st = np.zeros((len(zc), 13), np.float32)
+    st[:, 0:2] = rng.uniform(-40.0, 40.0, (len(zc), 2))
+    eta, _ = sdr.water(sea, st[:, 0], st[:, 1], np.zeros(len(zc)), step, dt)
+    st[:, 2] = (eta + zc).astype(np.float32)
+    st[:, 6] = 1.0
+    st[:, 7:10] = rng.uniform(-0.5, 0.5, (len(zc), 3))
+    return st

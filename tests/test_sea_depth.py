@@ -68,10 +68,13 @@ def test_header_and_binding_carry_the_entries():
                    "no finite-depth sea set : the launch and its bits are those of hydro_step_fused_tiled_multi_ens", "Set z_b = -h", "DESIGN.md section 32",
                    # out of scope, and said so
                    "depth-limited spectral shape (TMA)", "shoaling, breaking and a sloping bed", "depth in the 8-wave", "open-loop entries", "the plugin",
-                   "members of different depths", "sign-symmetry",
+                   "members of different depths",
+                   # the symmetry statement: positive since tests/test_symmetry_gpu.py runs this rung
+                   "SIGN SYMMETRY: exact at any depth",
                    # the sentences about the deep entries stay: they remain true of the entries they describe
                    "finite depth", "stays the deep-water one however shallow z_b makes the scene"):
         assert phrase in text, phrase
+    assert "a sign-symmetry statement" not in text                # no rung disclaims it any more
 
 
 def test_the_calls_are_plain_c(tmp_path):

@@ -62,8 +62,11 @@ def test_header_and_binding_carry_the_entries():
                    "no ensemble set : the launch and its bits are those of hydro_step_fused_tiled_multi_stat", "comes LAST",
                    "capture current-only members", "multiple of 256 bodies", "DESIGN.md section 31",
                    # out of scope, and said so
-                   "members with different component counts", "a per-body index table", "open-loop entries", "the plugin", "sign-symmetry"):
+                   "members with different component counts", "a per-body index table", "open-loop entries", "the plugin",
+                   # the symmetry statement: positive since tests/test_symmetry_gpu.py runs the ensemble
+                   "SIGN SYMMETRY: exact, member by member"):
         assert phrase in text, phrase
+    assert "a sign-symmetry statement" not in text                # no rung disclaims it any more
 
 
 def test_the_calls_are_plain_c(tmp_path):

@@ -31,7 +31,7 @@ from silver2_isaacsim_amd.simulate import ClosedLoopSim
 from designed_populations import BED, bed_pop, hold_pop, SEA  # noqa: F401  (fixtures are requested by name)
 from mooring_population import line_population, moored_pop  # noqa: F401  (fixtures are requested by name)
 from mooring_spread_population import spread_population
-from resident_harness import (_buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, _from, _guarded, _ke, _log, NAN, _rows, S_A, S_C, S_IN, S_OUT, S_PV,
+from resident_harness import (_buffers, COEFFS, COEFFS_SEMANTICS, DEV, DRAG, DT, _engine, _from, _guarded, _in_one_allocation, _ke, _log, NAN, _rows, S_A, S_C, S_IN, S_OUT, S_PV,
                               S_PVO, _same_bits, _tiled, _unguard, _untouched, _watched)
 from tether_net_population import net_for, net_population
 
@@ -458,6 +458,9 @@ def test_refusals_launch_nothing_and_leave_both_records(pop, native_built):
     out = torch.full((tiles * S_OUT,), NAN, device=DEV)
     pvo = torch.full((tiles * S_PVO,), NAN, device=DEV)
     record = _guarded_record(n)
+    # one allocation, a fixed order, gaps wider than any record's extent: a buffer handed over as ANOTHER record below makes the
+    # library claim that record's extent from its address, and the claim must meet nothing but the buffer itself
+    state, prev, lv, a, c17, m27, net, e8, p2, out, pvo, record = _in_one_allocation(state, prev, lv, a, c17, m27, net, e8, p2, out, pvo, record)
     E_ARG = -1
     last = lambda: eng._lib.hydro_last_error(eng._h).decode()  # noqa: E731
     # the reset's own refusals
@@ -499,8 +502,8 @@ def test_refusals_launch_nothing_and_leave_both_records(pop, native_built):
     assert all(torch.isnan(x).all() for x in (out, pvo, e8, p2))
     assert np.array_equal(_words(record), was) and _untouched(lv, lv_was)
     # the legal launch next to them
-    e8 = _guarded(Extremes.empty(n), S_E)
-    p2 = _guarded(np.zeros((n, 2), np.float32), S_P2)
+    e8.copy_(_guarded(Extremes.empty(n), S_E))
+    p2.copy_(_guarded(np.zeros((n, 2), np.float32), S_P2))
     assert call(steps=3, extremes=e8, peaks=p2) == (0, 0)
     torch.cuda.synchronize()
     got, rest = sx.unguard(_words(record), n)

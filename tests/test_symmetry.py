@@ -21,6 +21,15 @@
     says so if it stops holding).  Teeth: the tether's fairlead turned like an axial vector, a spread with one layer left
     unmapped, a spectrum whose ky is not flipped under mirror_y.  And the population of the resident rungs
     (tests/symmetry_population.py) is what tests/test_symmetry_gpu.py needs: few order-sensitive bodies, enough lines pulling.
+(f) The rungs behind _irr - statistics, sea ensemble, finite depth, sheared current.  symmetry.sea carries a spectrum's depth and
+    maps an ensemble member by member in the members' order.  The fp32 restatements - sea_depth_reference.water_fp32 and
+    current_profile_reference.profile_exact composed with it as the header composes them - give the predicted image EXACTLY: the
+    constants change sign only ((kx, ky), (cx, cy), U, V_0, D_l), the phase fma(kx, p_x, fma(ky, p_y, tau)) and eta keep their
+    bits.  The fp64 restatements (sea_depth_reference.water, current_profile_reference.water) agree with their images to 1e-12 of
+    the scales.  statistics.fold over mirrored samples and levels is symmetry.statistics of the fold, the up-crossing word of a
+    flipped channel left out (an up-crossing of L by x is a down-crossing of -L by -x) - and that word really differs.  Teeth: a
+    finite-depth sea whose ky is not flipped, a profile turned like an axial vector.  And the water column of the populations the
+    device tests run, by the fp64 reference: the shares inside the column and on its two clamps, the knot intervals held.
 """
 import ctypes
 import os
@@ -29,11 +38,14 @@ import sys
 import numpy as np
 import pytest
 
+import current_profile_reference as cpr
 import extremes_reference as er
 import mooring_reference as mr
 import mooring_spread_reference as msr
 import populations
 import pose_hold_reference as phr
+import sea_depth_reference as sdr
+import sea_ensemble_harness as seh
 import sea_reference as sr
 import sea_spectrum_reference as ssr
 import seabed_reference as br
@@ -46,6 +58,8 @@ from conftest import REPO, accel_of, load_golden
 from oracle import c_oracle
 from oracle import hydro_oracle as ho
 from oracle import integrator_oracle as io
+from sea_spectrum_reference import _fmaf
+from silver2_isaacsim_amd import statistics as stx
 from silver2_isaacsim_amd.extremes import Extremes
 from designed_populations import BED, bed_pop, contributing_corners, hold_pop, SEA, tilted_boxes  # noqa: F401  (fixtures are requested by name)
 from mooring_population import moored_pop as pop  # noqa: F401  (fixtures are requested by name)
@@ -553,3 +567,211 @@ def test_reseated_population_is_what_the_resident_rungs_need(n, reseated):
     assert np.array_equal(reseated["spread"][:n, 0:9], reseated["lines"][:n])
     still = reseated["st"][:n, 2] == reseated["drawn"][:n, 2]
     assert still[:8].all() and 0.1 <= still.mean() <= 0.5
+
+
+# ---- (f) ensembles, finite depth, the sheared current and the statistics fold ------------------------------------------------------------
+STEP0 = 11                                                        # the first step of the resident launches of tests/test_symmetry_gpu.py
+
+
+def _column_cases(reseated):
+    """[(name, sea, states)]: the reseated population in the designed sea at symmetry_population.FD_DEPTH - what the resident rungs
+    run - and sea_depth_reference.population() in the designed sea at its own depth - what the probes also run."""
+    return [("reseated", symmetry_population.fd_sea(), reseated["st"]), ("column", sdr.designed_sea(), sdr.population())]
+
+
+def test_the_sea_map_carries_the_depth_and_keeps_the_members_in_order():
+    """symmetry.sea on a spectrum with a depth gives a spectrum of that depth; on an ensemble the images of the members, in the
+    members' order, over the same bodies_per_sea."""
+    for g in sym.MAPS:
+        spec = symmetry_population.fd_sea(11)
+        image = sym.sea(g, spec)
+        assert type(image) is type(spec) and image.depth == spec.depth == symmetry_population.FD_DEPTH and len(image.waves) == 11
+        assert sym.sea(g, ssr.truncated(FULL, 11)).depth is None
+        for ens in (seh.ensemble(11, 321, 1), symmetry_population.fd_ensemble(11, 321, 4)):
+            ens_g = sym.sea(g, ens)
+            assert type(ens_g) is type(ens) and ens_g.count == ens.count and ens_g.bodies_per_sea == ens.bodies_per_sea and ens_g.depth == ens.depth
+            for a, b in zip(ens_g.members, ens.members):
+                want = sym.sea(g, b)
+                assert a.current == want.current and a.waves == want.waves and a.waves != b.waves
+            back = sym.sea(g, ens_g)                               # an involution
+            assert all(a.current == b.current and a.waves == b.waves for a, b in zip(back.members, ens.members))
+
+
+@MAPS
+@pytest.mark.parametrize("count", [11, 64])
+def test_finite_depth_restatement_fp32_is_exactly_symmetric(g, count, reseated):
+    """sea_depth_reference.water_fp32, the header's arithmetic: the constants of the image are the constants with the signs of a
+    polar vector on (kx, ky), (cx, cy) and U and nothing else changed; the phase fma(kx, p_x, fma(ky, p_y, tau)) is the same
+    bits; eta keeps its bits and u is the image of u - steps 0, 11 and 10^6."""
+    sx, sy, _ = sym.POLAR[g]
+    for name, full, st in _column_cases(reseated):
+        sea = sdr.truncated(full, count)
+        sea_g, image = sym.sea(g, sea), sym.state(g, st)
+        rows, q = sdr.device_constants(sea, sea.depth)
+        rows_g, q_g = sdr.device_constants(sea_g, sea_g.depth)
+        assert q_g == q
+        for (a, kx, ky, kl2, cx, cy, aw, gl), row_g in zip(rows, rows_g):
+            assert sym.equal(np.float32(row_g), np.float32((a, sx * kx, sy * ky, kl2, sx * cx, sy * cy, aw, gl))), (g, name)
+            tau = np.float32(0.37)
+            th = _fmaf(kx, st[:, 0], _fmaf(ky, st[:, 1], np.full(len(st), tau, np.float32)))
+            th_g = _fmaf(row_g[1], image[:, 0], _fmaf(row_g[2], image[:, 1], np.full(len(st), tau, np.float32)))
+            assert np.array_equal(th_g.view(np.uint32), th.view(np.uint32)), (g, name)
+        for step in (0, STEP0, 10 ** 6):
+            eta, u = sdr.water_fp32(sea, st[:, 0], st[:, 1], st[:, 2], step, DT)
+            eta_g, u_g = sdr.water_fp32(sea_g, image[:, 0], image[:, 1], image[:, 2], step, DT)
+            assert eta.dtype == np.float32 and np.array_equal(eta_g.view(np.uint32), eta.view(np.uint32)), (g, name, step)
+            assert sym.equal(u_g, sym._times(u, sym.POLAR[g])), (g, name, step)
+            assert eta.all() and u.all() and np.isfinite(u).all()
+
+
+def _sheared_fp32(sea, profile, st, step):
+    """(eta, u) of the exact restatements composed as the header composes them: water_fp32, the clamped depth, profile_exact, one
+    fp32 add per component."""
+    eta, u = sdr.water_fp32(sea, st[:, 0], st[:, 1], st[:, 2], step, DT)
+    zc = cpr.clamped_depth(st[:, 2], eta, sea.depth)
+    return eta, u + cpr.profile_exact(profile, zc), zc
+
+
+@MAPS
+@pytest.mark.parametrize("knots", [2, 16])
+def test_current_profile_restatement_is_exactly_symmetric(g, knots, reseated):
+    """current_profile_reference.profile_exact on the depths water_fp32 gives, and the two composed: the image's table is V_0 and
+    every D_l with the signs of a polar vector, z_l and inv_l unchanged; the profile and the sheared water of the image are the
+    images, eta the same bits.  The 16-knot turning profile's V_x and V_z and its slopes D_l,y and D_l,z take both signs (its
+    heading turns from 200 to 320 degrees: V_y itself stays negative and V_x only grows)."""
+    for name, full, st in _column_cases(reseated):
+        sea = sdr.truncated(full, 11)
+        profile = cpr.turning_profile(knots, depth=sea.depth)
+        profile_g, sea_g, image = sym.current_profile(g, profile), sym.sea(g, sea), sym.state(g, st)
+        for a, b, signs in zip(profile_g.table(), profile.table(), (sym.POLAR[g], 1, 1, sym.POLAR[g])):
+            assert sym.equal(a, sym._times(b, signs)), (g, name)
+        assert np.array_equal(profile_g.z, profile.z) and not sym.equal(profile_g.v, profile.v)
+        slopes = profile.table()[3]
+        assert knots < 16 or all((x > 0).any() and (x < 0).any() for x in (profile.v[:, 0], profile.v[:, 2], slopes[:, 1], slopes[:, 2]))
+        for step in (0, STEP0, 10 ** 6):
+            eta, u, zc = _sheared_fp32(sea, profile, st, step)
+            eta_g, u_g, zc_g = _sheared_fp32(sea_g, profile_g, image, step)
+            assert np.array_equal(eta_g.view(np.uint32), eta.view(np.uint32)) and np.array_equal(zc_g.view(np.uint32), zc.view(np.uint32)), (g, name, step)
+            assert sym.equal(cpr.profile_exact(profile_g, zc_g), sym._times(cpr.profile_exact(profile, zc), sym.POLAR[g])), (g, name, step)
+            assert sym.equal(u_g, sym._times(u, sym.POLAR[g])), (g, name, step)
+
+
+@MAPS
+def test_finite_depth_and_sheared_water_fp64_are_symmetric(g, reseated):
+    """sea_depth_reference.water and current_profile_reference.water: 1e-12 of sea_depth_reference.scales (the profile: and of
+    max |V|) - the suite's fp64 figure."""
+    for name, sea, st in _column_cases(reseated):
+        profile = cpr.turning_profile(16, depth=sea.depth)
+        sea_g, profile_g, image = sym.sea(g, sea), sym.current_profile(g, profile), sym.state(g, st)
+        s_eta, s_u = sdr.scales(sea, sea.depth)
+        for step in (0, STEP0, 10 ** 6):
+            for shear in (False, True):
+                if shear:
+                    eta, u = cpr.water(sea, profile, st[:, 0], st[:, 1], st[:, 2], step, DT)
+                    eta_g, u_g = cpr.water(sea_g, profile_g, image[:, 0], image[:, 1], image[:, 2], step, DT)
+                else:
+                    eta, u = sdr.water(sea, st[:, 0], st[:, 1], st[:, 2], step, DT)
+                    eta_g, u_g = sdr.water(sea_g, image[:, 0], image[:, 1], image[:, 2], step, DT)
+                assert (np.abs(eta_g - eta) <= TOL * s_eta).all(), (g, name, step, shear)
+                assert (np.abs(sym._times(u_g, sym.POLAR[g]) - u) <= TOL * (s_u + shear * np.abs(profile.v).max())).all(), (g, name, step, shear)
+                assert np.isfinite(u).all() and eta.all()
+
+
+@MAPS
+@pytest.mark.parametrize("pair", [(2, 6), (0, 4), (3, 1)], ids=["z-tension", "x-vy", "vx-y"])
+def test_statistics_fold_is_symmetric_but_for_the_up_word_of_a_flipped_channel(g, pair, reseated):
+    """statistics.fold over 24 samples of a swaying population and over their images, against symmetry.levels: the record of the
+    image is symmetry.statistics of the record - a slot the map does not flip keeps every word, a flipped slot has S1 negated and
+    S2 the same bits, n the same - with the up-crossing word of a flipped slot left out: an up-crossing of L by x is a
+    down-crossing of -L by -x.  The words left out really differ on some body, and up-crossings really occur."""
+    rng = np.random.default_rng(36)
+    st = reseated["st"]
+    n, rows = len(st), 24
+    sway = np.sin(np.arange(rows)[:, None, None] * rng.uniform(0.5, 2.5, (1, n, 13)) + rng.uniform(0, 6.28, (1, n, 13))) * rng.uniform(0.01, 0.5, (1, n, 13))
+    states = (st[None].astype(np.float64) + sway).astype(np.float32)
+    tension = np.maximum(rng.normal(0.0, 50.0, (rows, n)), 0.0).astype(np.float32)
+    lev = np.stack([np.zeros(n, np.float32) if c == 6 else st[:, stx.STATE_FIELD[c]] for c in pair], axis=1)
+    lev = (lev + rng.choice(np.array([-1e-3, 0.0, 1e-3], np.float32), size=lev.shape)).astype(np.float32)
+    want = stx.fold(None, stx.samples_of(states, tension, pair[0]), stx.samples_of(states, tension, pair[1]), lev)
+    image = sym.state(g, states)
+    got = stx.fold(None, stx.samples_of(image, tension, pair[0]), stx.samples_of(image, tension, pair[1]), sym.levels(g, lev, pair))
+    back = sym.statistics(g, got, pair)
+    assert not sym.statistics_differing(g, back, want, pair).any()
+    assert (got["n"] == rows).all() and (stx.upcrossings(want, 0) > 0).mean() > 0.5 and (stx.upcrossings(want, 1) > 0).mean() > 0.25
+    left_out = sym.statistics_left_out(g, pair)
+    assert left_out == [4 + slot for slot, c in enumerate(pair) if c < 6 and sym.POLAR[g][c % 3] < 0]
+    for slot, c in enumerate(pair):
+        if 4 + slot in left_out:
+            assert sym.equal(got["sums"][:, 2 * slot], -want["sums"][:, 2 * slot]) and sym.equal(got["sums"][:, 2 * slot + 1], want["sums"][:, 2 * slot + 1])
+            assert (got["up"][:, slot] != want["up"][:, slot]).any() and want["sums"][:, 2 * slot].any()
+        else:
+            assert sym.equal(got["sums"][:, 2 * slot:2 * slot + 2], want["sums"][:, 2 * slot:2 * slot + 2]) and np.array_equal(got["up"][:, slot], want["up"][:, slot])
+    assert len(left_out) == {"mirror_y": {(2, 6): 0, (0, 4): 1, (3, 1): 1}, "mirror_x": {(2, 6): 0, (0, 4): 1, (3, 1): 1},
+                             "half_turn": {(2, 6): 0, (0, 4): 2, (3, 1): 2}}[g][pair]
+
+
+# teeth
+@pytest.mark.parametrize("count", [11, 64])
+def test_teeth_a_finite_depth_sea_whose_ky_is_not_flipped_breaks_the_equality(count, reseated):
+    """mirror_y with every component's ky left alone, through water_fp32: at least half of the bodies differ in eta or u."""
+    g = "mirror_y"
+    for name, full, st in _column_cases(reseated):
+        sea = sdr.truncated(full, count)
+        wrong = sdr.with_depth(sea, sea.depth)
+        wrong.current = sym.sea(g, sea).current
+        image = sym.state(g, st)
+        eta, u = sdr.water_fp32(sea, st[:, 0], st[:, 1], st[:, 2], STEP0, DT)
+        eta_w, u_w = sdr.water_fp32(wrong, image[:, 0], image[:, 1], image[:, 2], STEP0, DT)
+        bad = sym.differing(eta_w, eta) | sym.differing(u_w, sym._times(u, sym.POLAR[g]))
+        print(f"[teeth, a finite-depth sea whose ky is not flipped, {count} components, {name}] differing: {bad.mean():.1%} of {len(st)} bodies")
+        assert bad.mean() >= 0.5
+
+
+@MAPS
+@pytest.mark.parametrize("knots", [2, 16])
+def test_teeth_an_axial_profile_breaks_the_equality(g, knots, reseated):
+    """The profile's V_l turned like an axial vector (under the half turn: left unturned): the sheared water differs from the image
+    on at least half of the bodies."""
+    for name, full, st in _column_cases(reseated):
+        sea = sdr.truncated(full, 11)
+        profile = cpr.turning_profile(knots, depth=sea.depth)
+        wrong = type(profile)(profile.z, sym._times(profile.v, sym.AXIAL[g] if g != "half_turn" else sym.SAME3))
+        image = sym.state(g, st)
+        _, u, _ = _sheared_fp32(sea, profile, st, STEP0)
+        _, u_w, _ = _sheared_fp32(sym.sea(g, sea), wrong, image, STEP0)
+        bad = sym.differing(u_w, sym._times(u, sym.POLAR[g]))
+        print(f"[teeth, a profile turned like an axial vector, {g}, {knots} knots, {name}] differing: {bad.mean():.1%} of {len(st)} bodies")
+        assert bad.mean() >= 0.5
+
+
+# the water column of the populations tests/test_symmetry_gpu.py runs, by the fp64 reference alone
+def test_the_column_populations_are_what_the_finite_depth_and_shear_tests_need(reseated):
+    """On the reseated population in water of symmetry_population.FD_DEPTH, at the resident launches' first step, n = 200 and 321:
+    at least 20 % of the bodies strictly inside the column, at least 5 % on the clamp zc = -h, eta non-zero for every body, the
+    2-knot profile's one interval held and at least 8 of the 16-knot profile's 15 (its five lowest lie within 4 cm of the bed).  The
+    surface clamp zc = 0 is NOT met by this population at any depth - it lies two metres down - and seven intervals stay empty:
+    both are printed, and the probes make up for them: sea_depth_reference.population() meets all three shares at steps 0 and
+    10^6, and symmetry_population.knot_population holds a body in EVERY interval, on the scene and on its three images."""
+    for n in SIZES:
+        st = reseated["st"][:n]
+        sea = symmetry_population.fd_sea()
+        got = symmetry_population.column_shares(sea, cpr.turning_profile(16, depth=sea.depth), st, STEP0, DT)
+        two = symmetry_population.column_shares(sea, cpr.turning_profile(2, depth=sea.depth), st, STEP0, DT)
+        print(f"[reseated population in {sea.depth:g} m of water, n = {n}, step {STEP0}] inside {got['inside']:.1%}, zc = -h {got['bed']:.1%}, zc = 0 {got['surface']:.1%}; "
+              f"knot intervals held: {got['intervals']} of 15 (2 knots: {two['intervals']} of 1)")
+        assert got["inside"] >= 0.2 and got["bed"] >= 0.05 and got["eta"] and two["intervals"] == 1 and got["intervals"] >= 8
+        for g in sym.MAPS:
+            assert symmetry_population.column_shares(sym.sea(g, sea), cpr.turning_profile(16, depth=sea.depth), sym.state(g, st), STEP0, DT) == got, g
+    sea, st = sdr.designed_sea(), sdr.population()
+    for step in (0, 10 ** 6):
+        got = symmetry_population.column_shares(sea, cpr.turning_profile(16), st, step, DT)
+        print(f"[sea_depth_reference.population() in {sea.depth:g} m, step {step}] inside {got['inside']:.1%}, zc = -h {got['bed']:.1%}, zc = 0 {got['surface']:.1%}; "
+              f"knot intervals held: {got['intervals']} of 15")
+        assert got["inside"] >= 0.2 and got["bed"] >= 0.05 and got["surface"] >= 0.05 and got["eta"]
+    for sea in (sdr.designed_sea(), symmetry_population.fd_sea()):
+        for knots in (2, 16):
+            profile = cpr.turning_profile(knots, depth=sea.depth)
+            st = symmetry_population.knot_population(profile, sea, 0, DT)
+            assert symmetry_population.column_shares(sea, profile, st, 0, DT)["intervals"] == knots - 1
+            for g in sym.MAPS:
+                assert symmetry_population.column_shares(sym.sea(g, sea), profile, sym.state(g, st), 0, DT)["intervals"] == knots - 1

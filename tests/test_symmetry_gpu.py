@@ -62,13 +62,39 @@ ON AN MI355X (f32 and f16 coefficients, both semantics, explicit and implicit dr
                         302 / 303 exact, 19 / 18 thrown through FAR's plane)
   teeth on the device   the net's fairleads turned like axial vectors: 48 .. 58 % of the bodies differ from the predicted image
                         after one step; the spectrum's ky not flipped under mirror_y: 100 %
+  top probes            hydro_sea_ensemble_sample (tiles_per_sea 1 and 4), hydro_sea_finite_depth_sample (an ensemble of one, an
+                        ensemble) and hydro_current_profile_sample (no profile, 2 and 16 knots), 11 and 64 components, steps 0
+                        and 10^6, on 200 and 321 bodies in 3 m of water, sea_depth_reference.population() (130 bodies over the
+                        column of 9 m) and a body in every knot interval: 324 images, 0 differ, eta the same bits
+  top rungs             stat, ens (tiles_per_sea 1 and 4), fd (an ensemble of one, an ensemble), shear (16 knots, 2 knots), each with
+                        everything on and a statistics record over (z, tension) and over (x, vy).  Over FAR at 1 and 7 steps:
+                        200 / 321 exact, none left out, under implicit drag and after one explicit step - log, state, prev_out,
+                        extremes, link tensions, the record (the up-crossing word of a flipped slot left out) and the energy
+                        pair; after 7 explicit steps 10 .. 17 of 200 and 18 .. 21 of 321 thrown through FAR's plane and left out.
+                        Over BED, one step: 175 / 277 exact, 25 / 44 left out (12 % / 14 %), every case, either drag, f32 and
+                        f16.  0 bodies differ.
+  shear variants        non_temporal = 1 and Warp semantics, FAR, 7 steps, n = 321: 321 exact under implicit drag (explicit:
+                        300 / 302 exact, 21 / 19 thrown through FAR's plane)
+  open-loop sea entries hydro_step_wrench_tiled_sea / _aos_sea under the 8-wave sea, _tiled_irr / _aos_irr under the spectrum, an
+                        ensemble and a finite-depth ensemble, both quaternion orders, with the samples at a time, times 0, 7 dt
+                        and 10^6 dt: edge_cases 81 bodies (68 wet; 79 under the ensembles), tests/symmetry_population.py 321
+                        (all wet) x 3 maps: 0 differ in the wrench, the engine-owned previous velocity or the sample
+  top teeth             one implicit step over FAR, n = 200 and 321: the finite-depth sea's ky not flipped under mirror_y 100 %
+                        of the bodies differ; the profile's V_l turned like an axial vector (mirror_y, mirror_x) 100 %; ONE
+                        member of the ensemble left unturned 100 % of that member's 64 bodies and not one body of another member
+  ClosedLoopSim, top    64 moored buoys in a depth-carrying ensemble under the 16-knot profile and their mirror_y image, 20
+                        steps in chunks of 7: 0 bodies differ
 So every device entry is exactly sign-symmetric under all three maps, but for the bed's corner sum - an order asymmetry, not
-a term of the wrong hand: no body with fewer than two contributing corners ever differs."""
+a term of the wrong hand: no body with fewer than two contributing corners ever differs.  (The statistics record's up-crossing
+word of a flipped channel is no exception to that: the image counts the scene's DOWN-crossings, tests/symmetry.py.)"""
 import numpy as np
 import pytest
 import torch
 
+import current_profile_reference as cpr
 import populations
+import sea_depth_reference as sdr
+import sea_ensemble_harness as seh
 import sea_reference as sr
 import sea_spectrum_reference as ssr
 import seabed_reference as br
@@ -77,10 +103,12 @@ import symmetry_population
 from conftest import load_golden
 from oracle import hydro_oracle as ho
 from oracle import integrator_oracle as io
+from silver2_isaacsim_amd import _native as nat
 from silver2_isaacsim_amd import scenes
+from silver2_isaacsim_amd import statistics as stx
 from silver2_isaacsim_amd.engine import HydroEngine
 from silver2_isaacsim_amd.mooring import Mooring
-from silver2_isaacsim_amd.sea import SeaState
+from silver2_isaacsim_amd.sea import SeaEnsemble, SeaState
 from silver2_isaacsim_amd.simulate import ClosedLoopSim
 from designed_populations import BED, bed_pop, contributing_corners, FAR, hold_pop, SEA, tilted_boxes  # noqa: F401  (fixtures are requested by name)
 from mooring_population import _buoys, DEPTH, line_population, moored_pop as pop  # noqa: F401  (fixtures are requested by name)
@@ -111,14 +139,22 @@ def engines(native_built):
         eng = made[k]
         eng.set_tuning()
         eng.set_semantics("numba")
-        eng.set_sea_spectrum(None)
-        eng.set_sea(None)
+        _no_water(eng)
         eng.set_seabed(None)
         eng.set_watch(None)
         return eng
     yield get
     for eng in made.values():
         eng.close()
+
+
+def _no_water(eng):
+    """Clear the profile and every kind of sea (they exclude each other: one must go before another is set)."""
+    eng.set_current_profile(None)
+    eng.set_sea_finite_depth(None)
+    eng.set_sea_ensemble(None)
+    eng.set_sea_spectrum(None)
+    eng.set_sea(None)
 
 
 def _soa(x):
@@ -355,55 +391,79 @@ def resident_pops(pop):
 ENTRIES = ("rec", "app-world", "app-body", "ctl", "ctl+app", "sea", "bed", "moor", "ext", "all", "all-far")
 WITH_BED = ("bed", "moor", "ext", "all")
 LATER = ("teth", "net", "peak", "spread", "irr")                  # the rungs behind _ext: each launched with everything it takes
+TOP = ("stat", "ens", "fd", "shear")                              # the rungs behind _irr: everything _irr takes and a statistics record
+CHANNEL_PAIRS = ((stx.Z, stx.TENSION), (stx.X, stx.VY))           # nothing flips under any map; each flips under two maps
 
 
-def _wrong_hand(m, what, net, sea):
-    """(net, sea): the images of the scene's `net` and `sea` under m with ONE of them of the wrong hand, for the teeth.  `tether`:
-    every fairlead of the net turned like an axial vector (under the half turn, where polar and axial vectors turn alike: left
-    unturned); `ky`: the sea's ky left as the scene has it."""
-    net_g, sea_g = sym.net(m, net), sym.sea(m, sea)
+def _wrong_hand(m, what, net, sea, profile=None):
+    """(net, sea, profile): the images of the scene's `net`, `sea` and `profile` under m with ONE of them of the wrong hand, for the
+    teeth.  `tether`: every fairlead of the net turned like an axial vector (under the half turn, where polar and axial vectors
+    turn alike: left unturned); `ky`: the sea's ky left as the scene has it (a spectrum keeps its depth); `profile`: the
+    profile's V_l turned like an axial vector; ("member", k): member k of the ensemble left as the scene has it."""
+    net_g, sea_g, profile_g = sym.net(m, net), sym.sea(m, sea), None if profile is None else sym.current_profile(m, profile)
     if what == "tether":
         hand = sym.AXIAL[m] if m != "half_turn" else sym.SAME3
         for l in range(net.shape[1] // 7):
             net_g[:, 7 * l:7 * l + 3] = sym._times(net[:, 7 * l:7 * l + 3], hand)
     elif what == "ky":
-        wrong = type(sea)(sea_g.current)
+        wrong = type(sea)(sea_g.current, sea.depth) if hasattr(sea, "depth") else type(sea)(sea_g.current)
         for (a, kx, _, om, ph), (_, _, ky, _, _) in zip(sea_g.waves, sea.waves):
             wrong.add_wave(a, kx, ky, om, ph)
         sea_g = wrong
+    elif what == "profile":
+        profile_g = type(profile)(profile.z, sym._times(profile.v, sym.AXIAL[m] if m != "half_turn" else sym.SAME3))
+    elif what[0] == "member":
+        members = list(sea_g.members)
+        members[what[1]] = sea.members[what[1]]
+        sea_g = type(sea)(members, sea.bodies_per_sea)
     else:
         raise ValueError(what)
-    return net_g, sea_g
+    return net_g, sea_g, profile_g
 
 
-def _resident(eng, entry, P, n, steps, implicit, m=None, bed=BED, wrong=None):
+def _levels_near(st, channels):
+    """(n, 2) fp32 levels near the initial values of the two channels (the tension's: near 0): some above, some below, some equal."""
+    rng = np.random.default_rng(37)
+    lev = np.stack([np.zeros(len(st), np.float32) if c == stx.TENSION else st[:, stx.STATE_FIELD[c]] for c in channels], axis=1)
+    return (lev + rng.choice(np.array([-1e-3, 0.0, 1e-3], np.float32), size=lev.shape)).astype(np.float32)
+
+
+def _resident(eng, entry, P, n, steps, implicit, m=None, bed=BED, wrong=None, sea=None, profile=None, channels=CHANNEL_PAIRS[0]):
     """One launch of `entry` on the population P (m: on its image under that map), every body watched and every step
     recorded with its wrench; returns the outputs MAPPED BACK (the image of the image's outputs): dict of state, prev_out,
     log (steps, n, 19), and where the entry has them extremes, ke and the link tensions (peaks).  The LATER entries take two
     more records of P - the tether net (all bodies, all layers: cut to n by tether_net_population.net_for) and the mooring spread -
-    and the bed they run over (`bed`); `wrong`: see _wrong_hand."""
+    and the bed they run over (`bed`); `wrong`: see _wrong_hand.  The TOP entries take all of that and a statistics record of
+    `channels`, reset, against levels near the scene's initial values (the image's: symmetry.levels of them); the record comes
+    back as `stat`, symmetry.statistics_words of symmetry.statistics of it, with `left_out`, the columns that are not
+    comparable.  `sea`: what the entry steps through - _stat a spectrum (default: the 64 components), _ens an ensemble, _fd and
+    _shear a spectrum or an ensemble with a depth; `profile`: _shear's."""
     st, pv, params, applied, ctl, rec = (x if isinstance(x, dict) else x[:n] for x in P[:6])
-    later = entry in LATER
+    top = entry in TOP
+    later = entry in LATER or top
     net = net_for(P[6], n, 1 if entry == "teth" else symmetry_population.NET_LAYERS) if later else None
     spread = np.ascontiguousarray(P[7][:n, 0:9 * symmetry_population.SPREAD_LAYERS]) if later else None
     ident = m is None
-    sea = FULL if entry == "irr" else SEA
+    if sea is None:
+        sea = FULL if entry in ("irr", "stat") else SEA
+    lev = _levels_near(st, channels) if top else None
     if not ident:
         st, pv, applied, ctl, rec = sym.state(m, st), sym.prev(m, pv), sym.applied(m, applied), sym.control(m, ctl), sym.mooring(m, rec)
         if wrong is not None:
-            net, sea = _wrong_hand(m, wrong, net, sea)
+            net, sea, profile = _wrong_hand(m, wrong, net, sea, profile)
         else:
             net, sea = (sym.net(m, net) if later else None), sym.sea(m, sea)
+            profile = None if profile is None else sym.current_profile(m, profile)
         spread = sym.spread(m, spread) if later else None
+        lev = sym.levels(m, lev, channels) if top else None
     eng.set_watch(list(range(n)))
     cur, old = _buffers(st, pv, n)
     log = torch.full((steps, 19, n), NAN, dtype=torch.float32, device=DEV)
     a, c17, m9 = _tiled(applied), _tiled(ctl), _tiled(rec)
     kw = dict(implicit_drag=implicit)
     rk = dict(log=log, every=1, phase=1, row0=0)
-    ke = record = peaks = None
-    eng.set_sea_spectrum(None)
-    eng.set_sea(None)
+    ke = record = peaks = stat = None
+    _no_water(eng)
     eng.set_seabed(None)
     if entry == "rec":
         eng.step_fused_tiled_multi_rec(cur, old, n, DT, steps, log, 1, 1, 0, **kw)
@@ -424,8 +484,14 @@ def _resident(eng, entry, P, n, steps, implicit, m=None, bed=BED, wrong=None):
     elif later:
         # everything the entry takes: log, body-frame applied wrench, pose hold, sea (irr: the 64-component spectrum), bed, lines
         # (spread, irr: the spread of three), extremes seeded from the state, the net (teth: one layer), link tensions, ke_out
-        if entry == "irr":
+        # (the TOP entries: and the statistics record; _ens the ensemble, _fd and _shear the finite-depth sea, _shear the profile)
+        if entry in ("irr", "stat"):
             eng.set_sea_spectrum(sea)
+        elif entry == "ens":
+            eng.set_sea_ensemble(sea)
+        elif entry in ("fd", "shear"):
+            eng.set_sea_finite_depth(sea, n)
+            eng.set_current_profile(profile if entry == "shear" else None)
         else:
             eng.set_sea(sea)
         eng.set_seabed(bed)
@@ -442,6 +508,11 @@ def _resident(eng, entry, P, n, steps, implicit, m=None, bed=BED, wrong=None):
             peaks = eng.alloc_tiled(net.shape[1] // 7, n)
             if entry == "peak":
                 eng.step_fused_tiled_multi_peak(cur, old, n, DT, steps, STEP0, t7, net.shape[1] // 7, peaks, record, m9, **tail)
+            elif top:
+                stat = eng.statistics_reset(torch.full((eng.tiles(n), nat.STAT_FIELDS, 64), NAN, dtype=torch.float32, device=DEV), n)
+                step = getattr(eng, "step_fused_tiled_multi_" + entry)
+                step(cur, old, n, DT, steps, STEP0, stat, _tiled(lev), channels[0], channels[1], _tiled(spread), spread.shape[1] // 9, t7,
+                     net.shape[1] // 7, peaks, record, **tail)
             else:
                 step = eng.step_fused_tiled_multi_irr if entry == "irr" else eng.step_fused_tiled_multi_spread
                 step(cur, old, n, DT, steps, STEP0, _tiled(spread), spread.shape[1] // 9, t7, net.shape[1] // 7, peaks, record, **tail)
@@ -464,8 +535,12 @@ def _resident(eng, entry, P, n, steps, implicit, m=None, bed=BED, wrong=None):
         out["ke"] = _np(ke)
     if peaks is not None:
         out["peaks"] = _from(peaks, n)                               # scalars: the image's are the scene's
+    if stat is not None:
+        words = stx.unpack(_np(stat), n)
+        out["stat"] = sym.statistics_words(words if ident else sym.statistics(m, words, channels))
+        out["left_out"] = [] if ident else sym.statistics_left_out(m, channels)
     if later:
-        eng.set_sea_spectrum(None)
+        _no_water(eng)
     if not ident:
         out["state"], out["prev_out"], out["log"] = sym.state(m, out["state"]), sym.prev(m, out["prev_out"]), sym.log_row(m, out["log"])
         if record is not None:
@@ -495,9 +570,13 @@ def _compare(entry, want, got, first, what):
         bad = sym.differing(got["log"][j][live], want["log"][j][live])
         assert not bad.any(), what + ("log row", j, int(bad.sum()), np.nonzero(live)[0][bad][:8])
     whole = first >= steps
-    for k in ("state", "prev_out", "extremes", "peaks"):
+    for k in ("state", "prev_out", "extremes", "peaks", "stat"):
         if k in want:
-            bad = sym.differing(got[k][whole], want[k][whole])
+            a, b = got[k], want[k]
+            if k == "stat":                                         # the up-crossing word of a flipped slot: left out on both sides
+                a, b = a.copy(), b.copy()
+                a[:, got["left_out"]], b[:, got["left_out"]] = 0.0, 0.0
+            bad = sym.differing(a[whole], b[whole])
             assert not bad.any(), what + (k, int(bad.sum()), np.nonzero(whole)[0][bad][:8])
     if "ke" in want and whole.all():
         assert sym.equal(got["ke"], want["ke"]), what + ("ke", got["ke"], want["ke"])
@@ -647,18 +726,19 @@ def test_tether_spread_and_spectrum_probes_are_exactly_symmetric(coeff, later_po
           "(11 and 64 components, steps 0 and 10^6), n = 200 and 321, 3 maps: 0 differ")
 
 
-def _later(eng, entry, P, pr, n, steps, implicit, bed, what, wrong=None):
+def _later(eng, entry, P, pr, n, steps, implicit, bed, what, **water):
     """The launch of `entry` on P and on its three images, compared by `_compare`: [(map, bodies exact, bodies left out)].  A body
     is left out from the first step whose input state has two or more contributing corners ON THE BED THAT IS SET, on the scene
     or on the image (_sensitive_from: the reference decides).  Over FAR that is nobody - but for a body that explicit drag has
     carried out of the scene: FAR is a plane at z = -10^6 m, and seven explicit steps take light bodies to 10^14 m and beyond
-    (the module's docstring), eight corners below any plane.  The callers assert that this happens under explicit drag only."""
-    want, st0 = _resident(eng, entry, P, n, steps, implicit, bed=bed)
+    (the module's docstring), eight corners below any plane.  The callers assert that this happens under explicit drag only.
+    `water`: the sea, profile and channels of a TOP entry (see _resident)."""
+    want, st0 = _resident(eng, entry, P, n, steps, implicit, bed=bed, **water)
     assert not sym.equal(want["state"], st0)
     first0 = _sensitive_from(st0, want["log"], pr[:n], bed)
     out = []
     for m in sym.MAPS:
-        got, st_g = _resident(eng, entry, P, n, steps, implicit, m, bed=bed)
+        got, st_g = _resident(eng, entry, P, n, steps, implicit, m, bed=bed, **water)
         first = np.minimum(first0, _sensitive_from(sym.state(m, st_g), got["log"], pr[:n], bed))
         exact, left = _compare(entry, want, got, first, what + (n, steps, m))
         if implicit:                                                # left out, but finite
@@ -669,6 +749,8 @@ def _later(eng, entry, P, pr, n, steps, implicit, bed, what, wrong=None):
         # the launch did what its name says: the lines pulled (tension_max), and where there are link tensions every layer of the net did
         assert (want["extremes"][:, 7] > 0).mean() >= 0.3 and np.isfinite(want["ke"]).all(), what + (n, steps)
         assert "peaks" not in want or ((want["peaks"] > 0).mean(axis=0) >= 0.2).all(), what + (n, steps)
+        # and the record holds what the launch sampled: n = steps for every body, both S2 non-zero for at least half of them
+        assert "stat" not in want or ((want["stat"][:, 6] == steps).all() and (want["stat"][:, [1, 3]] > 0).all(axis=1).mean() >= 0.5), what + (n, steps)
     return out
 
 
@@ -753,6 +835,228 @@ def test_teeth_on_the_device_wrong_hand_images_are_told_apart(coeff, later_pop, 
     print(f"[teeth on the device {coeff}] bodies that differ from the predicted image: " + "; ".join(shown))
 
 
+# ---- (g) statistics, ensembles, finite depth and the sheared current --------------------------------------------------------------------
+H = symmetry_population.FD_DEPTH                                  # the depth the resident rungs run at (tests/symmetry_population.py)
+
+
+def _top_water(case, n):
+    """(entry, dict(sea, profile)) of a case of the TOP rungs at n bodies."""
+    one = symmetry_population.fd_sea()
+    return {
+        "stat": ("stat", dict(sea=FULL)),
+        "ens-1": ("ens", dict(sea=seh.ensemble(64, n, 1))),                  # every wavefront reads its own member
+        "ens-4": ("ens", dict(sea=seh.ensemble(64, n, 4))),                  # a block shares one member; the last member lies partly past n
+        "fd-one": ("fd", dict(sea=one)),                                     # the designed sea as an ensemble of one
+        "fd-ens": ("fd", dict(sea=symmetry_population.fd_ensemble(64, n, 1))),
+        "shear-16": ("shear", dict(sea=one, profile=cpr.turning_profile(16, depth=H))),
+        "shear-2": ("shear", dict(sea=symmetry_population.fd_ensemble(64, n, 4), profile=cpr.turning_profile(2, depth=H))),
+    }[case]
+
+
+TOP_CASES = ("stat", "ens-1", "ens-4", "fd-one", "fd-ens", "shear-16", "shear-2")
+
+
+@COEFFS
+def test_ensemble_depth_and_profile_probes_are_exactly_symmetric(coeff, later_pop, engines):
+    """hydro_sea_ensemble_sample (tiles_per_sea 1 and 4), hydro_sea_finite_depth_sample (a spectrum as an ensemble of one, and an
+    ensemble) and hydro_current_profile_sample (without a profile, with 2 and with 16 knots), at 11 and 64 components and steps 0
+    and 10^6: the image's sample is symmetry.sea_sample of the sample and eta keeps its bits.  Populations: tests/
+    symmetry_population.py at n = 200 and 321 in FD_DEPTH of water; sea_depth_reference.population() (130 bodies over the whole
+    column of 9 m: both clamps and the inside, asserted in tests/test_symmetry.py); and for the profile
+    symmetry_population.knot_population, a body in every knot interval."""
+    st, _, params = later_pop[0], later_pop[1], later_pop[2]
+    column = sdr.population()
+    pops = [("reseated", st[:n], H, "designed") for n in SIZES] + [("column", column, sdr.DEPTH, "column")]
+    launches = 0
+    for name, s, depth, key in pops:
+        n = len(s)
+        eng = engines(key, params[coeff][:max(n, 130)], coeff)
+        for count in (11, 64):
+            one = sdr.designed_sea(count, depth)
+            fd_ens = symmetry_population.fd_ensemble(count, n, 1, depth)
+            cases = [("ensemble", seh.ensemble(count, n, tps), None, s) for tps in (1, 4)]
+            cases += [("finite_depth", one, None, s), ("finite_depth", fd_ens, None, s), ("profile", fd_ens, None, s)]
+            for knots in (2, 16):
+                profile = cpr.turning_profile(knots, depth=depth)
+                cases += [("profile", one, profile, s), ("profile", one, profile, symmetry_population.knot_population(profile, one, 0, DT))]
+            for kind, sea, profile, bodies in cases:
+                nb = len(bodies)
+
+                def sample(sea_, profile_, bodies_, step):
+                    _no_water(eng)
+                    if kind == "ensemble":
+                        eng.set_sea_ensemble(sea_)
+                        return _from(eng.sea_ensemble_sample(_tiled(bodies_), nb, step, DT), nb)
+                    eng.set_sea_finite_depth(sea_, nb)
+                    if kind == "finite_depth":
+                        return _from(eng.sea_finite_depth_sample(_tiled(bodies_), nb, step, DT), nb)
+                    eng.set_current_profile(profile_)
+                    return _from(eng.current_profile_sample(_tiled(bodies_), nb, step, DT), nb)
+                for step in (0, 10 ** 6):
+                    want = sample(sea, profile, bodies, step)
+                    assert np.isfinite(want).all() and want[:, 0].all() and want[:, 1:4].any(axis=0).all()
+                    for m in sym.MAPS:
+                        got = sample(sym.sea(m, sea), None if profile is None else sym.current_profile(m, profile), sym.state(m, bodies), step)
+                        bad = sym.differing(got, sym.sea_sample(m, want)) | (got[:, 0].view(np.uint32) != want[:, 0].view(np.uint32))
+                        assert not bad.any(), (kind, name, nb, count, step, m, None if profile is None else profile.knots, int(bad.sum()), np.nonzero(bad)[0][:8])
+                        launches += 1
+        _no_water(eng)
+    print(f"[probes {coeff}] hydro_sea_ensemble_sample, hydro_sea_finite_depth_sample and hydro_current_profile_sample (none, 2 and 16 knots), 11 and 64 "
+          f"components, steps 0 and 10^6, n = 200, 321 and 130 (the profile: and a body in every knot interval), 3 maps: {launches} images, 0 differ")
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("over", ["far", "bed"])
+@pytest.mark.parametrize("case", TOP_CASES)
+def test_top_rungs_are_exactly_symmetric(case, over, coeff, implicit, later_pop, engines):
+    """_stat, _ens, _fd and _shear, each with everything it takes switched on: everything _irr takes in
+    test_later_rungs_are_exactly_symmetric and a statistics record, reset, against levels near the initial values, once over the
+    channels (z, tension) - nothing flips under any map - and once over (x, vy), which flip under two maps each: S1 -> -S1, S2 and
+    n the same bits, the up-crossing word of the flipped slot left out (tests/symmetry.py).  The water: `_top_water`.  The
+    expectations are those of test_later_rungs_are_exactly_symmetric, with the statistics record among what is compared:
+      over FAR, at 1 and 7 steps: every body exact in every log row, state, prev_out, extremes, link tensions and the record, the
+        energy pair the same bits; nobody left out at 1 step nor at 7 implicit steps, at most 25 % after 7 explicit steps;
+      over BED, ONE step: the bodies with at most one contributing corner exact, the others left out and at most 25 %."""
+    P = (later_pop[0], later_pop[1], later_pop[2][coeff]) + later_pop[3:]
+    pr = P[2]
+    bed = BED if over == "bed" else FAR
+    report = []
+    for n in SIZES:
+        eng = engines("designed", pr[:n], coeff)
+        entry, water = _top_water(case, n)
+        for steps in (STEPS if over == "far" else (1,)):
+            for channels in CHANNEL_PAIRS:
+                runs = _later(eng, entry, P, pr, n, steps, implicit, bed, (case, over, channels), channels=channels, **water)
+                fewest, most = min(r[1] for r in runs), max(r[2] for r in runs)
+                if over == "bed":
+                    assert most <= 0.25 * n, (case, over, n, steps, most)
+                else:
+                    assert most == 0 or (not implicit and steps > 1 and most <= 0.25 * n), (case, over, n, steps, most)
+            report.append(f"n={n} x{steps}: {fewest} exact, {most} left out ({most / n:.0%}), 0 differ")
+    print(f"[resident {case} over {over.upper()} {coeff} {'implicit' if implicit else 'explicit'}, fewest / most over the 3 maps] " + "; ".join(report))
+
+
+@COEFFS
+@DRAG
+@pytest.mark.parametrize("variant", ["non_temporal", "warp"])
+def test_sheared_current_everything_on_non_temporal_and_warp(variant, coeff, implicit, later_pop, engines):
+    """The everything-on _shear launch (16 knots) over FAR, 7 steps, n = 321, with non_temporal = 1 and under Warp semantics,
+    both channel pairs."""
+    P = (later_pop[0], later_pop[1], later_pop[2][coeff]) + later_pop[3:]
+    n = 321
+    eng = engines("designed", P[2][:n], coeff)
+    if variant == "warp":
+        eng.set_semantics("warp")
+    else:
+        eng.set_tuning(0, 0, 1)
+    entry, water = _top_water("shear-16", n)
+    for channels in CHANNEL_PAIRS:
+        runs = _later(eng, entry, P, P[2], n, 7, implicit, FAR, (variant, "shear", channels), channels=channels, **water)
+        assert all(left == 0 if implicit else left <= 0.25 * n for _, _, left in runs)
+    print(f"[shear, everything on, {variant} {coeff} {'implicit' if implicit else 'explicit'}] n=321 steps=7 "
+          + "; ".join(f"{m}: {exact} exact, {left} left out, 0 differ" for m, exact, left in runs))
+
+
+def _reference_water(sea, st, time):
+    """(eta, u) in fp64 at `time` seconds of whatever kind of sea: sea_depth_reference.water serves a sea with and without a
+    depth; an ensemble goes block by block."""
+    if hasattr(sea, "members"):
+        eta, u = np.empty(len(st)), np.empty((len(st), 3))
+        for k, member in enumerate(sea.members):
+            at = slice(k * sea.bodies_per_sea, min((k + 1) * sea.bodies_per_sea, len(st)))
+            eta[at], u[at] = _reference_water(member, st[at], time)
+        return eta, u
+    with np.errstate(all="ignore"):
+        return sdr.water(sea, st[:, 0], st[:, 1], st[:, 2], 1, time)
+
+
+@COEFFS
+def test_open_loop_sea_entries_are_exactly_symmetric(coeff, later_pop, wrench_pops, engines):
+    """hydro_step_wrench_tiled_sea and hydro_step_wrench_aos_sea (both quaternion orders) under SEA with hydro_sea_sample at a
+    time; hydro_step_wrench_tiled_irr, hydro_step_wrench_aos_irr and the matching sample while the engine holds, in turn, the
+    64-component spectrum, an ensemble and a finite-depth ensemble - at times 0, 7 dt and 10^6 dt, on edge_cases (81 bodies) and
+    tests/symmetry_population.py at n = 321.  The image's wrench is symmetry.wrench of the wrench, the engine-owned previous
+    velocity afterwards the image of the scene's, the sample symmetry.sea_sample of the sample.  At least half of the bodies are
+    wet by the fp64 water and the oracle."""
+    fx = wrench_pops["edge_cases"]
+    pops = [("edge_cases",) + fx, ("reseated", later_pop[0], later_pop[1], later_pop[2][coeff], RHO, G, DT)]
+    for name, st, pv, pr, rho, g, dt in pops:
+        n = len(st)
+        eng = engines(name, pr, coeff, rho, g) if name == "edge_cases" else engines("designed", pr[:n], coeff)
+        holders = (("sea", SEA), ("spectrum", FULL), ("ensemble", seh.ensemble(64, n, 1)), ("finite depth", symmetry_population.fd_ensemble(64, n, 1)))
+
+        def entries(kind, sea, s, p, time):
+            """name -> (n, 6) wrench or (n, 4) sample, and name + ' prev' -> the engine-owned previous velocity after the call."""
+            _no_water(eng)
+            {"sea": eng.set_sea, "spectrum": eng.set_sea_spectrum, "ensemble": eng.set_sea_ensemble, "finite depth": eng.set_sea_finite_depth}[kind](sea)
+            tiled, aos, sample = ((eng.step_wrench_tiled_sea, eng.step_wrench_aos_sea, eng.sea_sample_at) if kind == "sea" else
+                                  (eng.step_wrench_tiled_irr, eng.step_wrench_aos_irr, eng.irregular_sea_sample_at))
+            out = {"sample": _from(sample(_tiled(s), n, time), n)}
+            eng.set_prev_velocity(_soa(p))
+            out["tiled"] = _from(tiled(_tiled(s), n, dt, time), n)
+            out["tiled prev"] = _np(eng.get_prev_velocity()).T
+            pos, vel = _rows(s[:, 0:3]), _rows(s[:, 7:13])
+            for which, quat, xyzw in (("aos_wxyz", s[:, [6, 3, 4, 5]], False), ("aos_xyzw", s[:, 3:7], True)):
+                eng.set_prev_velocity(_soa(p))
+                f, t = aos(pos, _rows(quat), vel, dt, time, quat_xyzw=xyzw)
+                out[which] = np.concatenate([_np(f), _np(t)], axis=1)
+                out[which + " prev"] = _np(eng.get_prev_velocity()).T
+            torch.cuda.synchronize()
+            return out
+        shown = []
+        for kind, sea in holders:
+            for time in (0.0, 7 * dt, 10 ** 6 * dt):
+                want = entries(kind, sea, st, pv, time)
+                eta, u = _reference_water(sea, st, time)
+                with np.errstate(all="ignore"):
+                    s_rel, pv_rel = sr.relative(st, pv, eta.astype(np.float32), u.astype(np.float32))
+                    wet = ho.step_wrench(s_rel, pv_rel, io._coeffs(pr, coeff), rho, g, dt)[2]["ratio"] > 0
+                assert wet.mean() >= 0.5, (name, kind, time, wet.mean())
+                assert (want["tiled"][wet] != 0).any(axis=1).mean() >= 0.9 and sym.equal(want["tiled prev"], st[:, 7:13])
+                for m in sym.MAPS:
+                    got = entries(kind, sym.sea(m, sea), sym.state(m, st), sym.prev(m, pv), time)
+                    for k, v in want.items():
+                        image = sym.sea_sample(m, v) if k == "sample" else sym.prev(m, v) if k.endswith("prev") else sym.wrench(m, v)
+                        bad = sym.differing(got[k], image)
+                        assert not bad.any(), (name, kind, time, m, k, int(bad.sum()), np.nonzero(bad)[0][:8])
+                    known = ~np.isnan(want["sample"][:, 0])                     # eta keeps its BITS (a NaN its being one)
+                    assert np.array_equal(got["sample"][known, 0].view(np.uint32), want["sample"][known, 0].view(np.uint32)), (name, kind, time, m)
+            shown.append(f"{kind} ({int(wet.sum())} wet)")
+        _no_water(eng)
+        print(f"[open-loop sea entries {coeff}] {name}: {n} bodies x 3 times x 3 maps x (tiled, aos wxyz, aos xyzw, sample; the previous velocity): "
+              + ", ".join(shown) + ": 0 differ")
+
+
+@COEFFS
+def test_teeth_on_the_device_depth_profile_and_member(coeff, later_pop, engines):
+    """Three images of the wrong hand through the same launches and the same comparison, one implicit step over FAR: (a) the
+    finite-depth sea's ky not flipped under mirror_y (_fd) and (b) the profile's V_l turned like an axial vector under mirror_y
+    and mirror_x (_shear): at least a quarter of the bodies differ from the predicted image; (c) ONE member of the ensemble at
+    tiles_per_sea = 1 left unturned under mirror_y (_ens): at least a quarter of THAT member's bodies differ and not one body of
+    any other member - the comparison resolves the member mapping.  With the right hand none differs in any of the three."""
+    P = (later_pop[0], later_pop[1], later_pop[2][coeff]) + later_pop[3:]
+    member = 2                                                      # bodies 128 .. 191, at either size
+    shown = []
+    for n in SIZES:
+        eng = engines("designed", P[2][:n], coeff)
+        for case, wrong, maps in (("fd-one", "ky", ("mirror_y",)), ("shear-16", "profile", ("mirror_y", "mirror_x")), ("ens-1", ("member", member), ("mirror_y",))):
+            entry, water = _top_water(case, n)
+            want, _ = _resident(eng, entry, P, n, 1, True, bed=FAR, **water)
+            for m in maps:
+                def apart(got):
+                    return sym.differing(got["state"], want["state"]) | sym.differing(got["prev_out"], want["prev_out"]) | sym.differing(got["log"][0], want["log"][0])
+                assert not apart(_resident(eng, entry, P, n, 1, True, m, bed=FAR, **water)[0]).any(), (case, n, m)
+                bad = apart(_resident(eng, entry, P, n, 1, True, m, bed=FAR, wrong=wrong, **water)[0])
+                if case == "ens-1":
+                    mine = water["sea"].sea_of(np.arange(n)) == member
+                    assert mine.sum() == 64 and not bad[~mine].any(), (case, n, m, np.nonzero(bad & ~mine)[0][:8])
+                    bad = bad[mine]
+                shown.append(f"{wrong if isinstance(wrong, str) else 'member'} {m} n={n}: {bad.mean():.0%}")
+                assert bad.mean() >= 0.25, (case, wrong, n, m, bad.mean())
+    print(f"[teeth on the device, depth, profile and member {coeff}] bodies that differ from the predicted image: " + "; ".join(shown))
+
+
 # ---- (f) ClosedLoopSim ------------------------------------------------------------------------------------------------------------------
 def test_closed_loop_sim_builds_its_records_without_a_hand(native_built):
     """64 moored buoys at 64 headings, a current with one wave component, an off-centre fairlead and a weak pose hold towards a
@@ -790,4 +1094,38 @@ def test_closed_loop_sim_builds_its_records_without_a_hand(native_built):
     assert (np.abs(finals["scene"][:, 0:3] - sc.state[:, 0:3]) > 1e-4).any(axis=1).all()
     bad = sym.differing(sym.state(m, finals["image"]), finals["scene"]) | sym.differing(sym.extremes(m, records["image"]), records["scene"])
     print(f"[ClosedLoopSim, 64 moored buoys and their mirror_y image, 20 steps in chunks of 7] {int(bad.sum())} bodies differ")
+    assert not bad.any(), np.nonzero(bad)[0]
+
+
+def test_closed_loop_sim_with_a_finite_depth_ensemble_and_a_sheared_current(native_built):
+    """The 64 moored buoys of the test above in a depth-carrying ensemble (two members of 11 components over 25 m of water; the
+    64 bodies step through the first) with the 16-knot turning profile, and the mirror_y image of all of it, both through
+    ClosedLoopSim's own set_sea / set_current_profile / set_mooring: run_resident(20, chunk=7) with track_extremes leaves the
+    image's final state and Extremes the images of the scene's."""
+    sc, anchors, z_eq, mass = _buoys()
+    k, c = Mooring.for_body(mass, sc.dt)
+    depth = 25.0
+    sea = SeaEnsemble([sdr.with_depth(member, depth) for member in seh.members(11, 2)], 64)
+    profile = cpr.turning_profile(16, depth=depth)
+    fairlead = np.array([0.05, 0.02, -0.05])
+    L0 = DEPTH - 0.2                                                # taut from the first step
+    m = "mirror_y"
+    polar = np.asarray(sym.POLAR[m], np.float64)
+    finals, records = {}, {}
+    for name in ("scene", "image"):
+        im = name == "image"
+        scene = scenes.Scene("buoys", sym.state(m, sc.state), sym.prev(m, sc.prev), sc.params, dt=sc.dt, rho=sc.rho, g=sc.g) if im else sc
+        sim = ClosedLoopSim(scene, implicit_drag=True)
+        sim.set_sea(sym.sea(m, sea) if im else sea)
+        sim.set_current_profile(sym.current_profile(m, profile) if im else profile)
+        sim.set_mooring(anchors * polar if im else anchors, fairlead * polar if im else fairlead, length=L0, stiffness=k, damping=c)
+        view = sim.track_extremes()
+        sim.run_resident(20, chunk=7)
+        finals[name], records[name] = sim.state(), view.bodies()
+        sim.close()
+    assert np.isfinite(finals["scene"]).all() and (records["scene"][:, 7] > 0).all()                     # every line pulled
+    assert (np.abs(finals["scene"][:, 0:3] - sc.state[:, 0:3]) > 1e-4).any(axis=1).all()
+    bad = sym.differing(sym.state(m, finals["image"]), finals["scene"]) | sym.differing(sym.extremes(m, records["image"]), records["scene"])
+    print(f"[ClosedLoopSim, 64 moored buoys in a finite-depth ensemble under a sheared current and their mirror_y image, 20 steps in chunks of 7] "
+          f"{int(bad.sum())} bodies differ")
     assert not bad.any(), np.nonzero(bad)[0]
